@@ -16,14 +16,20 @@ all-gathers its shard's descriptor block once over RCCL/xGMI (the one exchange s
 inside the timed region for N > 1; the same collective has run once before the clock starts).  Weights are the deterministic synthetic checkpoint of
 tests/synth.py (there is no network for real ones); oracle/ is imported by the cpu_baseline leg only.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs DIR is given and
+prints ONE JSON line on rank 0 (contract in the task statement) with the `roofline` object:
   roofline      the kernel with the largest time share (bound / achieved / peak / frac / traffic) AND
                 `kernels`: the same figures for every (kernel, layer shape) group of the step, plus the
                 step-level MFMA fraction - algorithmic FLOPs and bytes / event-timed launch durations
                 collected inside this process over the timed steps
+--dump-outputs DIR: DIR/descriptors.npy (float32) = the descriptors the last timed step returned (every rank's rows under
+N > 1); the inputs and weights are seeded, so two builds run with the same flags can be compared output for output.
+--full adds everything that takes runs of its own, after the timed steps (N = 1 only):
   cpu_baseline  the CPU oracle (a port of the reference forward) timed on this box's host cores
                 on a bounded sample of the same workload (rank 0, N == 1 only)
-and, inside `config`, measured outside the timed region (N = 1 only):
+and, inside `config`, measured outside the timed region:
+  side rates    the same step on the other feed and on the other checkpoint (<feed>_feed_images_per_sec,
+                calibrated_images_per_sec / he_init_images_per_sec)
   precision     the rates of the same step in the other formats (bf16 / fp16 / strict fp32: 20 steps each, median + min / max
                 over groups of 5) and every dtype's distance from the CPU oracle (descriptors on the calibrated checkpoint, mAP)
   workloads     BASELINE configs[3] and configs[4] on this GPU, 20 steps each + min / median / max over 4 more groups of 5
@@ -36,6 +42,7 @@ Two more workloads keep the same flags and JSON contract (the default above is B
                            are L2-normalised, so the similarity runs on two fp16 planes (dir_similarity_unit; the range is
                            established once per database, outside the timed steps; --sim-general = the six-product bf16 kernel)
   --workload multiscale    configs[4]: three scales of resident uint8 1200^2 images, fp16, device-side resize
+(their --dump-outputs: aps.npy, float64 [Q, easy / medium / hard], and descriptors.npy, float32 3-scale descriptors)
 """
 import argparse
 import gc
@@ -170,6 +177,22 @@ def cpu_baseline(arch, size, budget_s, sd=None, images=None):
            'sample': '%d x %s fp32 %dx%d forward, batch 1, oracle/dir_oracle.py (%.1f s)' % (n, arch, size, size, el)}
     out.update(reference_cli_scalars(arch, size))
     return out, torch.cat(outs).numpy()
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step, one DIR/<name>.npy per array -
+    tensors as float32, host lists (the APs) as float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().float().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float64)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+def last_step_rows(shard, allb, K, B, world):
+    """Rows [(K - 1) * B, K * B) of this rank's descriptor block or, after the all-gather, of every rank's block."""
+    if allb is None:
+        return shard[(K - 1) * B:K * B]
+    return torch.cat([allb[r * K * B + (K - 1) * B:(r + 1) * K * B] for r in range(world)])
 
 
 def step_spread(step, groups=4, per_group=5):
@@ -307,8 +330,8 @@ def other_workloads(args, x_bench):
     out = {}
     del x_bench
     torch.cuda.empty_cache()
-    for name, fn, over in (('distractors', bench_distractors, {'steps': 20, 'warmup': 2, 'cpu_seconds': 0.0}),
-                           ('multiscale', bench_multiscale, {'steps': 20, 'warmup': 2})):      # (keeps --cpu-seconds: its parity leg)
+    for name, fn, over in (('distractors', bench_distractors, {'steps': 20, 'warmup': 2, 'cpu_seconds': 0.0, 'dump_outputs': ''}),
+                           ('multiscale', bench_multiscale, {'steps': 20, 'warmup': 2, 'dump_outputs': ''})):      # (keeps --cpu-seconds: its parity leg)
         a = copy.copy(args)
         for k, v in over.items():
             setattr(a, k, v)
@@ -529,6 +552,8 @@ def bench_distractors(args, world, rank, dist):
         t = torch.tensor([el], device='cuda', dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if args.dump_outputs and rank == 0:      # the last timed step's APs, one row per query (the same on every rank)
+        dump_outputs(args.dump_outputs, {'aps': [[a['easy'], a['medium'], a['hard']] for a in aps]})
     spread = step_spread(lambda: step(False)) if world == 1 else None
     for _ in range(20):     # per-phase durations (events on torch's current stream, where every kernel above runs)
         step(True)
@@ -661,6 +686,8 @@ def bench_multiscale(args, world, rank, dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'descriptors': last_step_rows(shard, allb, K, B, world)})
     spread = step_spread(step) if world == 1 else None
     if rank != 0:
         return None
@@ -822,16 +849,22 @@ def main():
                          "synthetic images - the conditioned network the parity numbers (config.one_minus_cos) are quoted on (one fp32 CPU "
                          "forward of two images before the clock starts).  Since round 6 the OTHER checkpoint's rate of the same step rides "
                          "along as config.calibrated_images_per_sec / config.he_init_images_per_sec, with the dominant kernel's launch "
-                         "average on its activations (the 3x3 kernels are power-bound and data-dependent: ~4 % between the two)")
+                         "average on its activations (the 3x3 kernels are power-bound and data-dependent: ~4 %% between the two)")
     ap.add_argument('--autotune', action='store_true',
                     help='time every admissible tile variant per layer first (default: the built-in tile heuristic, '
                          'which the tuner no longer beats at this shape)')
     ap.add_argument('--no-autotune', action='store_true', help='(default; kept for old command lines)')
-    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='0 disables the CPU legs (baseline + precision)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure what takes runs of its own: the other feed / checkpoint rates, the CPU '
+                         'baseline, the other precisions and their parity with the CPU oracle, the bounded configs[3] / configs[4] '
+                         'runs (extract workload, N = 1).  Off by default: a plain run times the headline step only')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps, write what the last timed step returned as DIR/<name>.npy')
+    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='0 disables the CPU legs (baseline + precision; with --full)')
     ap.add_argument('--no-precision', action='store_true',
-                    help='skip the fp16 / strict-fp32 throughput and the parity-vs-oracle fields (config.precision)')
+                    help='skip the fp16 / strict-fp32 throughput and the parity-vs-oracle fields (config.precision; with --full)')
     ap.add_argument('--no-workloads', action='store_true',
-                    help='skip the bounded configs[3] / configs[4] runs that fill config.workloads')
+                    help='skip the bounded configs[3] / configs[4] runs that fill config.workloads (with --full)')
     ap.add_argument('--workload', default='extract', choices=['extract', 'distractors', 'multiscale'],
                     help="extract = BASELINE configs[1] (default); multiscale = configs[4] (3 scales of 1200^2, fp16); distractors = configs[3]: a database of --db-rows "
                          "2048-d descriptors sharded over the ranks, ONE all-gather, Q x N similarity, device rank + AP")
@@ -953,6 +986,8 @@ def main():
     gc.enable()
     prof = net.get_profile()
     net.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'descriptors': last_step_rows(shard, allb, K, B, world)})
 
     if rank == 0:
         nprof = len([k for k in range(K) if k % args.profile_every == 0])
@@ -1039,7 +1074,7 @@ def main():
         cpu, precision, workloads = None, None, None
         side = {}
         sd_cal = sd_timed if args.checkpoint == 'calibrated' else None
-        if world == 1:
+        if world == 1 and args.full:
             # the same step on the OTHER feed and on the OTHER checkpoint (20 steps each, median over groups of 5; the dominant
             # kernel's average launch from the profile records of 4 more steps)
             other_x = x_f32 if args.input == 'u8' else x_u8
@@ -1071,7 +1106,7 @@ def main():
                     side[tag + '_dominant_kernel_frac'] = round(dfl / dn / (sum(doms) / len(doms) * 1e-3) / 1e12 / peak_tf, 4) if not hbm_bound else None
                 del net2
         del x_f32, x_u8
-        if world == 1 and args.cpu_seconds > 0:
+        if world == 1 and args.full and args.cpu_seconds > 0:
             del shard
             net._ws = {}
             torch.cuda.empty_cache()
@@ -1096,7 +1131,7 @@ def main():
                        'timed_checkpoint': ('BatchNorm-calibrated synthetic (tests/synth.py; the checkpoint one_minus_cos is quoted on)'
                                             if args.checkpoint == 'calibrated' else
                                             'random-init (He-normal) synthetic (tests/synth.py), as rounds 1-5; the BatchNorm-calibrated one, on which '
-                                            'one_minus_cos is quoted, is timed beside it: calibrated_images_per_sec'),
+                                            'one_minus_cos is quoted, is timed beside it with --full: calibrated_images_per_sec'),
                        **side,
                        'gflop_per_image': GFLOP_PER_IMG.get((args.arch, S)),
                        # ---- parity of THIS line's dtype as flat scalars (measured in this run, outside the timed region):

@@ -10,7 +10,7 @@ timeout 900 python -m pytest tests/test_scale_gpu.py -m gpu -q -s -p no:cachepro
 grep -a "^\[timed\| passed\| failed\|^FAILED\|^ERROR\|Error\|s call" $O/pytest_timed.log | tail -30
 fi
 for SEG in ${SEGS:-0}; do
-DIRTORCH_AMD_STEM_U8_SEG=$SEG timeout 600 python bench.py --steps 20 --warmup 3 --cpu-seconds 0 --layers > $O/bench_u8_seg$SEG.json 2> $O/bench_u8_seg$SEG.txt; echo "bench u8 seg=$SEG rc=$?"
+DIRTORCH_AMD_STEM_U8_SEG=$SEG timeout 600 python bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 --layers > $O/bench_u8_seg$SEG.json 2> $O/bench_u8_seg$SEG.txt; echo "bench u8 seg=$SEG rc=$?"
 python - <<P
 import json
 d = json.loads(open('$O/bench_u8_seg$SEG.json').read().strip().splitlines()[-1])
@@ -19,5 +19,5 @@ P
 grep -a "prep_input\|conv1+maxpool\|layer1.0" $O/bench_u8_seg$SEG.txt | head -8
 done
 if [ -n "$FULL_BENCH" ]; then
-timeout 900 python bench.py --layers > $O/bench_full.json 2> $O/bench_full.txt; echo "bench full rc=$?"; tail -c 3000 $O/bench_full.json
+timeout 900 python bench.py --full --layers > $O/bench_full.json 2> $O/bench_full.txt; echo "bench full rc=$?"; tail -c 3000 $O/bench_full.json
 fi

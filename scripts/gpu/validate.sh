@@ -16,7 +16,7 @@ if [ -z "$SKIP_TESTS" ]; then
   grep -a "^\[scale\|^\[timed\|^\[strict\|^\[fp16p\|^\[pipeline\|^\[overflow\| passed\| failed\|^FAILED\|^ERROR\|Error" $O/pytest.log | tail -100
 fi
 if [ -z "$SKIP_BENCH" ]; then
-  timeout 900 python bench.py $BENCH_ARGS --layers --dump-launches $O/launches.json > $O/bench.json 2> $O/bench_layers.txt
+  timeout 900 python bench.py --full $BENCH_ARGS --layers --dump-launches $O/launches.json > $O/bench.json 2> $O/bench_layers.txt
   echo "bench rc=$?"; tail -c 4500 $O/bench.json | cut -c1-4500; tail -5 $O/bench_layers.txt
 fi
 if [ -z "$SKIP_PROF" ]; then
