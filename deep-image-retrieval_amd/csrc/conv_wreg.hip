@@ -137,6 +137,7 @@ __global__ void __launch_bounds__(512) conv1x1_wreg_kernel(const ConvArgs a) {
     u32x4_t rres0[4], rres1[4];
     load_res(tile, 0, rres0);
     store_x(xr, smem);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (this wave's LDS writes complete before the hand-off)
     ring_barrier();   // first tile staged (and the bias table written)
     for (;;) {
         const bool more = tile + per < mt;
@@ -226,6 +227,7 @@ __global__ void __launch_bounds__(512) conv1x1_wreg_kernel(const ConvArgs a) {
         store_x(xr, smem + (cur ^ 1) * XBUF);
         tile = next;
         cur ^= 1;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the published tile is in LDS before the hand-off)
         ring_barrier();
     }
     ovf.flush(a.ovf);

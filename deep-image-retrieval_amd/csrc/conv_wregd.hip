@@ -141,6 +141,7 @@ __global__ void __launch_bounds__(768) conv1x1_wregd_kernel(const ConvArgs a) {
         load_x(tile_at(0), xa);
         store_x(xa, smem);
         load_x(tile_at(1), xa);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (this wave's LDS writes complete before the hand-off)
         ring_barrier();   // first tile published (and the bias table written)
         int i = 0;
         for (; i < n; i += 2) {

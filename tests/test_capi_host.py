@@ -288,3 +288,72 @@ def test_profile_tooling_knows_every_engine_kernel():
                 re.match(r'^conv_f32<128x(64|128)>$', k) or re.match(r'^conv_pair<128x(64|128)_(patch3x3_)?x?w(/dual)?>$', k), (n, k)
         else:
             assert k in forward or k in other, (n, k)
+
+
+def _heuristic():
+    """dir_conv_heuristic as a function of (B, H, W, Cin, Cout, k, stride, pad, residual) -> (variant name, ksplit)."""
+    import ctypes
+    from dirtorch_amd import _lib
+    _lib.load()
+    buf, ks = ctypes.create_string_buffer(64), ctypes.c_int()
+
+    def pick(B, H, W, Cin, Cout, k, stride, pad, res):
+        OH, OW = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+        _lib.call('dir_conv_heuristic', B, H, W, Cin, Cout, k, k, stride, pad, OH, OW, int(res), buf, 64, ctypes.byref(ks))
+        return buf.value.decode(), ks.value
+    return pick
+
+
+def test_picker_cases_are_what_the_picker_launches():
+    """Every row of tests/picker_cases.py is the (variant, ksplit) the engine launches for its shape under the default
+    switches: a picker change moves the table with it (and the GPU sweep then runs the new pair)."""
+    from picker_cases import PICKER_CASES
+    pick = _heuristic()
+    for tag, B, H, W, Cin, Cout, k, stride, pad, res, relu, v, ks in PICKER_CASES:
+        assert pick(B, H, W, Cin, Cout, k, stride, pad, res) == (v, ks), \
+            '%s %s: the table says (%s, %d)' % (tag, (B, H, W, Cin, Cout, k, stride, pad, res), v, ks)
+    assert len({r[0] for r in PICKER_CASES}) == len(PICKER_CASES), 'duplicate tags'
+
+
+def test_every_pair_the_picker_emits_has_a_picker_case():
+    """Nothing the picker launches goes without an element-wise GPU test (tests/test_picker_parity_gpu.py runs the table):
+      * every (variant, ksplit) over the claimed workloads' layers has a row that IS one of those layers;
+      * every (variant, split or not) class, and every split-K pair, over a dense grid of launchable shapes has a row - a split
+        pair with a row whose K-steps the slices do not share evenly, wherever the grid has such a shape;
+      * every persistent kernel the picker uses has a row that walks >= 2 rounds of its grid, not a multiple of it, with a
+        ragged last pixel tile."""
+    import picker_cases as P
+    pick = _heuristic()
+    rows = [(r[1:10], (r[11], r[12])) for r in P.PICKER_CASES]
+    missing = []
+    # the workloads
+    layers = {l[2:11]: l for l in P.workload_layers()}
+    wl_pairs = {}
+    for shape, l in layers.items():
+        wl_pairs.setdefault(pick(*shape), l)
+    for pair, l in sorted(wl_pairs.items()):
+        if not any(p == pair and s in layers for s, p in rows):
+            missing.append('(%s, %d) on the workloads, e.g. %s.%s %s' % (pair + (l[0], l[1], l[2:11])))
+    # the grid
+    classes, splits, emitted = {}, {}, {pair: l[2:11] for pair, l in wl_pairs.items()}
+    for shape in P.synthetic_grid():
+        v, ks = pick(*shape)
+        classes.setdefault((v, ks > 1), shape)
+        emitted.setdefault((v, ks), shape)
+        if ks > 1:
+            uneven = P.k_steps(shape[3], shape[5]) % ks != 0
+            if (v, ks) not in splits or (uneven and not splits[(v, ks)][1]):
+                splits[(v, ks)] = (shape, uneven)
+    for (v, split), shape in sorted(classes.items()):
+        if not any(p[0] == v and (p[1] > 1) == split for _, p in rows):
+            missing.append('(%s, %s) on the grid, e.g. %s' % (v, 'split-K' if split else 'unsplit', shape))
+    for pair, (shape, uneven) in sorted(splits.items()):
+        if not any(p == pair and (not uneven or P.k_steps(s[3], s[5]) % pair[1] != 0) for s, p in rows):
+            missing.append('(%s, %d)%s on the grid, e.g. %s' % (pair + (' with uneven K-steps' if uneven else '', shape)))
+    # the persistent kernels
+    for v in sorted({v for v, _ in emitted if any(f in v for f in P.PERSISTENT)}):
+        if not any(p[0] == v and P.walks_rounds(v, s[:8]) for s, p in rows):
+            shape = next(s for (vv, _), s in emitted.items() if vv == v)
+            missing.append('(%s, 1) walking >= 2 rounds of its grid, not a multiple, ragged (emitted e.g. for %s)' % (v, shape))
+    assert not missing, 'tests/picker_cases.py has no row for:\n  ' + '\n  '.join(missing)
+    assert len(wl_pairs) >= 20 and len(classes) >= 20, (len(wl_pairs), len(classes))

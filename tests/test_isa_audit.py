@@ -7,7 +7,11 @@ when forwards overlapped on several HIP streams - csrc/dir_common.h `ring_barrie
 `__builtin_amdgcn_sched_barrier(0)`; these tests keep a raw `s_barrier` from coming back: no kernel source calls the
 builtin directly, and in the assembly of every ring kernel at least one barrier sits between two
 `; sched_barrier mask(0x00000000)` markers while no barrier that follows a hand-written `s_waitcnt` (an inline-asm
-block) is left without them."""
+block) is left without them.
+
+A second audit covers the other half of a hand-off, over every kernel of every source: a wave's own LDS writes must have
+completed (`s_waitcnt lgkmcnt(0)`) before the barrier that publishes them."""
+import glob
 import os
 import re
 import shutil
@@ -25,6 +29,10 @@ RING_KERNELS = re.compile(r'conv_igemm_kernel|conv_patch3x3\w*_kernel|conv_patch
                           r'conv1x1_wreg_kernel|conv1x1_lc_kernel|conv1x1_wregd_kernel|conv_c3c1ds_lc_kernel|sim_split\w*_kernel|whiten_split_kernel|stem_pool_persist_kernel|conv_pair_kernel|conv_pair_patch64_kernel|conv_seam3_kernel|stem_pool_pair_persist_kernel|stem_pool_u8_kernel')
 
 
+ALL_SOURCES = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(CSRC, '*.hip')))
+needs_hipcc = pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason='hipcc not available')
+
+
 def _asm(name, out_dir):
     out = os.path.join(out_dir, name + '.s')
     subprocess.run([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-S', '--cuda-device-only',
@@ -32,22 +40,32 @@ def _asm(name, out_dir):
     return open(out).read()
 
 
-@pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason='hipcc not available')
-def test_ring_kernels_fence_their_hand_off_barriers(tmp_path):
-    with ThreadPoolExecutor(max_workers=len(RING_SOURCES)) as ex:
-        texts = list(ex.map(lambda n: _asm(n, str(tmp_path)), RING_SOURCES))
+@pytest.fixture(scope='module')
+def asm(tmp_path_factory):
+    """gfx950 assembly of every csrc/*.hip, compiled once for the module: {source name: text}."""
+    out_dir = str(tmp_path_factory.mktemp('asm'))
+    with ThreadPoolExecutor(max_workers=16) as ex:
+        return dict(zip(ALL_SOURCES, ex.map(lambda n: _asm(n, out_dir), ALL_SOURCES)))
+
+
+def _functions(text, prefix=r'_ZN3dir'):
+    """[(mangled name, [stripped body lines])] of the functions of one assembly file, in order."""
+    func, funcs = None, []
+    for line in text.split('\n'):
+        m = re.match(r'^(%s\w+):' % prefix, line)
+        if m:
+            func = (m.group(1), [])
+            funcs.append(func)
+        elif func is not None:
+            func[1].append(line.strip())
+    return funcs
+
+
+@needs_hipcc
+def test_ring_kernels_fence_their_hand_off_barriers(asm):
     checked, kernels = 0, 0
-    for name, text in zip(RING_SOURCES, texts):
-        func, body = None, []
-        funcs = []
-        for line in text.split('\n'):
-            m = re.match(r'^(_ZN3dir\w+):', line)
-            if m:
-                func, body = m.group(1), []
-                funcs.append((func, body))
-            elif func is not None:
-                body.append(line.strip())
-        for func, body in funcs:
+    for name in RING_SOURCES:
+        for func, body in _functions(asm[name]):
             if not RING_KERNELS.search(func):
                 continue
             kernels += 1
@@ -67,7 +85,49 @@ def test_ring_kernels_fence_their_hand_off_barriers(tmp_path):
     assert kernels >= 40 and checked >= 60, (kernels, checked)
 
 
+# LDS writes and atomics: they count on lgkmcnt, and s_barrier waits for no counter.  (Reads, ds_permute / ds_bpermute and
+# ds_swizzle write no LDS; LDS-DMA loads count on vmcnt, which the hand-off barriers above are audited for.)
+DS_WRITE = re.compile(r'^ds_(write|store|add|sub|rsub|inc|dec|min|max|and|or|xor|mskor|wrxchg|cmpst|cmpswap|cond_xchg|pk_add|'
+                      r'append|consume)\w*$')
+# {(source name, kernel name regex): reason} - LDS writes a barrier may publish without lgkmcnt(0).  There are none.
+LDS_PUBLISH_EXCEPTIONS = {}
+
+
+@needs_hipcc
+def test_lds_writes_complete_before_the_barrier_that_publishes_them(asm):
+    """On gfx950 a wave's ds_write is in flight until its lgkmcnt drops, and the compiler puts no wait in front of a bare
+    s_barrier: a write the barrier is meant to publish can still be pending when another wave reads that LDS after it.  Every
+    LDS write or atomic must therefore reach an `s_waitcnt ... lgkmcnt(0)` before the next s_barrier, in the linear order of
+    each function's assembly (as conv_c3c1lc.hip's hand-off does)."""
+    bad, writes, barriers, funcs = {}, 0, 0, 0
+    for name, text in asm.items():
+        for func, body in _functions(text, prefix=r'_Z'):
+            funcs += 1
+            pending = None
+            for l in body:
+                if not l or l.startswith(('.', ';')):
+                    continue
+                op = l.split()[0]
+                if DS_WRITE.match(op):
+                    pending = l
+                    writes += 1
+                elif op == 's_waitcnt' and 'lgkmcnt(0)' in l:
+                    pending = None
+                elif op == 's_barrier':
+                    barriers += 1
+                    if pending is not None:
+                        if not any(src == name and re.search(k, func) for src, k in LDS_PUBLISH_EXCEPTIONS):
+                            bad.setdefault((name, func), []).append(pending)
+                        pending = None
+    assert funcs >= 150 and writes >= 2000 and barriers >= 400, (funcs, writes, barriers)
+    if bad:
+        import subprocess as sp
+        demangle = lambda f: sp.run(['c++filt', f], capture_output=True, text=True).stdout.strip() or f
+        pytest.fail('LDS writes reach an s_barrier with no s_waitcnt lgkmcnt(0) in between (add one before ring_barrier()):\n' +
+                    '\n'.join('  %s.hip: %s - %d barrier(s), last write before one: %s' % (src, demangle(f), len(w), w[-1])
+                               for (src, f), w in sorted(bad.items())))
+
+
 def test_no_kernel_calls_the_raw_barrier_builtin():
-    import glob
     for f in glob.glob(os.path.join(CSRC, '*.hip')):
         assert '__builtin_amdgcn_s_barrier' not in open(f).read(), '%s: use ring_barrier() (dir_common.h)' % os.path.basename(f)
