@@ -357,3 +357,33 @@ def test_every_pair_the_picker_emits_has_a_picker_case():
             missing.append('(%s, 1) walking >= 2 rounds of its grid, not a multiple, ragged (emitted e.g. for %s)' % (v, shape))
     assert not missing, 'tests/picker_cases.py has no row for:\n  ' + '\n  '.join(missing)
     assert len(wl_pairs) >= 20 and len(classes) >= 20, (len(wl_pairs), len(classes))
+
+
+def test_engine_cases_cover_every_launch_form_in_every_regime():
+    """tests/engine_cases.py (the engine's seams, two-source GEMMs, paired convs and stems; tests/test_engine_launch_parity_gpu.py
+    runs it) against its mirror of the engine's choices and against launch_geometry:
+      * every row with a workload is that workload's launch of the row's form, at that layer's operands, in the row's dtypes, and
+        every stem row uses the workload's image size;
+      * every form the mirror emits has a row in each regime - first and largest launch over the claimed workloads, a walk of >= 3
+        tiles per workgroup with a short last round and a ragged tile (the persistent forms), one tile per workgroup - and the
+        role-split DS seam walks with an odd and an even tile count;
+      * tags are unique.
+    A failure names the form and the regime (or the row)."""
+    import engine_cases as E
+    problems = E.table_problems()
+    assert not problems, 'tests/engine_cases.py:\n  ' + '\n  '.join(problems)
+    assert len(E.all_launches()) >= 18, sorted(E.all_launches())
+
+
+def test_engine_cases_mirror_the_engine_thresholds():
+    """The mirror's thresholds are the engine's: kSeamMinTiles (engine.hip) and conv_pick_dual_variant's unit counts
+    (conv_igemm.hip).  (The GPU gate checks the whole mirror against the engine's launch record.)"""
+    import engine_cases as E
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'deep-image-retrieval_amd', 'csrc')
+    engine = open(os.path.join(csrc, 'engine.hip')).read()
+    igemm = open(os.path.join(csrc, 'conv_igemm.hip')).read()
+    assert re.search(r'kSeamMinTiles = (\d+);', engine).group(1) == str(E.SEAM_MIN_TILES)
+    dual = igemm[igemm.index('int conv_pick_dual_variant('):]
+    dual = dual[:dual.index('\n}\n')]
+    assert re.search(r'\(a\.Cout / 256\) >= (\d+)\)', dual).group(1) == str(E.WREGD_MIN_UNITS)
+    assert re.search(r'\(a\.Cout / 256\) < (\d+)\)', dual).group(1) == str(E.X3_MIN_UNITS)
