@@ -423,6 +423,22 @@ int dir_conv_variant_admissible(int variant, int B, int H, int W, int Cin, int C
     DIR_CATCH
 }
 
+int dir_conv_variant_splitk(int variant, int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad,
+                            int OH, int OW, int has_residual, int* ksplit) {
+    DIR_TRY
+    if (!ksplit) return fail(DIR_ERR_INVALID, "conv_variant_splitk: null result pointer");
+    ConvArgs a;
+    static const float dummy = 0.f;   // host-only decision: the pointers are never dereferenced
+    int rc = fill_conv_args(a, &dummy, &dummy, &dummy, has_residual ? &dummy : nullptr, (void*)&dummy, B, H, W, Cin,
+                            Cout, R, S, stride, pad, OH, OW, 1);
+    if (rc != DIR_OK) return rc;
+    if (!conv_variant_admissible(variant, a)) return fail(DIR_ERR_INVALID, "conv_variant_splitk: variant not admissible for this shape");
+    const int s = conv_splitk_factor(variant, a);
+    *ksplit = s > 1 ? s : 1;
+    return DIR_OK;
+    DIR_CATCH
+}
+
 static int fill_conv_args(ConvArgs& a, const void* x, const void* w, const float* bias,
                           const void* res, void* y, int B, int H, int W, int Cin, int Cout, int R,
                           int S, int stride, int pad, int OH, int OW, int relu) {

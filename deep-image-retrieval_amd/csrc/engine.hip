@@ -627,6 +627,8 @@ int dir_engine::run_conv(ConvLayer& L, const uint16_t* x, const uint16_t* res, u
         DIR_HIP_CHECK(hipEventCreate(&e1));
         float best = 1e30f;
         for (int v = 0; v < conv_variant_count(); ++v) {
+            a.ksplit = 0;   // (the previous candidate's split must not decide this one's admissibility: conv_small, conv_patchs2
+                            // and conv_persistlc refuse a.ksplit > 1)
             if (!conv_variant_admissible(v, a)) continue;
             a.ksplit = conv_splitk_factor(v, a);
             int rc = conv_launch(a, kdtype(), v, stream);  // warm-up (also sets func attributes)
@@ -655,6 +657,7 @@ int dir_engine::run_conv(ConvLayer& L, const uint16_t* x, const uint16_t* res, u
     }
     // a tuning table written for another architecture shares layer names (resnet18 / resnet101 both
     // have layer1.0.conv1): an entry that does not fit this layer's shape is dropped, not an error
+    a.ksplit = 0;   // (judged as a plain launch, like dir_conv_variant_admissible: not with the last timed candidate's split)
     if (variant >= 0 && !conv_variant_admissible(variant, a)) {
         L.tuned.erase(a.M);
         variant = -1;

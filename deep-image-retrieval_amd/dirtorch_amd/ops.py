@@ -82,7 +82,7 @@ def conv_bn_act(x, w, bias, res=None, stride=1, pad=0, relu=True, out_hw=None, v
                 naive=False, ksplit=None):
     """x NHWC [B,H,W,Cin] 16-bit, w [Cout,R,S,Cin] 16-bit, bias fp32 [Cout] -> NHWC [B,OH,OW,Cout].
     ksplit: None = plain launch; n > 1 = split-K into n slices; -1 = the engine's own choice
-    (conv_bn_act.last_ksplit holds what was used)."""
+    (conv_bn_act.last_ksplit holds what was used; the fp32 scratch is sized for that factor, none when nothing splits)."""
     _need_cuda(x, w, bias, res)
     B, H, W, Cin = x.shape
     Cout, R, S, Cin2 = w.shape
@@ -97,8 +97,16 @@ def conv_bn_act(x, w, bias, res=None, stride=1, pad=0, relu=True, out_hw=None, v
     args = [ptr(x), ptr(w), ptr(bias), ptr(res), ptr(y), B, H, W, Cin, Cout, R, S, stride, pad, OH,
             OW, int(bool(relu)), _dtype_code(x)]
     if ksplit is not None:
-        n = 8 if ksplit < 0 else max(int(ksplit), 1)
-        scratch = torch.empty(n * B * OH * OW * Cout, dtype=torch.float32, device=x.device)
+        n = max(int(ksplit), 1)
+        if ksplit < 0:      # the engine's own factor for this launch: a host-only query, so that only its slices are reserved
+            q = ctypes.c_int()
+            shape = (B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, int(res is not None))
+            if variant < 0:
+                call('dir_conv_heuristic', *shape, ctypes.create_string_buffer(64), 64, ctypes.byref(q))
+            else:
+                call('dir_conv_variant_splitk', int(variant), *shape, ctypes.byref(q))
+            n = q.value
+        scratch = torch.empty(n * B * OH * OW * Cout if n > 1 else 0, dtype=torch.float32, device=x.device)
         used = ctypes.c_int()
         call('dir_conv_bn_act_splitk', *args, int(variant), int(ksplit), ptr(scratch), scratch.numel() * 4,
              ctypes.byref(used), stream_ptr())

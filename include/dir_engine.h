@@ -239,6 +239,12 @@ int dir_conv_heuristic(int B, int H, int W, int Cin, int Cout, int R, int S, int
  * tests' own mirror of the rule is pinned on the CPU (tests/test_capi_host.py). */
 int dir_conv_variant_admissible(int variant, int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad,
                                 int OH, int OW, int has_residual, int* admissible);
+/* How many K slices the engine (and its tuner) launches `variant` in on this shape: *ksplit = 1 (no split) or 2..8.  Pure host
+ * logic (conv_splitk_factor, what dir_conv_bn_act_splitk applies for ksplit < 0), exposed so that a caller can reserve exactly
+ * the scratch that factor needs (*ksplit * B*OH*OW * Cout floats when > 1, none otherwise) and the tests can group the tuner's
+ * candidate launches by their split.  DIR_ERR_INVALID when the variant is not admissible for the shape. */
+int dir_conv_variant_splitk(int variant, int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad,
+                            int OH, int OW, int has_residual, int* ksplit);
 /* Same convolution with the K loop cut into `ksplit` slices that run as separate workgroups and meet in
  * an fp32 scratch buffer (ksplit * B*OH*OW * Cout floats; slices are added in a fixed order, then bias /
  * residual / ReLU) - what the engine does for layers with too few output tiles to fill 256 CUs (batch 1

@@ -357,3 +357,60 @@ def test_in_place_identity_blocks_with_paired_weights_beyond_layer1(stages, monk
     d_pp, f_pp = ref(x), ref.forward_features(x)
     assert torch.equal(d_in, d_pp) and torch.equal(f_in, f_pp)
     assert torch.isfinite(d_in).all()
+
+
+def test_tuning_table_names_admissible_variants_and_round_trips():
+    """dir_engine_autotune at batch 1 on a small map - where the small-map, strided-patch and loader / consumer kernels are
+    candidates next to the split-K tiles.  Which variant wins is timing; these three properties are not:
+      * export_tuning() holds a line for every layer that the same forward's profile shows on a conv_igemm<...> launch of
+        run_conv (the fused seam, stem and two-source '/dual' launches do not pass the tuner);
+      * each line names the layer's pixel count and a variant the library admits for that layer's shape
+        (dir_conv_variant_admissible is exactly the tuner's candidate set: it judges every candidate as a plain launch, not with
+        the split factor left over from the previously timed one);
+      * import_tuning of that text into a fresh engine reproduces the tuned forward bit for bit."""
+    import ctypes
+    import dir_oracle as O
+    from dirtorch_amd import _lib, ops
+    from picker_cases import bottleneck_layers
+    B, H, W = 1, 256, 192
+    sd = O.synth_state_dict('resnet50', seed=7)
+    x = O.synth_images(6, B, H, W).cuda()
+    net = make_net('resnet50', {}, sd, 'bf16')
+    net.autotune = True
+    net.set_profiling(True)
+    tuned = net(x).clone()
+    prof = {r['name']: r['kernel'] for r in net.get_profile()}
+    net.set_profiling(False)
+    table = net.export_tuning()
+    lines = {}
+    for line in table.splitlines():
+        name, M, vname = line.split()
+        lines.setdefault(name, []).append((int(M), vname))
+    through_tuner = [n for n, k in prof.items() if k.startswith('conv_igemm<') and not k.endswith('/dual>')]
+    assert len(through_tuner) >= 20, prof
+    shapes = {l[0]: l[1:] for l in bottleneck_layers('resnet50', B, H, W)}
+    names = ops.conv_variant_names()
+    ok = ctypes.c_int()
+    for name in through_tuner:
+        assert name in lines, 'no tuning line for %s (%s)' % (name, prof[name])
+        if name == 'conv1':      # the unfused stem: the 4 x 4 stride-1 conv over the space-to-depth grid
+            sh, OH, OW = (B, (H + 1) // 2, (W + 1) // 2, 16, 64, 4, 1, 2, False), (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        else:
+            stage, block, conv = name.split('.')
+            sh = shapes['%s.%s.%s' % (stage, block if block == '0' else 'x', conv)][:9]
+            OH, OW = ((sh[1] + 2 * sh[7] - sh[5]) // sh[6] + 1, (sh[2] + 2 * sh[7] - sh[5]) // sh[6] + 1)
+        for M, vname in lines[name]:
+            assert M == B * OH * OW, (name, M, OH, OW)
+            _lib.call('dir_conv_variant_admissible', names.index(vname), sh[0], sh[1], sh[2], sh[3], sh[4], sh[5], sh[5], sh[6],
+                      sh[7], OH, OW, int(sh[8]), ctypes.byref(ok))
+            assert ok.value, '%s: tuned to %s, which is not admissible for %r' % (name, vname, sh)
+            assert prof[name][len('conv_igemm<'):-1].split('/')[0] == vname, (name, vname, prof[name])     # ... and it is what ran
+    fresh = make_net('resnet50', {}, sd, 'bf16')
+    fresh._build_engine()
+    fresh.import_tuning(table)
+    fresh.set_profiling(True)
+    again = fresh(x)
+    prof2 = {r['name']: r['kernel'] for r in fresh.get_profile()}
+    assert prof2 == prof
+    assert torch.equal(again, tuned)
+    assert torch.equal(fresh.forward_features(x), net.forward_features(x))
