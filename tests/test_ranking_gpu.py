@@ -356,8 +356,9 @@ def test_pair_similarity_range_and_selection():
 
 def test_split_similarity_keeps_the_fp32_exponent_range(monkeypatch):
     """Not only unit vectors: rows scaled by 2^+-40 (bf16 planes keep all 8 exponent bits, so no scaling step
-    exists to go wrong), an all-zero row, and a database row pitch view.  Relative to sum_k |q_k||d_k| the
-    error stays at the 1e-7 level."""
+    exists to go wrong) and an all-zero row.  Relative to sum_k |q_k||d_k| the error stays at the 1e-7 level.
+    (dir_similarity always passes ldp = D, so there is no row-pitch view to cover here; the entry point that does take
+    pitches, dir_gemm_nt_f32, is run on padded views in test_exact_planes_gpu.py::test_gemm_nt_row_pitches.)"""
     from dirtorch_amd import ops
     Q, N, D = 40, 33000, 256
     g = torch.Generator(device='cuda').manual_seed(5)
