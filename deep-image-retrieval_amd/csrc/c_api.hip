@@ -389,15 +389,20 @@ static int fill_conv_args(ConvArgs& a, const void* x, const void* w, const float
                           const void* res, void* y, int B, int H, int W, int Cin, int Cout, int R,
                           int S, int stride, int pad, int OH, int OW, int relu);
 
+// The shape-only queries below decide on the host: their ConvArgs carries pointers that only have to be non-null (never dereferenced).
+static int shape_only_conv_args(ConvArgs& a, int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int OH,
+                                int OW, int has_residual) {
+    static const float dummy = 0.f;
+    return fill_conv_args(a, &dummy, &dummy, &dummy, has_residual ? &dummy : nullptr, (void*)&dummy, B, H, W, Cin, Cout, R, S,
+                          stride, pad, OH, OW, 1);
+}
+
 int dir_conv_heuristic(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int OH,
                        int OW, int has_residual, char* name, int cap, int* ksplit) {
     DIR_TRY
     if (!name || cap <= 0) return fail(DIR_ERR_INVALID, "conv_heuristic: null name buffer");
     ConvArgs a;
-    // host-only decision: the pointers are never dereferenced, they only have to be non-null
-    static const float dummy = 0.f;
-    int rc = fill_conv_args(a, &dummy, &dummy, &dummy, has_residual ? &dummy : nullptr, (void*)&dummy, B, H, W, Cin,
-                            Cout, R, S, stride, pad, OH, OW, 1);
+    int rc = shape_only_conv_args(a, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, has_residual);
     if (rc != DIR_OK) return rc;
     const int v = conv_pick_variant(a);
     if (v < 0) return fail(DIR_ERR_INVALID, "conv_heuristic: no admissible variant for this shape");
@@ -414,9 +419,7 @@ int dir_conv_variant_admissible(int variant, int B, int H, int W, int Cin, int C
     if (!admissible) return fail(DIR_ERR_INVALID, "conv_variant_admissible: null result pointer");
     if (variant < 0 || variant >= conv_variant_count()) return fail(DIR_ERR_INVALID, "conv_variant_admissible: no such variant");
     ConvArgs a;
-    static const float dummy = 0.f;   // host-only decision: the pointers are never dereferenced
-    int rc = fill_conv_args(a, &dummy, &dummy, &dummy, has_residual ? &dummy : nullptr, (void*)&dummy, B, H, W, Cin,
-                            Cout, R, S, stride, pad, OH, OW, 1);
+    int rc = shape_only_conv_args(a, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, has_residual);
     if (rc != DIR_OK) return rc;
     *admissible = conv_variant_admissible(variant, a) ? 1 : 0;
     return DIR_OK;
@@ -428,9 +431,7 @@ int dir_conv_variant_splitk(int variant, int B, int H, int W, int Cin, int Cout,
     DIR_TRY
     if (!ksplit) return fail(DIR_ERR_INVALID, "conv_variant_splitk: null result pointer");
     ConvArgs a;
-    static const float dummy = 0.f;   // host-only decision: the pointers are never dereferenced
-    int rc = fill_conv_args(a, &dummy, &dummy, &dummy, has_residual ? &dummy : nullptr, (void*)&dummy, B, H, W, Cin,
-                            Cout, R, S, stride, pad, OH, OW, 1);
+    int rc = shape_only_conv_args(a, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, has_residual);
     if (rc != DIR_OK) return rc;
     if (!conv_variant_admissible(variant, a)) return fail(DIR_ERR_INVALID, "conv_variant_splitk: variant not admissible for this shape");
     const int s = conv_splitk_factor(variant, a);

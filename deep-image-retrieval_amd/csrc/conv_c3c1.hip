@@ -36,11 +36,10 @@
 // to the fp32 summation order of the K halves.  Weights of layer3 (1 MB per seam) do not fit the 512 KB
 // register file: that seam streams them from L2 through an LDS ring instead (conv_seam3.hip).
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 namespace dir {
-
-static constexpr uint32_t kOOBf = 0x80000000u;
 
 // P2 = planes of the block that conv1' opens: P inside a stage, 2 P across the layer1 -> layer2 boundary
 // (layer2's first conv1 is 1x1 stride 1 over the 256-wide layer1 output; the stride sits in its conv2).
@@ -76,17 +75,16 @@ __global__ void __launch_bounds__(512) conv_c3c1_kernel(const ConvArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lrow = lane & 31, lhi = lane >> 5;
 
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
     const __amdgpu_buffer_rsrc_t rsrc_x2 =      // DS: the block input [M][64]
-        __builtin_amdgcn_make_buffer_rsrc((void*)(DS ? a.x2 : a.x), 0, DS ? (uint32_t)((size_t)a.M * 128) : a.x_bytes, 0x00020000);
+        buffer_rsrc(DS ? a.x2 : a.x, DS ? (uint32_t)((size_t)a.M * 128) : a.x_bytes);
     const __amdgpu_buffer_rsrc_t rsrc_x2l =     // DS + WP3: its lo plane
-        __builtin_amdgcn_make_buffer_rsrc((void*)(DS && WP3 ? a.x2_lo : a.x), 0,
-                                          DS && WP3 ? (uint32_t)((size_t)a.M * 128) : a.x_bytes, 0x00020000);
+        buffer_rsrc(DS && WP3 ? a.x2_lo : a.x, DS && WP3 ? (uint32_t)((size_t)a.M * 128) : a.x_bytes);
     const uint32_t y_bytes = (uint32_t)((size_t)a.M * C4 * 2);
     const uint32_t y2_bytes = (uint32_t)((size_t)a.M * P2 * 2);
-    const __amdgpu_buffer_rsrc_t rsrc_r = __builtin_amdgcn_make_buffer_rsrc((void*)a.res, 0, y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void*)a.y, 0, y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_y2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.y2, 0, y2_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_r = buffer_rsrc(a.res, y_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_y = buffer_rsrc(a.y, y_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_y2 = buffer_rsrc(a.y2, y2_bytes);
 
     const int mt = (a.M + BM - 1) / BM;
     const int per = gridDim.x;
@@ -148,7 +146,7 @@ __global__ void __launch_bounds__(512) conv_c3c1_kernel(const ConvArgs a) {
 
     auto load_x = [&](int t, u32x4_t* xr) {
         const int m = t * BM + spix;
-        const uint32_t base = m < a.M ? (uint32_t)((m * P + sslot * 8) * 2) : kOOBf;
+        const uint32_t base = m < a.M ? (uint32_t)((m * P + sslot * 8) * 2) : kOOB;
         if (DS) {   // block 0 = t2 row, block 1 = block-input row [, block 2 = its lo plane] (64 channels = 128 bytes each)
             xr[0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, base, 0, 0);
             xr[1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_x2, base, 0, 0);
@@ -163,7 +161,7 @@ __global__ void __launch_bounds__(512) conv_c3c1_kernel(const ConvArgs a) {
         for (int i = 0; i < NX; ++i) *(u32x4_t*)(buf + i * (BM * 128) + sdst) = xr[i];
     };
     const uint32_t ncol2 = (uint32_t)((n_wave + ecol) * 2);
-    auto row_off = [&](int m) { return m < a.M ? (uint32_t)m * (uint32_t)(C4 * 2) + ncol2 : kOOBf; };
+    auto row_off = [&](int m) { return m < a.M ? (uint32_t)m * (uint32_t)(C4 * 2) + ncol2 : kOOB; };
     // residual of one 32-pixel strip: TA channel tiles x 2 passes of 16 B per lane
     auto load_res = [&](int t, int j, u32x4_t* r) {
 #pragma unroll
@@ -227,9 +225,7 @@ __global__ void __launch_bounds__(512) conv_c3c1_kernel(const ConvArgs a) {
                     const f32x4_t v = {acc[i][4 * g + 0], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]};
                     *(f32x4_t*)(ebase + lrow * EROW + (8 * g + 4 * lhi) * 4) = v;
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
                 const float* const bz = sbias3 + n_wave + i * 32 + ecol;
                 const f32x4_t b0 = *(const f32x4_t*)bz, b1 = *(const f32x4_t*)(bz + 4);
 #pragma unroll
@@ -241,18 +237,9 @@ __global__ void __launch_bounds__(512) conv_c3c1_kernel(const ConvArgs a) {
                                   f1[0] + b1[0], f1[1] + b1[1], f1[2] + b1[2], f1[3] + b1[3]};
                     if (!DS) {
                         const u32x4_t rv = j == 0 ? rres0[i * 2 + pass] : rres1[i * 2 + pass];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            float lo, hi;
-                            DT::unpack(rv[e], lo, hi);
-                            v[2 * e] += lo;
-                            v[2 * e + 1] += hi;
-                        }
+                        add_res8<DT>(v, rv);
                     }
-                    if (a.relu) {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                    }
+                    if (a.relu) relu8(v);
                     u32x4_t ov;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) ov[e] = DT::pack(v[2 * e], v[2 * e + 1]);
@@ -262,9 +249,7 @@ __global__ void __launch_bounds__(512) conv_c3c1_kernel(const ConvArgs a) {
                     const int n = n_wave + i * 32 + ecol, p = j * 32 + mrow;
                     *(u32x4_t*)(otile + (n >> 6) * (BM * 128) + p * 128 + ((((n & 63) >> 3) ^ ((p >> 1) & 7)) << 4)) = ov;
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
             }
             if (!DS && j == 0) load_res(next, 0, rres0);   // next tile's strip 0, one tile ahead
         }
@@ -324,9 +309,7 @@ __global__ void __launch_bounds__(512) conv_c3c1_kernel(const ConvArgs a) {
                     const f32x4_t v = {sum[4 * g + 0], sum[4 * g + 1], sum[4 * g + 2], sum[4 * g + 3]};
                     *(f32x4_t*)(ebase + lrow * EROW + (8 * g + 4 * lhi) * 4) = v;
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
                 const float* const bz = sbias1 + nt * 32 + ecol;
                 const f32x4_t b0 = *(const f32x4_t*)bz, b1 = *(const f32x4_t*)(bz + 4);
 #pragma unroll
@@ -336,15 +319,10 @@ __global__ void __launch_bounds__(512) conv_c3c1_kernel(const ConvArgs a) {
                     const f32x4_t f1 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4 + 16);
                     float v[8] = {f0[0] + b0[0], f0[1] + b0[1], f0[2] + b0[2], f0[3] + b0[3],
                                   f1[0] + b1[0], f1[1] + b1[1], f1[2] + b1[2], f1[3] + b1[3]};
-                    if (a.relu2) {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                    }
-                    u32x4_t ov;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) ov[e] = DT::pack(v[2 * e], v[2 * e + 1]);
+                    if (a.relu2) relu8(v);
+                    const u32x4_t ov = pack8<DT>(v);
                     const int m = m0 + j * 32 + mrow;
-                    const uint32_t off = m < a.M ? (uint32_t)m * (uint32_t)(P2 * 2) + (uint32_t)((nt * 32 + ecol) * 2) : kOOBf;
+                    const uint32_t off = m < a.M ? (uint32_t)m * (uint32_t)(P2 * 2) + (uint32_t)((nt * 32 + ecol) * 2) : kOOB;
                     __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y2, off, 0, 0);
                     ovf.see(ov);
                 }
@@ -387,7 +365,7 @@ static hipError_t launch_c3c1(const ConvArgs& a, hipStream_t stream) {
     static std::atomic<uint64_t> attr_done{0};
     if (hipError_t e = ensure_dynamic_lds((const void*)kern, LDS, attr_done); e != hipSuccess) return e;
     ConvArgs b = a;
-    b.x_bytes = (uint32_t)((size_t)a.M * a.Cin * 2);
+    b.x_bytes = (uint32_t)((size_t)a.M * a.Cin * 2);   // (not conv_fill_extents: the seam reads t2 as the flat [M][Cin] matrix its GEMM walks)
     const int mt = (a.M + 63) / 64;
     const int ncu = cu_count();
     hipLaunchKernelGGL(kern, dim3(mt < ncu ? mt : ncu), dim3(512), LDS, stream, b);

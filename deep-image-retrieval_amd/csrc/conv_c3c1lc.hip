@@ -22,11 +22,10 @@
 // GEMM, the 64-wide one is guarded by a "consumed" counter.
 // The structure conv_wregd.hip arrived at, with its measurements: profiles/r06_wregd.txt.
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 namespace dir {
-
-static constexpr uint32_t kOOBl = 0x80000000u;
 
 // WP: DIR_FP16P - the weights are fp16 PAIRS (a.w_lo, a.w2_lo) and the block input comes with its lo plane (a.x2_lo), staged as
 // a third 64-channel K block against the downsample's hi weights (conv_c3c1.hip WP3 / WP1)
@@ -89,12 +88,11 @@ __global__ void __launch_bounds__(768) conv_c3c1ds_lc_kernel(const ConvArgs a) {
     if (wave >= 8) {
         // ================================ memory waves ================================================================
         const int mtid = tid - 512;                        // 0 .. 255
-        const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (uint32_t)((size_t)a.M * 128), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsrc_x2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.x2, 0, (uint32_t)((size_t)a.M * 128), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsrc_x2l =
-            __builtin_amdgcn_make_buffer_rsrc((void*)(WP ? a.x2_lo : a.x2), 0, (uint32_t)((size_t)a.M * 128), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void*)a.y, 0, (uint32_t)((size_t)a.M * C4 * 2), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsrc_y2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.y2, 0, (uint32_t)((size_t)a.M * P2 * 2), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, (uint32_t)((size_t)a.M * 128));
+        const __amdgpu_buffer_rsrc_t rsrc_x2 = buffer_rsrc(a.x2, (uint32_t)((size_t)a.M * 128));
+        const __amdgpu_buffer_rsrc_t rsrc_x2l = buffer_rsrc(WP ? a.x2_lo : a.x2, (uint32_t)((size_t)a.M * 128));
+        const __amdgpu_buffer_rsrc_t rsrc_y = buffer_rsrc(a.y, (uint32_t)((size_t)a.M * C4 * 2));
+        const __amdgpu_buffer_rsrc_t rsrc_y2 = buffer_rsrc(a.y2, (uint32_t)((size_t)a.M * P2 * 2));
         sbias3[mtid] = a.bias[mtid];
         if (mtid < P2) sbias1[mtid] = a.bias2[mtid];
         if (mtid < 8) cnt[mtid] = 0;
@@ -106,7 +104,7 @@ __global__ void __launch_bounds__(768) conv_c3c1ds_lc_kernel(const ConvArgs a) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int m = t * BM + h * 32 + spix;
-                const uint32_t base = m < a.M ? (uint32_t)((m * 64 + sslot * 8) * 2) : kOOBl;
+                const uint32_t base = m < a.M ? (uint32_t)((m * 64 + sslot * 8) * 2) : kOOB;
                 xr[h * NXB + 0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, base, 0, 0);
                 xr[h * NXB + 1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_x2, base, 0, 0);
                 if (WP) xr[h * NXB + NXB - 1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_x2l, base, 0, 0);
@@ -127,7 +125,7 @@ __global__ void __launch_bounds__(768) conv_c3c1ds_lc_kernel(const ConvArgs a) {
                 const int pix = 2 * (k * 4 + owv) + opar;
                 const u32x4_t ov = *(const u32x4_t*)(ob + oblk * (BM * 128) + pix * 128 + ((oc8 ^ ((pix >> 1) & 7)) << 4));
                 const int m = m0 + pix;
-                const uint32_t off = m < a.M ? (uint32_t)m * (uint32_t)(C4 * 2) + (uint32_t)(oblk * 128 + oc8 * 16) : kOOBl;
+                const uint32_t off = m < a.M ? (uint32_t)m * (uint32_t)(C4 * 2) + (uint32_t)(oblk * 128 + oc8 * 16) : kOOB;
                 __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y, off, 0, 0);
             }
         };
@@ -137,7 +135,7 @@ __global__ void __launch_bounds__(768) conv_c3c1ds_lc_kernel(const ConvArgs a) {
                 const int pix = k * 32 + (mtid >> 3);
                 const u32x4_t ov = *(const u32x4_t*)(smem + T1_OFF + pix * 128 + ((oc8 ^ ((pix >> 1) & 7)) << 4));
                 const int m = m0 + pix;
-                const uint32_t off = m < a.M ? (uint32_t)m * (uint32_t)(P2 * 2) + (uint32_t)(oc8 * 16) : kOOBl;
+                const uint32_t off = m < a.M ? (uint32_t)m * (uint32_t)(P2 * 2) + (uint32_t)(oc8 * 16) : kOOB;
                 __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y2, off, 0, 0);
             }
         };

@@ -56,47 +56,74 @@ struct ConvArgs {
     uint32_t div_ow_mul, div_ow_shr;
 };
 
-typedef hipError_t (*ConvLaunchFn)(const ConvArgs&, hipStream_t);
+// ---- launcher prologue (host half of conv_device.h) ----------------------------------------------------------------------
+// Constants of fast_div (conv_device.h): q = umulhi(n, mul) >> shr is exact for 0 <= n < 2^31
+// (mul = ceil(2^(31+l) / d), l = ceil(log2 d)); mul == 0 encodes division by 1.
+inline void fastdiv_init(uint32_t d, uint32_t& mul, uint32_t& shr) {
+    if (d <= 1) {
+        mul = 0;
+        shr = 0;
+        return;
+    }
+    uint32_t l = 0;
+    while ((1ull << l) < d) ++l;
+    mul = (uint32_t)(((1ull << (31 + l)) + d - 1) / d);
+    shr = l - 1;
+}
 
+// What every launcher derives from the shape alone: the buffer-descriptor extents of the NHWC input(s) and the filter, and
+// the divisors that turn an output pixel index into (b, oh, ow).
+inline void conv_fill_extents(ConvArgs& b) {
+    b.x_bytes = (uint32_t)((size_t)b.B * b.H * b.W * b.Cin * 2);
+    b.w_bytes = (uint32_t)((size_t)b.Cout * b.Ktot * 2);
+    if (b.x2) b.x2_bytes = (uint32_t)((size_t)b.B * b.H2 * b.W2 * b.Cin2 * 2);
+    fastdiv_init((uint32_t)(b.OH * b.OW), b.div_ohw_mul, b.div_ohw_shr);
+    fastdiv_init((uint32_t)b.OW, b.div_ow_mul, b.div_ow_shr);
+}
+
+// ---- the variant table (conv_igemm.hip) ----------------------------------------------------------------------------------
+typedef bool (*ConvAdmissibleFn)(const ConvArgs&);
+typedef hipError_t (*ConvLaunchFn)(const ConvArgs&, int dtype, hipStream_t);
+
+// One row per kernel configuration.  A row says when it applies and how it is launched; conv_variant_admissible and
+// conv_launch only look the row up.  Rows keep their order and names: the index is what the tuner stores and exports.
 struct ConvVariant {
     const char* name;
-    int BM, BN, threads, stages, BK;
-    ConvLaunchFn launch[2];    // [dtype]
-    ConvLaunchFn launch16[2];  // Cin == 16 stem instantiation, or nullptr
-    int kind;                  // 0 = implicit GEMM (conv_igemm.hip), 1 = LDS-patch 3x3 (conv_patch.hip),
-                               // 2 = persistent 256x256 1x1 (conv_persist.hip),
-                               // 3 = register-stationary weights 1x1 (conv_wreg.hip),
-                               // 4 = kind 2 with the pixel operand three K-steps deep (conv_persist.hip, XDEEP),
-                               // 5 = LDS-patch 3x3 for wide layers, one 64-channel plane at a time (conv_patch.hip)
-                               // 6 = LDS-patch 3x3, 512 pixels x 128 channels, double-buffered 32-channel planes (conv_patchw.hip)
-                               // 7 = persistent 128x256 1x1 without a residual, one K ring over all tiles of a workgroup (conv_ring.hip)
-                               // 8 = 64 -> 64 channel 3x3 with the filter resident in LDS, loader / consumer waves (conv_patchlc.hip)
-                               // 9 = two-source 1x1 (launch_dual only) with register-stationary weights (conv_wregd.hip)
-                               // 11 = 64 x 64 tiles for small maps: loader / consumer waves on LDS counters (conv_small.hip; `stages` = ring depth)
-                               // 10 = kind 4's ring with loader / consumer wave roles, 1x1 without a residual and its two-source form (conv_persistlc.hip)
-    ConvLaunchFn launch_sk[2]; // split-K instantiation (ConvArgs::ksplit > 1), or nullptr
-    ConvLaunchFn launch_dual[2]; // two-source K instantiation (ConvArgs::x2: conv3 + downsample in one GEMM), or nullptr
+    int BM, BN, threads, stages, BK;   // tile, workgroup size, ring depth, K-step
+    ConvAdmissibleFn admissible;       // the plain form, or nullptr (a two-source-only row)
+    ConvLaunchFn launch;
+    bool has_splitk;                   // launch honours ConvArgs::ksplit > 1 (conv_splitk_finalize then reduces the slices)
+    ConvAdmissibleFn admissible_dual;  // the two-source form (ConvArgs::x2: conv3 + downsample in one GEMM), or nullptr
+    ConvLaunchFn launch_dual;
 };
 
-bool conv1x1_persist_admissible(const ConvArgs& a);
-hipError_t conv1x1_persist_launch(const ConvArgs& a, int dtype, hipStream_t stream, bool xdeep = false);
-hipError_t conv1x1_persist_dual_bf16(const ConvArgs& a, hipStream_t stream);   // conv3 + downsample, two K sources
-hipError_t conv1x1_persist_dual_fp16(const ConvArgs& a, hipStream_t stream);
-bool conv_patch64_lc_admissible(const ConvArgs& a);
+// the kernels of the other sources that the table's rows bind
+bool conv1x1_persist_admissible(const ConvArgs& a);                                 // conv_persist.hip: persistent 256 x 256 1x1
+hipError_t conv1x1_persist_launch(const ConvArgs& a, int dtype, hipStream_t stream);
+bool conv1x1_persist_x3_admissible(const ConvArgs& a);                              // ... with the pixel operand three K-steps deep (no residual)
+hipError_t conv1x1_persist_x3_launch(const ConvArgs& a, int dtype, hipStream_t stream);
+bool conv1x1_persist_dual_admissible(const ConvArgs& a);                            // ... and its two-source form
+hipError_t conv1x1_persist_dual_launch(const ConvArgs& a, int dtype, hipStream_t stream);
+bool conv_patch64_lc_admissible(const ConvArgs& a);                                 // conv_patchlc.hip
 hipError_t conv_patch64_lc_launch(const ConvArgs& a, int dtype, hipStream_t stream);
-bool conv1x1_ring_admissible(const ConvArgs& a);
+bool conv1x1_ring_admissible(const ConvArgs& a);                                    // conv_ring.hip (experiments builds)
 hipError_t conv1x1_ring_launch(const ConvArgs& a, int dtype, hipStream_t stream);
-bool conv1x1_wreg_admissible(const ConvArgs& a);
-bool conv_small_admissible(const ConvArgs& a);      // small maps: 64 x 64 tiles, four consumer + four loader waves, no workgroup barrier (conv_small.hip)
-hipError_t conv_small_launch(const ConvArgs& a, int dtype, int nst, hipStream_t stream);
-bool conv1x1_lc_admissible(const ConvArgs& a);      // the persistent 256 x 256 ring with loader / consumer roles (conv_persistlc.hip)
-hipError_t conv1x1_lc_launch(const ConvArgs& a, int dtype, hipStream_t stream);
-hipError_t conv1x1_lc_dual_bf16(const ConvArgs& a, hipStream_t stream);
-hipError_t conv1x1_lc_dual_fp16(const ConvArgs& a, hipStream_t stream);
-bool conv1x1_wregd_admissible(const ConvArgs& a);   // two-source form, K = 128 + 256 (layer2's first block)
-hipError_t conv1x1_wregd_bf16(const ConvArgs& a, hipStream_t stream);
-hipError_t conv1x1_wregd_fp16(const ConvArgs& a, hipStream_t stream);
+bool conv1x1_wreg_admissible(const ConvArgs& a);                                    // conv_wreg.hip
 hipError_t conv1x1_wreg_launch(const ConvArgs& a, int dtype, hipStream_t stream);
+// conv_small.hip - small maps: 64 x 64 tiles, four consumer + four loader waves, no workgroup barrier; an eight- or four-slot ring,
+// or four slots of two K-steps each (K2: an even number of K-steps only)
+bool conv_small_admissible(const ConvArgs& a);
+bool conv_small_k2_admissible(const ConvArgs& a);
+hipError_t conv_small_s8_launch(const ConvArgs& a, int dtype, hipStream_t stream);
+hipError_t conv_small_s4_launch(const ConvArgs& a, int dtype, hipStream_t stream);
+hipError_t conv_small_s4k2_launch(const ConvArgs& a, int dtype, hipStream_t stream);
+// conv_persistlc.hip - the persistent 256 x 256 ring with loader / consumer roles: 1x1 without a residual (x2 unset) and its two-source form
+bool conv1x1_lc_admissible(const ConvArgs& a);
+bool conv1x1_lc_plain_admissible(const ConvArgs& a);
+hipError_t conv1x1_lc_launch(const ConvArgs& a, int dtype, hipStream_t stream);
+hipError_t conv1x1_lc_dual_launch(const ConvArgs& a, int dtype, hipStream_t stream);
+bool conv1x1_wregd_admissible(const ConvArgs& a);   // conv_wregd.hip: two-source form, K = 128 + 256 (layer2's first block)
+hipError_t conv1x1_wregd_launch(const ConvArgs& a, int dtype, hipStream_t stream);
 // the layer3 seam (planes 256): weights streamed from L2 through an LDS ring by loader waves (conv_seam3.hip); reached
 // through conv_c3c1_admissible / conv_c3c1_launch like the register-stationary forms
 bool conv_seam3_admissible(const ConvArgs& a);
@@ -113,7 +140,7 @@ hipError_t conv_patch3x3w_pack(const uint16_t* w, uint16_t* out, int Cout, int C
 bool conv_patch3x3s2_admissible(const ConvArgs& a);   // conv_patchs2.hip: 3x3 stride 2
 hipError_t conv_patch3x3s2_launch(const ConvArgs& a, int dtype, hipStream_t stream);
 hipError_t conv_patch3x3s2_pack(const uint16_t* w, uint16_t* out, int Cout, int Cin, hipStream_t stream);   // same size as w
-bool conv_patch3x3_admissible(const ConvArgs& a);
+bool conv_patch3x3_admissible(const ConvArgs& a);     // conv_patch.hip: Cin == Cout == 64 or 128
 hipError_t conv_patch3x3_launch(const ConvArgs& a, int dtype, hipStream_t stream);
 
 // Paired-fp16 convolution (conv_pair.hip): three fp16 MFMAs per product term (wh.xh + wh.xl + wl.xh) into one fp32

@@ -26,6 +26,7 @@
 //   epilogue stages them through LDS (fp32) and emits whole 16-byte runs (8 channels) with
 //   residual add / ReLU / v_cvt_pk conversion fused.  Residual tiles are fetched before the K loop.
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 #include <stdlib.h>
@@ -33,21 +34,6 @@
 #include <algorithm>
 
 namespace dir {
-
-// voffset beyond any descriptor (tensors are < 2^31 bytes): the DMA writes zeros.  2^31 cannot wrap
-// in 32 bits when the scalar K offset is added, whichever way the bounds check treats soffset.
-static constexpr uint32_t kOOB = 0x80000000u;
-
-// 16 bytes per lane, global/L2 -> LDS at (wave-uniform `lds`) + lane * 16; `soff` rides in an SGPR.
-// (Kept in a __device__ function: used directly inside the kernel template's lambda, hipcc 7.2
-// silently drops the kernel's host stub.)
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds, uint32_t voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DIR_LDS void*)lds, 16, voff, soff, 0, 0);
-}
-
-__device__ inline uint32_t fast_div(uint32_t n, uint32_t mul, uint32_t shr) {
-    return mul ? (__umulhi(n, mul) >> shr) : n;  // mul == 0 encodes division by 1
-}
 
 // SPLITK instantiations (a few small-tile variants) carry the split-K bookkeeping; the others compile
 // exactly as if it did not exist - its extra scalar state costs 8-70 VGPRs in the big tiles.
@@ -90,10 +76,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_kernel(const ConvAr
     const int tile_n = wg % a.tiles_n;   // n fastest: blocks sharing an X tile run on one XCD
     const int tile_m = wg / a.tiles_n;
 
-    const __amdgpu_buffer_rsrc_t rsrc_x =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, a.w_bytes);
 
     // ---- per-lane source offsets (constant over the K loop) --------------------------------------
     // chunk slot `tid % CPR` of LDS row `tid / CPR (+ i*NT/CPR)` holds source chunk slot ^ swz(row):
@@ -337,9 +321,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_kernel(const ConvAr
                 const int n_local = i * 32 + 8 * g + 4 * lhi;
                 *(f32x4_t*)(ebase + lrow * EROW + n_local * 4) = v;
             }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
 #pragma unroll
         for (int pass = 0; pass < NPASS; ++pass) {
             const int mrow = pass * RPP + erow;
@@ -375,28 +357,12 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_kernel(const ConvAr
                 ovf.see(ov);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
     ovf.flush(a.ovf);
 }
 
 // ---- variant table ----------------------------------------------------------------------------
-static void fastdiv_init(uint32_t d, uint32_t& mul, uint32_t& shr) {
-    // q = umulhi(n, mul) >> shr is exact for 0 <= n < 2^31 (mul = ceil(2^(31+l) / d), l = ceil(log2 d))
-    if (d <= 1) {
-        mul = 0;
-        shr = 0;
-        return;
-    }
-    uint32_t l = 0;
-    while ((1ull << l) < d) ++l;
-    const uint32_t p = 31 + l;
-    mul = (uint32_t)(((1ull << p) + d - 1) / d);
-    shr = p - 32;
-}
-
 template <class DT, int BM, int BN, int WGM, int WGN, int NST, int BK, bool CIN16, bool SPLITK = false>
 static hipError_t launch_variant(const ConvArgs& a, hipStream_t stream) {
     constexpr int NT = 64 * WGM * WGN;
@@ -413,11 +379,8 @@ static hipError_t launch_variant(const ConvArgs& a, hipStream_t stream) {
     b.T = a.Ktot / BK;
     b.tiles_m = ceil_div(a.M, BM);
     b.tiles_n = a.Cout / BN;
-    b.x_bytes = (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 2);
-    b.w_bytes = (uint32_t)((size_t)a.Cout * a.Ktot * 2);
+    conv_fill_extents(b);
     b.flat = (a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0 && a.H == a.OH && a.W == a.OW);
-    fastdiv_init((uint32_t)(a.OH * a.OW), b.div_ohw_mul, b.div_ohw_shr);
-    fastdiv_init((uint32_t)a.OW, b.div_ow_mul, b.div_ow_shr);
     // a short K loop never touches the far slots of the ring: ask for less LDS, more residency
     const int used = (b.T < NST ? b.T : NST) * STAGE_BYTES;
     const int lds = used > EPI_BYTES ? used : EPI_BYTES;
@@ -426,26 +389,41 @@ static hipError_t launch_variant(const ConvArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-#define DIR_VARIANT(BM, BN, WGM, WGN, NST, BK, NAME)                                         \
-    {NAME, BM, BN, 64 * WGM * WGN, NST, BK,                                                  \
-     {launch_variant<BF16, BM, BN, WGM, WGN, NST, BK, false>,                                \
-      launch_variant<FP16, BM, BN, WGM, WGN, NST, BK, false>},                               \
-     {nullptr, nullptr}, 0, {nullptr, nullptr}, {nullptr, nullptr}}
+// What an implicit-GEMM row launches: the instantiation for the dtype, or - where the row has them - its Cin == 16 form (the
+// space-to-depth stem) or its split-K form (ConvArgs::ksplit > 1; conv_launch refuses that on a row without one).
+// (The forms are named in the order plain, Cin == 16, split-K: the order their kernels are instantiated and emitted in.)
+template <int BM, int BN, int WGM, int WGN, int NST, int BK, bool HAS16, bool HASSK>
+static hipError_t launch_igemm(const ConvArgs& a, int dtype, hipStream_t stream) {
+    const bool bf = dtype == DIR_BF16;
+    hipError_t (*fn)(const ConvArgs&, hipStream_t) = bf ? launch_variant<BF16, BM, BN, WGM, WGN, NST, BK, false>
+                                                        : launch_variant<FP16, BM, BN, WGM, WGN, NST, BK, false>;
+    if constexpr (HAS16)
+        if (a.Cin == 16) fn = bf ? launch_variant<BF16, BM, BN, WGM, WGN, NST, BK, true> : launch_variant<FP16, BM, BN, WGM, WGN, NST, BK, true>;
+    if constexpr (HASSK)
+        if (a.ksplit > 1) fn = bf ? launch_variant<BF16, BM, BN, WGM, WGN, NST, BK, false, true> : launch_variant<FP16, BM, BN, WGM, WGN, NST, BK, false, true>;
+    return fn(a, stream);
+}
+template <int BN, bool HAS16>
+static bool igemm_admissible(const ConvArgs& a) {
+    return a.Cout % BN == 0 && (HAS16 || a.Cin != 16);
+}
+// conv_patch.hip's one-tile-of-Cout kernel: a row per channel count
+template <int C>
+static bool patch3x3_admissible(const ConvArgs& a) {
+    return a.Cout == C && conv_patch3x3_admissible(a);
+}
+
+#define DIR_IGEMM_ROW(BM, BN, WGM, WGN, NST, BK, HAS16, HASSK, NAME)                         \
+    {NAME, BM, BN, 64 * WGM * WGN, NST, BK, igemm_admissible<BN, HAS16>,                     \
+     launch_igemm<BM, BN, WGM, WGN, NST, BK, HAS16, HASSK>, HASSK, nullptr, nullptr}
+#define DIR_VARIANT(BM, BN, WGM, WGN, NST, BK, NAME) DIR_IGEMM_ROW(BM, BN, WGM, WGN, NST, BK, false, false, NAME)
 // ... plus the split-K instantiation (small-M layers)
-#define DIR_VARIANT_SK(BM, BN, WGM, WGN, NST, BK, NAME)                                      \
-    {NAME, BM, BN, 64 * WGM * WGN, NST, BK,                                                  \
-     {launch_variant<BF16, BM, BN, WGM, WGN, NST, BK, false>,                                \
-      launch_variant<FP16, BM, BN, WGM, WGN, NST, BK, false>},                               \
-     {nullptr, nullptr}, 0,                                                                  \
-     {launch_variant<BF16, BM, BN, WGM, WGN, NST, BK, false, true>,                          \
-      launch_variant<FP16, BM, BN, WGM, WGN, NST, BK, false, true>}, {nullptr, nullptr}}
+#define DIR_VARIANT_SK(BM, BN, WGM, WGN, NST, BK, NAME) DIR_IGEMM_ROW(BM, BN, WGM, WGN, NST, BK, false, true, NAME)
 // BN == 64 variants also carry the Cin == 16 (space-to-depth stem) instantiation.
-#define DIR_VARIANT16(BM, BN, WGM, WGN, NST, NAME)                                           \
-    {NAME, BM, BN, 64 * WGM * WGN, NST, 64,                                                  \
-     {launch_variant<BF16, BM, BN, WGM, WGN, NST, 64, false>,                                \
-      launch_variant<FP16, BM, BN, WGM, WGN, NST, 64, false>},                               \
-     {launch_variant<BF16, BM, BN, WGM, WGN, NST, 64, true>,                                 \
-      launch_variant<FP16, BM, BN, WGM, WGN, NST, 64, true>}, 0, {nullptr, nullptr}, {nullptr, nullptr}}
+#define DIR_VARIANT16(BM, BN, WGM, WGN, NST, NAME) DIR_IGEMM_ROW(BM, BN, WGM, WGN, NST, 64, true, false, NAME)
+// a row bound to another source's kernel: {admissible, launch} and, where it has a two-source form, the same pair for it
+#define DIR_ROW(NAME, BM, BN, THREADS, NST, BK, ADM, LAUNCH) {NAME, BM, BN, THREADS, NST, BK, ADM, LAUNCH, false, nullptr, nullptr}
+#define DIR_ROW_DUAL(NAME, BM, BN, THREADS, NST, BK, ADM, LAUNCH, ADM2, LAUNCH2) {NAME, BM, BN, THREADS, NST, BK, ADM, LAUNCH, false, ADM2, LAUNCH2}
 
 // name = <pixels>x<channels>_w<waves m>x<waves n>[_s<ring depth>][_k<K-step>]
 static const ConvVariant kVariants[] = {
@@ -483,43 +461,42 @@ static const ConvVariant kVariants[] = {
     DIR_VARIANT_SK(64, 64, 2, 2, 8, 64, "64x64_w2x2_s8"),
     DIR_VARIANT_SK(64, 64, 2, 2, 4, 64, "64x64_w2x2_s4"),
     // 3x3 stride-1 from an LDS-resident input patch (conv_patch.hip): 8x32 pixels x all channels
-    {"256x64_patch3x3", 256, 64, 256, 3, 64, {nullptr, nullptr}, {nullptr, nullptr}, 1, {nullptr, nullptr}, {nullptr, nullptr}},
-    {"256x128_patch3x3", 256, 128, 512, 3, 64, {nullptr, nullptr}, {nullptr, nullptr}, 1, {nullptr, nullptr}, {nullptr, nullptr}},
+    DIR_ROW("256x64_patch3x3", 256, 64, 256, 3, 64, patch3x3_admissible<64>, conv_patch3x3_launch),
+    DIR_ROW("256x128_patch3x3", 256, 128, 512, 3, 64, patch3x3_admissible<128>, conv_patch3x3_launch),
     // ... 64 -> 64 channels without a residual: the whole filter resident in LDS, double-buffered patches, loader waves
     // fetch while consumer waves multiply (conv_patchlc.hip)
-    {"256x64_patchlc3x3", 256, 64, 512, 2, 64, {nullptr, nullptr}, {nullptr, nullptr}, 8, {nullptr, nullptr}, {nullptr, nullptr}},
+    DIR_ROW("256x64_patchlc3x3", 256, 64, 512, 2, 64, conv_patch64_lc_admissible, conv_patch64_lc_launch),
     // ... for the wide 3x3 layers (256 / 512 channels): the patch one 64-channel plane at a time, Cout tiled by 256
-    {"256x256_patch3x3s", 256, 256, 512, 2, 64, {nullptr, nullptr}, {nullptr, nullptr}, 5, {nullptr, nullptr}, {nullptr, nullptr}},
+    DIR_ROW("256x256_patch3x3s", 256, 256, 512, 2, 64, conv_patch3x3s_admissible, conv_patch3x3s_launch),
     // ... 512 pixels x 128 channels per workgroup, 32-channel planes double-buffered, one filter row per weight stage
-    {"512x128_patch3x3w", 512, 128, 512, 3, 32, {nullptr, nullptr}, {nullptr, nullptr}, 6, {nullptr, nullptr}, {nullptr, nullptr}},
+    DIR_ROW("512x128_patch3x3w", 512, 128, 512, 3, 32, conv_patch3x3w_admissible, conv_patch3x3w_launch),
     // 3x3 STRIDE 2 (conv2 of the first block of layers 2-4): persistent, 8 x 32 output pixels x 128 channels from a 17 x 65 patch,
     // 32-channel planes double-buffered with even / odd input columns apart, weights straight into registers (conv_patchs2.hip)
-    {"256x128_patchs2", 256, 128, 768, 2, 32, {nullptr, nullptr}, {nullptr, nullptr}, 12, {nullptr, nullptr}, {nullptr, nullptr}},
+    DIR_ROW("256x128_patchs2", 256, 128, 768, 2, 32, conv_patch3x3s2_admissible, conv_patch3x3s2_launch),
     // persistent workgroups, next tile's first K-stage issued before the epilogue (conv_persist.hip)
-    {"256x256_persist1x1", 256, 256, 512, 2, 64, {nullptr, nullptr}, {nullptr, nullptr}, 2, {nullptr, nullptr}, {nullptr, nullptr}},
+    DIR_ROW("256x256_persist1x1", 256, 256, 512, 2, 64, conv1x1_persist_admissible, conv1x1_persist_launch),
     // the same with three K-steps of the pixel operand in the ring (HBM requests in flight: 32 -> 64+ KB per CU)
     // ... and its two-source form (conv3 + downsample of the first block of layers 2-4)
-    {"256x256_persist1x1_x3", 256, 256, 512, 3, 64, {nullptr, nullptr}, {nullptr, nullptr}, 4, {nullptr, nullptr},
-     {conv1x1_persist_dual_bf16, conv1x1_persist_dual_fp16}},
+    DIR_ROW_DUAL("256x256_persist1x1_x3", 256, 256, 512, 3, 64, conv1x1_persist_x3_admissible, conv1x1_persist_x3_launch,
+                 conv1x1_persist_dual_admissible, conv1x1_persist_dual_launch),
     // persistent 128x256 tile, loader waves feed ONE three-slot K ring over all the tiles of a workgroup, consumer waves
     // multiply; 1x1 convs without a residual (conv_ring.hip)
 #ifdef DIR_EXPERIMENTS   // (csrc/build.sh with DIR_EXPERIMENTS=1: ties conv_persist.hip inside the network, not a default build's kernel)
-    {"128x256_ring1x1", 128, 256, 512, 3, 64, {nullptr, nullptr}, {nullptr, nullptr}, 7, {nullptr, nullptr}, {nullptr, nullptr}},
+    DIR_ROW("128x256_ring1x1", 128, 256, 512, 3, 64, conv1x1_ring_admissible, conv1x1_ring_launch),
 #endif
     // persistent, 64 output channels x K <= 256 per wave held in VGPRs, only pixels stream (conv_wreg.hip)
-    {"64x512_wreg1x1", 64, 512, 512, 2, 64, {nullptr, nullptr}, {nullptr, nullptr}, 3, {nullptr, nullptr}, {nullptr, nullptr}},
+    DIR_ROW("64x512_wreg1x1", 64, 512, 512, 2, 64, conv1x1_wreg_admissible, conv1x1_wreg_launch),
     // small maps (batch 1 at native size): 64 x 64 tiles, four consumer + four loader waves that meet on LDS counters, no workgroup
     // barrier in the loop (conv_small.hip); _s4 = 64 KB (two workgroups per CU), _s8 = 128 KB
-    {"64x64_small_s8", 64, 64, 512, 8, 64, {nullptr, nullptr}, {nullptr, nullptr}, 11, {nullptr, nullptr}, {nullptr, nullptr}},
-    {"64x64_small_s4", 64, 64, 512, 4, 64, {nullptr, nullptr}, {nullptr, nullptr}, 11, {nullptr, nullptr}, {nullptr, nullptr}},
-    {"64x64_small_s4k2", 64, 64, 512, 5, 64, {nullptr, nullptr}, {nullptr, nullptr}, 11, {nullptr, nullptr}, {nullptr, nullptr}},   // 4 slots x 2 K-steps per stage
+    DIR_ROW("64x64_small_s8", 64, 64, 512, 8, 64, conv_small_admissible, conv_small_s8_launch),
+    DIR_ROW("64x64_small_s4", 64, 64, 512, 4, 64, conv_small_admissible, conv_small_s4_launch),
+    DIR_ROW("64x64_small_s4k2", 64, 64, 512, 4, 64, conv_small_k2_admissible, conv_small_s4k2_launch),   // 4 slots x 2 K-steps per stage
     // the deep-X ring with loader / consumer wave roles (eight consumers, four loaders): 1x1 without a residual, and its two-source form
-    {"256x256_lc1x1", 256, 256, 768, 3, 64, {nullptr, nullptr}, {nullptr, nullptr}, 10, {nullptr, nullptr},
-     {conv1x1_lc_dual_bf16, conv1x1_lc_dual_fp16}},
+    DIR_ROW_DUAL("256x256_lc1x1", 256, 256, 768, 3, 64, conv1x1_lc_plain_admissible, conv1x1_lc_launch,
+                 conv1x1_lc_admissible, conv1x1_lc_dual_launch),
     // the two-source GEMM of layer2's first block (K = 128 + 256) with 32 output channels x 384 inputs per wave held in VGPRs,
-    // 256 channels per workgroup (conv_wregd.hip); a launch_dual-only entry
-    {"64x256_wregd1x1", 64, 256, 512, 2, 64, {nullptr, nullptr}, {nullptr, nullptr}, 9, {nullptr, nullptr},
-     {conv1x1_wregd_bf16, conv1x1_wregd_fp16}},
+    // 256 channels per workgroup (conv_wregd.hip); a two-source-only row: never admissible for a plain conv
+    DIR_ROW_DUAL("64x256_wregd1x1", 64, 256, 512, 2, 64, nullptr, nullptr, conv1x1_wregd_admissible, conv1x1_wregd_launch),
 };
 static constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 
@@ -527,25 +504,7 @@ int conv_variant_count() { return kNumVariants; }
 const ConvVariant& conv_variant(int i) { return kVariants[i]; }
 
 bool conv_variant_admissible(int v, const ConvArgs& a) {
-    if (v < 0 || v >= kNumVariants) return false;
-    const ConvVariant& cv = kVariants[v];
-    if (cv.kind == 1) return a.Cout == cv.BN && conv_patch3x3_admissible(a);
-    if (cv.kind == 5) return conv_patch3x3s_admissible(a);
-    if (cv.kind == 6) return conv_patch3x3w_admissible(a);
-    if (cv.kind == 2) return conv1x1_persist_admissible(a);
-    if (cv.kind == 4) return conv1x1_persist_admissible(a) && a.res == nullptr;   // the deep-X form has no residual path
-    if (cv.kind == 3) return conv1x1_wreg_admissible(a);
-#ifdef DIR_EXPERIMENTS
-    if (cv.kind == 7) return conv1x1_ring_admissible(a);
-#endif
-    if (cv.kind == 8) return conv_patch64_lc_admissible(a);
-    if (cv.kind == 12) return conv_patch3x3s2_admissible(a);
-    if (cv.kind == 11) return conv_small_admissible(a) && (cv.stages != 5 || (a.Ktot / 64) % 2 == 0);
-    if (cv.kind == 10) return a.x2 == nullptr && conv1x1_lc_admissible(a);
-    if (cv.kind == 9) return conv1x1_wregd_admissible(a);   // (two-source shapes only: never true for a plain conv)
-    if (a.Cout % cv.BN != 0) return false;
-    if (a.Cin == 16 && cv.launch16[0] == nullptr) return false;
-    return true;
+    return v >= 0 && v < kNumVariants && kVariants[v].admissible != nullptr && kVariants[v].admissible(a);
 }
 
 int conv_splitk_factor(int v, const ConvArgs& a);
@@ -586,7 +545,7 @@ int conv_pick_variant(const ConvArgs& a) {
             return v;
     }
     for (int v = 0; v < kNumVariants; ++v)
-        if (kVariants[v].kind == 1 && a.Cin == 64 && conv_variant_admissible(v, a)) return v;
+        if (kVariants[v].launch == conv_patch3x3_launch && a.Cin == 64 && conv_variant_admissible(v, a)) return v;
     // the residual 1x1 convs with K <= 256 (layer2/3 conv3): weights stationary in registers, as long
     // as every persistent workgroup gets at least ~4 pixel tiles to amortise loading them
     {
@@ -723,7 +682,7 @@ int conv_pick_variant(const ConvArgs& a) {
     }
     // nothing fills the chip: the smallest tile, unless it is the split-K fallback of a list whose
     // deep-ring sibling still gets ~100 workgroups
-    if (prev >= 0 && last >= 0 && kVariants[last].launch_sk[0] != nullptr &&
+    if (prev >= 0 && last >= 0 && kVariants[last].has_splitk &&
         strcmp(kVariants[prev].name, "64x128_w2x2_s4") == 0 &&
         (long)ceil_div(a.M, 64) * (a.Cout / 128) >= 96)
         return prev;
@@ -756,7 +715,7 @@ int conv_pick_dual_variant(const ConvArgs& a, bool any_size) {
         if (vl >= 0 && conv1x1_lc_admissible(a)) return vl;
     }
     const int v = find_variant("256x256_persist1x1_x3");
-    if (v < 0 || kVariants[v].launch_dual[0] == nullptr) return -1;
+    if (v < 0 || kVariants[v].launch_dual == nullptr) return -1;
     return v;
 }
 
@@ -791,13 +750,8 @@ __global__ void conv_splitk_finalize_kernel(const float* __restrict__ partial, c
             v[2 * e + 1] += hi;
         }
     }
-    if (relu) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-    }
-    u32x4_t ov;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ov[e] = DT::pack(v[2 * e], v[2 * e + 1]);
+    if (relu) relu8(v);
+    const u32x4_t ov = pack8<DT>(v);
     gstore16(y + o, ov);
     Ovf<DT> ovf;
     ovf.see(ov);
@@ -812,7 +766,7 @@ size_t conv_splitk_bytes(const ConvArgs& a, int ksplit) {
 // is cut into slices that run as separate workgroups.  Only the implicit-GEMM variants split, only
 // when each slice keeps >= 4 K-steps, and only within the scratch the engine reserves.
 int conv_splitk_factor(int v, const ConvArgs& a) {
-    if (v < 0 || v >= kNumVariants || kVariants[v].launch_sk[0] == nullptr || a.Cin == 16) return 1;
+    if (v < 0 || v >= kNumVariants || !kVariants[v].has_splitk || a.Cin == 16) return 1;
     const ConvVariant& cv = kVariants[v];
     const long tiles = (long)ceil_div(a.M, cv.BM) * (a.Cout / cv.BN);
     const int T = a.Ktot / cv.BK;
@@ -841,12 +795,12 @@ int conv_launch(const ConvArgs& a, int dtype, int variant, hipStream_t stream) {
     if (dtype != DIR_BF16 && dtype != DIR_FP16) return fail(DIR_ERR_INVALID, "conv: bad dtype");
     if (a.x2) {   // two-source K: conv3 + downsample in one GEMM
         if (variant < 0) variant = conv_pick_dual_variant(a);
-        if (variant < 0 || variant >= kNumVariants || kVariants[variant].launch_dual[0] == nullptr ||
-            a.Cout % kVariants[variant].BN != 0 || (kVariants[variant].kind == 9 && !conv1x1_wregd_admissible(a)) || (kVariants[variant].kind == 10 && !conv1x1_lc_admissible(a)) || a.R != 1 || a.S != 1 || a.stride != 1 || a.res || a.ksplit > 1 ||
+        if (variant < 0 || variant >= kNumVariants || kVariants[variant].launch_dual == nullptr ||
+            !kVariants[variant].admissible_dual(a) || a.R != 1 || a.S != 1 || a.stride != 1 || a.res || a.ksplit > 1 ||
             a.Cin2 % 64 != 0 || a.Ktot != a.Cin + a.Cin2 || ((uintptr_t)a.x2 & 15) ||
             (long)a.B * a.H2 * a.W2 * a.Cin2 >= (1L << 30))
             return fail(DIR_ERR_INVALID, "conv: no two-source form for this shape / variant");
-        hipError_t e = kVariants[variant].launch_dual[dtype](a, stream);
+        hipError_t e = kVariants[variant].launch_dual(a, dtype, stream);
         if (e != hipSuccess)
             return fail(DIR_ERR_HIP, std::string("conv launch ") + kVariants[variant].name + "/dual: " + hipGetErrorString(e));
         return DIR_OK;
@@ -856,27 +810,13 @@ int conv_launch(const ConvArgs& a, int dtype, int variant, hipStream_t stream) {
         return fail(DIR_ERR_INVALID, "conv: variant not admissible for this shape");
     const ConvVariant& cv = kVariants[variant];
     if (a.ksplit > 1) {
-        if (cv.launch_sk[0] == nullptr || cin16)
+        if (!cv.has_splitk || cin16)
             return fail(DIR_ERR_INVALID, "conv: this variant has no split-K form");
         if (!a.partial || ((uintptr_t)a.partial & 15))
             return fail(DIR_ERR_INVALID, "conv: split-K needs a 16-byte aligned fp32 scratch buffer");
         if (a.ksplit > a.Ktot / cv.BK) return fail(DIR_ERR_INVALID, "conv: more K slices than K-steps");
     }
-    hipError_t e = cv.kind == 1   ? conv_patch3x3_launch(a, dtype, stream)
-                   : cv.kind == 5 ? conv_patch3x3s_launch(a, dtype, stream)
-                   : cv.kind == 6 ? conv_patch3x3w_launch(a, dtype, stream)
-                   : cv.kind == 2 ? conv1x1_persist_launch(a, dtype, stream)
-                   : cv.kind == 4 ? conv1x1_persist_launch(a, dtype, stream, true)
-                   : cv.kind == 3 ? conv1x1_wreg_launch(a, dtype, stream)
-#ifdef DIR_EXPERIMENTS
-                   : cv.kind == 7 ? conv1x1_ring_launch(a, dtype, stream)
-#endif
-                   : cv.kind == 8 ? conv_patch64_lc_launch(a, dtype, stream)
-                   : cv.kind == 12 ? conv_patch3x3s2_launch(a, dtype, stream)
-                   : cv.kind == 10 ? conv1x1_lc_launch(a, dtype, stream)
-                   : cv.kind == 11 ? conv_small_launch(a, dtype, cv.stages, stream)
-                   : a.ksplit > 1 ? cv.launch_sk[dtype](a, stream)
-                                  : (cin16 ? cv.launch16 : cv.launch)[dtype](a, stream);
+    hipError_t e = cv.launch(a, dtype, stream);
     if (e != hipSuccess)
         return fail(DIR_ERR_HIP, std::string("conv launch ") + cv.name + ": " + hipGetErrorString(e));
     if (a.ksplit > 1) {

@@ -18,6 +18,7 @@
 // Structure (LDS-DMA through buffer descriptors, XOR-swizzled rows, swapped MFMA roles, bias-initialised accumulators,
 // fp32 LDS staging for 16-byte stores) is conv_igemm.hip's; only what the pairs change is new.
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 #include "pointwise.h"
 
@@ -28,15 +29,6 @@
 #endif
 
 namespace dir {
-
-static constexpr uint32_t kOOBp = 0x80000000u;
-
-__device__ __forceinline__ void dma16p(__amdgpu_buffer_rsrc_t rsrc, char* lds, uint32_t voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DIR_LDS void*)lds, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ uint32_t fast_div_p(uint32_t n, uint32_t mul, uint32_t shr) {
-    return mul ? (__umulhi(n, mul) >> shr) : n;
-}
 
 // fp32 pair (a, b) -> packed hi word and packed lo word: hi = fp16(v), lo = fp16(v - hi)
 __device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
@@ -82,14 +74,12 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_pair_kernel(const ConvArg
     const int tile_n = wg % a.tiles_n;   // n fastest: the channel tiles of one pixel tile share an XCD's L2
     const int tile_m = wg / a.tiles_n;
 
-    const __amdgpu_buffer_rsrc_t rsrc_xh = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_xl =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(XP ? a.x_lo : a.x), 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_wh = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_wl = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_lo, 0, a.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_x2h = __builtin_amdgcn_make_buffer_rsrc((void*)(DUAL ? a.x2 : a.x), 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_x2l =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(DUAL && XP ? a.x2_lo : a.x), 0, a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_xh = buffer_rsrc(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_xl = buffer_rsrc(XP ? a.x_lo : a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_wh = buffer_rsrc(a.w, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_wl = buffer_rsrc(a.w_lo, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_x2h = buffer_rsrc(DUAL ? a.x2 : a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_x2l = buffer_rsrc(DUAL && XP ? a.x2_lo : a.x, a.x_bytes);
 
     // per-lane source offsets: chunk slot tid % 4 of LDS row tid / 4 (+ i * NT/4) holds source chunk slot ^ swz(row)
     const int srcchunk = (tid & 3) ^ ((tid >> 4) & 3);
@@ -106,9 +96,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_pair_kernel(const ConvArg
             xmask[i] = mvalid ? 1u : 0u;
         } else {
             const uint32_t mm = mvalid ? (uint32_t)m : 0u;
-            const uint32_t b = fast_div_p(mm, a.div_ohw_mul, a.div_ohw_shr);
+            const uint32_t b = fast_div(mm, a.div_ohw_mul, a.div_ohw_shr);
             const uint32_t rem = mm - b * (uint32_t)(a.OH * a.OW);
-            const uint32_t oh = fast_div_p(rem, a.div_ow_mul, a.div_ow_shr);
+            const uint32_t oh = fast_div(rem, a.div_ow_mul, a.div_ow_shr);
             const uint32_t ow = rem - oh * (uint32_t)a.OW;
             const int ih0 = (int)oh * a.stride - a.pad;
             const int iw0 = (int)ow * a.stride - a.pad;
@@ -135,21 +125,21 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_pair_kernel(const ConvArg
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             char* dst = stage + (i * NT + wave * 64) * 16;
-            const uint32_t v = ((xmask[i] >> tap) & 1u) ? (uint32_t)(xbase[i] + (one_tap ? 0 : koff)) : kOOBp;
+            const uint32_t v = ((xmask[i] >> tap) & 1u) ? (uint32_t)(xbase[i] + (one_tap ? 0 : koff)) : kOOB;
             const int so = one_tap ? koff : 0;   // 1x1: the K-step rides in the scalar offset
             if (DUAL && second) {                // same pixel, same width: only the tensor differs
-                dma16p(rsrc_x2h, dst, v, so);
-                if (XP) dma16p(rsrc_x2l, dst + XS, v, so);
+                dma16(rsrc_x2h, dst, v, so);
+                if (XP) dma16(rsrc_x2l, dst + XS, v, so);
             } else {
-                dma16p(rsrc_xh, dst, v, so);
-                if (XP) dma16p(rsrc_xl, dst + XS, v, so);
+                dma16(rsrc_xh, dst, v, so);
+                if (XP) dma16(rsrc_xl, dst + XS, v, so);
             }
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             char* dst = stage + WOFF + (i * NT + wave * 64) * 16;
-            dma16p(rsrc_wh, dst, wvoff[i], wstep * RB);
-            dma16p(rsrc_wl, dst + WS, wvoff[i], wstep * RB);
+            dma16(rsrc_wh, dst, wvoff[i], wstep * RB);
+            dma16(rsrc_wl, dst + WS, wvoff[i], wstep * RB);
         }
     };
 
@@ -262,9 +252,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_pair_kernel(const ConvArg
                 f32x4_t v = {acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
                 *(f32x4_t*)(ebase + lrow * EROW + (i * 32 + 8 * g + 4 * lhi) * 4) = v;
             }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
 #pragma unroll
         for (int pass = 0; pass < NPASS; ++pass) {
             const int mrow = pass * RPP + erow;
@@ -276,28 +264,13 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_pair_kernel(const ConvArg
                 const size_t o = (size_t)m * a.Cout + n_glob;
                 if (a.res) {
                     const u32x4_t rh = rres_h[j][pass];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float lo, hi;
-                        DT::unpack(rh[e], lo, hi);
-                        v[2 * e] += lo;
-                        v[2 * e + 1] += hi;
-                    }
+                    add_res8<DT>(v, rh);
                     if (a.res_lo) {
                         const u32x4_t rl = rres_l[j][pass];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            float lo, hi;
-                            DT::unpack(rl[e], lo, hi);
-                            v[2 * e] += lo;
-                            v[2 * e + 1] += hi;
-                        }
+                        add_res8<DT>(v, rl);
                     }
                 }
-                if (a.relu) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
+                if (a.relu) relu8(v);
                 u32x4_t oh, ol;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -311,9 +284,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_pair_kernel(const ConvArg
                 ovf.see(oh);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
     ovf.flush(a.ovf);
 }
@@ -355,10 +326,10 @@ __global__ void __launch_bounds__(256, 2) conv_pair_patch64_kernel(const ConvArg
     const int b = wg / tiles_y;
     const int oy0 = ty * TH, ox0 = tx * TW;
 
-    const __amdgpu_buffer_rsrc_t rsrc_xh = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_xl = __builtin_amdgcn_make_buffer_rsrc((void*)a.x_lo, 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_wh = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_wl = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_lo, 0, a.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_xh = buffer_rsrc(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_xl = buffer_rsrc(a.x_lo, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_wh = buffer_rsrc(a.w, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_wl = buffer_rsrc(a.w_lo, a.w_bytes);
 
     // ---- patch pair: PP pixels x 128 B per plane, chunks XOR-swizzled with (p >> 1) & 7, loaded once ----------------------
 #pragma unroll
@@ -368,9 +339,9 @@ __global__ void __launch_bounds__(256, 2) conv_pair_patch64_kernel(const ConvArg
         const int py = p / PW, px = p - py * PW;
         const int iy = oy0 - 1 + py, ix = ox0 - 1 + px;
         const bool ok = p < PP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-        const uint32_t v = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * C + ((slot ^ ((p >> 1) & 7)) << 3)) * 2) : kOOBp;
-        dma16p(rsrc_xh, smem + (i * NTH + wave * 64) * 16, v, 0);
-        dma16p(rsrc_xl, smem + PLANE_BYTES + (i * NTH + wave * 64) * 16, v, 0);
+        const uint32_t v = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * C + ((slot ^ ((p >> 1) & 7)) << 3)) * 2) : kOOB;
+        dma16(rsrc_xh, smem + (i * NTH + wave * 64) * 16, v, 0);
+        dma16(rsrc_xl, smem + PLANE_BYTES + (i * NTH + wave * 64) * 16, v, 0);
     }
     // ---- weights: step sigma = (tap, plane) -> the [64][64] slice of that tap from w_hi / w_lo -----------------------------
     const int srcchunk = (tid & 7) ^ ((tid >> 4) & 7);
@@ -383,9 +354,9 @@ __global__ void __launch_bounds__(256, 2) conv_pair_patch64_kernel(const ConvArg
         for (int i = 0; i < NBW; ++i) {
             char* dst = smem + WOFF + slot * WSTAGE + (i * NTH + wave * 64) * 16;
             if (sigma & 1) {
-                dma16p(rsrc_wl, dst, wvoff[i], tap * 128);
+                dma16(rsrc_wl, dst, wvoff[i], tap * 128);
             } else {
-                dma16p(rsrc_wh, dst, wvoff[i], tap * 128);
+                dma16(rsrc_wh, dst, wvoff[i], tap * 128);
             }
         }
     };
@@ -487,9 +458,7 @@ __global__ void __launch_bounds__(256, 2) conv_pair_patch64_kernel(const ConvArg
             f32x4_t v = {acc[i][4 * g + 0], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]};
             *(f32x4_t*)(ebase + lrow * EROW + (i * 32 + 8 * g + 4 * lhi) * 4) = v;
         }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const int oy = oy0 + wave;
 #pragma unroll
     for (int pass = 0; pass < NPASS; ++pass) {
@@ -499,10 +468,7 @@ __global__ void __launch_bounds__(256, 2) conv_pair_patch64_kernel(const ConvArg
         const int ox = ox0 + mrow;
         if (oy < a.OH && ox < a.OW) {
             float v[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
-            if (a.relu) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-            }
+            if (a.relu) relu8(v);
             u32x4_t oh, ol;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -530,23 +496,10 @@ static hipError_t launch_pair_patch64(const ConvArgs& a, hipStream_t stream) {
     static std::atomic<uint64_t> attr_done{0};
     if (hipError_t e = ensure_dynamic_lds((const void*)conv_pair_patch64_kernel, LDS, attr_done); e != hipSuccess) return e;
     ConvArgs b = a;
-    b.x_bytes = (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 2);
-    b.w_bytes = (uint32_t)((size_t)a.Cout * a.Ktot * 2);
+    conv_fill_extents(b);
     const long blocks = (long)a.B * ((a.OH + 3) / 4) * ((a.OW + 31) / 32);
     hipLaunchKernelGGL(conv_pair_patch64_kernel, dim3((unsigned)blocks), dim3(256), LDS, stream, b);
     return hipGetLastError();
-}
-
-static void fastdiv_init_p(uint32_t d, uint32_t& mul, uint32_t& shr) {
-    if (d <= 1) {
-        mul = 0;
-        shr = 0;
-        return;
-    }
-    uint32_t l = 0;
-    while ((1ull << l) < d) ++l;
-    mul = (uint32_t)(((1ull << (31 + l)) + d - 1) / d);
-    shr = l - 1;
 }
 
 template <int BM, int BN, int WGM, int WGN, bool XP, bool DUAL = false>
@@ -565,11 +518,8 @@ static hipError_t launch_pair(const ConvArgs& a, hipStream_t stream) {
     b.T = a.Ktot / 32;
     b.tiles_m = ceil_div(a.M, BM);
     b.tiles_n = a.Cout / BN;
-    b.x_bytes = (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 2);
-    b.w_bytes = (uint32_t)((size_t)a.Cout * a.Ktot * 2);
+    conv_fill_extents(b);
     b.flat = (a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0 && a.H == a.OH && a.W == a.OW);
-    fastdiv_init_p((uint32_t)(a.OH * a.OW), b.div_ohw_mul, b.div_ohw_shr);
-    fastdiv_init_p((uint32_t)a.OW, b.div_ow_mul, b.div_ow_shr);
     const int used = (b.T < 2 ? b.T : 2) * STAGE_BYTES;
     const int lds = used > EPI_BYTES ? used : EPI_BYTES;
     hipLaunchKernelGGL(kern, dim3(b.tiles_m * b.tiles_n), dim3(NT), lds, stream, b);
@@ -667,10 +617,10 @@ __global__ void __launch_bounds__(256) stem_pool_pair_kernel(const StemPairArgs 
     const int ph0 = ty * PTH, pw0 = tx * PTW;
     const int oy0 = 2 * ph0 - 1, ox0 = 2 * pw0 - 1;
 
-    const __amdgpu_buffer_rsrc_t rsrc_xh = __builtin_amdgcn_make_buffer_rsrc((void*)a.xh, 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_xl = __builtin_amdgcn_make_buffer_rsrc((void*)a.xl, 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_wh = __builtin_amdgcn_make_buffer_rsrc((void*)a.wh, 0, 64 * 256 * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_wl = __builtin_amdgcn_make_buffer_rsrc((void*)a.wl, 0, 64 * 256 * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_xh = buffer_rsrc(a.xh, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_xl = buffer_rsrc(a.xl, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_wh = buffer_rsrc(a.wh, 64 * 256 * 2);
+    const __amdgpu_buffer_rsrc_t rsrc_wl = buffer_rsrc(a.wl, 64 * 256 * 2);
 
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -679,9 +629,9 @@ __global__ void __launch_bounds__(256) stem_pool_pair_kernel(const StemPairArgs 
         const int py = p / QW, px = p - py * QW;
         const int iy = oy0 - 2 + py, ix = ox0 - 2 + px;
         const bool ok = p < QP && (unsigned)iy < (unsigned)a.H2 && (unsigned)ix < (unsigned)a.W2;
-        const uint32_t v = ok ? (uint32_t)((((b * a.H2 + iy) * a.W2 + ix) * 16 + plane * 8) * 2) : kOOBp;
-        dma16p(rsrc_xh, smem + (i * 256 + wave * 64) * 16, v, 0);
-        dma16p(rsrc_xl, smem + PATCH + (i * 256 + wave * 64) * 16, v, 0);
+        const uint32_t v = ok ? (uint32_t)((((b * a.H2 + iy) * a.W2 + ix) * 16 + plane * 8) * 2) : kOOB;
+        dma16(rsrc_xh, smem + (i * 256 + wave * 64) * 16, v, 0);
+        dma16(rsrc_xl, smem + PATCH + (i * 256 + wave * 64) * 16, v, 0);
     }
     const int srcchunk = (tid & 7) ^ ((tid >> 4) & 7);
 #pragma unroll
@@ -690,8 +640,8 @@ __global__ void __launch_bounds__(256) stem_pool_pair_kernel(const StemPairArgs 
         for (int i = 0; i < 2; ++i) {
             const int n = i * 32 + (tid >> 3);
             const uint32_t v = (uint32_t)((n * 256 + srcchunk * 8) * 2);
-            dma16p(rsrc_wh, smem + WOFF + R * 8192 + (i * 256 + wave * 64) * 16, v, R * 128);
-            dma16p(rsrc_wl, smem + WOFF + WBYTES + R * 8192 + (i * 256 + wave * 64) * 16, v, R * 128);
+            dma16(rsrc_wh, smem + WOFF + R * 8192 + (i * 256 + wave * 64) * 16, v, R * 128);
+            dma16(rsrc_wl, smem + WOFF + WBYTES + R * 8192 + (i * 256 + wave * 64) * 16, v, R * 128);
         }
 
     f32x16_t acc[2][2];
@@ -832,8 +782,8 @@ __global__ void __launch_bounds__(512) stem_pool_pair_persist_kernel(const StemP
     const int tiles_y = (a.PH + PTH - 1) / PTH;
     const int ntiles = a.B * tiles_y * tiles_x;
 
-    const __amdgpu_buffer_rsrc_t rsrc_xh = __builtin_amdgcn_make_buffer_rsrc((void*)a.xh, 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_xl = __builtin_amdgcn_make_buffer_rsrc((void*)a.xl, 0, a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_xh = buffer_rsrc(a.xh, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_xl = buffer_rsrc(a.xl, a.x_bytes);
 
     frag_t wfh[4][4], wfl[4][4];
 #pragma unroll
@@ -861,10 +811,10 @@ __global__ void __launch_bounds__(512) stem_pool_pair_persist_kernel(const StemP
             const int py = p / QW, px = p - py * QW;
             const int iy = oy0 - 2 + py, ix = ox0 - 2 + px;
             const bool ok = p < QP && (unsigned)iy < (unsigned)a.H2 && (unsigned)ix < (unsigned)a.W2;
-            const uint32_t v = ok ? (uint32_t)((((b * a.H2 + iy) * a.W2 + ix) * 16 + plane * 8) * 2) : kOOBp;
+            const uint32_t v = ok ? (uint32_t)((((b * a.H2 + iy) * a.W2 + ix) * 16 + plane * 8) * 2) : kOOB;
             if (DIR_STEMP_ABL & 4) continue;   // (experiment: no patch DMA)
-            dma16p(rsrc_xh, dst + (i * 512 + wave * 64) * 16, v, 0);
-            dma16p(rsrc_xl, dst + PATCH + (i * 512 + wave * 64) * 16, v, 0);
+            dma16(rsrc_xh, dst + (i * 512 + wave * 64) * 16, v, 0);
+            dma16(rsrc_xl, dst + PATCH + (i * 512 + wave * 64) * 16, v, 0);
         }
     };
 
@@ -1011,7 +961,7 @@ int stem_pool_pair_launch(const void* s2d_hi, const void* s2d_lo, const void* w_
     a.B = B; a.H2 = H2; a.W2 = W2; a.OH = OH; a.OW = OW;
     a.PH = (OH - 1) / 2 + 1;
     a.PW = (OW - 1) / 2 + 1;
-    a.x_bytes = (uint32_t)((size_t)B * H2 * W2 * 32);
+    a.x_bytes = (uint32_t)((size_t)B * H2 * W2 * 32);   // (its own extent: the space-to-depth plane [B][H2][W2][16], not a ConvArgs tensor)
     a.ovf = ovf;
     const long blocks = (long)B * ((a.PH + 2) / 3) * ((a.PW + 14) / 15);
     const bool v1 = env().stem_v1;   // A/B and bisecting (dir_reload_env after flipping it)

@@ -14,15 +14,10 @@
 // MFMA roles, bias-initialised accumulators and the LDS-staged 16-byte-store epilogue are those of
 // conv_igemm.hip; the weight layout [Cout][3][3][Cin] is shared with it.
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 namespace dir {
-
-static constexpr uint32_t kOOBp = 0x80000000u;
-
-__device__ __forceinline__ void dma16p(__amdgpu_buffer_rsrc_t rsrc, char* lds, uint32_t voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DIR_LDS void*)lds, 16, voff, soff, 0, 0);
-}
 
 // NTH = 256: four waves, each two output rows x all of Cout.  NTH = 512 (the 128-channel layers):
 // eight waves, the second four take the upper half of Cout - same LDS image, two waves per SIMD.
@@ -66,10 +61,8 @@ __global__ void __launch_bounds__(NTH) conv_patch3x3_kernel(const ConvArgs a) {
     const int b = wg / tiles_y;
     const int oy0 = ty * TH, ox0 = tx * TW;
 
-    const __amdgpu_buffer_rsrc_t rsrc_x =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, a.w_bytes);
 
     // ---- patch: PP pixels x KC planes, loaded once -----------------------------------------------
 #pragma unroll
@@ -82,10 +75,10 @@ __global__ void __launch_bounds__(NTH) conv_patch3x3_kernel(const ConvArgs a) {
         const bool ok = p < PP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
         const uint32_t v = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * CIN +
                                             ((slot ^ ((p >> 1) & 7)) << 3)) * 2)
-                              : kOOBp;
+                              : kOOB;
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc)
-            dma16p(rsrc_x, smem + kc * PLANE_BYTES + (i * NTH + wave * 64) * 16, v, kc * 128);
+            dma16(rsrc_x, smem + kc * PLANE_BYTES + (i * NTH + wave * 64) * 16, v, kc * 128);
     }
 
     // ---- weights: one [Cout][64] slice per K-step through an NSTW-slot ring ----------------------
@@ -97,7 +90,7 @@ __global__ void __launch_bounds__(NTH) conv_patch3x3_kernel(const ConvArgs a) {
     auto issue_w = [&](int t, int slot) {
 #pragma unroll
         for (int i = 0; i < NBW; ++i)
-            dma16p(rsrc_w, smem + WOFF + slot * WSTAGE + (i * NTH + wave * 64) * 16, wvoff[i], t * 128);
+            dma16(rsrc_w, smem + WOFF + slot * WSTAGE + (i * NTH + wave * 64) * 16, wvoff[i], t * 128);
     };
 
     // ---- accumulators start at the bias ------------------------------------------------------------
@@ -189,9 +182,7 @@ __global__ void __launch_bounds__(NTH) conv_patch3x3_kernel(const ConvArgs a) {
                              acc[i][j][4 * g + 3]};
                 *(f32x4_t*)(ebase + lrow * EROW + (i * 32 + 8 * g + 4 * lhi) * 4) = v;
             }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const int oy = oy0 + wrow * TMR + j;
 #pragma unroll
         for (int pass = 0; pass < NPASS; ++pass) {
@@ -212,20 +203,13 @@ __global__ void __launch_bounds__(NTH) conv_patch3x3_kernel(const ConvArgs a) {
                         v[2 * e + 1] += hi;
                     }
                 }
-                if (a.relu) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
-                u32x4_t ov;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) ov[e] = DT::pack(v[2 * e], v[2 * e + 1]);
+                if (a.relu) relu8(v);
+                const u32x4_t ov = pack8<DT>(v);
                 gstore16(a.y + o, ov);
                 ovf.see(ov);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
     ovf.flush(a.ovf);
 }
@@ -248,8 +232,7 @@ static hipError_t launch_patch(const ConvArgs& a, hipStream_t stream) {
     static std::atomic<uint64_t> attr_done{0};
     if (hipError_t e = ensure_dynamic_lds((const void*)kern, LDS, attr_done); e != hipSuccess) return e;
     ConvArgs b = a;
-    b.x_bytes = (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 2);
-    b.w_bytes = (uint32_t)((size_t)a.Cout * a.Ktot * 2);
+    conv_fill_extents(b);
     const long blocks = (long)a.B * ((a.OH + 7) / 8) * ((a.OW + 31) / 32);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NTH), LDS, stream, b);
     return hipGetLastError();
@@ -308,8 +291,8 @@ __global__ void __launch_bounds__(512) conv_patch3x3s_kernel(const ConvArgs a) {
     const int b = wg / tiles_y;
     const int oy0 = ty * TH, ox0 = tx * TW;
 
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, a.w_bytes);
 
     // patch: per-lane source offsets of plane 0 (plane kc adds kc * 128 bytes through the scalar offset)
     uint32_t pvoff[NPL];
@@ -320,11 +303,11 @@ __global__ void __launch_bounds__(512) conv_patch3x3s_kernel(const ConvArgs a) {
         const int py = p / PW, px = p - py * PW;
         const int iy = oy0 - 1 + py, ix = ox0 - 1 + px;
         const bool ok = p < PP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-        pvoff[i] = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * CIN + ((slot ^ ((p >> 1) & 7)) << 3)) * 2) : kOOBp;
+        pvoff[i] = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * CIN + ((slot ^ ((p >> 1) & 7)) << 3)) * 2) : kOOB;
     }
     auto issue_plane = [&](int kc) {
 #pragma unroll
-        for (int i = 0; i < NPL; ++i) dma16p(rsrc_x, smem + (i * NTH + wave * 64) * 16, pvoff[i], kc * 128);
+        for (int i = 0; i < NPL; ++i) dma16(rsrc_x, smem + (i * NTH + wave * 64) * 16, pvoff[i], kc * 128);
     };
     const int srcchunk = (tid & 7) ^ ((tid >> 4) & 7);
     uint32_t wvoff[NBW];
@@ -336,7 +319,7 @@ __global__ void __launch_bounds__(512) conv_patch3x3s_kernel(const ConvArgs a) {
         const int kcw = t / 9, tapw = t - kcw * 9;
 #pragma unroll
         for (int i = 0; i < NBW; ++i)
-            dma16p(rsrc_w, smem + WOFF + slot * WSTAGE + (i * NTH + wave * 64) * 16, wvoff[i], (tapw * KC + kcw) * 128);
+            dma16(rsrc_w, smem + WOFF + slot * WSTAGE + (i * NTH + wave * 64) * 16, wvoff[i], (tapw * KC + kcw) * 128);
     };
 
     f32x16_t acc[TN][TMR];
@@ -434,9 +417,7 @@ __global__ void __launch_bounds__(512) conv_patch3x3s_kernel(const ConvArgs a) {
                 f32x4_t v = {acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
                 *(f32x4_t*)(ebase + lrow * EROW + (i * 32 + 8 * g + 4 * lhi) * 4) = v;
             }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const int oy = oy0 + wrow * TMR + j;
 #pragma unroll
         for (int pass = 0; pass < NPASS; ++pass) {
@@ -457,20 +438,13 @@ __global__ void __launch_bounds__(512) conv_patch3x3s_kernel(const ConvArgs a) {
                         v[2 * e + 1] += hi;
                     }
                 }
-                if (a.relu) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
-                u32x4_t ov;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) ov[e] = DT::pack(v[2 * e], v[2 * e + 1]);
+                if (a.relu) relu8(v);
+                const u32x4_t ov = pack8<DT>(v);
                 gstore16(a.y + o, ov);
                 ovf.see(ov);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
     ovf.flush(a.ovf);
 }
@@ -488,8 +462,7 @@ static hipError_t launch_patch_s(const ConvArgs& a, hipStream_t stream) {
     static std::atomic<uint64_t> attr_done{0};
     if (hipError_t e = ensure_dynamic_lds((const void*)kern, LDS, attr_done); e != hipSuccess) return e;
     ConvArgs b = a;
-    b.x_bytes = (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 2);
-    b.w_bytes = (uint32_t)((size_t)a.Cout * a.Ktot * 2);
+    conv_fill_extents(b);
     const long blocks = (long)a.B * ((a.OH + 7) / 8) * ((a.OW + 31) / 32) * (a.Cout / 256);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), LDS, stream, b);
     return hipGetLastError();

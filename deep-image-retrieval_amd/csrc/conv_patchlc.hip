@@ -17,15 +17,10 @@
 // (A = weights, B = pixels), bias-initialised accumulators, tap and K order are those of conv_patch3x3_kernel: the
 // outputs are bit-identical to it.
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 namespace dir {
-
-static constexpr uint32_t kOOBl = 0x80000000u;
-
-__device__ __forceinline__ void dma16l(__amdgpu_buffer_rsrc_t rsrc, char* lds, uint32_t voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DIR_LDS void*)lds, 16, voff, 0, 0, 0);
-}
 
 template <class DT>
 __global__ void __launch_bounds__(512) conv_patch64_lc_kernel(const ConvArgs a) {
@@ -54,13 +49,13 @@ __global__ void __launch_bounds__(512) conv_patch64_lc_kernel(const ConvArgs a) 
 
     // ---- the filter, once: tap s = piece / 8, channels (piece % 8) * 8 .. + 7, 16-byte chunks swizzled with (n >> 1) & 7 ----
     {
-        const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.w_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, a.w_bytes);
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
             const int q = k * 8 + wave;           // 72 pieces over 8 waves
             const int s = q >> 3, n = (q & 7) * 8 + (lane >> 3);
             const int chunk = (lane & 7) ^ ((n >> 1) & 7);
-            dma16l(rsrc_w, smem + q * 1024, (uint32_t)(((n * 9 + s) * C + chunk * 8) * 2));
+            dma16(rsrc_w, smem + q * 1024, (uint32_t)(((n * 9 + s) * C + chunk * 8) * 2), 0);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ring_barrier();
@@ -73,7 +68,7 @@ __global__ void __launch_bounds__(512) conv_patch64_lc_kernel(const ConvArgs a) 
     if (wave >= 4) {
         // ================================ loaders ==============================================================
         const int lw = wave - 4;
-        const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
         // (always_inline: left as a call, the lambda takes the by-value argument struct by reference and parks it in scratch)
         auto issue = [&](int tile, int buf) __attribute__((always_inline)) {
             int t = tile;
@@ -92,8 +87,8 @@ __global__ void __launch_bounds__(512) conv_patch64_lc_kernel(const ConvArgs a) 
                     const int iy = oy0 - 1 + py, ix = ox0 - 1 + px;
                     const bool ok = p < PP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
                     const int chunk = (lane & 7) ^ ((p >> 1) & 7);
-                    const uint32_t v = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * C + chunk * 8) * 2) : kOOBl;
-                    dma16l(rsrc_x, dst + q * 1024, v);
+                    const uint32_t v = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * C + chunk * 8) * 2) : kOOB;
+                    dma16(rsrc_x, dst + q * 1024, v, 0);
                 }
             }
         };
@@ -212,8 +207,7 @@ static hipError_t launch_patch_lc(const ConvArgs& a, hipStream_t stream) {
     static std::atomic<uint64_t> attr_done{0};
     if (hipError_t e = ensure_dynamic_lds((const void*)kern, LDS, attr_done); e != hipSuccess) return e;
     ConvArgs b = a;
-    b.x_bytes = (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 2);
-    b.w_bytes = (uint32_t)((size_t)a.Cout * a.Ktot * 2);
+    conv_fill_extents(b);
     const long tiles = (long)a.B * ((a.OH + 7) / 8) * ((a.OW + 31) / 32);
     const int ncu = cu_count();
     const int grid = tiles < ncu ? (int)tiles : ncu;

@@ -23,15 +23,10 @@
 // 8-11 only issue LDS-DMA (18 x 1 KB pieces per plane each) and wait for it; ONE workgroup barrier per plane is the
 // hand-off in both directions.  LDS: 2 x 70 KB.
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 namespace dir {
-
-static constexpr uint32_t kOOBs2 = 0x80000000u;
-
-__device__ __forceinline__ void dma16s2(__amdgpu_buffer_rsrc_t rsrc, char* lds, uint32_t voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DIR_LDS void*)lds, 16, voff, soff, 0, 0);
-}
 
 template <class DT>
 __global__ void __launch_bounds__(768) conv_patch3x3s2_kernel(const ConvArgs a) {
@@ -63,7 +58,7 @@ __global__ void __launch_bounds__(768) conv_patch3x3s2_kernel(const ConvArgs a) 
     if (wave >= 8) {
         // ================================ loaders ==============================================================================
         const int lw = wave - 8;
-        const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
         // this lane's slot of piece k (the same in every plane of every tile): patch row / input column offset, chunk
         int ppos[LP];
 #pragma unroll
@@ -87,14 +82,14 @@ __global__ void __launch_bounds__(768) conv_patch3x3s2_kernel(const ConvArgs a) 
             for (int k = 0; k < LP; ++k) {
                 const int iy = iy0 + (ppos[k] >> 16), ix = ix0 + ((ppos[k] >> 4) & 0xfff);
                 const bool ok = ppos[k] >= 0 && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-                pvoff[k] = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * a.Cin + (ppos[k] & 15) * 8) * 2) : kOOBs2;
+                pvoff[k] = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * a.Cin + (ppos[k] & 15) * 8) * 2) : kOOB;
             }
         };
         auto issue = [&](int q, int buf) __attribute__((always_inline)) {
             char* dst = smem + buf * PBUF;
 #pragma unroll
             for (int k = 0; k < LP; ++k)
-                if (k * NL + lw < NPIECE) dma16s2(rsrc_x, dst + (k * NL + lw) * 1024, pvoff[k], q * 64);
+                if (k * NL + lw < NPIECE) dma16(rsrc_x, dst + (k * NL + lw) * 1024, pvoff[k], q * 64);
         };
         const int NG = my_tiles * NQ;
         int it = 0, q = 0;
@@ -117,7 +112,7 @@ __global__ void __launch_bounds__(768) conv_patch3x3s2_kernel(const ConvArgs a) 
 
     // ==================================== consumers ================================================================================
     const int ct = wave & 3, rh = wave >> 2;
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)a.w_s2, 0, a.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w_s2, a.w_bytes);
     const uint32_t wvoff = (uint32_t)(lane * 16);
     frag_t W[2][3][2];   // two sets (this filter row / the next one) x tap x K half
     auto load_w = [&](frag_t (&w)[3][2], int tile_n, int q, int r) __attribute__((always_inline)) {
@@ -270,8 +265,7 @@ static hipError_t launch_patch_s2(const ConvArgs& a, hipStream_t stream) {
     static std::atomic<uint64_t> attr_done{0};
     if (hipError_t e = ensure_dynamic_lds((const void*)kern, LDS, attr_done); e != hipSuccess) return e;
     ConvArgs b = a;
-    b.x_bytes = (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 2);
-    b.w_bytes = (uint32_t)((size_t)a.Cout * a.Ktot * 2);
+    conv_fill_extents(b);
     void* scratch = nullptr;
     if (!b.w_s2) {   // the per-op entry point (dir_conv_bn_act): no packed copy kept anywhere - stream-ordered scratch for this launch
         if (hipError_t e = hipMallocAsync(&scratch, b.w_bytes, stream); e != hipSuccess) return e;

@@ -16,6 +16,7 @@
 // MFMA roles (A = weights, B = pixels), bias-initialised accumulators, XOR-swizzled rows (here 64-byte rows, the four
 // 16-byte chunks swizzled by (row >> 2) & 3), fp32 staging for coalesced 16-byte stores.
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 // Timing-only experiment builds (scripts/exp_abl.sh conv_patchw DIR_PATCHW_ABL <bits>): 1 = no global stores in the epilogue
@@ -36,12 +37,6 @@
 #endif
 
 namespace dir {
-
-static constexpr uint32_t kOOBw = 0x80000000u;
-
-__device__ __forceinline__ void dma16w(__amdgpu_buffer_rsrc_t rsrc, char* lds, uint32_t voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DIR_LDS void*)lds, 16, voff, soff, 0, 0);
-}
 
 template <class DT>
 __global__ void __launch_bounds__(512) conv_patch3x3w_kernel(const ConvArgs a) {
@@ -80,8 +75,8 @@ __global__ void __launch_bounds__(512) conv_patch3x3w_kernel(const ConvArgs a) {
     const int b = wg / tiles_y;
     const int oy0 = ty * TH, ox0 = tx * TW;
 
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, a.w_bytes);
 
     // patch: 4 lanes per pixel (64 bytes of plane 0; plane q adds q * 64 bytes through the scalar offset)
     uint32_t pvoff[NPL];
@@ -92,17 +87,17 @@ __global__ void __launch_bounds__(512) conv_patch3x3w_kernel(const ConvArgs a) {
         const int py = p / PW, px = p - py * PW;
         const int iy = oy0 - 1 + py, ix = ox0 - 1 + px;
         const bool ok = p < PP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-        pvoff[i] = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * a.Cin + ((pos ^ ((p >> 2) & 3)) << 3)) * 2) : kOOBw;
+        pvoff[i] = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * a.Cin + ((pos ^ ((p >> 2) & 3)) << 3)) * 2) : kOOB;
     }
     auto issue_plane = [&](int q) {
         if (DIR_PATCHW_ABL & 64) return;
         char* dst = smem + (q & 1) * PLANE_BYTES;
 #pragma unroll
-        for (int i = 0; i < NPL; ++i) dma16w(rsrc_x, dst + (i * NTH + wave * 64) * 16, pvoff[i], q * 64);
+        for (int i = 0; i < NPL; ++i) dma16(rsrc_x, dst + (i * NTH + wave * 64) * 16, pvoff[i], q * 64);
 #pragma unroll
         for (int rep = 0; rep < NPL_X; ++rep)       // (experiment: the same plane again - same destination, same bytes)
 #pragma unroll
-            for (int i = 0; i < NPL; ++i) dma16w(rsrc_x, dst + (i * NTH + wave * 64) * 16, pvoff[i], q * 64);
+            for (int i = 0; i < NPL; ++i) dma16(rsrc_x, dst + (i * NTH + wave * 64) * 16, pvoff[i], q * 64);
     };
     // weights of stage (q, r): LDS image [tap s][channel n][64 B]; linear index L = (s * 128 + n) * 4 + pos
     uint32_t wvoff[NBW];
@@ -117,10 +112,10 @@ __global__ void __launch_bounds__(512) conv_patch3x3w_kernel(const ConvArgs a) {
         const int q = sigma / 3, r = sigma - q * 3;
         char* dst = smem + WOFF + slot * WSTAGE;
 #pragma unroll
-        for (int i = 0; i < NBW; ++i) dma16w(rsrc_w, dst + (i * NTH + wave * 64) * 16, wvoff[i], (r * 3 * a.Cin + q * 32) * 2);
+        for (int i = 0; i < NBW; ++i) dma16(rsrc_w, dst + (i * NTH + wave * 64) * 16, wvoff[i], (r * 3 * a.Cin + q * 32) * 2);
 #pragma unroll
         for (int i = 0; i < NBW_X; ++i)             // (experiment: 16 / 9 of the weight bytes, from the neighbouring filter row)
-            dma16w(rsrc_w, dst + (i * NTH + wave * 64) * 16, wvoff[i], (((r + 1) % 3) * 3 * a.Cin + q * 32) * 2);
+            dma16(rsrc_w, dst + (i * NTH + wave * 64) * 16, wvoff[i], (((r + 1) % 3) * 3 * a.Cin + q * 32) * 2);
     };
 
     f32x16_t acc[TN][TMR];
@@ -233,9 +228,7 @@ __global__ void __launch_bounds__(512) conv_patch3x3w_kernel(const ConvArgs a) {
                 f32x4_t v = {acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
                 *(f32x4_t*)(ebase + lrow * EROW + (i * 32 + 8 * g + 4 * lhi) * 4) = v;
             }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const int oy = oy0 + wave * TMR + j;
 #pragma unroll
         for (int pass = 0; pass < NPASS; ++pass) {
@@ -256,20 +249,13 @@ __global__ void __launch_bounds__(512) conv_patch3x3w_kernel(const ConvArgs a) {
                         v[2 * e + 1] += hi;
                     }
                 }
-                if (a.relu) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
-                u32x4_t ov;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) ov[e] = DT::pack(v[2 * e], v[2 * e + 1]);
+                if (a.relu) relu8(v);
+                const u32x4_t ov = pack8<DT>(v);
                 if (!(DIR_PATCHW_ABL & 1) || ov[0] == 0x12345678u) gstore16(a.y + o, ov);
                 ovf.see(ov);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
     ovf.flush(a.ovf);
 }
@@ -281,7 +267,7 @@ __global__ void __launch_bounds__(512) conv_patch3x3w_kernel(const ConvArgs a) {
 // CU's request queue is busy: round-3 finding, conv_ring.hip / sim_split_lc_kernel).  Same tile, stages, LDS map, fragment
 // reads and MFMA order here - bit-identical results - with the work split by wave role: TWELVE waves, waves 0-7 only read
 // fragments and multiply (two per SIMD), waves 8-11 only issue LDS-DMA and wait for it (one per SIMD; 10 instructions per plane
-// and 6 per weight stage each, a counted vmcnt over one kind of op).  One barrier per stage is the hand-off in both directions.
+// and 6 per weight stage each, a counted vmcnt over one type of op).  One barrier per stage is the hand-off in both directions.
 // (s_setprio on either role - consumers 1 / 3, loaders 1 - measured: 14.11-14.18 ms per step in every combination, 14.13-14.15
 // without; not kept.)
 // Twelve waves = three per SIMD = 168 VGPRs per wave: the consumers' 128 accumulator registers leave 40, so fragments are
@@ -325,7 +311,7 @@ __global__ void __launch_bounds__(768) conv_patch3x3w_lc_kernel(const ConvArgs a
         // ================================ loaders ==============================================================================
         const int lt = tid - 512;              // 0 .. 255
         const int lw = wave - 8;
-        const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
         uint32_t pvoff[NPL];
 #pragma unroll
         for (int i = 0; i < NPL; ++i) {
@@ -334,12 +320,12 @@ __global__ void __launch_bounds__(768) conv_patch3x3w_lc_kernel(const ConvArgs a
             const int py = p / PW, px = p - py * PW;
             const int iy = oy0 - 1 + py, ix = ox0 - 1 + px;
             const bool ok = p < PP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-            pvoff[i] = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * a.Cin + ((pos ^ ((p >> 2) & 3)) << 3)) * 2) : kOOBw;
+            pvoff[i] = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * a.Cin + ((pos ^ ((p >> 2) & 3)) << 3)) * 2) : kOOB;
         }
         // a.w_pw (conv_patch3x3w_pack): the filter as the sequence of 24 KB LDS stage images - a DMA instruction copies one
         // contiguous KB instead of gathering sixteen 64-byte runs of the [Cout][3][3][Cin] layout
         const bool packed = a.w_pw != nullptr;
-        const __amdgpu_buffer_rsrc_t rsrc_wp = __builtin_amdgcn_make_buffer_rsrc((void*)(packed ? a.w_pw : a.w), 0, a.w_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_wp = buffer_rsrc(packed ? a.w_pw : a.w, a.w_bytes);
         uint32_t wvoff[NBW];
 #pragma unroll
         for (int i = 0; i < NBW; ++i) {
@@ -350,14 +336,14 @@ __global__ void __launch_bounds__(768) conv_patch3x3w_lc_kernel(const ConvArgs a
         auto issue_plane = [&](int q) {
             char* dst = smem + (q & 1) * PLANE_BYTES;
 #pragma unroll
-            for (int i = 0; i < NPL; ++i) dma16w(rsrc_x, dst + (i * NLD + lw * 64) * 16, pvoff[i], q * 64);
+            for (int i = 0; i < NPL; ++i) dma16(rsrc_x, dst + (i * NLD + lw * 64) * 16, pvoff[i], q * 64);
         };
         auto issue_w = [&](int sigma, int slot) {
             const int q = sigma / 3, r = sigma - q * 3;
             char* dst = smem + WOFF + slot * WSTAGE;
             const int soff = packed ? (tile_n * NS + sigma) * WSTAGE : (r * 3 * a.Cin + q * 32) * 2;
 #pragma unroll
-            for (int i = 0; i < NBW; ++i) dma16w(rsrc_wp, dst + (i * NLD + lw * 64) * 16, wvoff[i], soff);
+            for (int i = 0; i < NBW; ++i) dma16(rsrc_wp, dst + (i * NLD + lw * 64) * 16, wvoff[i], soff);
         };
         // prologue: plane 0, weight stages 0 and 1 - in this order (the counted waits below rely on it)
         issue_plane(0);
@@ -465,9 +451,7 @@ __global__ void __launch_bounds__(768) conv_patch3x3w_lc_kernel(const ConvArgs a
                 f32x4_t v = {acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
                 *(f32x4_t*)(ebase + lrow * EROW + (i * 32 + 8 * g + 4 * lhi) * 4) = v;
             }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const int oy = oy0 + wave * TMR + j;
 #pragma unroll
         for (int pass = 0; pass < NPASS; ++pass) {
@@ -488,20 +472,13 @@ __global__ void __launch_bounds__(768) conv_patch3x3w_lc_kernel(const ConvArgs a
                         v[2 * e + 1] += hi;
                     }
                 }
-                if (a.relu) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
-                u32x4_t ov;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) ov[e] = DT::pack(v[2 * e], v[2 * e + 1]);
+                if (a.relu) relu8(v);
+                const u32x4_t ov = pack8<DT>(v);
                 gstore16(a.y + o, ov);
                 ovf.see(ov);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
     ovf.flush(a.ovf);
 }
@@ -542,8 +519,7 @@ static hipError_t launch_patch_w(const ConvArgs& a, hipStream_t stream) {
     constexpr int LDS = 2 * 5 * 512 * 16 + 3 * 3 * 128 * 64;   // two planes + three weight stages = 152 KiB
     static_assert(LDS <= 160 * 1024 && LDS >= 8 * 32 * (4 * 128 + 16), "LDS map (the staging area aliases it)");
     ConvArgs b = a;
-    b.x_bytes = (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 2);
-    b.w_bytes = (uint32_t)((size_t)a.Cout * a.Ktot * 2);
+    conv_fill_extents(b);
     const long blocks = (long)a.B * ((a.OH + 15) / 16) * ((a.OW + 31) / 32) * (a.Cout / 128);
     if (!env().no_patchw_lc) {   // the loader / consumer form (twelve waves); DIRTORCH_AMD_NO_PATCHW_LC = the one-role kernel
         void* scratch = nullptr;

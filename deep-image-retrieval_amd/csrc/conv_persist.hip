@@ -14,18 +14,10 @@
 // LDS map: slot 0 = [0, 64K), slot 1 = [64K, 128K); epilogue staging = [64K, 64K + 68K): 8 waves x
 // 32 pixel rows x (64 fp32 + pad), one 64-channel half of a wave's 128 channels at a time.
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 namespace dir {
-
-static constexpr uint32_t kOOBq = 0x80000000u;
-
-__device__ __forceinline__ void dma16q(__amdgpu_buffer_rsrc_t rsrc, char* lds, uint32_t voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DIR_LDS void*)lds, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ uint32_t fast_div_q(uint32_t n, uint32_t mul, uint32_t shr) {
-    return mul ? (__umulhi(n, mul) >> shr) : n;
-}
 
 // XDEEP = false: the map above (2 slots of X+W).
 // XDEEP = true : THREE slots for the pixel operand, two for the weights, K-step still 64:
@@ -35,7 +27,7 @@ __device__ __forceinline__ uint32_t fast_div_q(uint32_t n, uint32_t mul, uint32_
 //   window's limit; round 3's probes put the limit elsewhere - waves that both issue LDS-DMA and multiply
 //   serialise the two, and the layer's read/write mix caps HBM at ~5.2 TB/s: conv_ring.hip).  Here
 //   X runs two K-steps ahead and W one (issue order W(t+1), X(t+2); the wait before step t leaves exactly
-//   X(t+1) - the newest ops, all of the LDS-DMA kind - in flight), so 64-96 KB of HBM requests per CU
+//   X(t+1) - the newest ops, all of the LDS-DMA type - in flight), so 64-96 KB of HBM requests per CU
 //   are outstanding.  Next tile's W(0) / X(0) still go out before the epilogue, X(1) right after it.
 // DUAL (deep-X form only, round 4): the K dimension comes from TWO tensors - K-steps [0, Cin/64) from x (flat: the
 // conv3 input t2), the rest from x2 (the block input, gathered at stride2: the 1x1 downsample) - against weights and
@@ -63,12 +55,9 @@ __global__ void __launch_bounds__(512) conv1x1_persist_kernel(const ConvArgs a) 
     const int lrow = lane & 31, lhi = lane >> 5;
     const int srcchunk = (tid & 7) ^ ((tid >> 4) & 7);
 
-    const __amdgpu_buffer_rsrc_t rsrc_x =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_x2 =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(DUAL ? a.x2 : a.x), 0, DUAL ? a.x2_bytes : a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_x2 = buffer_rsrc(DUAL ? a.x2 : a.x, DUAL ? a.x2_bytes : a.x_bytes);
 
     const int ntiles = a.tiles_m * a.tiles_n;
     const int T = a.T;
@@ -90,23 +79,23 @@ __global__ void __launch_bounds__(512) conv1x1_persist_kernel(const ConvArgs a) 
 #endif
             } else {  // strided 1x1 (downsample): output pixel -> input pixel
                 const uint32_t mm = m < a.M ? (uint32_t)m : 0u;
-                const uint32_t b = fast_div_q(mm, a.div_ohw_mul, a.div_ohw_shr);
+                const uint32_t b = fast_div(mm, a.div_ohw_mul, a.div_ohw_shr);
                 const uint32_t rem = mm - b * (uint32_t)(a.OH * a.OW);
-                const uint32_t oh = fast_div_q(rem, a.div_ow_mul, a.div_ow_shr);
+                const uint32_t oh = fast_div(rem, a.div_ow_mul, a.div_ow_shr);
                 const uint32_t ow = rem - oh * (uint32_t)a.OW;
                 off = (uint32_t)((((b * a.H + oh * a.stride) * a.W + ow * a.stride) * a.Cin +
                                   srcchunk * 8) * 2);
             }
-            xvoff[i] = m < a.M ? off : kOOBq;
+            xvoff[i] = m < a.M ? off : kOOB;
             if (DUAL) {   // output pixel -> pixel (oh * stride2, ow * stride2) of the second source
                 const uint32_t mm = m < a.M ? (uint32_t)m : 0u;
-                const uint32_t b = fast_div_q(mm, a.div_ohw_mul, a.div_ohw_shr);
+                const uint32_t b = fast_div(mm, a.div_ohw_mul, a.div_ohw_shr);
                 const uint32_t rem = mm - b * (uint32_t)(a.OH * a.OW);
-                const uint32_t oh = fast_div_q(rem, a.div_ow_mul, a.div_ow_shr);
+                const uint32_t oh = fast_div(rem, a.div_ow_mul, a.div_ow_shr);
                 const uint32_t ow = rem - oh * (uint32_t)a.OW;
                 const uint32_t off2 = (uint32_t)((((b * a.H2 + oh * a.stride2) * a.W2 + ow * a.stride2) * a.Cin2 +
                                                   srcchunk * 8) * 2);
-                xvoff2[DUAL ? i : 0] = m < a.M ? off2 : kOOBq;
+                xvoff2[DUAL ? i : 0] = m < a.M ? off2 : kOOB;
             }
         }
 #pragma unroll
@@ -117,19 +106,19 @@ __global__ void __launch_bounds__(512) conv1x1_persist_kernel(const ConvArgs a) 
         if (DUAL && t >= T1) {
 #pragma unroll
             for (int i = 0; i < NA; ++i)
-                dma16q(rsrc_x2, dst + (i * NT + wave * 64) * 16, xvoff2[DUAL ? i : 0], (t - T1) * 128);
+                dma16(rsrc_x2, dst + (i * NT + wave * 64) * 16, xvoff2[DUAL ? i : 0], (t - T1) * 128);
             return;
         }
 #pragma unroll
 #ifdef DIR_PERSIST_BLOCKED
-        for (int i = 0; i < NA; ++i) dma16q(rsrc_x, dst + (i * NT + wave * 64) * 16, xvoff[i], a.flat ? t * (BM * 128) : t * 128);
+        for (int i = 0; i < NA; ++i) dma16(rsrc_x, dst + (i * NT + wave * 64) * 16, xvoff[i], a.flat ? t * (BM * 128) : t * 128);
 #else
-        for (int i = 0; i < NA; ++i) dma16q(rsrc_x, dst + (i * NT + wave * 64) * 16, xvoff[i], t * 128);
+        for (int i = 0; i < NA; ++i) dma16(rsrc_x, dst + (i * NT + wave * 64) * 16, xvoff[i], t * 128);
 #endif
     };
     auto issue_w = [&](int t, char* dst) {
 #pragma unroll
-        for (int i = 0; i < NB; ++i) dma16q(rsrc_w, dst + (i * NT + wave * 64) * 16, wvoff[i], t * 128);
+        for (int i = 0; i < NB; ++i) dma16(rsrc_w, dst + (i * NT + wave * 64) * 16, wvoff[i], t * 128);
     };
     auto issue = [&](int t, char* stage) {
         issue_x(t, stage);
@@ -217,8 +206,8 @@ __global__ void __launch_bounds__(512) conv1x1_persist_kernel(const ConvArgs a) 
         // ---- K loop: stage 0 is already in flight (issued by the previous tile or the preamble) --
         if (XDEEP) {
             for (int t = 0; t < T; ++t) {
-                // need X(t), W(t); may leave X(t+1) - the 4 newest ops, same kind - in flight.  With a
-                // residual the tile's first wait also covers the (newer, VGPR-kind) residual loads.
+                // need X(t), W(t); may leave X(t+1) - the 4 newest ops, same type - in flight.  With a
+                // residual the tile's first wait also covers the (newer, VGPR-type) residual loads.
                 if (t + 1 < T && !(RES && t == 0 && a.res)) {
                     asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NA) : "memory");
                 } else {
@@ -296,9 +285,7 @@ __global__ void __launch_bounds__(512) conv1x1_persist_kernel(const ConvArgs a) 
                                      acc[i][j][4 * g + 3]};
                         *(f32x4_t*)(ebase + lrow * EROW + (ii * 32 + 8 * g + 4 * lhi) * 4) = v;
                     }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
 #pragma unroll
                 for (int pass = 0; pass < 4; ++pass) {
                     const int mrow = pass * 8 + erow;
@@ -317,20 +304,13 @@ __global__ void __launch_bounds__(512) conv1x1_persist_kernel(const ConvArgs a) 
                                 v[2 * e + 1] += hi;
                             }
                         }
-                        if (a.relu) {
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                        }
-                        u32x4_t ov;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) ov[e] = DT::pack(v[2 * e], v[2 * e + 1]);
+                        if (a.relu) relu8(v);
+                        const u32x4_t ov = pack8<DT>(v);
                         gstore16(a.y + ((size_t)m * a.Cout + n_wave + h * 64 + ecol), ov);
                         ovf.see(ov);
                     }
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
             }
         if (next >= ntiles) break;
         if (XDEEP && T > 1) {
@@ -362,22 +342,10 @@ static hipError_t launch_persist(const ConvArgs& a, hipStream_t stream) {
     b.T = a.Ktot / 64;
     b.tiles_m = ceil_div(a.M, 256);
     b.tiles_n = a.Cout / 256;
-    b.x_bytes = (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 2);
-    b.w_bytes = (uint32_t)((size_t)a.Cout * a.Ktot * 2);
-    if (DUAL) b.x2_bytes = (uint32_t)((size_t)a.B * a.H2 * a.W2 * a.Cin2 * 2);
+    conv_fill_extents(b);
     b.flat = (a.stride == 1 && a.H == a.OH && a.W == a.OW);
     const bool no_xcd_map = env().no_xcdmap;   // A/B and bisecting
     b.no_xcd_map = no_xcd_map;
-    // exact n / d for n < 2^31 (same constants as conv_igemm.hip)
-    auto fd = [](uint32_t d, uint32_t& mul, uint32_t& shr) {
-        if (d <= 1) { mul = 0; shr = 0; return; }
-        uint32_t l = 0;
-        while ((1ull << l) < d) ++l;
-        mul = (uint32_t)(((1ull << (31 + l)) + d - 1) / d);
-        shr = l - 1;
-    };
-    fd((uint32_t)(a.OH * a.OW), b.div_ohw_mul, b.div_ohw_shr);
-    fd((uint32_t)a.OW, b.div_ow_mul, b.div_ow_shr);
     const int ntiles = b.tiles_m * b.tiles_n;
     const int ncu = cu_count();
     const int grid = ntiles < ncu ? ntiles : ncu;
@@ -385,12 +353,20 @@ static hipError_t launch_persist(const ConvArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-// the two-source form: a = the conv3 (1x1 stride 1 over t2) with x2 / Cin2 / H2 / W2 / stride2 set (ConvArgs in conv_igemm.h)
-hipError_t conv1x1_persist_dual_bf16(const ConvArgs& a, hipStream_t stream) { return launch_persist<BF16, true, true>(a, stream); }
-hipError_t conv1x1_persist_dual_fp16(const ConvArgs& a, hipStream_t stream) { return launch_persist<FP16, true, true>(a, stream); }
+// the two-source form: a = the conv3 (1x1 stride 1 over t2) with x2 / Cin2 / H2 / W2 / stride2 set (ConvArgs in conv_igemm.h);
+// conv_launch checks what every two-source row shares (1x1, stride 1, no residual, no split, Cin2 % 64, K = Cin + Cin2)
+bool conv1x1_persist_dual_admissible(const ConvArgs& a) { return a.Cout % 256 == 0; }
+hipError_t conv1x1_persist_dual_launch(const ConvArgs& a, int dtype, hipStream_t stream) {
+    return dtype == DIR_BF16 ? launch_persist<BF16, true, true>(a, stream) : launch_persist<FP16, true, true>(a, stream);
+}
 
-hipError_t conv1x1_persist_launch(const ConvArgs& a, int dtype, hipStream_t stream, bool xdeep) {
-    if (xdeep) return dtype == DIR_BF16 ? launch_persist<BF16, true>(a, stream) : launch_persist<FP16, true>(a, stream);
+// the deep-X form has no residual path
+bool conv1x1_persist_x3_admissible(const ConvArgs& a) { return conv1x1_persist_admissible(a) && a.res == nullptr; }
+hipError_t conv1x1_persist_x3_launch(const ConvArgs& a, int dtype, hipStream_t stream) {
+    return dtype == DIR_BF16 ? launch_persist<BF16, true>(a, stream) : launch_persist<FP16, true>(a, stream);
+}
+
+hipError_t conv1x1_persist_launch(const ConvArgs& a, int dtype, hipStream_t stream) {
     return dtype == DIR_BF16 ? launch_persist<BF16, false>(a, stream) : launch_persist<FP16, false>(a, stream);
 }
 

@@ -21,15 +21,10 @@
 //     kernels start their accumulators at it): results agree with theirs to fp32 rounding, not bit for bit;
 //   * DUAL: K-steps [0, Cin / 64) from x, the rest from x2 gathered at stride2 (conv_persist.hip's two-source form).
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 namespace dir {
-
-static constexpr uint32_t kOOBp = 0x80000000u;
-
-__device__ __forceinline__ void dma16p(__amdgpu_buffer_rsrc_t rsrc, char* lds, uint32_t voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DIR_LDS void*)lds, 16, voff, soff, 0, 0);
-}
 
 template <class DT, bool DUAL>
 __global__ void __launch_bounds__(768) conv1x1_lc_kernel(const ConvArgs a) {
@@ -62,10 +57,8 @@ __global__ void __launch_bounds__(768) conv1x1_lc_kernel(const ConvArgs a) {
         const int ahead = is_x ? 2 : 1;                    // stages this panel runs ahead of the consumers
         const int nslot = is_x ? 3 : 2;
         const int T1 = DUAL ? a.Cin / 64 : T;              // K-steps served by the first source
-        const __amdgpu_buffer_rsrc_t rsrc =
-            __builtin_amdgcn_make_buffer_rsrc((void*)(is_x ? a.x : a.w), 0, is_x ? a.x_bytes : a.w_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsrc2 =
-            __builtin_amdgcn_make_buffer_rsrc((void*)(DUAL ? a.x2 : a.x), 0, DUAL ? a.x2_bytes : a.x_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc = buffer_rsrc(is_x ? a.x : a.w, is_x ? a.x_bytes : a.w_bytes);
+        const __amdgpu_buffer_rsrc_t rsrc2 = buffer_rsrc(DUAL ? a.x2 : a.x, DUAL ? a.x2_bytes : a.x_bytes);
         const int dst0 = (is_x ? 0 : WOFF) + half * NL * 1024;
         // Instruction k of a stage covers rows 8 k .. 8 k + 7 of this wave's half (8 lanes x 16 B per 128-byte row); the chunks of a
         // row are XOR-swizzled with (row >> 1) & 7 on the SOURCE side (the LDS image is lane-linear).  For a flat source the
@@ -94,7 +87,7 @@ __global__ void __launch_bounds__(768) conv1x1_lc_kernel(const ConvArgs a) {
                         const uint32_t oh = __umulhi(rem, a.div_ow_mul) >> a.div_ow_shr;
                         const uint32_t ow = rem - oh * (uint32_t)a.OW;
                         const uint32_t off2 = (((b * a.H2 + oh * a.stride2) * a.W2 + ow * a.stride2) * a.Cin2 + ((k & 1) ? chO : chE) * 8) * 2;
-                        voff2[k] = m < a.M ? off2 : kOOBp;
+                        voff2[k] = m < a.M ? off2 : kOOB;
                     }
                 }
             } else {
@@ -114,15 +107,15 @@ __global__ void __launch_bounds__(768) conv1x1_lc_kernel(const ConvArgs a) {
             if (second) {
                 if constexpr (DUAL) {
 #pragma unroll
-                    for (int k = 0; k < NL; ++k) dma16p(rsrc2, dst + k * 1024, voff2[k], (is_t - T1) * 128);
+                    for (int k = 0; k < NL; ++k) dma16(rsrc2, dst + k * 1024, voff2[k], (is_t - T1) * 128);
                 }
             } else {
 #pragma unroll
                 for (int k2 = 0; k2 < NL / 2; ++k2) {
-                    const uint32_t offe = m0 + 16 * k2 < mlim ? baseE + (uint32_t)(2 * k2) * rstride : kOOBp;
-                    dma16p(rsrc, dst + (2 * k2) * 1024, offe, is_t * 128);
-                    const uint32_t offo = m0 + 16 * k2 + 8 < mlim ? baseO + (uint32_t)(2 * k2 + 1) * rstride : kOOBp;
-                    dma16p(rsrc, dst + (2 * k2 + 1) * 1024, offo, is_t * 128);
+                    const uint32_t offe = m0 + 16 * k2 < mlim ? baseE + (uint32_t)(2 * k2) * rstride : kOOB;
+                    dma16(rsrc, dst + (2 * k2) * 1024, offe, is_t * 128);
+                    const uint32_t offo = m0 + 16 * k2 + 8 < mlim ? baseO + (uint32_t)(2 * k2 + 1) * rstride : kOOB;
+                    dma16(rsrc, dst + (2 * k2 + 1) * 1024, offo, is_t * 128);
                 }
             }
             is_slot = is_slot + 1 == nslot ? 0 : is_slot + 1;
@@ -241,6 +234,8 @@ bool conv1x1_lc_admissible(const ConvArgs& a) {
     return base && a.Cin >= 128;
 }
 
+bool conv1x1_lc_plain_admissible(const ConvArgs& a) { return a.x2 == nullptr && conv1x1_lc_admissible(a); }
+
 template <class DT, bool DUAL>
 static hipError_t launch_lc(const ConvArgs& a, hipStream_t stream) {
     constexpr int LDS = 5 * 256 * 128;   // three pixel slots + two weight slots: all 160 KiB
@@ -252,20 +247,8 @@ static hipError_t launch_lc(const ConvArgs& a, hipStream_t stream) {
     b.T = a.Ktot / 64;
     b.tiles_m = ceil_div(a.M, 256);
     b.tiles_n = a.Cout / 256;
-    b.x_bytes = (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 2);
-    b.w_bytes = (uint32_t)((size_t)a.Cout * a.Ktot * 2);
-    if (DUAL) b.x2_bytes = (uint32_t)((size_t)a.B * a.H2 * a.W2 * a.Cin2 * 2);
+    conv_fill_extents(b);
     b.no_xcd_map = env().no_xcdmap;
-    auto fd = [](uint32_t d, uint32_t& mul, uint32_t& shr) {   // exact n / d for 1 < d, n < 2^31 (conv_igemm.hip's constants)
-        uint32_t l = 0;
-        while ((1ull << l) < d) ++l;
-        mul = (uint32_t)(((1ull << (31 + l)) + d - 1) / d);
-        shr = l - 1;
-    };
-    if (DUAL) {
-        fd((uint32_t)(a.OH * a.OW), b.div_ohw_mul, b.div_ohw_shr);
-        fd((uint32_t)a.OW, b.div_ow_mul, b.div_ow_shr);
-    }
     const int ntiles = b.tiles_m * b.tiles_n;
     const int ncu = cu_count();
     hipLaunchKernelGGL(kern, dim3(ntiles < ncu ? ntiles : ncu), dim3(768), LDS, stream, b);
@@ -275,7 +258,8 @@ static hipError_t launch_lc(const ConvArgs& a, hipStream_t stream) {
 hipError_t conv1x1_lc_launch(const ConvArgs& a, int dtype, hipStream_t stream) {
     return dtype == DIR_BF16 ? launch_lc<BF16, false>(a, stream) : launch_lc<FP16, false>(a, stream);
 }
-hipError_t conv1x1_lc_dual_bf16(const ConvArgs& a, hipStream_t stream) { return launch_lc<BF16, true>(a, stream); }
-hipError_t conv1x1_lc_dual_fp16(const ConvArgs& a, hipStream_t stream) { return launch_lc<FP16, true>(a, stream); }
+hipError_t conv1x1_lc_dual_launch(const ConvArgs& a, int dtype, hipStream_t stream) {
+    return dtype == DIR_BF16 ? launch_lc<BF16, true>(a, stream) : launch_lc<FP16, true>(a, stream);
+}
 
 }  // namespace dir

@@ -6,7 +6,7 @@
 // phase-ablation builds said (profiles/r03_window_probe.txt, r03_ring_ablation*.txt, r03_read_store_mix_probe.txt):
 //   * L2 hits ride nearly free next to HBM misses: a CU pulls 23.4 GB/s of HBM bytes (6.0 TB/s for the chip, the
 //     read ceiling) AND the same rate of L2-resident bytes when ~100 KB of LDS-DMA requests are outstanding (one 64 KB
-//     stage in flight: 20 + 20).  The "per-CU request window" of round 2 is not a byte budget shared by both kinds.
+//     stage in flight: 20 + 20).  The "per-CU request window" of round 2 is not a byte budget shared by both types.
 //   * When every wave does "issue the next stage, then multiply this one", the two phases do not overlap: a
 //     memory-bound CU's request queue is full, so each LDS-DMA instruction holds its wave at issue until the queue
 //     drains - all eight waves stall together, then multiply together (ring alone 46 us, MFMAs alone ~40 us, both
@@ -34,11 +34,12 @@
 //     K-slice ks + 1 issued before the MFMAs of ks: one wave per SIMD has nobody else to hide LDS latency behind);
 //   * output straight from the accumulators: ReLU, pack, v_permlane32_swap pairs the two half-waves' 8-byte pieces
 //     into 16-byte stores (CDNA guide T21) - no LDS staging, no extra barrier;
-//   * bias in LDS; the loaders issue nothing but LDS-DMA, so their counted vmcnt sees one kind of op, in order.
+//   * bias in LDS; the loaders issue nothing but LDS-DMA, so their counted vmcnt sees one type of op, in order.
 // Everything else is the conv_igemm design: descriptor LDS-DMA with the K-step in the scalar offset, XOR-swizzled
 // 128-byte rows, swapped MFMA roles (A = weights, B = pixels), accumulators that start at the bias; the K order and
 // the fp32 sums are those of every other 1x1 kernel here (bit-identical outputs).
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 // Timing-only experiment builds (scripts/exp_abl.sh conv_ring DIR_RING_ABL <bits>): -DDIR_RING_ABL=<bits> compiles phases out - 1 = no pixel DMA,
@@ -48,15 +49,6 @@
 #endif
 
 namespace dir {
-
-static constexpr uint32_t kOOBr = 0x80000000u;
-
-__device__ __forceinline__ void dma16r(__amdgpu_buffer_rsrc_t rsrc, char* lds, uint32_t voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DIR_LDS void*)lds, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ uint32_t fast_div_r(uint32_t n, uint32_t mul, uint32_t shr) {
-    return mul ? (__umulhi(n, mul) >> shr) : n;
-}
 
 // LDS map: [0, 144K) ring, [144K, 152K) bias (Cout <= 2048).
 template <class DT>
@@ -84,7 +76,7 @@ __global__ void __launch_bounds__(512) conv1x1_ring_kernel(const ConvArgs a) {
     const int total = my_tiles * T;
 
     for (int i = tid; i < a.Cout; i += 512) lbias[i] = a.bias[i];
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // the only VGPR-kind loads of the kernel
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // the only VGPR-type loads of the kernel
     ring_barrier();
 
     // Where piece p of the output tile `tile` goes, for the lane that holds (or mirrors) consumer wave cw's lane:
@@ -113,7 +105,7 @@ __global__ void __launch_bounds__(512) conv1x1_ring_kernel(const ConvArgs a) {
         const bool is_x = lw == 0;
         const uint16_t* src_base = is_x ? a.x : a.w;
         const uint32_t src_bytes = is_x ? a.x_bytes : a.w_bytes;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)src_base, 0, src_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc = buffer_rsrc(src_base, src_bytes);
         const int dst0 = is_x ? 0 : XS + (lw - 1) * NL * 1024;
         uint32_t voff[NL];
         // (always_inline: left as a call, the lambda takes the by-value argument struct by reference and parks it in scratch)
@@ -130,14 +122,14 @@ __global__ void __launch_bounds__(512) conv1x1_ring_kernel(const ConvArgs a) {
                         off = (uint32_t)((m * a.Cin + chunk * 8) * 2);
                     } else {  // strided 1x1: output pixel (b, oh, ow) -> input pixel (b, oh * s, ow * s)
                         const uint32_t mm = m < a.M ? (uint32_t)m : 0u;
-                        const uint32_t b = fast_div_r(mm, a.div_ohw_mul, a.div_ohw_shr);
+                        const uint32_t b = fast_div(mm, a.div_ohw_mul, a.div_ohw_shr);
                         const uint32_t rem = mm - b * (uint32_t)(a.OH * a.OW);
-                        const uint32_t oh = fast_div_r(rem, a.div_ow_mul, a.div_ow_shr);
+                        const uint32_t oh = fast_div(rem, a.div_ow_mul, a.div_ow_shr);
                         const uint32_t ow = rem - oh * (uint32_t)a.OW;
                         const uint32_t sh = (uint32_t)a.H, sw = (uint32_t)a.W, st = (uint32_t)a.stride, sc = (uint32_t)a.Cin;
                         off = (uint32_t)((((b * sh + oh * st) * sw + ow * st) * sc + chunk * 8) * 2);
                     }
-                    voff[k] = m < a.M ? off : kOOBr;
+                    voff[k] = m < a.M ? off : kOOB;
                 }
             } else {
 #pragma unroll
@@ -154,7 +146,7 @@ __global__ void __launch_bounds__(512) conv1x1_ring_kernel(const ConvArgs a) {
             char* dst = smem + is_slot * STAGE + dst0;
 #pragma unroll
             for (int k = 0; k < NL; ++k)
-                if (!(DIR_RING_ABL & (is_x ? 1 : 2))) dma16r(rsrc, dst + k * 1024, voff[k], is_t * 128);
+                if (!(DIR_RING_ABL & (is_x ? 1 : 2))) dma16(rsrc, dst + k * 1024, voff[k], is_t * 128);
             is_slot = is_slot + 1 == NSLOT ? 0 : is_slot + 1;
             if (++is_t == T) {
                 is_t = 0;
@@ -288,20 +280,10 @@ static hipError_t launch_ring(const ConvArgs& a, hipStream_t stream) {
     b.T = a.Ktot / 64;
     b.tiles_m = ceil_div(a.M, 128);
     b.tiles_n = a.Cout / 256;
-    b.x_bytes = (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 2);
-    b.w_bytes = (uint32_t)((size_t)a.Cout * a.Ktot * 2);
+    conv_fill_extents(b);
     b.flat = (a.stride == 1 && a.H == a.OH && a.W == a.OW);
     const bool no_xcd_map = env().no_xcdmap;   // A/B and bisecting
     b.no_xcd_map = no_xcd_map;
-    auto fd = [](uint32_t d, uint32_t& mul, uint32_t& shr) {   // exact n / d for n < 2^31 (as in conv_igemm.hip)
-        if (d <= 1) { mul = 0; shr = 0; return; }
-        uint32_t l = 0;
-        while ((1ull << l) < d) ++l;
-        mul = (uint32_t)(((1ull << (31 + l)) + d - 1) / d);
-        shr = l - 1;
-    };
-    fd((uint32_t)(a.OH * a.OW), b.div_ohw_mul, b.div_ohw_shr);
-    fd((uint32_t)a.OW, b.div_ow_mul, b.div_ow_shr);
     const int ntiles = b.tiles_m * b.tiles_n;
     const int ncu = cu_count();
     const int grid = ntiles < ncu ? ntiles : ncu;

@@ -20,7 +20,7 @@
 //   B0, B1  W1[:, 128 c + 64 kb ... + 64) - phase B:  acc1 += W1_chunk . Y   (128 ch x 32 px per wave, resident over
 //           the 8 chunks); after B1(7): + bias1 (initial value) -> ReLU -> pack -> HBM
 // waves 4-7  loaders: nothing but LDS-DMA (8 instructions each per slot, + 4 each for the residual chunk that travels
-//            with A0), two slots ahead, counted vmcnt over one kind of op
+//            with A0), two slots ahead, counted vmcnt over one type of op
 // waves 0-3  consumers (pixel half pt = w & 1, channel half = w >> 1): LDS reads, MFMAs, 16-byte stores
 //            (v_permlane32_swap pairs the half-waves' pieces: conv_ring.hip's epilogue); no VMEM loads, no vmcnt waits
 // One s_barrier per slot is the hand-off in both directions (slot g landed / slot g - 1 is free); the Y tile and the
@@ -29,6 +29,7 @@
 // conv1' consumes exactly the 16-bit values stored to HBM: the result equals the two-kernel path up to fp32 summation
 // order.
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 // Timing-only experiment builds (scripts/exp_abl.sh conv_seam3 DIR_SEAM3_ABL <bits>): phases compiled out - 1 = no weight
@@ -38,10 +39,6 @@
 #endif
 
 namespace dir {
-
-__device__ __forceinline__ void dma16m(__amdgpu_buffer_rsrc_t rsrc, char* lds, uint32_t voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DIR_LDS void*)lds, 16, voff, soff, 0, 0);
-}
 
 template <class DT>
 __global__ void __launch_bounds__(512) conv_seam3_kernel(const ConvArgs a) {
@@ -71,19 +68,17 @@ __global__ void __launch_bounds__(512) conv_seam3_kernel(const ConvArgs a) {
 
     for (int i = tid; i < C4; i += 512) lbias3[i] = a.bias[i];
     if (tid < P) lbias1[tid] = a.bias2[tid];
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // the only VGPR-kind loads of the kernel
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // the only VGPR-type loads of the kernel
     ring_barrier();
 
     if (wave >= 4) {
         // ================================ loaders =============================================================
         const int lw = wave - 4;
-        const __amdgpu_buffer_rsrc_t rsrc_t2 =
-            __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (uint32_t)((size_t)a.M * P * 2), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsrc_res =
-            __builtin_amdgcn_make_buffer_rsrc((void*)a.res, 0, (uint32_t)((size_t)a.M * C4 * 2), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsrc_w3 = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, C4 * P * 2, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsrc_w1 = __builtin_amdgcn_make_buffer_rsrc((void*)a.w2, 0, P * C4 * 2, 0x00020000);
-        // Per-lane source offsets of this wave's 8 instructions (1 KiB of LDS each, lane-linear) per slot kind; the tile /
+        const __amdgpu_buffer_rsrc_t rsrc_t2 = buffer_rsrc(a.x, (uint32_t)((size_t)a.M * P * 2));
+        const __amdgpu_buffer_rsrc_t rsrc_res = buffer_rsrc(a.res, (uint32_t)((size_t)a.M * C4 * 2));
+        const __amdgpu_buffer_rsrc_t rsrc_w3 = buffer_rsrc(a.w, C4 * P * 2);
+        const __amdgpu_buffer_rsrc_t rsrc_w1 = buffer_rsrc(a.w2, P * C4 * 2);
+        // Per-lane source offsets of this wave's 8 instructions (1 KiB of LDS each, lane-linear) per slot type; the tile /
         // chunk / K position rides in the scalar offset.  The XOR swizzles are applied on the SOURCE side.
         uint32_t vT[8], vA[8], vB[8], vR[4];
 #pragma unroll
@@ -119,22 +114,22 @@ __global__ void __launch_bounds__(512) conv_seam3_kernel(const ConvArgs a) {
             if (is_s == 0) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
-                    if (!(DIR_SEAM3_ABL & 2)) dma16m(rsrc_t2, dst + j * 1024, vT[j], m0 * (P * 2));
+                    if (!(DIR_SEAM3_ABL & 2)) dma16(rsrc_t2, dst + j * 1024, vT[j], m0 * (P * 2));
             } else {
                 const int q = is_s - 1, c = q >> 2, ph = q & 3;
                 if (ph < 2) {
                     if (ph == 0) {   // the residual chunk of c travels with (and BEFORE) A0(c): landed by the same wait
 #pragma unroll
                         for (int j = 0; j < 4; ++j)
-                            if (!(DIR_SEAM3_ABL & 2)) dma16m(rsrc_res, smem + RES_OFF + (lw * 4 + j) * 1024, vR[j], (m0 * C4 + 128 * c) * 2);
+                            if (!(DIR_SEAM3_ABL & 2)) dma16(rsrc_res, smem + RES_OFF + (lw * 4 + j) * 1024, vR[j], (m0 * C4 + 128 * c) * 2);
                     }
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
-                        if (!(DIR_SEAM3_ABL & 1)) dma16m(rsrc_w3, dst + j * 1024, vA[j], (128 * c * P + ph * 128) * 2);
+                        if (!(DIR_SEAM3_ABL & 1)) dma16(rsrc_w3, dst + j * 1024, vA[j], (128 * c * P + ph * 128) * 2);
                 } else {
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
-                        if (!(DIR_SEAM3_ABL & 1)) dma16m(rsrc_w1, dst + j * 1024, vB[j], (128 * c + 64 * (ph - 2)) * 2);
+                        if (!(DIR_SEAM3_ABL & 1)) dma16(rsrc_w1, dst + j * 1024, vB[j], (128 * c + 64 * (ph - 2)) * 2);
                 }
             }
             is_slot = is_slot + 1 == NSLOT ? 0 : is_slot + 1;
@@ -169,8 +164,8 @@ __global__ void __launch_bounds__(512) conv_seam3_kernel(const ConvArgs a) {
     const int psw = p & 15;
     const uint32_t out_bytes = (uint32_t)((size_t)a.M * C4 * 2);
     const uint32_t t1_bytes = (uint32_t)((size_t)a.M * P * 2);
-    const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void*)a.y, 0, out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_y2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.y2, 0, t1_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_y = buffer_rsrc(a.y, out_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_y2 = buffer_rsrc(a.y2, t1_bytes);
     char* const ytile = smem + Y_OFF;
     const char* const rtile = smem + RES_OFF;
     Ovf<DT> ovf;

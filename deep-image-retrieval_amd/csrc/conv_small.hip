@@ -24,15 +24,10 @@
 // Every spin is bounded: a wave that waits ~0.5 s raises bit 1 of the overflow word and lets go (results are then garbage,
 // the host sees the flag; a lost hand-off must not hang the GPU).
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 namespace dir {
-
-static constexpr uint32_t kOOBs = 0x80000000u;
-
-__device__ __forceinline__ void dma16s(__amdgpu_buffer_rsrc_t rsrc, char* lds, uint32_t voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DIR_LDS void*)lds, 16, voff, soff, 0, 0);
-}
 
 // The LOADERS' counter traffic goes through inline assembly: hipcc's waitcnt pass orders every LDS instruction it can see behind
 // pending LDS-DMA ("may alias the DMA's destination") with an s_waitcnt vmcnt(0) - one poll or one flag store per stage would drain
@@ -83,8 +78,8 @@ __global__ void __launch_bounds__(512) conv_small_kernel(const ConvArgs a) {
     if (wave >= 4) {
         // ================================ loaders ======================================================================
         const int l = wave - 4;
-        const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.w_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
+        const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, a.w_bytes);
         // instruction i (0..7) of a panel covers rows 8 i .. 8 i + 7 (8 lanes x 16 B per 128-byte row); this wave issues
         // instructions 2 l and 2 l + 1 of both panels
         int xbase[2];
@@ -137,11 +132,11 @@ __global__ void __launch_bounds__(512) conv_small_kernel(const ConvArgs a) {
                 const int wstep = tap * (a.Cin / 64) + cc;
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    const uint32_t v = ((xmask[i] >> tap) & 1u) ? (uint32_t)(xbase[i] + koff) : kOOBs;
-                    dma16s(rsrc_x, dst + i * 1024, v, 0);
+                    const uint32_t v = ((xmask[i] >> tap) & 1u) ? (uint32_t)(xbase[i] + koff) : kOOB;
+                    dma16(rsrc_x, dst + i * 1024, v, 0);
                 }
 #pragma unroll
-                for (int i = 0; i < 2; ++i) dma16s(rsrc_w, dst + XS + i * 1024, wvoff[i], wstep * 128);
+                for (int i = 0; i < 2; ++i) dma16(rsrc_w, dst + XS + i * 1024, wvoff[i], wstep * 128);
                 // K order: channel slice outermost, taps innermost (conv_igemm.hip)
                 ++tap;
                 if (++s == a.S) {
@@ -257,22 +252,11 @@ __global__ void __launch_bounds__(512) conv_small_kernel(const ConvArgs a) {
                 v8[e] = __builtin_bit_cast(float, (uint32_t)r[0]);
                 v8[4 + e] = __builtin_bit_cast(float, (uint32_t)r[1]);
             }
-            if (a.res) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float lo, hi;
-                    DT::unpack(rres[h][e], lo, hi);
-                    v8[2 * e] += lo;
-                    v8[2 * e + 1] += hi;
-                }
-            }
+            if (a.res) add_res8<DT>(v8, rres[h]);
             if (a.relu) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v8[e] = fmaxf(v8[e], 0.f);
+                relu8(v8);
             }
-            u32x4_t ov;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ov[e] = DT::pack(v8[2 * e], v8[2 * e + 1]);
+            const u32x4_t ov = pack8<DT>(v8);
             if (mok) {
                 gstore16(a.y + ((size_t)m * a.Cout + n_wave + h * 16 + lhi * 8), ov);
                 ovf.see(ov);
@@ -330,26 +314,22 @@ static hipError_t launch_small(const ConvArgs& a, hipStream_t stream) {
     b.T = a.Ktot / 64;
     b.tiles_m = ceil_div(a.M, 64);
     b.tiles_n = a.Cout / 64;
-    b.x_bytes = (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 2);
-    b.w_bytes = (uint32_t)((size_t)a.Cout * a.Ktot * 2);
-    auto fd = [](uint32_t d, uint32_t& mul, uint32_t& shr) {   // exact n / d for n < 2^31 (conv_igemm.hip's constants; d <= 1: mul = 0)
-        if (d <= 1) { mul = 0; shr = 0; return; }
-        uint32_t l = 0;
-        while ((1ull << l) < d) ++l;
-        mul = (uint32_t)(((1ull << (31 + l)) + d - 1) / d);
-        shr = l - 1;
-    };
-    fd((uint32_t)(a.OH * a.OW), b.div_ohw_mul, b.div_ohw_shr);
-    fd((uint32_t)a.OW, b.div_ow_mul, b.div_ow_shr);
+    conv_fill_extents(b);
     const int ntiles = b.tiles_m * b.tiles_n;
     const int slots = cu_count() * (LDS <= 80 * 1024 ? 2 : 1);
     hipLaunchKernelGGL(kern, dim3(ntiles < slots ? ntiles : slots), dim3(512), LDS, stream, b);
     return hipGetLastError();
 }
 
-hipError_t conv_small_launch(const ConvArgs& a, int dtype, int nst, hipStream_t stream) {
-    if (nst == 4) return dtype == DIR_BF16 ? launch_small<BF16, 4>(a, stream) : launch_small<FP16, 4>(a, stream);
-    if (nst == 5) return dtype == DIR_BF16 ? launch_small<BF16, 4, 2>(a, stream) : launch_small<FP16, 4, 2>(a, stream);   // (table: stages 5 = 4 slots x 2 K-steps)
+hipError_t conv_small_s4_launch(const ConvArgs& a, int dtype, hipStream_t stream) {
+    return dtype == DIR_BF16 ? launch_small<BF16, 4>(a, stream) : launch_small<FP16, 4>(a, stream);
+}
+// four slots x two K-steps per stage: an even number of K-steps only
+bool conv_small_k2_admissible(const ConvArgs& a) { return conv_small_admissible(a) && (a.Ktot / 64) % 2 == 0; }
+hipError_t conv_small_s4k2_launch(const ConvArgs& a, int dtype, hipStream_t stream) {
+    return dtype == DIR_BF16 ? launch_small<BF16, 4, 2>(a, stream) : launch_small<FP16, 4, 2>(a, stream);
+}
+hipError_t conv_small_s8_launch(const ConvArgs& a, int dtype, hipStream_t stream) {
     return dtype == DIR_BF16 ? launch_small<BF16, 8>(a, stream) : launch_small<FP16, 8>(a, stream);
 }
 

@@ -16,11 +16,10 @@
 // stores, K order = channel order.  The bias is added in the epilogue (the tiled kernels start their
 // accumulators at it), so results agree with them to fp32 rounding, not bit for bit.
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 namespace dir {
-
-static constexpr uint32_t kOOBr = 0x80000000u;
 
 // KB = K / 64 (2 or 4): 64-channel blocks of the input
 template <class DT, int KB>
@@ -44,14 +43,13 @@ __global__ void __launch_bounds__(512) conv1x1_wreg_kernel(const ConvArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lrow = lane & 31, lhi = lane >> 5;
 
-    const __amdgpu_buffer_rsrc_t rsrc_x =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
     // residual loads and output stores go through bounds-checked descriptors too: a ragged last tile
     // needs no branch (out-of-range rows read zeros / drop the store), and with every VMEM op of the
     // loop unconditional the compiler's vmcnt bookkeeping is exact instead of "wait for everything"
     const uint32_t y_bytes = (uint32_t)((size_t)a.M * a.Cout * 2);
-    const __amdgpu_buffer_rsrc_t rsrc_r = __builtin_amdgcn_make_buffer_rsrc((void*)a.res, 0, y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void*)a.y, 0, y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_r = buffer_rsrc(a.res, y_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_y = buffer_rsrc(a.y, y_bytes);
 
     // work split: workgroup g serves channel slice g % nsl, pixel tiles (g / nsl) + i * (G / nsl)
     const int nsl = a.Cout / 512;
@@ -91,7 +89,7 @@ __global__ void __launch_bounds__(512) conv1x1_wreg_kernel(const ConvArgs a) {
     // loads (residual prefetch) in flight next to the input prefetch, and a counted vmcnt is only a
     // guarantee among loads that return in issue order - LDS-DMA and VGPR loads do not (measured: with
     // the input on LDS-DMA the first tile of every workgroup was computed from a half-landed buffer).
-    // With one kind of load every wait is the compiler's own exact count.
+    // With one type of load every wait is the compiler's own exact count.
     const int spix = (tid >> 3) & 63;                  // pixel row this lane stages (NT / 8 = 64 rows)
     const int sslot = tid & 7;                         // 16-byte chunk of the 128-byte row
     const int sdst = spix * 128 + ((sslot ^ ((spix >> 1) & 7)) << 4);
@@ -110,7 +108,7 @@ __global__ void __launch_bounds__(512) conv1x1_wreg_kernel(const ConvArgs a) {
     auto phys = [&](int t) { return a.rev_m ? mt - 1 - t : t; };
     auto load_x = [&](int t, u32x4_t* xr) {
         const int m = phys(t) * BM + spix;
-        const uint32_t base = m < a.M ? (uint32_t)((m * a.Cin + sslot * 8) * 2) : kOOBr;
+        const uint32_t base = m < a.M ? (uint32_t)((m * a.Cin + sslot * 8) * 2) : kOOB;
 #pragma unroll
         for (int i = 0; i < NX; ++i) xr[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, base, i * 128, 0);
     };
@@ -120,7 +118,7 @@ __global__ void __launch_bounds__(512) conv1x1_wreg_kernel(const ConvArgs a) {
     };
     // residual of one 32-pixel strip (this wave's 64 channels): 4 x 16 B per lane
     const uint32_t ncol2 = (uint32_t)((n_wave + ecol) * 2);
-    auto row_off = [&](int m) { return m < a.M ? (uint32_t)m * (uint32_t)(a.Cout * 2) + ncol2 : kOOBr; };
+    auto row_off = [&](int m) { return m < a.M ? (uint32_t)m * (uint32_t)(a.Cout * 2) + ncol2 : kOOB; };
     auto load_res = [&](int t, int j, u32x4_t* r) {
 #pragma unroll
         for (int pass = 0; pass < 4; ++pass)
@@ -184,9 +182,7 @@ __global__ void __launch_bounds__(512) conv1x1_wreg_kernel(const ConvArgs a) {
                     const f32x4_t v = {acc[i][4 * g + 0], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]};
                     *(f32x4_t*)(ebase + lrow * EROW + (i * 32 + 8 * g + 4 * lhi) * 4) = v;
                 }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
 #pragma unroll
             for (int pass = 0; pass < 4; ++pass) {
                 const int mrow = pass * 8 + erow;
@@ -198,27 +194,14 @@ __global__ void __launch_bounds__(512) conv1x1_wreg_kernel(const ConvArgs a) {
                     float v[8] = {f0[0] + b0[0], f0[1] + b0[1], f0[2] + b0[2], f0[3] + b0[3],
                                   f1[0] + b1[0], f1[1] + b1[1], f1[2] + b1[2], f1[3] + b1[3]};
                     const u32x4_t rv = j == 0 ? rres0[pass] : rres1[pass];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float lo, hi;
-                        DT::unpack(rv[e], lo, hi);
-                        v[2 * e] += lo;
-                        v[2 * e + 1] += hi;
-                    }
-                    if (a.relu) {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                    }
-                    u32x4_t ov;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) ov[e] = DT::pack(v[2 * e], v[2 * e + 1]);
+                    add_res8<DT>(v, rv);
+                    if (a.relu) relu8(v);
+                    const u32x4_t ov = pack8<DT>(v);
                     __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y, row_off(m), 0, 0);
                     ovf.see(ov);
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             if (j == 0) load_res(next, 0, rres0);   // next tile's strip 0, one tile ahead
         }
         if (!more) break;
@@ -248,8 +231,7 @@ static hipError_t launch_wreg(const ConvArgs& a, hipStream_t stream) {
     static std::atomic<uint64_t> attr_done{0};
     if (hipError_t e = ensure_dynamic_lds((const void*)kern, LDS, attr_done); e != hipSuccess) return e;
     ConvArgs b = a;
-    b.x_bytes = (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 2);
-    b.w_bytes = (uint32_t)((size_t)a.Cout * a.Ktot * 2);
+    conv_fill_extents(b);
     const int nsl = a.Cout / 512;
     const int mt = (a.M + 63) / 64;
     int per = 256 / nsl;                       // one persistent workgroup per CU

@@ -18,6 +18,7 @@
 // [64 px][256 ch] 16-bit staging tile (16-byte chunks XOR-swizzled by the pixel row); the memory waves store the tile as
 // 512-byte pixel rows (16 bytes per lane, consecutive lanes consecutive chunks).
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 #ifndef DIR_WREGD_ABL   // experiment builds only (scripts/exp_abl.sh conv_wregd DIR_WREGD_ABL <bits>): 1 no MFMAs, 2 no stores,
@@ -25,8 +26,6 @@
 #endif
 
 namespace dir {
-
-static constexpr uint32_t kOOBd = 0x80000000u;
 
 // KB1 / KB2 = 64-channel blocks of the first (flat) / second (strided) source
 //
@@ -77,10 +76,10 @@ __global__ void __launch_bounds__(768) conv1x1_wregd_kernel(const ConvArgs a) {
     if (wave >= 8) {
         // ================================ memory waves ================================================================
         const int mtid = tid - 512;                        // 0 .. 255
-        const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsrc_x2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.x2, 0, a.x2_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
+        const __amdgpu_buffer_rsrc_t rsrc_x2 = buffer_rsrc(a.x2, a.x2_bytes);
         const uint32_t y_bytes = (uint32_t)((size_t)a.M * a.Cout * 2);
-        const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc((void*)a.y, 0, y_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_y = buffer_rsrc(a.y, y_bytes);
         // input tile image in LDS: block kb (64 channels), pixel row p, 16-byte chunk c at
         //   kb*8192 + p*128 + ((c ^ ((p >> 1) & 7)) << 4)           (conv_igemm's swizzle); staged through registers:
         // a lane carries chunk `sslot` of pixel rows spix and spix + 32, all KB blocks (2 KB registers)
@@ -96,7 +95,7 @@ __global__ void __launch_bounds__(768) conv1x1_wregd_kernel(const ConvArgs a) {
                 const bool in = m < a.M;
                 const uint32_t mm = in ? (uint32_t)m : 0u;
                 const uint32_t off1 = (mm * (uint32_t)a.Cin + sslot * 8) * 2;
-                const uint32_t base = in ? off1 : kOOBd;
+                const uint32_t base = in ? off1 : kOOB;
 #pragma unroll
                 for (int i = 0; i < KB1; ++i) xr[h * KB + i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, base, i * 128, 0);
                 // output pixel -> pixel (oh * stride2, ow * stride2) of the second source
@@ -105,7 +104,7 @@ __global__ void __launch_bounds__(768) conv1x1_wregd_kernel(const ConvArgs a) {
                 const uint32_t oh = __umulhi(rem, a.div_ow_mul) >> a.div_ow_shr;
                 const uint32_t ow = rem - oh * (uint32_t)a.OW;
                 const uint32_t off2 = (((b * a.H2 + oh * a.stride2) * a.W2 + ow * a.stride2) * a.Cin2 + sslot * 8) * 2;
-                const uint32_t base2 = (DIR_WREGD_ABL & 4) ? (in ? (mm * (uint32_t)a.Cin2 + sslot * 8) * 2 : kOOBd) : (in ? off2 : kOOBd);
+                const uint32_t base2 = (DIR_WREGD_ABL & 4) ? (in ? (mm * (uint32_t)a.Cin2 + sslot * 8) * 2 : kOOB) : (in ? off2 : kOOB);
 #pragma unroll
                 for (int i = 0; i < KB2; ++i)
                     xr[h * KB + KB1 + i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_x2, base2, i * 128, 0);
@@ -126,7 +125,7 @@ __global__ void __launch_bounds__(768) conv1x1_wregd_kernel(const ConvArgs a) {
                 const int pix = k * 8 + cpix;
                 const u32x4_t ov = *(const u32x4_t*)(sb + pix * SROW + ((cchunk ^ (pix & 31)) << 4));
                 const int m = m0 + pix;
-                const uint32_t off = m < a.M ? (uint32_t)m * (uint32_t)(a.Cout * 2) + ycol : kOOBd;
+                const uint32_t off = m < a.M ? (uint32_t)m * (uint32_t)(a.Cout * 2) + ycol : kOOB;
                 if (!(DIR_WREGD_ABL & 2)) __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y, off, 0, 0);
             }
         };
@@ -245,18 +244,7 @@ static hipError_t launch_wregd(const ConvArgs& a, hipStream_t stream) {
     static std::atomic<uint64_t> attr_done{0};
     if (hipError_t e = ensure_dynamic_lds((const void*)kern, LDS, attr_done); e != hipSuccess) return e;
     ConvArgs b = a;
-    b.x_bytes = (uint32_t)((size_t)a.B * a.H * a.W * a.Cin * 2);
-    b.x2_bytes = (uint32_t)((size_t)a.B * a.H2 * a.W2 * a.Cin2 * 2);
-    b.w_bytes = (uint32_t)((size_t)a.Cout * a.Ktot * 2);
-    auto fd = [](uint32_t d, uint32_t& mul, uint32_t& shr) {   // exact n / d for n < 2^31 (conv_igemm.hip's constants)
-        if (d <= 1) { mul = 0; shr = 0; return; }
-        uint32_t l = 0;
-        while ((1ull << l) < d) ++l;
-        mul = (uint32_t)(((1ull << (31 + l)) + d - 1) / d);
-        shr = l - 1;
-    };
-    fd((uint32_t)(a.OH * a.OW), b.div_ohw_mul, b.div_ohw_shr);
-    fd((uint32_t)a.OW, b.div_ow_mul, b.div_ow_shr);
+    conv_fill_extents(b);   // (admissible only with x2 set)
     const int nsl = a.Cout / 256;
     const int mt = (a.M + 63) / 64;
     int per = cu_count() / nsl;                // one persistent workgroup per CU
@@ -267,7 +255,8 @@ static hipError_t launch_wregd(const ConvArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t conv1x1_wregd_bf16(const ConvArgs& a, hipStream_t stream) { return launch_wregd<BF16, 2, 4>(a, stream); }
-hipError_t conv1x1_wregd_fp16(const ConvArgs& a, hipStream_t stream) { return launch_wregd<FP16, 2, 4>(a, stream); }
+hipError_t conv1x1_wregd_launch(const ConvArgs& a, int dtype, hipStream_t stream) {
+    return dtype == DIR_BF16 ? launch_wregd<BF16, 2, 4>(a, stream) : launch_wregd<FP16, 2, 4>(a, stream);
+}
 
 }  // namespace dir

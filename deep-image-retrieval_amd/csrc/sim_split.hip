@@ -33,6 +33,7 @@
 // k), so their re-streaming from L2 is a linear copy.  Three stages of (32 KB database + 18 KB query planes) in LDS,
 // two in flight; one barrier per K slab.  Algorithmic bytes per launch: N*K*4 (database, once) + Q*N*4 (scores).
 #include "dir_common.h"
+#include "conv_device.h"
 
 namespace dir {
 
@@ -49,10 +50,6 @@ static constexpr int kSlabQ2 = 2 * kPlane;        // 12288
 static constexpr int kStage2 = kSlabP + kSlabQ2;  // 45056
 static constexpr int kLds2 = kStages * kStage2;   // 135168
 static constexpr float kPairScale = 1024.f;       // 2^10: |x| < 64 stays finite in fp16, unit-vector entries mid-range
-
-__device__ __forceinline__ void dma16s(__amdgpu_buffer_rsrc_t rsrc, char* lds, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DIR_LDS void*)lds, 16, voff, soff, 0, 0);
-}
 
 // x0, x1 -> packed bf16 planes (low half = x0)
 __device__ __forceinline__ void split2(float x0, float x1, uint32_t& h, uint32_t& m, uint32_t& l) {
@@ -117,10 +114,8 @@ __global__ void __launch_bounds__(512) sim_split_kernel(const float* __restrict_
     const int rows = min(kRowsP, NP - i0);
 
     // the database can exceed the 4 GB a buffer descriptor spans: one descriptor per workgroup, based at its rows
-    const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(P + (size_t)i0 * ldp), 0, (int)((((size_t)rows - 1) * ldp + K) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_q = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)img + (size_t)qb * T * kSlabQ), 0, T * kSlabQ, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (int)((((size_t)rows - 1) * ldp + K) * 4));
+    const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc((const char*)img + (size_t)qb * T * kSlabQ, T * kSlabQ);
 
     // database: instruction j = i * 8 + wave covers rows 8j .. 8j+7 (8 lanes x 16 bytes = one 128-byte piece)
     uint32_t pvoff[4];
@@ -134,11 +129,11 @@ __global__ void __launch_bounds__(512) sim_split_kernel(const float* __restrict_
 
     auto issue = [&](int u, char* stage) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) dma16s(rsrc_p, stage + (i * 8 + wave) * 1024, pvoff[i], (uint32_t)u * 128u);
+        for (int i = 0; i < 4; ++i) dma16(rsrc_p, stage + (i * 8 + wave) * 1024, pvoff[i], (uint32_t)u * 128u);
         char* qd = stage + kSlabP + wave * (kSlabQ / 8);
-        dma16s(rsrc_q, qd, qvoff, (uint32_t)u * kSlabQ);
-        dma16s(rsrc_q, qd + 1024, qvoff + 1024, (uint32_t)u * kSlabQ);
-        if (lane < 16) dma16s(rsrc_q, qd + 2048, qvoff + 2048, (uint32_t)u * kSlabQ);
+        dma16(rsrc_q, qd, qvoff, (uint32_t)u * kSlabQ);
+        dma16(rsrc_q, qd + 1024, qvoff + 1024, (uint32_t)u * kSlabQ);
+        if (lane < 16) dma16(rsrc_q, qd + 2048, qvoff + 2048, (uint32_t)u * kSlabQ);
     };
     constexpr int kOps = 7;   // LDS-DMA instructions per wave per stage
 
@@ -258,10 +253,8 @@ __global__ void __launch_bounds__(768) sim_split_lc_kernel(const float* __restri
     if (wave >= 8) {
         // ================================ loaders ==============================================================
         const int lw = wave - 8;
-        const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(P + (size_t)i0 * ldp), 0, (int)((((size_t)rows - 1) * ldp + K) * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsrc_q = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)((const char*)img + (size_t)qb * T * kSlabQ), 0, T * kSlabQ, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (int)((((size_t)rows - 1) * ldp + K) * 4));
+        const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc((const char*)img + (size_t)qb * T * kSlabQ, T * kSlabQ);
         // database piece j = lw * 8 + i covers rows 8j .. 8j+7 (8 lanes x 16 bytes = one 128-byte run per row)
         uint32_t pvoff[8];
 #pragma unroll
@@ -279,12 +272,12 @@ __global__ void __launch_bounds__(768) sim_split_lc_kernel(const float* __restri
             char* stage = smem + (t % kStages) * kStage;
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                if (!(DIR_SIM_ABL & 1)) dma16s(rsrc_p, stage + (lw * 8 + i) * 1024, pvoff[i], (uint32_t)u * 128u);
+                if (!(DIR_SIM_ABL & 1)) dma16(rsrc_p, stage + (lw * 8 + i) * 1024, pvoff[i], (uint32_t)u * 128u);
 #pragma unroll
             for (int i = 0; i < (PAIR ? 3 : 4); ++i)
                 if (!(DIR_SIM_ABL & 2))
-                    dma16s(rsrc_q, stage + kSlabP + (q0 + i) * 1024, (uint32_t)((q0 + i) * 1024 + lane * 16), (uint32_t)u * kSlabQ);
-            if (five && !(DIR_SIM_ABL & 2)) dma16s(rsrc_q, stage + kSlabP + (q0 + 4) * 1024, (uint32_t)((q0 + 4) * 1024 + lane * 16), (uint32_t)u * kSlabQ);
+                    dma16(rsrc_q, stage + kSlabP + (q0 + i) * 1024, (uint32_t)((q0 + i) * 1024 + lane * 16), (uint32_t)u * kSlabQ);
+            if (five && !(DIR_SIM_ABL & 2)) dma16(rsrc_q, stage + kSlabP + (q0 + 4) * 1024, (uint32_t)((q0 + 4) * 1024 + lane * 16), (uint32_t)u * kSlabQ);
         };
         issue(0);
         if (T > 1) issue(1);
@@ -422,10 +415,8 @@ __global__ void __launch_bounds__(768) whiten_split_kernel(const float* __restri
     if (wave >= 8) {
         // ================================ loaders (as sim_split_lc_kernel<true>) ================================
         const int lw = wave - 8;
-        const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(P + (size_t)i0 * ldp), 0, (int)((((size_t)rows - 1) * ldp + K) * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsrc_q = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)((const char*)img + (size_t)qb * T * kSlabQ), 0, T * kSlabQ, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (int)((((size_t)rows - 1) * ldp + K) * 4));
+        const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc((const char*)img + (size_t)qb * T * kSlabQ, T * kSlabQ);
         uint32_t pvoff[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -439,10 +430,10 @@ __global__ void __launch_bounds__(768) whiten_split_kernel(const float* __restri
             u = u >= T ? u - T : u;
             char* stage = smem + (t % kStages) * kStage;
 #pragma unroll
-            for (int i = 0; i < 8; ++i) dma16s(rsrc_p, stage + (lw * 8 + i) * 1024, pvoff[i], (uint32_t)u * 128u);
+            for (int i = 0; i < 8; ++i) dma16(rsrc_p, stage + (lw * 8 + i) * 1024, pvoff[i], (uint32_t)u * 128u);
 #pragma unroll
             for (int i = 0; i < 3; ++i)
-                dma16s(rsrc_q, stage + kSlabP + (q0 + i) * 1024, (uint32_t)((q0 + i) * 1024 + lane * 16), (uint32_t)u * kSlabQ);
+                dma16(rsrc_q, stage + kSlabP + (q0 + i) * 1024, (uint32_t)((q0 + i) * 1024 + lane * 16), (uint32_t)u * kSlabQ);
         };
         issue(0);
         if (T > 1) issue(1);

@@ -15,16 +15,12 @@
 // Out-of-image conv outputs are stored as 0, which is exact for the max: every pool window holds
 // at least one real post-ReLU (>= 0) value.
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 
 namespace dir {
 
-static constexpr uint32_t kOOBs = 0x80000000u;
 typedef __attribute__((ext_vector_type(8))) unsigned short u16x8_t;
-
-__device__ __forceinline__ void dma16s(__amdgpu_buffer_rsrc_t rsrc, char* lds, uint32_t voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DIR_LDS void*)lds, 16, voff, soff, 0, 0);
-}
 
 struct StemPoolArgs {
     const uint16_t* x;   // s2d image [B, H2, W2, 16]
@@ -65,10 +61,8 @@ __global__ void __launch_bounds__(256) stem_pool_kernel(const StemPoolArgs a) {
     const int ph0 = ty * PTH, pw0 = tx * PTW;
     const int oy0 = 2 * ph0 - 1, ox0 = 2 * pw0 - 1;  // conv-output origin of the tile
 
-    const __amdgpu_buffer_rsrc_t rsrc_x =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, 64 * 256 * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, 64 * 256 * 2);
 
     // ---- patch (2 planes x 512 slots) and the whole filter ------------------------------------------
 #pragma unroll
@@ -78,8 +72,8 @@ __global__ void __launch_bounds__(256) stem_pool_kernel(const StemPoolArgs a) {
         const int py = p / QW, px = p - py * QW;
         const int iy = oy0 - 2 + py, ix = ox0 - 2 + px;  // s2d pixel (conv pad 2 on top/left)
         const bool ok = p < QP && (unsigned)iy < (unsigned)a.H2 && (unsigned)ix < (unsigned)a.W2;
-        const uint32_t v = ok ? (uint32_t)((((b * a.H2 + iy) * a.W2 + ix) * 16 + plane * 8) * 2) : kOOBs;
-        dma16s(rsrc_x, smem + (i * 256 + wave * 64) * 16, v, 0);
+        const uint32_t v = ok ? (uint32_t)((((b * a.H2 + iy) * a.W2 + ix) * 16 + plane * 8) * 2) : kOOB;
+        dma16(rsrc_x, smem + (i * 256 + wave * 64) * 16, v, 0);
     }
     const int srcchunk = (tid & 7) ^ ((tid >> 4) & 7);
 #pragma unroll
@@ -87,7 +81,7 @@ __global__ void __launch_bounds__(256) stem_pool_kernel(const StemPoolArgs a) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int n = i * 32 + (tid >> 3);
-            dma16s(rsrc_w, smem + WOFF + R * 8192 + (i * 256 + wave * 64) * 16,
+            dma16(rsrc_w, smem + WOFF + R * 8192 + (i * 256 + wave * 64) * 16,
                    (uint32_t)((n * 256 + srcchunk * 8) * 2), R * 128);
         }
 
@@ -209,8 +203,7 @@ __global__ void __launch_bounds__(256, 2) stem_pool_persist_kernel(const StemPoo
     const int tiles_y = (a.PH + PTH - 1) / PTH;
     const int ntiles = a.B * tiles_y * tiles_x;
 
-    const __amdgpu_buffer_rsrc_t rsrc_x =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
 
     // filter fragments: A operand of step (R, ks) for channel tile i = 8 K-elements of row i*32 + lrow
     frag_t wf[4][4][2];
@@ -241,8 +234,8 @@ __global__ void __launch_bounds__(256, 2) stem_pool_persist_kernel(const StemPoo
             const int py = p / QW, px = p - py * QW;
             const int iy = oy0 - 2 + py, ix = ox0 - 2 + px;
             const bool ok = p < QP && (unsigned)iy < (unsigned)a.H2 && (unsigned)ix < (unsigned)a.W2;
-            const uint32_t v = ok ? (uint32_t)((((b * a.H2 + iy) * a.W2 + ix) * 16 + plane * 8) * 2) : kOOBs;
-            dma16s(rsrc_x, dst + (i * 256 + wave * 64) * 16, v, 0);
+            const uint32_t v = ok ? (uint32_t)((((b * a.H2 + iy) * a.W2 + ix) * 16 + plane * 8) * 2) : kOOB;
+            dma16(rsrc_x, dst + (i * 256 + wave * 64) * 16, v, 0);
         }
     };
 
@@ -359,7 +352,7 @@ int stem_pool_launch(const void* s2d, const void* w, const float* bias, void* y,
     a.B = B; a.H2 = H2; a.W2 = W2; a.OH = OH; a.OW = OW;
     a.PH = (OH - 1) / 2 + 1;
     a.PW = (OW - 1) / 2 + 1;
-    a.x_bytes = (uint32_t)((size_t)B * H2 * W2 * 32);
+    a.x_bytes = (uint32_t)((size_t)B * H2 * W2 * 32);   // (its own extent: the space-to-depth plane [B][H2][W2][16], not a ConvArgs tensor)
     a.ovf = ovf;
     const long blocks = (long)B * ((a.PH + 2) / 3) * ((a.PW + 14) / 15);
     if (dtype != DIR_BF16 && dtype != DIR_FP16) return fail(DIR_ERR_INVALID, "stem_pool: bad dtype");

@@ -25,6 +25,7 @@
 //       double, patch buffers triple): ONE barrier per tile.
 // Layouts (patch planes, filter fragments straight in MFMA operand layout, swapped MFMA roles) are conv_pair.hip's.
 #include "dir_common.h"
+#include "conv_device.h"
 #include "conv_igemm.h"
 #include "pointwise.h"
 
@@ -41,11 +42,6 @@
 
 namespace dir {
 
-static constexpr uint32_t kOOBu = 0x80000000u;
-
-__device__ __forceinline__ void dma16u(__amdgpu_buffer_rsrc_t rsrc, char* lds, uint32_t voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (DIR_LDS void*)lds, 16, voff, 0, 0, 0);
-}
 __device__ __forceinline__ void split2u(float a, float b, uint32_t& hi, uint32_t& lo) {
     hi = FP16::pack(a, b);
     float ha, hb;
@@ -134,9 +130,8 @@ __global__ void __launch_bounds__(128 * NRP, NRP == 2 ? 2 : 1) stem_pool_u8_kern
     const int lrow = lane & 31, lhi = lane >> 5;
     const int ci = wave & 1, rp = wave >> 1;     // channel tile, conv row pair
 
-    const __amdgpu_buffer_rsrc_t rsrc_x = RAW ? __builtin_amdgcn_make_buffer_rsrc((void*)a.img, 0, a.img_bytes, 0x00020000)
-                                              : __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_xl = __builtin_amdgcn_make_buffer_rsrc((void*)(XPAIR ? a.xl : a.x), 0, a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = RAW ? buffer_rsrc(a.img, a.img_bytes) : buffer_rsrc(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_xl = buffer_rsrc(XPAIR ? a.xl : a.x, a.x_bytes);
 
     // ---- the filter pair of this wave's channel tile, straight in MFMA operand layout (128 VGPRs, fetched once) ----------
     frag_t wfh[4][4], wfl[4][4];
@@ -188,13 +183,13 @@ __global__ void __launch_bounds__(128 * NRP, NRP == 2 ? 2 : 1) stem_pool_u8_kern
         const int iy = d.c - 2 + ppy, ix = 2 * d.pw0 - 3 + ppx;
         const bool ok = tid < QP && (unsigned)iy < (unsigned)a.H2 && (unsigned)ix < (unsigned)a.W2;
         const int base = ((d.b * a.H2 + d.c - 2) * a.W2 + 2 * d.pw0 - 3) * 32;       // (wave-uniform)
-        const uint32_t v = ok ? (uint32_t)(base + ppoff) : kOOBu;
+        const uint32_t v = ok ? (uint32_t)(base + ppoff) : kOOB;
         if (DIR_STEMU8_ABL & 4) return;
-        dma16u(rsrc_x, dst + (wave * 64) * 16, v);
-        dma16u(rsrc_x, dst + (NT + wave * 64) * 16, ok ? v + 16 : kOOBu);
+        dma16(rsrc_x, dst + (wave * 64) * 16, v, 0);
+        dma16(rsrc_x, dst + (NT + wave * 64) * 16, ok ? v + 16 : kOOB, 0);
         if (XPAIR) {
-            dma16u(rsrc_xl, dst + (2 * NT + wave * 64) * 16, v);
-            dma16u(rsrc_xl, dst + (3 * NT + wave * 64) * 16, ok ? v + 16 : kOOBu);
+            dma16(rsrc_xl, dst + (2 * NT + wave * 64) * 16, v, 0);
+            dma16(rsrc_xl, dst + (3 * NT + wave * 64) * 16, ok ? v + 16 : kOOB, 0);
         }
     };
 
@@ -205,21 +200,21 @@ __global__ void __launch_bounds__(128 * NRP, NRP == 2 ? 2 : 1) stem_pool_u8_kern
         const bool ok = tid < QP && (unsigned)iy < (unsigned)a.H2 && (unsigned)ix < (unsigned)a.W2;
         if (XPAIR) {   // fp32 NCHW: floats (c, 2 iy + dy, 2 ix) and (.., 2 ix + 1) as one 8-byte load; W even keeps them 8-byte aligned
             const int plane = a.H * a.W;
-            const uint32_t o0 = ok ? (uint32_t)((((d.b * 3) * a.H + 2 * iy) * a.W + 2 * ix) * 4) : kOOBu;
+            const uint32_t o0 = ok ? (uint32_t)((((d.b * 3) * a.H + 2 * iy) * a.W + 2 * ix) * 4) : kOOB;
             const bool row1 = ok && 2 * iy + 1 < a.H;
 #pragma unroll
             for (int c = 0; c < 3; ++c)
 #pragma unroll
                 for (int dy = 0; dy < 2; ++dy) {
-                    const uint32_t o = (dy == 0 ? ok : row1) ? o0 + (uint32_t)((c * plane + dy * a.W) * 4) : kOOBu;
+                    const uint32_t o = (dy == 0 ? ok : row1) ? o0 + (uint32_t)((c * plane + dy * a.W) * 4) : kOOB;
                     const u32x2_t v = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_raw_buffer_load_b64(rsrc_x, o, 0, 0));
                     rw[(c * 2 + dy) * 2] = v[0];
                     rw[(c * 2 + dy) * 2 + 1] = v[1];
                 }
             return;
         }
-        const uint32_t o0 = ok ? (uint32_t)(((d.b * a.H + 2 * iy) * a.W + 2 * ix) * 3) : kOOBu;      // offsets >= 2^31 read as 0
-        const uint32_t o1 = (ok && 2 * iy + 1 < a.H) ? o0 + (uint32_t)(a.W * 3) : kOOBu;
+        const uint32_t o0 = ok ? (uint32_t)(((d.b * a.H + 2 * iy) * a.W + 2 * ix) * 3) : kOOB;      // offsets >= 2^31 read as 0
+        const uint32_t o1 = (ok && 2 * iy + 1 < a.H) ? o0 + (uint32_t)(a.W * 3) : kOOB;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             rw[k] = __builtin_amdgcn_raw_buffer_load_b16(rsrc_x, o0 + 2 * k, 0, 0);
@@ -634,7 +629,7 @@ int stem_pool_u8_launch(const void* img, const void* s2d, const void* w_hi, cons
     a.PW = (a.OW - 1) / 2 + 1;
     if (!raw && (size_t)B * a.H2 * a.W2 * 32 >= (1ull << 31))
         return fail(DIR_ERR_INVALID, "stem_pool_u8: input exceeds 2^31 bytes; lower the batch");
-    a.x_bytes = raw ? 0 : (uint32_t)((size_t)B * a.H2 * a.W2 * 32);
+    a.x_bytes = raw ? 0 : (uint32_t)((size_t)B * a.H2 * a.W2 * 32);   // (its own extent: the space-to-depth plane [B][H2][W2][16], not a ConvArgs tensor)
     a.tiles_x = (a.PW + 14) / 15;
     // NRP = 2 (two 4-wave workgroups per CU) unless DIRTORCH_AMD_STEM_U8_WG8 asks for the one-workgroup form.
     // Segment length: seg_rows = 2 T' - 1 pooled rows are exactly T' tiles of TH conv rows (no wasted row); 31 unless that leaves
@@ -710,7 +705,7 @@ int stem_pool_pair_walk_launch(const void* s2d_hi, const void* s2d_lo, const voi
     a.H2 = H2; a.W2 = W2; a.OH = OH; a.OW = OW;
     a.PH = (OH - 1) / 2 + 1;
     a.PW = (OW - 1) / 2 + 1;
-    a.x_bytes = raw ? 0 : (uint32_t)((size_t)B * H2 * W2 * 32);
+    a.x_bytes = raw ? 0 : (uint32_t)((size_t)B * H2 * W2 * 32);   // (its own extent: the space-to-depth plane [B][H2][W2][16], not a ConvArgs tensor)
     a.tiles_x = (a.PW + 14) / 15;
     const int cus = cu_count(), slots = 2 * cus;
     int T = 8;

@@ -359,6 +359,47 @@ def test_every_pair_the_picker_emits_has_a_picker_case():
     assert len(wl_pairs) >= 20 and len(classes) >= 20, (len(wl_pairs), len(classes))
 
 
+DISPATCH_SHAPES = 56769
+DISPATCH_DIGEST = 'c1d80d7c215354b7fb0c125c97910e8423f66988c91d5da94189f2ab7f3c241b'
+
+
+def test_host_dispatch_digest_is_unchanged():
+    """The host side of conv dispatch as one number: under the default switches, SHA-256 over (picked variant, ksplit) of
+    every shape of the synthetic grid and the claimed workloads, and over every variant's admissibility bit (and, where
+    admissible, its split-K factor) on those shapes.  The constant was taken from the library as it stood before the variant
+    table learned to dispatch itself; a table or picker refactor must leave it alone (a deliberate picker change moves it
+    together with tests/picker_cases.py)."""
+    import ctypes
+    import hashlib
+    import picker_cases as P
+    from dirtorch_amd import _lib, ops
+    saved = {k: os.environ.pop(k) for k in list(os.environ) if k.startswith('DIRTORCH_AMD_') and k != 'DIRTORCH_AMD_LIB'}
+    try:
+        lib = _lib.load()
+        _lib.reload_env()
+        nv = len(ops.conv_variant_names())
+        shapes = list(P.synthetic_grid()) + [l[2:11] for l in P.workload_layers()]
+        h, out, buf = hashlib.sha256(), ctypes.c_int(), ctypes.create_string_buffer(64)
+        pout = ctypes.byref(out)
+        adm, spl = lib.dir_conv_variant_admissible, lib.dir_conv_variant_splitk   # (bound once: 2 M calls)
+        for B, H, W, Cin, Cout, k, stride, pad, res in shapes:
+            OH, OW = P.out_hw(H, W, k, stride, pad)
+            geo = (B, H, W, Cin, Cout, k, k, stride, pad, OH, OW, int(res))
+            assert lib.dir_conv_heuristic(*geo, buf, 64, pout) == 0
+            rec = ['%s/%d' % (buf.value.decode(), out.value)]
+            for v in range(nv):
+                assert adm(v, *geo, pout) == 0
+                if out.value:
+                    assert spl(v, *geo, pout) == 0
+                    rec.append('%d:%d' % (v, out.value))
+            h.update((' '.join(rec) + '\n').encode())
+    finally:
+        os.environ.update(saved)
+        _lib.reload_env()
+    assert len(shapes) == DISPATCH_SHAPES
+    assert h.hexdigest() == DISPATCH_DIGEST
+
+
 def test_engine_cases_cover_every_launch_form_in_every_regime():
     """tests/engine_cases.py (the engine's seams, two-source GEMMs, paired convs and stems; tests/test_engine_launch_parity_gpu.py
     runs it) against its mirror of the engine's choices and against launch_geometry:

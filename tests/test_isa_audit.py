@@ -129,5 +129,14 @@ def test_lds_writes_complete_before_the_barrier_that_publishes_them(asm):
 
 
 def test_no_kernel_calls_the_raw_barrier_builtin():
-    for f in glob.glob(os.path.join(CSRC, '*.hip')):
-        assert '__builtin_amdgcn_s_barrier' not in open(f).read(), '%s: use ring_barrier() (dir_common.h)' % os.path.basename(f)
+    """No source and no header calls the raw builtin, except the one call that IS ring_barrier() (dir_common.h): a raw barrier
+    cannot come back through a shared header (conv_device.h) either."""
+    files = sorted(glob.glob(os.path.join(CSRC, '*.hip')) + glob.glob(os.path.join(CSRC, '*.h')))
+    assert len(files) >= 30 and os.path.join(CSRC, 'conv_device.h') in files
+    for f in files:
+        src = open(f).read()
+        if os.path.basename(f) == 'dir_common.h':
+            body = re.search(r'__device__ __forceinline__ void ring_barrier\(\) \{\n(.*?)\n\}\n', src, re.S)
+            assert body and body.group(1).count('__builtin_amdgcn_s_barrier') == 1
+            src = src.replace(body.group(0), '')
+        assert '__builtin_amdgcn_s_barrier' not in src, '%s: use ring_barrier() (dir_common.h)' % os.path.basename(f)
