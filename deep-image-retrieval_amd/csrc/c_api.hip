@@ -721,6 +721,16 @@ int dir_gemm_nt_f32(const float* P, int ldp, const float* Q, int ldq, float* out
     DIR_CATCH
 }
 
+/* host-only: R, the rows one fp32 chain of dir_cov_accumulate runs over before it is folded into fp64 */
+int dir_cov_chain_rows(void) { return cov_chain_rows(); }
+
+int dir_cov_accumulate(const float* X, int ldx, int N, int D, const float* shift, double* gram, double* sums,
+                       void* stream) {
+    DIR_TRY
+    return cov_accumulate(X, ldx, N, D, shift, gram, sums, (hipStream_t)stream);   // (validates its arguments before any HIP call)
+    DIR_CATCH
+}
+
 int dir_fc_l2(const float* x, int B, int K, const float* W, const float* b, int D, float* out,
               void* stream) {
     DIR_TRY

@@ -55,6 +55,10 @@ int gemm_splitk_factor(int NP, int NQ, int K);
 int gemm_nt_f32(const float* P, int ldp, const float* Q, int ldq, float* out, int ldo, int NP,
                 int NQ, int K, const float* qsub, const float* bias, const float* alpha,
                 hipStream_t stream, float* scratch = nullptr, size_t scratch_bytes = 0);
+// the N-dependent half of a PCA fit (cov_f32.hip): gram += (X - shift)^T (X - shift), sums += column sums, both fp64
+int cov_chain_rows();
+int cov_accumulate(const float* X, int ldx, int N, int D, const float* shift, double* gram, double* sums,
+                   hipStream_t stream);
 // large-database similarity on the bf16 matrix cores at fp32 accuracy (sim_split.hip)
 size_t similarity_split_workspace_bytes(int NQ, int K);
 bool similarity_split_admissible(const float* P, int ldp, const float* Q, int ldq, int NP, int NQ, int K);

@@ -279,6 +279,36 @@ def gemm_nt(P, Q, qsub=None, bias=None, alpha=None):
     return out
 
 
+def cov_chain_rows():
+    """R of dir_cov_accumulate: the rows one fp32 chain runs over before it is folded into fp64 (host-only query)."""
+    return int(_lib.load().dir_cov_chain_rows())
+
+
+def cov_accumulate(X, shift, gram, sums):
+    """gram += (X - shift)^T (X - shift), sums += column sums of X - shift (dir_cov_accumulate, csrc/cov_f32.hip): the
+    N-dependent half of a PCA fit.  X [N,D] fp32 CUDA with unit column stride and any row pitch >= D (a column slice of
+    a wider tensor is taken as it is), shift [D] fp32, gram [D,D] and sums [D] fp64 contiguous accumulators, updated
+    in place and returned."""
+    for t in (X, shift, gram, sums):
+        if not t.is_cuda:
+            raise ValueError('device tensor expected')
+    if X.dtype != torch.float32 or shift.dtype != torch.float32 or X.dim() != 2:
+        raise TypeError('X [N,D] and shift [D] must be float32')
+    if gram.dtype != torch.float64 or sums.dtype != torch.float64:
+        raise TypeError('gram and sums must be float64')
+    N, D = X.shape
+    if X.is_contiguous() or X.stride(1) != 1 or X.stride(0) < D:
+        X, ldx = X.contiguous(), D
+    else:
+        ldx = X.stride(0)
+    if tuple(shift.shape) != (D,) or tuple(gram.shape) != (D, D) or tuple(sums.shape) != (D,):
+        raise ValueError('shift [D], gram [D,D], sums [D] expected for X [N,D]')
+    if not (shift.is_contiguous() and gram.is_contiguous() and sums.is_contiguous()):
+        raise ValueError('contiguous shift, gram and sums expected')
+    call('dir_cov_accumulate', ptr(X), int(ldx), N, D, ptr(shift), ptr(gram), ptr(sums), stream_ptr())
+    return gram, sums
+
+
 def similarity(queries, database, unit_range=False):
     """scores [Q, N] = queries . database^T, fp32 (dir_similarity).  Databases of >= 32768 rows with a width that
     is a multiple of 32 run as a three-plane bf16 split on the matrix cores (products to 2^-23, fp32

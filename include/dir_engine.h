@@ -382,6 +382,24 @@ int dir_similarity(const float* queries, int Q, const float* database, int N, in
                    void* stream);
 int dir_similarity_unit(const float* queries, int Q, const float* database, int N, int D, float* scores,
                         void* stream);
+/* Fitting a PCA whitening: the N-dependent half, on the device.  The reference has no call to cite - it ships the
+ * Landmarks18_pca image list and no code for the fit; what this feeds is the PCA that dirtorch/utils/common.py:221-232
+ * reads (mean_, components_, explained_variance_), which dirtorch_amd/whitening.py derives on the host from gram and sums.
+ *   a[n][i]     = X[n][i] - shift[i]            (fp32, subtracted at load, before any product: the shifted-data form -
+ *                                                with shift near the column mean the sums sums^T / n correction is tiny)
+ *   gram[i][j] += sum_n a[n][i] * a[n][j]       fp64 [D][D] contiguous, both triangles written, bit-symmetric
+ *   sums[i]    += sum_n a[n][i]                 fp64 [D]
+ *   X: [N,D] fp32 with row pitch ldx >= D; shift: [D] fp32; all device pointers.  Any D >= 1, N >= 0 (N = 0 leaves the
+ *   accumulators untouched, and X may then be NULL); 16-byte loads when D and ldx are multiples of 4 and X, shift 16-byte aligned, an
+ *   element-wise gather otherwise.  The caller zeroes gram and sums before the first call; calls add, so a set of any
+ *   size is fed in chunks.  Products on v_mfma_f32_32x32x2_f32 (exact products, fp32 fma chain); a chain runs over at
+ *   most dir_cov_chain_rows() rows (host-only query) and is then folded into an fp64 accumulator, so every entry is within
+ *   (R + 3) 2^-24 sum_n |a_ni| |a_nj| of the exact sum whatever N is.  Upper-triangle tiles of 128 x 128 x up to 64 row
+ *   slices; the slices' fp64 partials (stream-ordered scratch, hipMallocAsync: slices x tiles x 128 KiB, <= 1024 tiles x
+ *   slices) are added in slice order by a second kernel - no atomics, run-to-run identical. */
+int dir_cov_chain_rows(void);
+int dir_cov_accumulate(const float* X, int ldx, int N, int D, const float* shift, double* gram, double* sums,
+                       void* stream);
 /* K10: multi-scale pooling of S descriptor sets [S][N][D] -> [N][D] (common.py:41-55):
  * mode 0 = mean, 1 = signed-power ("gem") mean with exponent gemp; no final L2 (caller does it). */
 int dir_multiscale_pool(const float* x, float* out, int S, int N, int D, int mode, float gemp,
