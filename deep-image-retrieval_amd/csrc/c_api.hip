@@ -1,5 +1,6 @@
 // c_api.hip — the extern "C" surface declared in include/dir_engine.h.
 // Nothing above this file knows about Python or torch; nothing below it throws.
+#include <initializer_list>
 #include <new>
 
 #include "engine.h"
@@ -118,8 +119,7 @@ int dir_workspace_bytes(const dir_engine* e, int B, int H, int W, size_t* bytes)
     DIR_TRY
     if (!e || !bytes) return fail(DIR_ERR_INVALID, "workspace_bytes: null argument");
     Plan p;
-    int rc = e->plan(B, H, W, &p);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(e->plan(B, H, W, &p));
     *bytes = p.total;
     return DIR_OK;
     DIR_CATCH
@@ -144,12 +144,7 @@ int dir_conv_bn_act_f32(const float* x, const float* w, const float* bias, const
     if (OH != (H + 2 * pad - R) / stride + 1 || OW != (W + 2 * pad - S) / stride + 1)
         return fail(DIR_ERR_INVALID, "conv_bn_act_f32: OH/OW do not match the conv geometry");
     ConvF32Args a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.w = w; a.bias = bias; a.res = res; a.y = y;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.OH = OH; a.OW = OW; a.Cout = Cout;
-    a.R = R; a.S = S; a.stride = stride; a.pad = pad; a.relu = relu;
-    a.M = B * OH * OW;
-    a.Ktot = R * S * Cin;
+    conv_geom_fill(a, {B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, relu}, x, w, bias, res, y);
     return conv_f32_launch(a, (hipStream_t)stream);
     DIR_CATCH
 }
@@ -164,16 +159,12 @@ int dir_conv_bn_act_pair(const void* x_hi, const void* x_lo, const void* w_hi, c
     if (OH != (H + 2 * pad - R) / stride + 1 || OW != (W + 2 * pad - S) / stride + 1 || OH <= 0 || OW <= 0)
         return fail(DIR_ERR_INVALID, "conv_bn_act_pair: OH/OW do not match the conv geometry");
     ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = (const uint16_t*)x_hi; a.x_lo = (const uint16_t*)x_lo;
-    a.w = (const uint16_t*)w_hi; a.w_lo = (const uint16_t*)w_lo;
-    a.bias = bias;
-    a.res = (const uint16_t*)res_hi; a.res_lo = (const uint16_t*)res_lo;
-    a.y = (uint16_t*)y_hi; a.y_lo = (uint16_t*)y_lo;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.OH = OH; a.OW = OW; a.Cout = Cout;
-    a.R = R; a.S = S; a.stride = stride; a.pad = pad; a.relu = relu ? 1 : 0;
-    a.M = B * OH * OW;
-    a.Ktot = R * S * Cin;
+    conv_args_init(a, {B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, relu ? 1 : 0}, (const uint16_t*)x_hi, (const uint16_t*)w_hi,
+                   bias, (const uint16_t*)res_hi, (uint16_t*)y_hi);
+    a.x_lo = (const uint16_t*)x_lo;
+    a.w_lo = (const uint16_t*)w_lo;
+    a.res_lo = (const uint16_t*)res_lo;
+    a.y_lo = (uint16_t*)y_lo;
     return conv_pair_launch(a, (hipStream_t)stream);
     DIR_CATCH
 }
@@ -186,16 +177,12 @@ int dir_conv_pair_dual(const void* t2_hi, const void* t2_lo, const void* x_hi, c
         return fail(DIR_ERR_INVALID, "conv_pair_dual: null argument");
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return fail(DIR_ERR_INVALID, "conv_pair_dual: bad dimension");
     ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = (const uint16_t*)t2_hi; a.x_lo = (const uint16_t*)t2_lo;
-    a.x2 = (const uint16_t*)x_hi; a.x2_lo = (const uint16_t*)x_lo;
-    a.w = (const uint16_t*)wcat_hi; a.w_lo = (const uint16_t*)wcat_lo;
-    a.bias = bias;
-    a.y = (uint16_t*)y_hi; a.y_lo = (uint16_t*)y_lo;
-    a.B = B; a.H = a.OH = H; a.W = a.OW = W; a.Cin = a.Cin2 = Cin; a.Cout = Cout;
-    a.R = a.S = 1; a.stride = 1; a.relu = relu ? 1 : 0;
-    a.M = B * H * W;
-    a.Ktot = 2 * Cin;
+    conv_args_init(a, {B, H, W, Cin, Cout, 1, 1, 1, 0, H, W, relu ? 1 : 0}, (const uint16_t*)t2_hi, (const uint16_t*)wcat_hi, bias,
+                   nullptr, (uint16_t*)y_hi);
+    a.x_lo = (const uint16_t*)t2_lo;
+    a.w_lo = (const uint16_t*)wcat_lo;
+    a.y_lo = (uint16_t*)y_lo;
+    conv_args_second_source(a, (const uint16_t*)x_hi, (const uint16_t*)x_lo, Cin);
     return conv_pair_launch(a, (hipStream_t)stream);
     DIR_CATCH
 }
@@ -229,8 +216,7 @@ int dir_stem_pool_u8(const void* img_u8, const float* w_oihw, const float* bn_sc
     if (B <= 0 || H < 7 || W < 7) return fail(DIR_ERR_INVALID, "stem_pool_u8: bad dimension (the image must hold the 7x7 filter)");
     std::vector<uint16_t> hi, lo;
     std::vector<float> b2, corr;
-    int rc = fold_stem_u8(w_oihw, bn_scale, bn_bias, mean3, std3, hi, lo, b2, corr);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(fold_stem_u8(w_oihw, bn_scale, bn_bias, mean3, std3, hi, lo, b2, corr));
     // (a per-call upload: this is the parity entry point; the engine folds once at finalize and keeps the tables)
     char* d = nullptr;
     const size_t nw = hi.size() * 2, nb = b2.size() * 4, nc = corr.size() * 4;
@@ -244,7 +230,7 @@ int dir_stem_pool_u8(const void* img_u8, const float* w_oihw, const float* bn_sc
         return fail(DIR_ERR_HIP, std::string("stem_pool_u8 upload: ") + hipGetErrorString(e));
     }
     const bool raw = stem_pool_u8_raw_ok(img_u8, B, H, W);
-    rc = raw ? DIR_OK : prep_input_u8(img_u8, s2d_ws, B, H, W, (hipStream_t)stream);
+    int rc = raw ? DIR_OK : prep_input_u8(img_u8, s2d_ws, B, H, W, (hipStream_t)stream);
     if (rc == DIR_OK)
         rc = stem_pool_u8_launch(raw ? img_u8 : nullptr, s2d_ws, d, d + nw, (const float*)(d + 2 * nw), (const float*)(d + 2 * nw + nb), y_hi, y_lo, B, H, W,
                                  (hipStream_t)stream, nullptr, seg_tiles);
@@ -385,9 +371,18 @@ int dir_conv_variant_name(int variant, char* buf, int cap) {
     return DIR_OK;
 }
 
+// Validates the arguments every 16-bit per-op conv shares and builds its ConvArgs (ovf and partial stay null here).
 static int fill_conv_args(ConvArgs& a, const void* x, const void* w, const float* bias,
                           const void* res, void* y, int B, int H, int W, int Cin, int Cout, int R,
-                          int S, int stride, int pad, int OH, int OW, int relu);
+                          int S, int stride, int pad, int OH, int OW, int relu) {
+    if (!x || !w || !bias || !y) return fail(DIR_ERR_INVALID, "conv: null pointer");
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || R <= 0 || S <= 0 || stride <= 0 ||
+        pad < 0 || OH <= 0 || OW <= 0)
+        return fail(DIR_ERR_INVALID, "conv: bad dimension");
+    conv_args_init(a, {B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, relu ? 1 : 0}, (const uint16_t*)x, (const uint16_t*)w, bias,
+                   (const uint16_t*)res, (uint16_t*)y);
+    return DIR_OK;
+}
 
 // The shape-only queries below decide on the host: their ConvArgs carries pointers that only have to be non-null (never dereferenced).
 static int shape_only_conv_args(ConvArgs& a, int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int OH,
@@ -402,8 +397,7 @@ int dir_conv_heuristic(int B, int H, int W, int Cin, int Cout, int R, int S, int
     DIR_TRY
     if (!name || cap <= 0) return fail(DIR_ERR_INVALID, "conv_heuristic: null name buffer");
     ConvArgs a;
-    int rc = shape_only_conv_args(a, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, has_residual);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(shape_only_conv_args(a, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, has_residual));
     const int v = conv_pick_variant(a);
     if (v < 0) return fail(DIR_ERR_INVALID, "conv_heuristic: no admissible variant for this shape");
     strncpy(name, conv_variant(v).name, cap - 1);
@@ -419,8 +413,7 @@ int dir_conv_variant_admissible(int variant, int B, int H, int W, int Cin, int C
     if (!admissible) return fail(DIR_ERR_INVALID, "conv_variant_admissible: null result pointer");
     if (variant < 0 || variant >= conv_variant_count()) return fail(DIR_ERR_INVALID, "conv_variant_admissible: no such variant");
     ConvArgs a;
-    int rc = shape_only_conv_args(a, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, has_residual);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(shape_only_conv_args(a, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, has_residual));
     *admissible = conv_variant_admissible(variant, a) ? 1 : 0;
     return DIR_OK;
     DIR_CATCH
@@ -431,8 +424,7 @@ int dir_conv_variant_splitk(int variant, int B, int H, int W, int Cin, int Cout,
     DIR_TRY
     if (!ksplit) return fail(DIR_ERR_INVALID, "conv_variant_splitk: null result pointer");
     ConvArgs a;
-    int rc = shape_only_conv_args(a, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, has_residual);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(shape_only_conv_args(a, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, has_residual));
     if (!conv_variant_admissible(variant, a)) return fail(DIR_ERR_INVALID, "conv_variant_splitk: variant not admissible for this shape");
     const int s = conv_splitk_factor(variant, a);
     *ksplit = s > 1 ? s : 1;
@@ -440,34 +432,12 @@ int dir_conv_variant_splitk(int variant, int B, int H, int W, int Cin, int Cout,
     DIR_CATCH
 }
 
-static int fill_conv_args(ConvArgs& a, const void* x, const void* w, const float* bias,
-                          const void* res, void* y, int B, int H, int W, int Cin, int Cout, int R,
-                          int S, int stride, int pad, int OH, int OW, int relu) {
-    if (!x || !w || !bias || !y) return fail(DIR_ERR_INVALID, "conv: null pointer");
-    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || R <= 0 || S <= 0 || stride <= 0 ||
-        pad < 0 || OH <= 0 || OW <= 0)
-        return fail(DIR_ERR_INVALID, "conv: bad dimension");
-    memset(&a, 0, sizeof(a));
-    a.x = (const uint16_t*)x;
-    a.w = (const uint16_t*)w;
-    a.bias = bias;
-    a.res = (const uint16_t*)res;
-    a.y = (uint16_t*)y;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.OH = OH; a.OW = OW; a.Cout = Cout;
-    a.R = R; a.S = S; a.stride = stride; a.pad = pad; a.relu = relu ? 1 : 0;
-    a.M = B * OH * OW;
-    a.Ktot = R * S * Cin;
-    a.T = a.Ktot / 64;
-    return DIR_OK;
-}
-
 int dir_conv_bn_act(const void* x, const void* w, const float* bias, const void* res, void* y,
                     int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad,
                     int OH, int OW, int relu, int dtype, int variant, void* stream) {
     DIR_TRY
     ConvArgs a;
-    int rc = fill_conv_args(a, x, w, bias, res, y, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, relu);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(fill_conv_args(a, x, w, bias, res, y, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, relu));
     return conv_launch(a, dtype, variant, (hipStream_t)stream);
     DIR_CATCH
 }
@@ -478,8 +448,7 @@ int dir_conv_bn_act_splitk(const void* x, const void* w, const float* bias, cons
                            size_t scratch_bytes, int* ksplit_used, void* stream) {
     DIR_TRY
     ConvArgs a;
-    int rc = fill_conv_args(a, x, w, bias, res, y, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, relu);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(fill_conv_args(a, x, w, bias, res, y, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, relu));
     if (variant < 0) variant = conv_pick_variant(a);
     a.ksplit = ksplit < 0 ? conv_splitk_factor(variant, a) : ksplit;
     a.partial = (float*)scratch;
@@ -490,28 +459,27 @@ int dir_conv_bn_act_splitk(const void* x, const void* w, const float* bias, cons
     DIR_CATCH
 }
 
+// How the four seam entry points end: every tensor 16-byte aligned, then the launch, its hipError_t mapped to a dir_status.
+static int launch_c3c1(const char* who, const ConvArgs& a, int dtype, void* stream, std::initializer_list<const void*> tensors) {
+    for (const void* q : tensors)
+        if ((uintptr_t)q & 15) return fail(DIR_ERR_INVALID, std::string(who) + ": tensors must be 16-byte aligned");
+    hipError_t e = conv_c3c1_launch(a, dtype, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(DIR_ERR_HIP, std::string(who) + " launch: " + hipGetErrorString(e));
+    return DIR_OK;
+}
+
 int dir_conv_c3c1(const void* t2, const void* w3, const float* bias3, const void* res, void* y, const void* w1,
                   const float* bias1, void* t1, int B, int H, int W, int P, int P2, int relu3, int relu1, int dtype,
                   void* stream) {
     DIR_TRY
     ConvArgs a;
-    int rc = fill_conv_args(a, t2, w3, bias3, res, y, B, H, W, P, 4 * P, 1, 1, 1, 0, H, W, relu3);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(fill_conv_args(a, t2, w3, bias3, res, y, B, H, W, P, 4 * P, 1, 1, 1, 0, H, W, relu3));
     if (!w1 || !bias1 || !t1 || !res) return fail(DIR_ERR_INVALID, "conv_c3c1: null pointer");
     if (dtype != DIR_BF16 && dtype != DIR_FP16) return fail(DIR_ERR_INVALID, "conv_c3c1: bad dtype");
-    a.w2 = (const uint16_t*)w1;
-    a.bias2 = bias1;
-    a.y2 = (uint16_t*)t1;
-    a.Cout2 = P2;
-    a.relu2 = relu1 ? 1 : 0;
+    conv_args_next_conv1(a, (const uint16_t*)w1, nullptr, bias1, (uint16_t*)t1, P2, relu1 ? 1 : 0);
     if (!conv_c3c1_admissible(a))
         return fail(DIR_ERR_INVALID, "conv_c3c1: planes must be 64, 128 (P2 = P, or 128 after 64) or 256 (P2 = 256, B*H*W % 64 == 0)");
-    if (((uintptr_t)t2 & 15) || ((uintptr_t)w3 & 15) || ((uintptr_t)res & 15) || ((uintptr_t)y & 15) ||
-        ((uintptr_t)w1 & 15) || ((uintptr_t)t1 & 15) || ((uintptr_t)bias3 & 15) || ((uintptr_t)bias1 & 15))
-        return fail(DIR_ERR_INVALID, "conv_c3c1: tensors must be 16-byte aligned");
-    hipError_t e = conv_c3c1_launch(a, dtype, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DIR_ERR_HIP, std::string("conv_c3c1 launch: ") + hipGetErrorString(e));
-    return DIR_OK;
+    return launch_c3c1("conv_c3c1", a, dtype, stream, {t2, w3, res, y, w1, t1, bias3, bias1});
     DIR_CATCH
 }
 
@@ -520,24 +488,14 @@ int dir_conv_c3c1_ds(const void* t2, const void* x, const void* wcat, const floa
                      void* stream) {
     DIR_TRY
     ConvArgs a;
-    int rc = fill_conv_args(a, t2, wcat, bias, nullptr, y, B, H, W, 64, 256, 1, 1, 1, 0, H, W, relu3);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(fill_conv_args(a, t2, wcat, bias, nullptr, y, B, H, W, 64, 256, 1, 1, 1, 0, H, W, relu3));
     if (!x || !w1 || !bias1 || !t1) return fail(DIR_ERR_INVALID, "conv_c3c1_ds: null pointer");
     if (dtype != DIR_BF16 && dtype != DIR_FP16) return fail(DIR_ERR_INVALID, "conv_c3c1_ds: bad dtype");
     a.x2 = (const uint16_t*)x;
     a.Cin2 = 64;
-    a.w2 = (const uint16_t*)w1;
-    a.bias2 = bias1;
-    a.y2 = (uint16_t*)t1;
-    a.Cout2 = 64;
-    a.relu2 = relu1 ? 1 : 0;
+    conv_args_next_conv1(a, (const uint16_t*)w1, nullptr, bias1, (uint16_t*)t1, 64, relu1 ? 1 : 0);
     if (!conv_c3c1_admissible(a)) return fail(DIR_ERR_INVALID, "conv_c3c1_ds: shape not admissible");
-    if (((uintptr_t)t2 & 15) || ((uintptr_t)x & 15) || ((uintptr_t)wcat & 15) || ((uintptr_t)y & 15) ||
-        ((uintptr_t)w1 & 15) || ((uintptr_t)t1 & 15) || ((uintptr_t)bias & 15) || ((uintptr_t)bias1 & 15))
-        return fail(DIR_ERR_INVALID, "conv_c3c1_ds: tensors must be 16-byte aligned");
-    hipError_t e = conv_c3c1_launch(a, dtype, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DIR_ERR_HIP, std::string("conv_c3c1_ds launch: ") + hipGetErrorString(e));
-    return DIR_OK;
+    return launch_c3c1("conv_c3c1_ds", a, dtype, stream, {t2, x, wcat, y, w1, t1, bias, bias1});
     DIR_CATCH
 }
 
@@ -546,24 +504,13 @@ int dir_conv_c3c1_wpair(const void* t2, const void* w3, const void* w3_lo, const
                         int relu3, int relu1, void* stream) {
     DIR_TRY
     ConvArgs a;
-    int rc = fill_conv_args(a, t2, w3, bias3, res, y, B, H, W, 64, 256, 1, 1, 1, 0, H, W, relu3);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(fill_conv_args(a, t2, w3, bias3, res, y, B, H, W, 64, 256, 1, 1, 1, 0, H, W, relu3));
     if (!w3_lo || !w1 || !bias1 || !t1 || !res) return fail(DIR_ERR_INVALID, "conv_c3c1_wpair: null pointer");
     a.w_lo = (const uint16_t*)w3_lo;
-    a.w2 = (const uint16_t*)w1;
-    a.w2_lo = (const uint16_t*)w1_lo;
-    a.bias2 = bias1;
-    a.y2 = (uint16_t*)t1;
-    a.Cout2 = P2;
-    a.relu2 = relu1 ? 1 : 0;
+    conv_args_next_conv1(a, (const uint16_t*)w1, (const uint16_t*)w1_lo, bias1, (uint16_t*)t1, P2, relu1 ? 1 : 0);
     if (!conv_c3c1_admissible(a))
         return fail(DIR_ERR_INVALID, "conv_c3c1_wpair: planes 64; P2 = 64 (w1_lo required) or 128 (w1_lo optional)");
-    const void* ptrs[] = {t2, w3, w3_lo, res, y, w1, w1_lo, t1, bias3, bias1};
-    for (const void* q : ptrs)
-        if ((uintptr_t)q & 15) return fail(DIR_ERR_INVALID, "conv_c3c1_wpair: tensors must be 16-byte aligned");
-    hipError_t e = conv_c3c1_launch(a, DIR_FP16, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DIR_ERR_HIP, std::string("conv_c3c1_wpair launch: ") + hipGetErrorString(e));
-    return DIR_OK;
+    return launch_c3c1("conv_c3c1_wpair", a, DIR_FP16, stream, {t2, w3, w3_lo, res, y, w1, w1_lo, t1, bias3, bias1});
     DIR_CATCH
 }
 
@@ -572,26 +519,15 @@ int dir_conv_c3c1_ds_wpair(const void* t2, const void* x, const void* x_lo, cons
                            int B, int H, int W, int relu3, int relu1, void* stream) {
     DIR_TRY
     ConvArgs a;
-    int rc = fill_conv_args(a, t2, wcat, bias, nullptr, y, B, H, W, 64, 256, 1, 1, 1, 0, H, W, relu3);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(fill_conv_args(a, t2, wcat, bias, nullptr, y, B, H, W, 64, 256, 1, 1, 1, 0, H, W, relu3));
     if (!x || !x_lo || !wcat_lo || !w1 || !w1_lo || !bias1 || !t1) return fail(DIR_ERR_INVALID, "conv_c3c1_ds_wpair: null pointer");
     a.x2 = (const uint16_t*)x;
     a.x2_lo = (const uint16_t*)x_lo;
     a.Cin2 = 64;
     a.w_lo = (const uint16_t*)wcat_lo;
-    a.w2 = (const uint16_t*)w1;
-    a.w2_lo = (const uint16_t*)w1_lo;
-    a.bias2 = bias1;
-    a.y2 = (uint16_t*)t1;
-    a.Cout2 = 64;
-    a.relu2 = relu1 ? 1 : 0;
+    conv_args_next_conv1(a, (const uint16_t*)w1, (const uint16_t*)w1_lo, bias1, (uint16_t*)t1, 64, relu1 ? 1 : 0);
     if (!conv_c3c1_admissible(a)) return fail(DIR_ERR_INVALID, "conv_c3c1_ds_wpair: shape not admissible");
-    const void* ptrs[] = {t2, x, x_lo, wcat, wcat_lo, y, w1, w1_lo, t1, bias, bias1};
-    for (const void* q : ptrs)
-        if ((uintptr_t)q & 15) return fail(DIR_ERR_INVALID, "conv_c3c1_ds_wpair: tensors must be 16-byte aligned");
-    hipError_t e = conv_c3c1_launch(a, DIR_FP16, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DIR_ERR_HIP, std::string("conv_c3c1_ds_wpair launch: ") + hipGetErrorString(e));
-    return DIR_OK;
+    return launch_c3c1("conv_c3c1_ds_wpair", a, DIR_FP16, stream, {t2, x, x_lo, wcat, wcat_lo, y, w1, w1_lo, t1, bias, bias1});
     DIR_CATCH
 }
 
@@ -599,19 +535,15 @@ int dir_conv_dual(const void* t2, const void* x, const void* wcat, const float* 
                   int Cin, int Cout, int Cin2, int H2, int W2, int stride2, int relu, int dtype, void* stream) {
     DIR_TRY
     ConvArgs a;
-    int rc = fill_conv_args(a, t2, wcat, bias, nullptr, y, B, OH, OW, Cin, Cout, 1, 1, 1, 0, OH, OW, relu);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(fill_conv_args(a, t2, wcat, bias, nullptr, y, B, OH, OW, Cin, Cout, 1, 1, 1, 0, OH, OW, relu));
     if (!x || Cin2 <= 0 || H2 <= 0 || W2 <= 0 || stride2 <= 0) return fail(DIR_ERR_INVALID, "conv_dual: bad argument");
     if ((OH - 1) * stride2 >= H2 || (OW - 1) * stride2 >= W2)
         return fail(DIR_ERR_INVALID, "conv_dual: the strided pixel map leaves the second source");
     if (Cin % 64 || Cin2 % 64) return fail(DIR_ERR_INVALID, "conv_dual: channel counts must be multiples of 64");
-    a.x2 = (const uint16_t*)x;
-    a.Cin2 = Cin2;
+    conv_args_second_source(a, (const uint16_t*)x, nullptr, Cin2);
     a.H2 = H2;
     a.W2 = W2;
     a.stride2 = stride2;
-    a.Ktot = Cin + Cin2;
-    a.T = a.Ktot / 64;
     if (((uintptr_t)t2 & 15) || ((uintptr_t)wcat & 15) || ((uintptr_t)y & 15) || ((uintptr_t)bias & 15))
         return fail(DIR_ERR_INVALID, "conv_dual: tensors must be 16-byte aligned");
     if ((long)a.M * Cout >= (1L << 30) || (long)a.M * Cin >= (1L << 30))
@@ -630,8 +562,7 @@ int dir_conv_bn_act_naive(const void* x, const void* w, const float* bias, const
                           int OH, int OW, int relu, int dtype, void* stream) {
     DIR_TRY
     ConvArgs a;
-    int rc = fill_conv_args(a, x, w, bias, res, y, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, relu);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(fill_conv_args(a, x, w, bias, res, y, B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, relu));
     if (dtype != DIR_BF16 && dtype != DIR_FP16) return fail(DIR_ERR_INVALID, "conv: bad dtype");
     return conv_launch_naive(a, dtype, (hipStream_t)stream);
     DIR_CATCH
@@ -735,8 +666,7 @@ int dir_fc_l2(const float* x, int B, int K, const float* W, const float* b, int 
               void* stream) {
     DIR_TRY
     if (!x || !W || !out || B <= 0 || K <= 0 || D <= 0) return fail(DIR_ERR_INVALID, "fc_l2: bad argument");
-    int rc = gemm_nt_f32(W, K, x, K, out, D, D, B, K, nullptr, b, nullptr, (hipStream_t)stream);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(gemm_nt_f32(W, K, x, K, out, D, D, B, K, nullptr, b, nullptr, (hipStream_t)stream));
     return l2norm_rows(out, B, D, 1e-12f, (hipStream_t)stream);
     DIR_CATCH
 }

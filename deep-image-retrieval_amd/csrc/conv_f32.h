@@ -1,6 +1,6 @@
 // conv_f32.h — host-side contract of the strict fp32 path (conv_f32.hip).
 #pragma once
-#include "dir_common.h"
+#include "conv_igemm.h"   // ConvGeom, conv_geom_fill: ConvF32Args is built like ConvArgs
 
 namespace dir {
 

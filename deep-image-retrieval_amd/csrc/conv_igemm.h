@@ -81,6 +81,63 @@ inline void conv_fill_extents(ConvArgs& b) {
     fastdiv_init((uint32_t)b.OW, b.div_ow_mul, b.div_ow_shr);
 }
 
+// ---- how a geometry and its tensors become a ConvArgs ---------------------------------------------------------------------
+// What a layer and an input shape fix about one convolution.
+struct ConvGeom {
+    int B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, relu;
+};
+// Zero-fills `a` (padding included: every optional pointer null, split-K off), fills the geometry and the primary tensors
+// and derives M = B*OH*OW and Ktot = R*S*Cin.  A template because the strict path's ConvF32Args (conv_f32.h) is filled the same way.
+template <class Args, class Elem>
+inline void conv_geom_fill(Args& a, const ConvGeom& g, const Elem* x, const Elem* w, const float* bias, const Elem* res, Elem* y) {
+    memset(&a, 0, sizeof(a));
+    a.x = x;
+    a.w = w;
+    a.bias = bias;
+    a.res = res;
+    a.y = y;
+    a.B = g.B;
+    a.H = g.H;
+    a.W = g.W;
+    a.Cin = g.Cin;
+    a.OH = g.OH;
+    a.OW = g.OW;
+    a.Cout = g.Cout;
+    a.R = g.R;
+    a.S = g.S;
+    a.stride = g.stride;
+    a.pad = g.pad;
+    a.relu = g.relu;
+    a.M = g.B * g.OH * g.OW;
+    a.Ktot = g.R * g.S * g.Cin;
+}
+// ... and for ConvArgs T as well.  The two-source, seam and paired fields are the caller's, below or by plain assignment.
+inline void conv_args_init(ConvArgs& a, const ConvGeom& g, const uint16_t* x, const uint16_t* w, const float* bias,
+                           const uint16_t* res, uint16_t* y) {
+    conv_geom_fill(a, g, x, w, bias, res, y);
+    a.T = a.Ktot / 64;
+}
+// A second K source appended to a 1x1 conv's own (conv3 + the block's downsample as ONE GEMM over [x ; x2], w and bias
+// concatenated / summed by the caller): K grows by Cin2.  (The seam kernels' DS form sets x2 / Cin2 by plain assignment and
+// leaves Ktot = Cin: conv_c3c1.hip never reads it.)
+inline void conv_args_second_source(ConvArgs& a, const uint16_t* x2, const uint16_t* x2_lo, int Cin2) {
+    a.x2 = x2;
+    a.x2_lo = x2_lo;
+    a.Cin2 = Cin2;
+    a.Ktot = a.Cin + Cin2;
+    a.T = a.Ktot / 64;
+}
+// The fused seam (conv_c3c1.hip): the following block's conv1 applied to this conv's output tile.
+inline void conv_args_next_conv1(ConvArgs& a, const uint16_t* w2, const uint16_t* w2_lo, const float* bias2, uint16_t* y2,
+                                 int Cout2, int relu2) {
+    a.w2 = w2;
+    a.w2_lo = w2_lo;
+    a.bias2 = bias2;
+    a.y2 = y2;
+    a.Cout2 = Cout2;
+    a.relu2 = relu2;
+}
+
 // ---- the variant table (conv_igemm.hip) ----------------------------------------------------------------------------------
 typedef bool (*ConvAdmissibleFn)(const ConvArgs&);
 typedef hipError_t (*ConvLaunchFn)(const ConvArgs&, int dtype, hipStream_t);

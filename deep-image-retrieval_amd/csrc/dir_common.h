@@ -35,6 +35,13 @@ int fail(int code, const std::string& msg);
             return ::dir::fail(DIR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
 
+// Returns a dir_status that is not DIR_OK to the caller (whoever produced it has set the error string).
+#define DIR_CHECK(expr)                  \
+    do {                                 \
+        const int _rc = (expr);          \
+        if (_rc != DIR_OK) return _rc;   \
+    } while (0)
+
 // ---- A/B switches --------------------------------------------------------------------------------------
 // Every DIRTORCH_AMD_* switch the library honours.  The environment is read ONCE (first use) and again only when the
 // host calls dir_reload_env() - what a test or an A/B script does after flipping a variable inside one process; an

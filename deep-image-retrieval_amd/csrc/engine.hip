@@ -279,12 +279,10 @@ int dir_engine::finalize(int dt) {
                             packed[(((size_t)o * L.R + r) * L.S + s) * L.Cin + c] = v;
                         }
         }
-        DIR_HIP_CHECK(hipMalloc((void**)&L.d_bias, L.Cout * 4));
-        DIR_HIP_CHECK(hipMemcpy(L.d_bias, bias.data(), L.Cout * 4, hipMemcpyHostToDevice));
+        DIR_CHECK(upload(&L.dev.bias, bias));
         L.tuned.clear();
         if (dt == DIR_F32) {
-            DIR_HIP_CHECK(hipMalloc((void**)&L.d_wf, packed.size() * 4));
-            DIR_HIP_CHECK(hipMemcpy(L.d_wf, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
+            DIR_CHECK(upload(&L.dev.wf, packed));
             continue;
         }
         std::vector<uint16_t> packed16(packed.size());
@@ -297,21 +295,19 @@ int dir_engine::finalize(int dt) {
                 return fail(DIR_ERR_RANGE, "finalize: a BatchNorm-folded weight of " + L.name + " (" +
                                                std::to_string(packed[i]) + ") exceeds the fp16 range; use DIR_BF16 or DIR_F32");
         }
-        DIR_HIP_CHECK(hipMalloc((void**)&L.d_w, packed16.size() * 2));
-        DIR_HIP_CHECK(hipMemcpy(L.d_w, packed16.data(), packed16.size() * 2, hipMemcpyHostToDevice));
+        DIR_CHECK(upload(&L.dev.w, packed16));
         if (!L.stem && L.R == 3 && L.S == 3 && L.stride == 1 && L.pad == 1 && L.Cin % 32 == 0 && L.Cin >= 64 && L.Cout % 128 == 0) {
             // conv2 of layers 2-4: conv_patchw.hip's loaders copy their 24 KB weight stages as contiguous KBs from this copy
-            DIR_HIP_CHECK(hipMalloc((void**)&L.d_w_pw, packed16.size() * 2));
-            DIR_HIP_CHECK(conv_patch3x3w_pack(L.d_w, L.d_w_pw, L.Cout, L.Cin, nullptr));
+            DIR_CHECK(alloc(&L.dev.w_pw, packed16.size()));
+            DIR_HIP_CHECK(conv_patch3x3w_pack(L.dev.w, L.dev.w_pw, L.Cout, L.Cin, nullptr));
         }
         if (!L.stem && L.R == 3 && L.S == 3 && L.stride == 2 && L.pad == 1 && L.Cin % 64 == 0 && L.Cout % 128 == 0) {
             // conv2 of a stage's first block: conv_patchs2.hip reads its weight fragments as contiguous KBs from this copy
-            DIR_HIP_CHECK(hipMalloc((void**)&L.d_w_s2, packed16.size() * 2));
-            DIR_HIP_CHECK(conv_patch3x3s2_pack(L.d_w, L.d_w_s2, L.Cout, L.Cin, nullptr));
+            DIR_CHECK(alloc(&L.dev.w_s2, packed16.size()));
+            DIR_HIP_CHECK(conv_patch3x3s2_pack(L.dev.w, L.dev.w_s2, L.Cout, L.Cin, nullptr));
         }
         if (L.stem && dt == DIR_FP16P) {   // (after the range check above: a weight the plain form refuses is reported as that layer's)
-            const int rc = fold_stem_u8(L, w->data.data(), scale.data(), bias.data());
-            if (rc != DIR_OK) return rc;
+            DIR_CHECK(fold_stem_u8(L, w->data.data(), scale.data(), bias.data()));
         }
         if (is_pair[li]) {   // lo plane: what the hi plane's rounding left over, itself rounded to fp16
             std::vector<uint16_t> lo16(packed.size());
@@ -320,8 +316,7 @@ int dir_engine::finalize(int dt) {
                 if ((lo16[i] & 0x7c00u) == 0x7c00u && std::isfinite(packed[i]))   // (unreachable once hi is finite: |lo| <= ulp(hi) / 2)
                     return fail(DIR_ERR_RANGE, "finalize: the lo plane of a paired weight of " + L.name + " is not finite");
             }
-            DIR_HIP_CHECK(hipMalloc((void**)&L.d_w_lo, lo16.size() * 2));
-            DIR_HIP_CHECK(hipMemcpy(L.d_w_lo, lo16.data(), lo16.size() * 2, hipMemcpyHostToDevice));
+            DIR_CHECK(upload(&L.dev.w_lo, lo16));
             L.h_w_lo.swap(lo16);
         }
         L.h_w.swap(packed16);
@@ -347,17 +342,14 @@ int dir_engine::finalize(int dt) {
             memcpy(&cat[(size_t)o * (K3 + Kd) + K3], &ds.h_w[(size_t)o * Kd], Kd * 2);
             bsum[o] = c3.h_bias[o] + ds.h_bias[o];
         }
-        DIR_HIP_CHECK(hipMalloc((void**)&c3.d_w_ds, cat.size() * 2));
-        DIR_HIP_CHECK(hipMemcpy(c3.d_w_ds, cat.data(), cat.size() * 2, hipMemcpyHostToDevice));
-        DIR_HIP_CHECK(hipMalloc((void**)&c3.d_bias_ds, N * 4));
-        DIR_HIP_CHECK(hipMemcpy(c3.d_bias_ds, bsum.data(), N * 4, hipMemcpyHostToDevice));
+        DIR_CHECK(upload(&c3.dev.w_ds, cat));
+        DIR_CHECK(upload(&c3.dev.bias_ds, bsum));
         if (is_pair[bd.conv3]) {   // the lo planes, concatenated the same way
             for (int o = 0; o < N; ++o) {
                 memcpy(&cat[(size_t)o * (K3 + Kd)], &c3.h_w_lo[(size_t)o * K3], K3 * 2);
                 memcpy(&cat[(size_t)o * (K3 + Kd) + K3], &ds.h_w_lo[(size_t)o * Kd], Kd * 2);
             }
-            DIR_HIP_CHECK(hipMalloc((void**)&c3.d_w_ds_lo, cat.size() * 2));
-            DIR_HIP_CHECK(hipMemcpy(c3.d_w_ds_lo, cat.data(), cat.size() * 2, hipMemcpyHostToDevice));
+            DIR_CHECK(upload(&c3.dev.w_ds_lo, cat));
         }
     }
     for (ConvLayer& L : convs) {
@@ -384,13 +376,11 @@ int dir_engine::finalize(int dt) {
         if (fw->shape.size() != 2 || fw->shape[0] != desc.out_dim || fw->shape[1] != head_dim ||
             (int)fb->data.size() != desc.out_dim)
             return fail(DIR_ERR_INVALID, "bad shape for fc.weight / fc.bias");
-        DIR_HIP_CHECK(hipMalloc((void**)&d_fc_w, fw->data.size() * 4));
-        DIR_HIP_CHECK(hipMemcpy(d_fc_w, fw->data.data(), fw->data.size() * 4, hipMemcpyHostToDevice));
-        DIR_HIP_CHECK(hipMalloc((void**)&d_fc_b, fb->data.size() * 4));
-        DIR_HIP_CHECK(hipMemcpy(d_fc_b, fb->data.data(), fb->data.size() * 4, hipMemcpyHostToDevice));
+        DIR_CHECK(upload(&dev.fc_w, fw->data));
+        DIR_CHECK(upload(&dev.fc_b, fb->data));
     }
-    DIR_HIP_CHECK(hipMalloc((void**)&d_ovf, 256));
-    DIR_HIP_CHECK(hipMemset(d_ovf, 0, 256));
+    DIR_CHECK(alloc(&dev.ovf, 256 / sizeof(int)));
+    DIR_HIP_CHECK(hipMemset(dev.ovf, 0, 256));
     DIR_HIP_CHECK(hipDeviceSynchronize());
     finalized = true;
     return DIR_OK;
@@ -412,45 +402,26 @@ int dir_engine::fold_stem_u8(ConvLayer& L, const float* w, const float* scale, c
     // a preprocess whose 1 / (255 std) pushes a folded weight out of the fp16 range (or a std <= 0) only rules the uint8 stem out:
     // the tables stay null and dir_forward keeps the generic paired stem (normalisation in prep_input_pair) for that engine
     if (rc == DIR_ERR_RANGE || rc == DIR_ERR_INVALID) return DIR_OK;
-    if (rc != DIR_OK) return rc;
-    DIR_HIP_CHECK(hipMalloc((void**)&d_stem_u8_w, hi.size() * 2));
-    DIR_HIP_CHECK(hipMemcpy(d_stem_u8_w, hi.data(), hi.size() * 2, hipMemcpyHostToDevice));
-    DIR_HIP_CHECK(hipMalloc((void**)&d_stem_u8_w_lo, lo.size() * 2));
-    DIR_HIP_CHECK(hipMemcpy(d_stem_u8_w_lo, lo.data(), lo.size() * 2, hipMemcpyHostToDevice));
-    DIR_HIP_CHECK(hipMalloc((void**)&d_stem_u8_bias, b2.size() * 4));
-    DIR_HIP_CHECK(hipMemcpy(d_stem_u8_bias, b2.data(), b2.size() * 4, hipMemcpyHostToDevice));
-    DIR_HIP_CHECK(hipMalloc((void**)&d_stem_u8_corr, corr.size() * 4));
-    DIR_HIP_CHECK(hipMemcpy(d_stem_u8_corr, corr.data(), corr.size() * 4, hipMemcpyHostToDevice));
+    DIR_CHECK(rc);
+    DIR_CHECK(upload(&dev.stem_u8_w, hi));
+    DIR_CHECK(upload(&dev.stem_u8_w_lo, lo));
+    DIR_CHECK(upload(&dev.stem_u8_bias, b2));
+    return upload(&dev.stem_u8_corr, corr);
+}
+
+// ---- device memory: every allocation is registered, release() frees the list -----------------------------------------------
+int dir_engine::alloc_bytes(void** out, size_t bytes) {
+    owned.push_back(nullptr);   // (registered first: a failed push_back must not strand a live allocation)
+    DIR_HIP_CHECK(hipMalloc(&owned.back(), bytes));
+    *out = owned.back();
     return DIR_OK;
 }
 
 void dir_engine::release() {
-    for (void** p : {(void**)&d_stem_u8_w, (void**)&d_stem_u8_w_lo, (void**)&d_stem_u8_bias, (void**)&d_stem_u8_corr}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    for (ConvLayer& L : convs) {
-        if (L.d_w) (void)hipFree(L.d_w);
-        if (L.d_wf) (void)hipFree(L.d_wf);
-        L.d_wf = nullptr;
-        if (L.d_w_lo) (void)hipFree(L.d_w_lo);
-        L.d_w_lo = nullptr;
-        if (L.d_w_s2) (void)hipFree(L.d_w_s2);
-        if (L.d_w_pw) (void)hipFree(L.d_w_pw);
-        L.d_w_s2 = L.d_w_pw = nullptr;
-        if (L.d_bias) (void)hipFree(L.d_bias);
-        if (L.d_w_ds) (void)hipFree(L.d_w_ds);
-        if (L.d_w_ds_lo) (void)hipFree(L.d_w_ds_lo);
-        L.d_w_ds_lo = nullptr;
-        if (L.d_bias_ds) (void)hipFree(L.d_bias_ds);
-        L.d_w = L.d_w_ds = nullptr;
-        L.d_bias = L.d_bias_ds = nullptr;
-    }
-    if (d_fc_w) (void)hipFree(d_fc_w);
-    if (d_fc_b) (void)hipFree(d_fc_b);
-    d_fc_w = d_fc_b = nullptr;
-    if (d_ovf) (void)hipFree(d_ovf);
-    d_ovf = nullptr;
+    for (void* p : owned) (void)hipFree(p);
+    owned.clear();
+    for (ConvLayer& L : convs) L.dev = {};
+    dev = {};
     finalized = false;
 }
 
@@ -459,8 +430,8 @@ void dir_engine::release() {
 int dir_engine::overflow(hipStream_t stream, int* overflowed) {
     if (!finalized) return fail(DIR_ERR_STATE, "overflow query before finalize");
     int host = 0;
-    DIR_HIP_CHECK(hipMemcpyAsync(&host, d_ovf, sizeof(int), hipMemcpyDeviceToHost, stream));
-    DIR_HIP_CHECK(hipMemsetAsync(d_ovf, 0, sizeof(int), stream));
+    DIR_HIP_CHECK(hipMemcpyAsync(&host, dev.ovf, sizeof(int), hipMemcpyDeviceToHost, stream));
+    DIR_HIP_CHECK(hipMemsetAsync(dev.ovf, 0, sizeof(int), stream));
     DIR_HIP_CHECK(hipStreamSynchronize(stream));
     *overflowed = host != 0;
     return DIR_OK;
@@ -479,30 +450,40 @@ int dir_engine::plan(int B, int H, int W, Plan* p) const {
     p->PH = conv_out(p->OH1, 3, 2, 1);
     p->PW = conv_out(p->OW1, 3, 2, 1);
     const size_t es = dtype == DIR_F32 ? 4 : 2;   // bytes per stored activation
-    size_t io = 0, t1 = 0, t2 = 0, ds = 0, x4 = 0;
-    int h = p->PH, w = p->PW;
-    io = (size_t)B * h * w * 64 * es;
-    for (size_t bi = 0; bi < blocks.size(); ++bi) {
-        const BlockDef& bd = blocks[bi];
-        const int oh = conv_out(h, 3, bd.stride, 1), ow = conv_out(w, 3, bd.stride, 1);
-        const ConvLayer& c1 = convs[bd.conv1];
-        const ConvLayer& cl = convs[desc.bottleneck ? bd.conv3 : bd.conv2];
-        if (desc.bottleneck) {
-            t1 = std::max(t1, (size_t)B * h * w * c1.Cout * es);
-            t2 = std::max(t2, (size_t)B * oh * ow * convs[bd.conv2].Cout * es);
-        } else {
-            t1 = std::max(t1, (size_t)B * oh * ow * c1.Cout * es);
+    // One walk over blocks [0, nb) at `eb` bytes per element: the widest t1 / t2 / downsample tensor and block output (io),
+    // layer3's kept output (x4) and the map size after the last block.  Run for the activations of the whole net and again
+    // for the lo planes of the paired head, which only use t1 / t2 / ds of it.
+    struct Extents {
+        size_t t1 = 0, t2 = 0, ds = 0, io = 0, x4 = 0;
+        int h = 0, w = 0;
+    };
+    auto block_extents = [&](size_t eb, size_t nb) {
+        Extents e;
+        e.h = p->PH;
+        e.w = p->PW;
+        e.io = (size_t)B * e.h * e.w * 64 * eb;
+        for (size_t bi = 0; bi < nb; ++bi) {
+            const BlockDef& bd = blocks[bi];
+            const int oh = conv_out(e.h, 3, bd.stride, 1), ow = conv_out(e.w, 3, bd.stride, 1);
+            const ConvLayer& c1 = convs[bd.conv1];
+            const ConvLayer& cl = convs[desc.bottleneck ? bd.conv3 : bd.conv2];
+            if (desc.bottleneck) {
+                e.t1 = std::max(e.t1, (size_t)B * e.h * e.w * c1.Cout * eb);
+                e.t2 = std::max(e.t2, (size_t)B * oh * ow * convs[bd.conv2].Cout * eb);
+            } else {
+                e.t1 = std::max(e.t1, (size_t)B * oh * ow * c1.Cout * eb);
+            }
+            if (bd.down >= 0) e.ds = std::max(e.ds, (size_t)B * oh * ow * convs[bd.down].Cout * eb);
+            e.io = std::max(e.io, (size_t)B * oh * ow * cl.Cout * eb);
+            e.h = oh;
+            e.w = ow;
+            if ((int)bi == x4_block) e.x4 = (size_t)B * e.h * e.w * x4_dim * eb;
         }
-        if (bd.down >= 0) ds = std::max(ds, (size_t)B * oh * ow * convs[bd.down].Cout * es);
-        io = std::max(io, (size_t)B * oh * ow * cl.Cout * es);
-        h = oh;
-        w = ow;
-        if ((int)bi == x4_block) {  // FPN heads keep x4; the lateral path reuses t1 / t2 / a ping-pong buffer
-            x4 = (size_t)B * h * w * x4_dim * es;
-            t2 = std::max(t2, x4);
-        }
-    }
-    if (conv1x5 >= 0) t1 = std::max(t1, (size_t)B * h * w * x4_dim * es);
+        return e;
+    };
+    Extents act = block_extents(es, blocks.size());
+    act.t2 = std::max(act.t2, act.x4);   // FPN heads keep x4; the lateral path reuses t1 / t2 / a ping-pong buffer
+    if (conv1x5 >= 0) act.t1 = std::max(act.t1, (size_t)B * act.h * act.w * x4_dim * es);
     size_t off = 0;
     auto take = [&](size_t bytes) {
         const size_t o = off;
@@ -511,35 +492,20 @@ int dir_engine::plan(int B, int H, int W, Plan* p) const {
     };
     p->s2d = take((size_t)B * p->H2 * p->W2 * 16 * es);
     p->stem = take((size_t)B * p->OH1 * p->OW1 * 64 * es);
-    p->bufA = take(io);
-    p->bufB = take(io);
-    p->t1 = take(t1);
-    p->t2 = take(t2 ? t2 : 256);
-    p->ds = take(ds ? ds : 256);
-    p->x4 = take(x4 ? x4 : 256);
+    p->bufA = take(act.io);
+    p->bufB = take(act.io);
+    p->t1 = take(act.t1);
+    p->t2 = take(act.t2 ? act.t2 : 256);
+    p->ds = take(act.ds ? act.ds : 256);
+    p->x4 = take(act.x4 ? act.x4 : 256);
     p->lo_s2d = p->lo_stem = p->lo_t1 = p->lo_t2 = p->lo_ds = 0;
     if (dtype == DIR_FP16P) {   // lo planes of the paired head: image, stem output [, t1 / t2 / downsample of its blocks]
-        size_t pt1 = 0, pt2 = 0, pds = 0;
-        int ph = p->PH, pw = p->PW;
-        for (int bi = 0; pair_acts && bi < pair_blocks && bi < (int)blocks.size(); ++bi) {
-            const BlockDef& bd = blocks[bi];
-            const int oh = conv_out(ph, 3, bd.stride, 1), ow = conv_out(pw, 3, bd.stride, 1);
-            const ConvLayer& c1 = convs[bd.conv1];
-            if (desc.bottleneck) {
-                pt1 = std::max(pt1, (size_t)B * ph * pw * c1.Cout * 2);
-                pt2 = std::max(pt2, (size_t)B * oh * ow * convs[bd.conv2].Cout * 2);
-            } else {
-                pt1 = std::max(pt1, (size_t)B * oh * ow * c1.Cout * 2);
-            }
-            if (bd.down >= 0) pds = std::max(pds, (size_t)B * oh * ow * convs[bd.down].Cout * 2);
-            ph = oh;
-            pw = ow;
-        }
+        const Extents lo = block_extents(2, pair_acts ? std::min((size_t)pair_blocks, blocks.size()) : 0);
         p->lo_s2d = take((size_t)B * p->H2 * p->W2 * 16 * 2);
         p->lo_stem = take((size_t)B * p->PH * p->PW * 64 * 2);
-        p->lo_t1 = take(pt1 ? pt1 : 256);
-        p->lo_t2 = take(pt2 ? pt2 : 256);
-        p->lo_ds = take(pds ? pds : 256);
+        p->lo_t1 = take(lo.t1 ? lo.t1 : 256);
+        p->lo_t2 = take(lo.t2 ? lo.t2 : 256);
+        p->lo_ds = take(lo.ds ? lo.ds : 256);
     }
     p->splitk = take(kSplitKMaxBytes);   // fp32 partial sums of split-K convs (small-M layers)
     p->pooled = take((size_t)B * head_dim * 4);
@@ -549,70 +515,71 @@ int dir_engine::plan(int B, int H, int W, Plan* p) const {
 }
 
 // ---- profiling --------------------------------------------------------------------------------
-int dir_engine::prof_begin(const std::string& name, const std::string& kernel, double flops,
-                           double bytes, hipStream_t stream) {
-    if (!profiling || prof_paused) return DIR_OK;
+int dir_engine::prof_slot(ProfSlot** slot) {
     if (prof_used == prof.size()) {
         ProfSlot s;
         DIR_HIP_CHECK(hipEventCreate(&s.start));
         DIR_HIP_CHECK(hipEventCreate(&s.stop));
         prof.push_back(s);
     }
-    ProfSlot& s = prof[prof_used];
-    s.name = name;
-    s.kernel = kernel;
-    s.flops = flops;
-    s.bytes = bytes;
-    DIR_HIP_CHECK(hipEventRecord(s.start, stream));
-    return DIR_OK;
-}
-int dir_engine::prof_end(hipStream_t stream) {
-    if (!profiling || prof_paused) return DIR_OK;
-    DIR_HIP_CHECK(hipEventRecord(prof[prof_used].stop, stream));
-    ++prof_used;
+    *slot = &prof[prof_used];
     return DIR_OK;
 }
 
 // ---- one convolution ----------------------------------------------------------------------------
+// A layer on a (B, H, W) input as the kernels see it.  The stem runs in its space-to-depth form: 4x4 stride 1 over the 16
+// channels of the s2d image, and (H, W) is that grid.
+static ConvGeom layer_geom(const ConvLayer& L, int B, int H, int W, int OH, int OW) {
+    const int relu = L.relu ? 1 : 0;
+    if (L.stem) return {B, H, W, 16, L.Cout, 4, 4, 1, 2, OH, OW, relu};
+    return {B, H, W, L.Cin, L.Cout, L.R, L.S, L.stride, L.pad, OH, OW, relu};
+}
+
+// Autotune: time every admissible variant on the live input, keep the fastest.
+int dir_engine::tune_conv(ConvLayer& L, ConvArgs& a, hipStream_t stream, int* variant) {
+    hipEvent_t e0, e1;
+    DIR_HIP_CHECK(hipEventCreate(&e0));
+    DIR_HIP_CHECK(hipEventCreate(&e1));
+    float best = 1e30f;
+    for (int v = 0; v < conv_variant_count(); ++v) {
+        a.ksplit = 0;   // (the previous candidate's split must not decide this one's admissibility: conv_small, conv_patchs2
+                        // and conv_persistlc refuse a.ksplit > 1)
+        if (!conv_variant_admissible(v, a)) continue;
+        a.ksplit = conv_splitk_factor(v, a);
+        DIR_CHECK(conv_launch(a, kdtype(), v, stream));  // warm-up (also sets func attributes)
+        float ms = 1e30f;
+        for (int round = 0; round < 2; ++round) {  // best of two timings of 3 launches
+            DIR_HIP_CHECK(hipEventRecord(e0, stream));
+            for (int rep = 0; rep < 3; ++rep) DIR_CHECK(conv_launch(a, kdtype(), v, stream));
+            DIR_HIP_CHECK(hipEventRecord(e1, stream));
+            DIR_HIP_CHECK(hipEventSynchronize(e1));
+            float t = 0.f;
+            DIR_HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
+            ms = t < ms ? t : ms;
+        }
+        if (ms < best) {
+            best = ms;
+            *variant = v;
+        }
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    L.tuned[a.M] = *variant;
+    return DIR_OK;
+}
+
 int dir_engine::run_conv(ConvLayer& L, const uint16_t* x, const uint16_t* res, uint16_t* y, int B,
                          int H, int W, int OH, int OW, hipStream_t stream, bool rev_m) {
     // DIR_FP16P: a layer whose weights are a pair multiplies both planes (conv_pair.hip; single-plane input and output here)
-    if (dtype == DIR_FP16P && L.d_w_lo && !L.stem)
+    if (dtype == DIR_FP16P && L.dev.w_lo && !L.stem)
         return run_conv_pair(L, x, nullptr, res, nullptr, y, nullptr, B, H, W, OH, OW, stream);
     ConvArgs a;
-    memset(&a, 0, sizeof(a));
+    conv_args_init(a, layer_geom(L, B, H, W, OH, OW), x, L.dev.w, L.dev.bias, res, y);
     a.rev_m = rev_m ? 1 : 0;
-    a.x = x;
-    a.w = L.d_w;
-    a.w_s2 = L.d_w_s2;
-    a.w_pw = env().no_patchw_pack ? nullptr : L.d_w_pw;
-    a.bias = L.d_bias;
-    a.res = res;
-    a.y = y;
-    a.B = B;
-    a.H = H;
-    a.W = W;
-    a.OH = OH;
-    a.OW = OW;
-    a.Cout = L.Cout;
-    if (L.stem) {  // (H, W) is the space-to-depth grid here
-        a.Cin = 16;
-        a.R = a.S = 4;
-        a.stride = 1;
-        a.pad = 2;
-    } else {
-        a.Cin = L.Cin;
-        a.R = L.R;
-        a.S = L.S;
-        a.stride = L.stride;
-        a.pad = L.pad;
-    }
-    a.relu = L.relu ? 1 : 0;
-    a.ovf = d_ovf;
+    a.w_s2 = L.dev.w_s2;
+    a.w_pw = env().no_patchw_pack ? nullptr : L.dev.w_pw;
+    a.ovf = dev.ovf;
     a.partial = splitk_scratch;
-    a.M = B * OH * OW;
-    a.Ktot = a.R * a.S * a.Cin;
-    a.T = a.Ktot / 64;
     const double macs = (double)a.M * L.Cout * (double)(L.R * L.S * L.Cin);  // true taps (stem: 147)
     const double bytes = 2.0 * ((double)B * H * W * a.Cin + (double)a.M * L.Cout * (res ? 2 : 1) +
                                 (double)L.Cout * a.Ktot);
@@ -620,41 +587,7 @@ int dir_engine::run_conv(ConvLayer& L, const uint16_t* x, const uint16_t* res, u
     int variant = -1;
     auto it = L.tuned.find(a.M);
     if (it != L.tuned.end()) variant = it->second;
-    if (tuning && it == L.tuned.end()) {
-        // time every admissible variant on the live input, keep the fastest
-        hipEvent_t e0, e1;
-        DIR_HIP_CHECK(hipEventCreate(&e0));
-        DIR_HIP_CHECK(hipEventCreate(&e1));
-        float best = 1e30f;
-        for (int v = 0; v < conv_variant_count(); ++v) {
-            a.ksplit = 0;   // (the previous candidate's split must not decide this one's admissibility: conv_small, conv_patchs2
-                            // and conv_persistlc refuse a.ksplit > 1)
-            if (!conv_variant_admissible(v, a)) continue;
-            a.ksplit = conv_splitk_factor(v, a);
-            int rc = conv_launch(a, kdtype(), v, stream);  // warm-up (also sets func attributes)
-            if (rc != DIR_OK) return rc;
-            float ms = 1e30f;
-            for (int round = 0; round < 2; ++round) {  // best of two timings of 3 launches
-                DIR_HIP_CHECK(hipEventRecord(e0, stream));
-                for (int rep = 0; rep < 3; ++rep) {
-                    rc = conv_launch(a, kdtype(), v, stream);
-                    if (rc != DIR_OK) return rc;
-                }
-                DIR_HIP_CHECK(hipEventRecord(e1, stream));
-                DIR_HIP_CHECK(hipEventSynchronize(e1));
-                float t = 0.f;
-                DIR_HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
-                ms = t < ms ? t : ms;
-            }
-            if (ms < best) {
-                best = ms;
-                variant = v;
-            }
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        L.tuned[a.M] = variant;
-    }
+    if (tuning && it == L.tuned.end()) DIR_CHECK(tune_conv(L, a, stream, &variant));
     // a tuning table written for another architecture shares layer names (resnet18 / resnet101 both
     // have layer1.0.conv1): an entry that does not fit this layer's shape is dropped, not an error
     a.ksplit = 0;   // (judged as a plain launch, like dir_conv_variant_admissible: not with the last timed candidate's split)
@@ -664,70 +597,43 @@ int dir_engine::run_conv(ConvLayer& L, const uint16_t* x, const uint16_t* res, u
     }
     if (variant < 0) variant = conv_pick_variant(a);
     a.ksplit = conv_splitk_factor(variant, a);
-    int rc = DIR_OK;
-    if (profiling && !prof_paused)   // (the label strings are only built when somebody will read them)
-        rc = prof_begin(L.name, std::string("conv_igemm<") + conv_variant(variant).name +
-                                    (a.ksplit > 1 ? "/k" + std::to_string(a.ksplit) : "") + ">",
-                        2.0 * macs, bytes, stream);
-    if (rc != DIR_OK) return rc;
-    rc = conv_launch(a, kdtype(), variant, stream);
-    if (rc != DIR_OK) return rc;
-    return prof_end(stream);
+    return profiled(
+        [&](std::string& name, std::string& kernel) {   // (the label strings are only built when somebody will read them)
+            name = L.name;
+            kernel = std::string("conv_igemm<") + conv_variant(variant).name + (a.ksplit > 1 ? "/k" + std::to_string(a.ksplit) : "") + ">";
+        },
+        2.0 * macs, bytes, stream, [&] { return conv_launch(a, kdtype(), variant, stream); });
 }
 
 // ---- one convolution on fp16 pairs (DIR_FP16P head, conv_pair.hip) -------------------------------------------------
 int dir_engine::run_conv_pair(ConvLayer& L, const uint16_t* x, const uint16_t* x_lo, const uint16_t* res,
                               const uint16_t* res_lo, uint16_t* y, uint16_t* y_lo, int B, int H, int W, int OH, int OW,
                               hipStream_t stream, const uint16_t* x2, const uint16_t* x2_lo) {
-    if (!L.d_w_lo) return fail(DIR_ERR_STATE, "paired conv on a layer without a lo weight plane: " + L.name);
-    if (x2 && !L.d_w_ds_lo) return fail(DIR_ERR_STATE, "two-source paired conv without concatenated weights: " + L.name);
+    if (!L.dev.w_lo) return fail(DIR_ERR_STATE, "paired conv on a layer without a lo weight plane: " + L.name);
+    if (x2 && !L.dev.w_ds_lo) return fail(DIR_ERR_STATE, "two-source paired conv without concatenated weights: " + L.name);
     ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x;
+    conv_args_init(a, layer_geom(L, B, H, W, OH, OW), x, L.dev.w, L.dev.bias, res, y);
     a.x_lo = x_lo;
-    a.w = L.d_w;
-    a.w_lo = L.d_w_lo;
-    a.bias = L.d_bias;
-    a.res = res;
+    a.w_lo = L.dev.w_lo;
     a.res_lo = res_lo;
-    a.y = y;
     a.y_lo = y_lo;
-    a.B = B;
-    a.H = H;
-    a.W = W;
-    a.OH = OH;
-    a.OW = OW;
-    a.Cin = L.Cin;
-    a.Cout = L.Cout;
-    a.R = L.R;
-    a.S = L.S;
-    a.stride = L.stride;
-    a.pad = L.pad;
-    a.relu = L.relu ? 1 : 0;
-    a.ovf = d_ovf;
-    a.M = B * OH * OW;
-    a.Ktot = a.R * a.S * a.Cin;
+    a.ovf = dev.ovf;
     if (x2) {   // conv3 + the block's stride-1 downsample: K = [t2 ; block input], weights / biases concatenated at finalize
-        a.x2 = x2;
-        a.x2_lo = x2_lo;
-        a.Cin2 = a.Cin;
-        a.w = L.d_w_ds;
-        a.w_lo = L.d_w_ds_lo;
-        a.bias = L.d_bias_ds;
-        a.Ktot = 2 * a.Cin;
+        conv_args_second_source(a, x2, x2_lo, a.Cin);
+        a.w = L.dev.w_ds;
+        a.w_lo = L.dev.w_ds_lo;
+        a.bias = L.dev.bias_ds;
     }
     const double macs = (double)a.M * L.Cout * (double)a.Ktot;
     // every tensor a pair: twice the bytes of the 16-bit form (single-plane operands counted once)
     const double bytes = 2.0 * ((double)B * H * W * a.Cin * (x_lo ? 2 : 1) * (x2 ? 2 : 1) + (double)a.M * L.Cout * (y_lo ? 2 : 1) +
                                 (double)a.M * L.Cout * (res ? (res_lo ? 2 : 1) : 0) + 2.0 * L.Cout * a.Ktot);
-    int rc = DIR_OK;
-    if (profiling && !prof_paused)
-        rc = prof_begin(x2 ? L.name.substr(0, L.name.rfind('.')) + ".ds+conv3" : L.name,
-                        std::string("conv_pair<") + conv_pair_variant_name(a) + ">", 2.0 * macs, bytes, stream);
-    if (rc != DIR_OK) return rc;
-    rc = conv_pair_launch(a, stream);
-    if (rc != DIR_OK) return rc;
-    return prof_end(stream);
+    return profiled(
+        [&](std::string& name, std::string& kernel) {
+            name = x2 ? L.name.substr(0, L.name.rfind('.')) + ".ds+conv3" : L.name;
+            kernel = std::string("conv_pair<") + conv_pair_variant_name(a) + ">";
+        },
+        2.0 * macs, bytes, stream, [&] { return conv_pair_launch(a, stream); });
 }
 
 // ---- DIR_FP16P: image -> stem -> the paired residual blocks ---------------------------------------------------------
@@ -737,52 +643,42 @@ int dir_engine::forward_pair_stem(const void* img, int B, int H, int W, int fmt,
                                   hipStream_t stream) {
     uint16_t* s2d = (uint16_t*)(base + p.s2d);
     uint16_t* s2d_lo = (uint16_t*)(base + p.lo_s2d);
-    int rc;
-    if (img && fmt == DIR_IMG_U8_NHWC && d_stem_u8_w && !sw.no_stem_u8) {
+    uint16_t* y = (uint16_t*)(base + p.bufA);
+    uint16_t* y_lo = (uint16_t*)(base + p.lo_stem);
+    const double stem_flops = 2.0 * B * p.OH1 * p.OW1 * 64.0 * 147.0;
+    const double out_bytes = 4.0 * ((double)B * p.PH * p.PW * 64 + 64 * 256);
+    if (img && fmt == DIR_IMG_U8_NHWC && dev.stem_u8_w && !sw.no_stem_u8) {
         // the raw uint8 image is exact in ONE fp16 plane: Normalize folded into the filter pair and the bias, two MFMAs per
         // term, pooled in registers (stem_u8.hip)
         const bool raw = stem_pool_u8_raw_ok(img, B, H, W);   // the stem reads the image itself: no prep launch, no s2d plane
-        if (!raw) {
-            rc = prof_begin("prep_input", "prep_input_u8", 0, (double)B * H * W * 3 + (double)B * p.H2 * p.W2 * 32, stream);
-            if (rc != DIR_OK) return rc;
-            rc = prep_input_u8(img, s2d, B, H, W, stream);
-            if (rc != DIR_OK) return rc;
-            if ((rc = prof_end(stream)) != DIR_OK) return rc;
-        }
-        rc = prof_begin("conv1+maxpool", "stem_pool_u8", 2.0 * B * p.OH1 * p.OW1 * 64.0 * 147.0,
-                        (raw ? (double)B * H * W * 3 : 2.0 * (double)B * p.H2 * p.W2 * 16) + 4.0 * ((double)B * p.PH * p.PW * 64 + 64 * 256),
-                        stream);
-        if (rc != DIR_OK) return rc;
-        rc = stem_pool_u8_launch(raw ? img : nullptr, s2d, d_stem_u8_w, d_stem_u8_w_lo, d_stem_u8_bias, d_stem_u8_corr,
-                                 (uint16_t*)(base + p.bufA), (uint16_t*)(base + p.lo_stem), B, H, W, stream, d_ovf, sw.stem_u8_seg);
-        if (rc != DIR_OK) return rc;
-        return prof_end(stream);
+        if (!raw)
+            DIR_CHECK(profiled("prep_input", "prep_input_u8", 0, (double)B * H * W * 3 + (double)B * p.H2 * p.W2 * 32, stream,
+                               [&] { return prep_input_u8(img, s2d, B, H, W, stream); }));
+        return profiled("conv1+maxpool", "stem_pool_u8", stem_flops,
+                        (raw ? (double)B * H * W * 3 : 2.0 * (double)B * p.H2 * p.W2 * 16) + out_bytes, stream, [&] {
+                            return stem_pool_u8_launch(raw ? img : nullptr, s2d, dev.stem_u8_w, dev.stem_u8_w_lo, dev.stem_u8_bias,
+                                                       dev.stem_u8_corr, y, y_lo, B, H, W, stream, dev.ovf, sw.stem_u8_seg);
+                        });
     }
     const bool raw_f32 = img && fmt == DIR_IMG_F32_NCHW && stem_pool_pair_raw_ok(img, B, H, W);   // the stem splits the fp32 image itself
     if (img && !raw_f32) {
-        rc = prof_begin("prep_input", "prep_input_pair", 0, (double)B * H * W * 3 * (fmt == DIR_IMG_U8_NHWC ? 1 : 4) +
-                        (double)B * p.H2 * p.W2 * 64, stream);
-        if (rc != DIR_OK) return rc;
-        rc = prep_input_pair(img, fmt, desc.mean, desc.std, s2d, s2d_lo, B, H, W, stream);
-        if (rc != DIR_OK) return rc;
-        if ((rc = prof_end(stream)) != DIR_OK) return rc;
+        DIR_CHECK(profiled("prep_input", "prep_input_pair", 0,
+                           (double)B * H * W * 3 * (fmt == DIR_IMG_U8_NHWC ? 1 : 4) + (double)B * p.H2 * p.W2 * 64, stream,
+                           [&] { return prep_input_pair(img, fmt, desc.mean, desc.std, s2d, s2d_lo, B, H, W, stream); }));
     } else if (!img) {   // autotune: synthetic noise (the paired kernels themselves have nothing to tune)
         const long n = (long)B * p.H2 * p.W2 * 16;
         hipLaunchKernelGGL(fill_noise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, s2d, n, DIR_FP16);
         DIR_HIP_CHECK(hipGetLastError());
         DIR_HIP_CHECK(hipMemsetAsync(s2d_lo, 0, (size_t)n * 2, stream));
     }
-    rc = prof_begin("conv1+maxpool", "stem_pool_pair", 2.0 * B * p.OH1 * p.OW1 * 64.0 * 147.0,
-                    (raw_f32 ? (double)B * H * W * 12 : 4.0 * (double)B * p.H2 * p.W2 * 16) + 4.0 * ((double)B * p.PH * p.PW * 64 + 64 * 256), stream);
-    if (rc != DIR_OK) return rc;
-    if (raw_f32)
-        rc = stem_pool_pair_walk_launch(nullptr, nullptr, convs[0].d_w, convs[0].d_w_lo, convs[0].d_bias, (uint16_t*)(base + p.bufA),
-                                        (uint16_t*)(base + p.lo_stem), B, p.H2, p.W2, p.OH1, p.OW1, stream, d_ovf, img, H, W);
-    else
-        rc = stem_pool_pair_launch(s2d, s2d_lo, convs[0].d_w, convs[0].d_w_lo, convs[0].d_bias, (uint16_t*)(base + p.bufA),
-                                   (uint16_t*)(base + p.lo_stem), B, p.H2, p.W2, p.OH1, p.OW1, stream, d_ovf);
-    if (rc != DIR_OK) return rc;
-    return prof_end(stream);
+    const ConvLayer::Dev& c = convs[0].dev;
+    return profiled("conv1+maxpool", "stem_pool_pair", stem_flops,
+                    (raw_f32 ? (double)B * H * W * 12 : 4.0 * (double)B * p.H2 * p.W2 * 16) + out_bytes, stream, [&] {
+                        return raw_f32 ? stem_pool_pair_walk_launch(nullptr, nullptr, c.w, c.w_lo, c.bias, y, y_lo, B, p.H2, p.W2,
+                                                                    p.OH1, p.OW1, stream, dev.ovf, img, H, W)
+                                       : stem_pool_pair_launch(s2d, s2d_lo, c.w, c.w_lo, c.bias, y, y_lo, B, p.H2, p.W2, p.OH1,
+                                                               p.OW1, stream, dev.ovf);
+                    });
 }
 
 int dir_engine::forward_pair_head(const void* img, int B, int H, int W, int fmt, char* base, const Plan& p,
@@ -795,8 +691,7 @@ int dir_engine::forward_pair_head(const void* img, int B, int H, int W, int fmt,
     uint16_t* t1_lo = (uint16_t*)(base + p.lo_t1);
     uint16_t* t2_lo = (uint16_t*)(base + p.lo_t2);
     uint16_t* ds_lo = (uint16_t*)(base + p.lo_ds);
-    int rc = forward_pair_stem(img, B, H, W, fmt, base, p, stream);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(forward_pair_stem(img, B, H, W, fmt, base, p, stream));
     int cur = 0;
 
     // pair_acts form.  Which tensors are pairs (tests/precision_decomposition.py prices every storage point): the image,
@@ -813,29 +708,23 @@ int dir_engine::forward_pair_head(const void* img, int B, int H, int W, int fmt,
         const uint16_t *resid = x, *resid_lo = x_lo;
         // first block of a stage: the downsample rides in conv3's GEMM when it is pixel-aligned with t2 (stride 1, same
         // width: layer1); otherwise it is its own paired conv
-        const bool fuse_ds = bd.down >= 0 && desc.bottleneck && convs[bd.conv3].d_w_ds_lo != nullptr && x_lo != nullptr;
+        const bool fuse_ds = bd.down >= 0 && desc.bottleneck && convs[bd.conv3].dev.w_ds_lo != nullptr && x_lo != nullptr;
         if (bd.down >= 0 && !fuse_ds) {
-            rc = run_conv_pair(convs[bd.down], x, x_lo, nullptr, nullptr, ds, ds_lo, B, h, w, oh, ow, stream);
-            if (rc != DIR_OK) return rc;
+            DIR_CHECK(run_conv_pair(convs[bd.down], x, x_lo, nullptr, nullptr, ds, ds_lo, B, h, w, oh, ow, stream));
             resid = ds;
             resid_lo = ds_lo;
         }
         if (desc.bottleneck) {
-            rc = run_conv_pair(convs[bd.conv1], x, x_lo, nullptr, nullptr, t1, t1_lo, B, h, w, h, w, stream);
-            if (rc != DIR_OK) return rc;
-            rc = run_conv_pair(convs[bd.conv2], t1, t1_lo, nullptr, nullptr, t2, t2_lo, B, h, w, oh, ow, stream);
-            if (rc != DIR_OK) return rc;
+            DIR_CHECK(run_conv_pair(convs[bd.conv1], x, x_lo, nullptr, nullptr, t1, t1_lo, B, h, w, h, w, stream));
+            DIR_CHECK(run_conv_pair(convs[bd.conv2], t1, t1_lo, nullptr, nullptr, t2, t2_lo, B, h, w, oh, ow, stream));
             if (fuse_ds)
-                rc = run_conv_pair(convs[bd.conv3], t2, t2_lo, nullptr, nullptr, pp[nxt], nullptr, B, oh, ow, oh, ow, stream,
-                                   x, x_lo);
+                DIR_CHECK(run_conv_pair(convs[bd.conv3], t2, t2_lo, nullptr, nullptr, pp[nxt], nullptr, B, oh, ow, oh, ow, stream,
+                                        x, x_lo));
             else
-                rc = run_conv_pair(convs[bd.conv3], t2, t2_lo, resid, resid_lo, pp[nxt], nullptr, B, oh, ow, oh, ow, stream);
-            if (rc != DIR_OK) return rc;
+                DIR_CHECK(run_conv_pair(convs[bd.conv3], t2, t2_lo, resid, resid_lo, pp[nxt], nullptr, B, oh, ow, oh, ow, stream));
         } else {
-            rc = run_conv_pair(convs[bd.conv1], x, x_lo, nullptr, nullptr, t1, t1_lo, B, h, w, oh, ow, stream);
-            if (rc != DIR_OK) return rc;
-            rc = run_conv_pair(convs[bd.conv2], t1, t1_lo, resid, resid_lo, pp[nxt], nullptr, B, oh, ow, oh, ow, stream);
-            if (rc != DIR_OK) return rc;
+            DIR_CHECK(run_conv_pair(convs[bd.conv1], x, x_lo, nullptr, nullptr, t1, t1_lo, B, h, w, oh, ow, stream));
+            DIR_CHECK(run_conv_pair(convs[bd.conv2], t1, t1_lo, resid, resid_lo, pp[nxt], nullptr, B, oh, ow, oh, ow, stream));
         }
         cur = nxt;
         h = oh;
@@ -855,118 +744,80 @@ int dir_engine::forward_pair_head(const void* img, int B, int H, int W, int fmt,
 static constexpr long kSeamMinTiles = 2048;
 static constexpr long kSeam3MinTiles = 768;   // conv_seam3.hip: three 64-pixel tiles per CU
 
-int dir_engine::run_seam(ConvLayer& c3, ConvLayer& c1, const uint16_t* t2, const uint16_t* res, uint16_t* y,
-                         uint16_t* t1, int B, int H, int W, hipStream_t stream, int* used,
-                         const uint16_t* block_in, const uint16_t* block_in_lo) {
-    *used = 0;
+// No side effects: builds the kernel's arguments in *a and says whether it takes this shape (forward asks before it launches
+// the downsample that the DS form would fold in).
+bool dir_engine::pick_seam(const ConvLayer& c3, const ConvLayer& c1, const uint16_t* t2, const uint16_t* res, uint16_t* y,
+                           uint16_t* t1, int B, int H, int W, const uint16_t* block_in, const uint16_t* block_in_lo,
+                           ConvArgs* ap) const {
+    ConvArgs& a = *ap;
     // DIRTORCH_AMD_C3C1: "0" = never (A/B and bisecting), "force" = whenever the shapes qualify, default =
     // when every persistent workgroup gets at least ~8 pixel tiles to amortise loading both weight sets
-    if (sw.c3c1_off) return DIR_OK;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = t2;
-    a.w = c3.d_w;
-    a.w_lo = c3.d_w_lo;       // DIR_FP16P: the weights of layer1's 1x1s are pairs (conv_c3c1.hip WP3 / WP1)
-    a.w2_lo = c1.d_w_lo;
-    a.bias = c3.d_bias;
-    a.res = res;
+    if (sw.c3c1_off) return false;
+    conv_args_init(a, layer_geom(c3, B, H, W, H, W), t2, c3.dev.w, c3.dev.bias, res, y);
+    a.w_lo = c3.dev.w_lo;       // DIR_FP16P: the weights of layer1's 1x1s are pairs (conv_c3c1.hip WP3 / WP1)
     if (block_in) {   // DS form: the residual is the downsample conv of the block input, folded into this GEMM
-        if (!c3.d_w_ds || c3.Cin != 64) return DIR_OK;   // (the caller checks the downsample's own shape)
-        a.w = c3.d_w_ds;
-        a.w_lo = c3.d_w_ds_lo;
-        a.bias = c3.d_bias_ds;
+        if (!c3.dev.w_ds || c3.Cin != 64) return false;   // (the caller checks the downsample's own shape)
+        a.w = c3.dev.w_ds;
+        a.w_lo = c3.dev.w_ds_lo;
+        a.bias = c3.dev.bias_ds;
         a.res = nullptr;
         a.x2 = block_in;
         a.x2_lo = block_in_lo;
         a.Cin2 = 64;
-        if ((c3.d_w_lo != nullptr) != (a.w_lo != nullptr)) return DIR_OK;   // (a paired conv3 without the concatenated lo plane)
+        if ((c3.dev.w_lo != nullptr) != (a.w_lo != nullptr)) return false;   // (a paired conv3 without the concatenated lo plane)
     }
-    a.y = y;
-    a.B = B;
-    a.H = a.OH = H;
-    a.W = a.OW = W;
-    a.Cin = c3.Cin;
-    a.Cout = c3.Cout;
-    a.R = c3.R;
-    a.S = c3.S;
-    a.stride = c3.stride;
-    a.pad = c3.pad;
-    a.relu = c3.relu ? 1 : 0;
-    a.M = B * H * W;
-    a.Ktot = a.Cin;
-    a.w2 = c1.d_w;
-    a.bias2 = c1.d_bias;
-    a.y2 = t1;
-    a.Cout2 = c1.Cout;
-    a.relu2 = c1.relu ? 1 : 0;
-    a.ovf = d_ovf;
+    conv_args_next_conv1(a, c1.dev.w, c1.dev.w_lo, c1.dev.bias, t1, c1.Cout, c1.relu ? 1 : 0);
+    a.ovf = dev.ovf;
     if (c1.R != 1 || c1.S != 1 || c1.stride != 1 || c1.pad != 0 || c1.Cin != c3.Cout || !conv_c3c1_admissible(a))
-        return DIR_OK;
+        return false;
     // (the layer3 form streams its weights per tile anyway: it only needs a few tiles per persistent workgroup)
-    if (!sw.c3c1_force && (a.M + 63) / 64 < (a.Cin == 256 ? kSeam3MinTiles : kSeamMinTiles)) return DIR_OK;
-    if (a.Cin == 256 && !sw.experiments) return DIR_OK;   // conv_seam3.hip: experiments builds only (it loses: profiles/r04_seam3_ablation.txt)
+    if (!sw.c3c1_force && (a.M + 63) / 64 < (a.Cin == 256 ? kSeam3MinTiles : kSeamMinTiles)) return false;
+    if (a.Cin == 256 && !sw.experiments) return false;   // conv_seam3.hip: experiments builds only (it loses: profiles/r04_seam3_ablation.txt)
+    return true;
+}
+
+int dir_engine::run_seam(const ConvLayer& c3, const ConvLayer& c1, const ConvArgs& a, hipStream_t stream) {
+    const bool ds = a.x2 != nullptr;
     const double macs = (double)a.M * ((double)c3.Cout * (c3.Cin + a.Cin2) + (double)c1.Cout * c1.Cin);
-    const double bytes = 2.0 * ((double)a.M * (c3.Cin + a.Cin2 * (block_in_lo ? 2 : 1) + (block_in ? 1.0 : 2.0) * c3.Cout + c1.Cout) +
+    const double bytes = 2.0 * ((double)a.M * (c3.Cin + a.Cin2 * (a.x2_lo ? 2 : 1) + (ds ? 1.0 : 2.0) * c3.Cout + c1.Cout) +
                                 (double)c3.Cout * (c3.Cin + a.Cin2) * (a.w_lo ? 2 : 1) + (double)c1.Cout * c1.Cin * (a.w2_lo ? 2 : 1));
-    // profile row "layerS.J.c3c1": conv3 of block J + conv1 of block J+1
-    int rc = DIR_OK;
-    if (profiling && !prof_paused)
-        rc = prof_begin(c3.name.substr(0, c3.name.rfind('.')) + (block_in ? ".ds+c3c1" : ".c3c1"),
-                        (c3.Cin == 256 ? "conv_seam3<" : "conv_c3c1<") + std::to_string(c3.Cin) + (block_in ? ",ds" : "") +
-                            (a.w_lo ? ",wp>" : ">"),
-                        2.0 * macs, bytes, stream);
-    if (rc != DIR_OK) return rc;
-    hipError_t e = conv_c3c1_launch(a, kdtype(), stream);
-    if (e != hipSuccess) return fail(DIR_ERR_HIP, std::string("conv_c3c1 launch: ") + hipGetErrorString(e));
-    *used = 1;
-    return prof_end(stream);
+    return profiled(
+        [&](std::string& name, std::string& kernel) {   // profile row "layerS.J.c3c1": conv3 of block J + conv1 of block J+1
+            name = c3.name.substr(0, c3.name.rfind('.')) + (ds ? ".ds+c3c1" : ".c3c1");
+            kernel = (c3.Cin == 256 ? "conv_seam3<" : "conv_c3c1<") + std::to_string(c3.Cin) + (ds ? ",ds" : "") +
+                     (a.w_lo ? ",wp>" : ">");
+        },
+        2.0 * macs, bytes, stream, [&]() -> int {
+            hipError_t e = conv_c3c1_launch(a, kdtype(), stream);
+            if (e != hipSuccess) return fail(DIR_ERR_HIP, std::string("conv_c3c1 launch: ") + hipGetErrorString(e));
+            return DIR_OK;
+        });
 }
 
 // ---- conv3 + downsample as one two-source GEMM ------------------------------------------------------------
-int dir_engine::run_conv_dual(ConvLayer& c3, const ConvLayer& ds, const uint16_t* t2, const uint16_t* xin,
-                              uint16_t* y, int B, int Hin, int Win, int OH, int OW, hipStream_t stream, int* used,
-                              bool dry) {
-    *used = 0;
-    if (!c3.d_w_ds || sw.no_dual || c3.d_w_lo) return DIR_OK;   // (paired weights: conv_pair.hip has no strided two-source form)
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = t2;
-    a.w = c3.d_w_ds;
-    a.bias = c3.d_bias_ds;
-    a.y = y;
-    a.B = B;
-    a.H = a.OH = OH;
-    a.W = a.OW = OW;
-    a.Cin = c3.Cin;
-    a.Cout = c3.Cout;
-    a.R = a.S = 1;
-    a.stride = 1;
-    a.relu = c3.relu ? 1 : 0;
-    a.ovf = d_ovf;
-    a.M = B * OH * OW;
-    a.x2 = xin;
-    a.Cin2 = ds.Cin;
-    a.H2 = Hin;
-    a.W2 = Win;
-    a.stride2 = ds.stride;
-    a.Ktot = a.Cin + a.Cin2;
-    a.T = a.Ktot / 64;
-    const int variant = conv_pick_dual_variant(a);
-    if (variant < 0) return DIR_OK;
-    *used = 1;
-    if (dry) return DIR_OK;
+int dir_engine::pick_conv_dual(const ConvLayer& c3, const ConvLayer& ds, const uint16_t* t2, const uint16_t* xin, uint16_t* y,
+                               int B, int Hin, int Win, int OH, int OW, ConvArgs* a) const {
+    if (!c3.dev.w_ds || sw.no_dual || c3.dev.w_lo) return -1;   // (paired weights: conv_pair.hip has no strided two-source form)
+    conv_args_init(*a, {B, OH, OW, c3.Cin, c3.Cout, 1, 1, 1, 0, OH, OW, c3.relu ? 1 : 0}, t2, c3.dev.w_ds, c3.dev.bias_ds, nullptr, y);
+    a->ovf = dev.ovf;
+    conv_args_second_source(*a, xin, nullptr, ds.Cin);
+    a->H2 = Hin;
+    a->W2 = Win;
+    a->stride2 = ds.stride;
+    return conv_pick_dual_variant(*a);
+}
+
+int dir_engine::run_conv_dual(const ConvLayer& c3, const ConvLayer& ds, const ConvArgs& a, int variant, hipStream_t stream) {
     const double macs = (double)a.M * c3.Cout * (double)a.Ktot;
     const double bytes = 2.0 * ((double)a.M * (c3.Cin + ds.Cin + c3.Cout) + (double)c3.Cout * a.Ktot);
-    int rc = DIR_OK;
-    if (profiling && !prof_paused)
-        rc = prof_begin(c3.name.substr(0, c3.name.rfind('.')) + ".ds+conv3",
-                        // ("conv_igemm<VARIANT>" is the family label of every entry of the variant table; the variant name says
-                        // which kernel file runs it: 256x256_persist1x1_x3 = conv_persist.hip's deep-X ring, DUAL form)
-                        std::string("conv_igemm<") + conv_variant(variant).name + "/dual>", 2.0 * macs, bytes, stream);
-    if (rc != DIR_OK) return rc;
-    rc = conv_launch(a, kdtype(), variant, stream);
-    if (rc != DIR_OK) return rc;
-    return prof_end(stream);
+    return profiled(
+        [&](std::string& name, std::string& kernel) {
+            name = c3.name.substr(0, c3.name.rfind('.')) + ".ds+conv3";
+            // ("conv_igemm<VARIANT>" is the family label of every entry of the variant table; the variant name says
+            // which kernel file runs it: 256x256_persist1x1_x3 = conv_persist.hip's deep-X ring, DUAL form)
+            kernel = std::string("conv_igemm<") + conv_variant(variant).name + "/dual>";
+        },
+        2.0 * macs, bytes, stream, [&] { return conv_launch(a, kdtype(), variant, stream); });
 }
 
 // ---- forward ------------------------------------------------------------------------------------
@@ -980,8 +831,7 @@ int dir_engine::forward(const void* img, int B, int H, int W, int fmt, float* de
         return fail(DIR_ERR_STATE, "forward: the current HIP device (" + std::to_string(cur_dev) +
                                        ") is not the engine's device (" + std::to_string(device) + ")");
     Plan p;
-    int rc = plan(B, H, W, &p);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(plan(B, H, W, &p));
     if (!ws || ws_bytes < p.total)
         return fail(DIR_ERR_WORKSPACE, "workspace too small: need " + std::to_string(p.total) +
                                            " bytes, got " + std::to_string(ws_bytes));
@@ -1005,24 +855,19 @@ int dir_engine::forward(const void* img, int B, int H, int W, int fmt, float* de
     const uint16_t* cur_lo = nullptr;   // lo plane of the block input (DIR_FP16P: the stem's pooled output)
     if (dtype == DIR_FP16P && pair_acts) {
         // 1-2'. paired head: image, stem and the first pair_blocks residual blocks on fp16 pairs (conv_pair.hip)
-        rc = forward_pair_head(img, B, H, W, fmt, base, p, stream, &cur, &h, &w, &first_block);
-        if (rc != DIR_OK) return rc;
+        DIR_CHECK(forward_pair_head(img, B, H, W, fmt, base, p, stream, &cur, &h, &w, &first_block));
     } else if (dtype == DIR_FP16P) {
         // 1-2''. image and stem on pairs; the blocks run below on single fp16 planes, with paired 1x1 WEIGHTS in layer1
-        rc = forward_pair_stem(img, B, H, W, fmt, base, p, stream);
-        if (rc != DIR_OK) return rc;
+        DIR_CHECK(forward_pair_stem(img, B, H, W, fmt, base, p, stream));
         cur_lo = (const uint16_t*)(base + p.lo_stem);
         h = p.PH;
         w = p.PW;
     } else {
         // 1. image -> space-to-depth NHWC16
         if (img) {
-            rc = prof_begin("prep_input", "prep_input", 0, (double)B * H * W * 3 * (fmt == DIR_IMG_U8_NHWC ? 1 : 4) +
-                            (double)B * p.H2 * p.W2 * 32, stream);
-            if (rc != DIR_OK) return rc;
-            rc = prep_input(img, fmt, desc.mean, desc.std, s2d, B, H, W, kd, stream);
-            if (rc != DIR_OK) return rc;
-            if ((rc = prof_end(stream)) != DIR_OK) return rc;
+            DIR_CHECK(profiled("prep_input", "prep_input", 0,
+                               (double)B * H * W * 3 * (fmt == DIR_IMG_U8_NHWC ? 1 : 4) + (double)B * p.H2 * p.W2 * 32, stream,
+                               [&] { return prep_input(img, fmt, desc.mean, desc.std, s2d, B, H, W, kd, stream); }));
         } else {  // autotune: synthetic noise straight into the s2d buffer
             const long n = (long)B * p.H2 * p.W2 * 16;
             hipLaunchKernelGGL(fill_noise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
@@ -1031,23 +876,15 @@ int dir_engine::forward(const void* img, int B, int H, int W, int fmt, float* de
         }
         // 2. stem + maxpool: one kernel (stem_pool.hip) unless DIRTORCH_AMD_UNFUSED_STEM=1
         if (sw.unfused_stem) {
-            rc = run_conv(convs[0], s2d, nullptr, stem, B, p.H2, p.W2, p.OH1, p.OW1, stream);
-            if (rc != DIR_OK) return rc;
-            rc = prof_begin("maxpool", "maxpool_3x3s2", 0,
-                            2.0 * ((double)B * p.OH1 * p.OW1 * 64 + (double)B * p.PH * p.PW * 64), stream);
-            if (rc != DIR_OK) return rc;
-            rc = maxpool_3x3s2(stem, cur, B, p.OH1, p.OW1, 64, kd, stream);
-            if (rc != DIR_OK) return rc;
-            if ((rc = prof_end(stream)) != DIR_OK) return rc;
+            DIR_CHECK(run_conv(convs[0], s2d, nullptr, stem, B, p.H2, p.W2, p.OH1, p.OW1, stream));
+            DIR_CHECK(profiled("maxpool", "maxpool_3x3s2", 0, 2.0 * ((double)B * p.OH1 * p.OW1 * 64 + (double)B * p.PH * p.PW * 64),
+                               stream, [&] { return maxpool_3x3s2(stem, cur, B, p.OH1, p.OW1, 64, kd, stream); }));
         } else {
-            rc = prof_begin("conv1+maxpool", "stem_pool", 2.0 * B * p.OH1 * p.OW1 * 64.0 * 147.0,
-                            2.0 * ((double)B * p.H2 * p.W2 * 16 + (double)B * p.PH * p.PW * 64 + 64 * 256),
-                            stream);
-            if (rc != DIR_OK) return rc;
-            rc = stem_pool_launch(s2d, convs[0].d_w, convs[0].d_bias, cur, B, p.H2, p.W2, p.OH1, p.OW1,
-                                  kd, stream, d_ovf);
-            if (rc != DIR_OK) return rc;
-            if ((rc = prof_end(stream)) != DIR_OK) return rc;
+            DIR_CHECK(profiled("conv1+maxpool", "stem_pool", 2.0 * B * p.OH1 * p.OW1 * 64.0 * 147.0,
+                               2.0 * ((double)B * p.H2 * p.W2 * 16 + (double)B * p.PH * p.PW * 64 + 64 * 256), stream, [&] {
+                                   return stem_pool_launch(s2d, convs[0].dev.w, convs[0].dev.bias, cur, B, p.H2, p.W2, p.OH1, p.OW1, kd,
+                                                           stream, dev.ovf);
+                               }));
         }
         h = p.PH;
         w = p.PW;
@@ -1072,66 +909,45 @@ int dir_engine::forward(const void* img, int B, int H, int W, int fmt, float* de
         // (A/B on one box) - and layer3's footprint in the workspace halves.
         if (!sw.no_inplace && desc.bottleneck && bd.down < 0 && !keep && !tuning && convs[bd.conv3].Cin >= 256) nxt = cur;
         const uint16_t* resid = cur;
-        // layer1's first block: the downsample can ride in the seam kernel as extra K (conv_c3c1.hip, DS
-        // form) - only if that kernel will actually run for this shape, decided before anything launches
-        // (the next block's conv1 is 1x1 stride 1 even across a stage boundary - the stride sits in conv2 -
-        // so the seam kernel also serves layer1 -> layer2; run_seam checks the widths it can hold)
+        // How a first block's downsample runs is decided here, before anything launches.  In layer1 it can ride in the seam
+        // kernel as extra K (conv_c3c1.hip, DS form), if pick_seam says that kernel will run for this shape: the next
+        // block's conv1 is 1x1 stride 1 even across a stage boundary (the stride sits in conv2), but the DS form needs it 64
+        // wide, so a layer1 of a single block, followed by layer2's 128-wide conv1, does not qualify; nor does a batch too
+        // large for the kernel, which is left to conv_launch's own 2^31-byte error.  Otherwise the downsample joins conv3 in a
+        // two-source GEMM (pick_conv_dual), or else runs as its own launch.
         const bool seam_next = desc.bottleneck && bi + 1 < blocks.size() && !tuning;
+        ConvArgs seam;
         bool ds_in_seam = false;
-        // (the DS form also needs the NEXT block's conv1 to be 64 wide - conv_c3c1_admissible: Cout2 == Cin; a
-        // layer1 of a single block is followed by layer2's 128-wide conv1 and takes the two-source GEMM instead)
-        if (bd.down >= 0 && seam_next && convs[bd.conv3].d_w_ds && convs[bd.conv3].Cin == 64 &&
-            convs[bd.down].Cin == 64 && convs[bd.down].stride == 1 && convs[blocks[bi + 1].conv1].Cout == 64 &&
-            convs[blocks[bi + 1].conv1].Cin == convs[bd.conv3].Cout) {
-            // (oversized batches are left to conv_launch's own 2^31-byte error)
-            ds_in_seam = !sw.c3c1_off && !sw.no_ds_seam && (sw.c3c1_force || ((long)B * oh * ow + 63) / 64 >= kSeamMinTiles) &&
-                         (long)B * oh * ow * convs[bd.conv3].Cout < (1L << 30);
-        }
-        // the other stages' first blocks: conv3 + downsample as one two-source GEMM (conv_persist.hip, DUAL)
-        int ds_dual = 0;
-        if (bd.down >= 0 && !ds_in_seam && desc.bottleneck && !tuning && !cur_lo) {
-            rc = run_conv_dual(convs[bd.conv3], convs[bd.down], t2, cur, nxt, B, h, w, oh, ow, stream, &ds_dual, true);
-            if (rc != DIR_OK) return rc;
-        }
-        if (bd.down >= 0 && !ds_in_seam && !ds_dual) {
-            rc = cur_lo ? run_conv_pair(convs[bd.down], cur, cur_lo, nullptr, nullptr, ds, nullptr, B, h, w, oh, ow, stream)
-                        : run_conv(convs[bd.down], cur, nullptr, ds, B, h, w, oh, ow, stream);
-            if (rc != DIR_OK) return rc;
+        if (bd.down >= 0 && seam_next && !sw.no_ds_seam && convs[bd.down].Cin == 64 && convs[bd.down].stride == 1)
+            ds_in_seam = pick_seam(convs[bd.conv3], convs[blocks[bi + 1].conv1], t2, nullptr, nxt, t1, B, oh, ow, cur, cur_lo, &seam);
+        ConvArgs dual;   // the other stages' first blocks (conv_persist.hip, DUAL)
+        int dual_variant = -1;
+        if (bd.down >= 0 && !ds_in_seam && desc.bottleneck && !tuning && !cur_lo)
+            dual_variant = pick_conv_dual(convs[bd.conv3], convs[bd.down], t2, cur, nxt, B, h, w, oh, ow, &dual);
+        if (bd.down >= 0 && !ds_in_seam && dual_variant < 0) {
+            DIR_CHECK(cur_lo ? run_conv_pair(convs[bd.down], cur, cur_lo, nullptr, nullptr, ds, nullptr, B, h, w, oh, ow, stream)
+                             : run_conv(convs[bd.down], cur, nullptr, ds, B, h, w, oh, ow, stream));
             resid = ds;
         }
         if (desc.bottleneck) {
-            if (!t1_ready) {   // (the previous block's fused seam kernel may have produced t1 already)
-                rc = cur_lo ? run_conv_pair(convs[bd.conv1], cur, cur_lo, nullptr, nullptr, t1, nullptr, B, h, w, h, w, stream)
-                            : run_conv(convs[bd.conv1], cur, nullptr, t1, B, h, w, h, w, stream, sw.rev_conv1);
-                if (rc != DIR_OK) return rc;
-            }
+            if (!t1_ready)   // (the previous block's fused seam kernel may have produced t1 already)
+                DIR_CHECK(cur_lo ? run_conv_pair(convs[bd.conv1], cur, cur_lo, nullptr, nullptr, t1, nullptr, B, h, w, h, w, stream)
+                                 : run_conv(convs[bd.conv1], cur, nullptr, t1, B, h, w, h, w, stream, sw.rev_conv1));
             t1_ready = false;
-            rc = run_conv(convs[bd.conv2], t1, nullptr, t2, B, h, w, oh, ow, stream);
-            if (rc != DIR_OK) return rc;
-            int fused = 0;
-            if (ds_dual) {
-                rc = run_conv_dual(convs[bd.conv3], convs[bd.down], t2, cur, nxt, B, h, w, oh, ow, stream, &fused, false);
-                if (rc != DIR_OK) return rc;
-                if (!fused) return fail(DIR_ERR_STATE, "two-source conv declined a downsample it was promised");
-                fused = 2;   // block output written; the next block's conv1 still has to run
-            } else if (seam_next) {
+            DIR_CHECK(run_conv(convs[bd.conv2], t1, nullptr, t2, B, h, w, oh, ow, stream));
+            if (dual_variant >= 0) {   // (block output written; the next block's conv1 still has to run)
+                DIR_CHECK(run_conv_dual(convs[bd.conv3], convs[bd.down], dual, dual_variant, stream));
+            } else if (seam_next && (ds_in_seam || pick_seam(convs[bd.conv3], convs[blocks[bi + 1].conv1], t2, resid, nxt, t1, B, oh,
+                                                             ow, nullptr, nullptr, &seam))) {
                 // conv3 + the next block's conv1 in one kernel: the block output is not re-read (conv_c3c1.hip)
-                rc = run_seam(convs[bd.conv3], convs[blocks[bi + 1].conv1], t2, resid, nxt, t1, B, oh, ow, stream,
-                              &fused, ds_in_seam ? cur : nullptr, ds_in_seam ? cur_lo : nullptr);
-                if (rc != DIR_OK) return rc;
-                if (ds_in_seam && !fused) return fail(DIR_ERR_STATE, "seam kernel declined a downsample it was promised");
-            }
-            if (fused == 1) {
+                DIR_CHECK(run_seam(convs[bd.conv3], convs[blocks[bi + 1].conv1], seam, stream));
                 t1_ready = true;
-            } else if (!fused) {
-                rc = run_conv(convs[bd.conv3], t2, resid, nxt, B, oh, ow, oh, ow, stream, sw.rev_conv3);
-                if (rc != DIR_OK) return rc;
+            } else {
+                DIR_CHECK(run_conv(convs[bd.conv3], t2, resid, nxt, B, oh, ow, oh, ow, stream, sw.rev_conv3));
             }
         } else {
-            rc = run_conv(convs[bd.conv1], cur, nullptr, t1, B, h, w, oh, ow, stream);
-            if (rc != DIR_OK) return rc;
-            rc = run_conv(convs[bd.conv2], t1, resid, nxt, B, oh, ow, oh, ow, stream);
-            if (rc != DIR_OK) return rc;
+            DIR_CHECK(run_conv(convs[bd.conv1], cur, nullptr, t1, B, h, w, oh, ow, stream));
+            DIR_CHECK(run_conv(convs[bd.conv2], t1, resid, nxt, B, oh, ow, oh, ow, stream));
         }
         cur = nxt;
         cur_lo = nullptr;   // block outputs are single planes in every mode
@@ -1159,54 +975,41 @@ int dir_engine::forward(const void* img, int B, int H, int W, int fmt, float* de
         const uint16_t* c4 = x4;
         if (conv1x5 >= 0) {
             uint16_t* sum = cur == pp[0] ? pp[1] : pp[0];
-            rc = run_conv(convs[conv1x5], cur, nullptr, t1, B, h, w, h, w, stream);
-            if (rc != DIR_OK) return rc;
-            rc = prof_begin("x4+up(c5)", "upsample_add", 0,
-                            2.0 * ((double)B * h4 * w4 * x4_dim * 2 + (double)B * h * w * x4_dim), stream);
-            if (rc != DIR_OK) return rc;
-            rc = upsample_add(x4, t1, sum, B, h4, w4, h, w, x4_dim, kd, stream, d_ovf);
-            if (rc != DIR_OK) return rc;
-            if ((rc = prof_end(stream)) != DIR_OK) return rc;
-            rc = run_conv(convs[conv3c4], sum, nullptr, t2, B, h4, w4, h4, w4, stream);
-            if (rc != DIR_OK) return rc;
+            DIR_CHECK(run_conv(convs[conv1x5], cur, nullptr, t1, B, h, w, h, w, stream));
+            DIR_CHECK(profiled("x4+up(c5)", "upsample_add", 0, 2.0 * ((double)B * h4 * w4 * x4_dim * 2 + (double)B * h * w * x4_dim),
+                               stream, [&] { return upsample_add(x4, t1, sum, B, h4, w4, h, w, x4_dim, kd, stream, dev.ovf); }));
+            DIR_CHECK(run_conv(convs[conv3c4], sum, nullptr, t2, B, h4, w4, h4, w4, stream));
             c4 = t2;
         }
-        rc = prof_begin("adpoolc4", "global_pool", 0, (double)B * h4 * w4 * x4_dim * 2, stream);
-        if (rc != DIR_OK) return rc;
-        rc = global_pool(c4, pooled, head_dim, B, h4, w4, x4_dim, DIR_POOL_GEM, gem_p4, 1e-6f, 0.f,
-                         kd, stream);
-        if (rc != DIR_OK) return rc;
-        if ((rc = prof_end(stream)) != DIR_OK) return rc;
+        DIR_CHECK(profiled("adpoolc4", "global_pool", 0, (double)B * h4 * w4 * x4_dim * 2, stream, [&] {
+            return global_pool(c4, pooled, head_dim, B, h4, w4, x4_dim, DIR_POOL_GEM, gem_p4, 1e-6f, 0.f, kd, stream);
+        }));
     }
-    rc = prof_begin(fpn ? "adpoolx5" : "adpool", "global_pool", 0,
-                    (double)B * h * w * feat_dim * 2 + (double)B * feat_dim * 4, stream);
-    if (rc != DIR_OK) return rc;
     // the FPN forward never applies center_bias (rmac_resnet_fpn.py:50-86), the classifier averages
-    rc = global_pool(cur, pooled + (fpn ? x4_dim : 0), head_dim, B, h, w, feat_dim,
-                     classifier ? DIR_POOL_AVG : desc.pooling, gem_p, 1e-6f,
-                     (fpn || classifier) ? 0.f : desc.center_bias, kd, stream);
-    if (rc != DIR_OK) return rc;
-    if ((rc = prof_end(stream)) != DIR_OK) return rc;
-    if (desc.norm_features && !classifier) {
-        rc = l2norm_rows(pooled, B, head_dim, 1e-12f, stream);
-        if (rc != DIR_OK) return rc;
-    }
+    DIR_CHECK(profiled(fpn ? "adpoolx5" : "adpool", "global_pool", 0, (double)B * h * w * feat_dim * 2 + (double)B * feat_dim * 4,
+                       stream, [&] {
+                           return global_pool(cur, pooled + (fpn ? x4_dim : 0), head_dim, B, h, w, feat_dim,
+                                              classifier ? DIR_POOL_AVG : desc.pooling, gem_p, 1e-6f,
+                                              (fpn || classifier) ? 0.f : desc.center_bias, kd, stream);
+                       }));
+    return finish_descriptor(pooled, fcout, B, desc_out, stream);
+}
+
+// ---- what follows pooling, in every dtype: (L2) -> FC (fp32 MFMA) -> L2 -> the caller's buffer ------------------------------
+int dir_engine::finish_descriptor(float* pooled, float* fcout, int B, float* desc_out, hipStream_t stream) {
+    const bool classifier = desc.head == DIR_HEAD_CLASSIFIER;
+    if (desc.norm_features && !classifier) DIR_CHECK(l2norm_rows(pooled, B, head_dim, 1e-12f, stream));
     const int D = desc.without_fc ? head_dim : desc.out_dim;
     if (!desc.without_fc) {
-        rc = prof_begin("fc", "gemm_nt_f32", 2.0 * B * head_dim * (double)D,
-                        4.0 * ((double)D * head_dim + (double)B * (head_dim + D)), stream);
-        if (rc != DIR_OK) return rc;
-        rc = gemm_nt_f32(d_fc_w, head_dim, pooled, head_dim, fcout, D, D, B, head_dim, nullptr,
-                         d_fc_b, nullptr, stream, splitk_scratch, kSplitKMaxBytes);   // the convs are done with it
-        if (rc != DIR_OK) return rc;
-        if ((rc = prof_end(stream)) != DIR_OK) return rc;
+        DIR_CHECK(profiled("fc", "gemm_nt_f32", 2.0 * B * head_dim * (double)D,
+                           4.0 * ((double)D * head_dim + (double)B * (head_dim + D)), stream, [&] {
+                               return gemm_nt_f32(dev.fc_w, head_dim, pooled, head_dim, fcout, D, D, B, head_dim, nullptr, dev.fc_b,
+                                                  nullptr, stream, splitk_scratch, kSplitKMaxBytes);   // the convs are done with it
+                           }));
     } else {
         fcout = pooled;
     }
-    if (!classifier) {
-        rc = l2norm_rows(fcout, B, D, 1e-12f, stream);
-        if (rc != DIR_OK) return rc;
-    }
+    if (!classifier) DIR_CHECK(l2norm_rows(fcout, B, D, 1e-12f, stream));
     DIR_HIP_CHECK(hipMemcpyAsync(desc_out, fcout, (size_t)B * D * 4, hipMemcpyDeviceToDevice, stream));
     return DIR_OK;
 }
@@ -1219,43 +1022,15 @@ int dir_engine::forward(const void* img, int B, int H, int W, int fmt, float* de
 int dir_engine::run_conv_f32(ConvLayer& L, const float* x, const float* res, float* y, int B, int H, int W, int OH,
                              int OW, hipStream_t stream) {
     ConvF32Args a;
-    memset(&a, 0, sizeof(a));
-    a.x = x;
-    a.w = L.d_wf;
-    a.bias = L.d_bias;
-    a.res = res;
-    a.y = y;
-    a.B = B;
-    a.H = H;
-    a.W = W;
-    a.OH = OH;
-    a.OW = OW;
-    a.Cout = L.Cout;
-    if (L.stem) {  // (H, W) is the space-to-depth grid
-        a.Cin = 16;
-        a.R = a.S = 4;
-        a.stride = 1;
-        a.pad = 2;
-    } else {
-        a.Cin = L.Cin;
-        a.R = L.R;
-        a.S = L.S;
-        a.stride = L.stride;
-        a.pad = L.pad;
-    }
-    a.relu = L.relu ? 1 : 0;
-    a.M = B * OH * OW;
-    a.Ktot = a.R * a.S * a.Cin;
+    conv_geom_fill(a, layer_geom(L, B, H, W, OH, OW), x, L.dev.wf, L.dev.bias, res, y);
     const double macs = (double)a.M * L.Cout * (double)(L.R * L.S * L.Cin);
     const double bytes = 4.0 * ((double)B * H * W * a.Cin + (double)a.M * L.Cout * (res ? 2 : 1) + (double)L.Cout * a.Ktot);
-    int rc = DIR_OK;
-    if (profiling && !prof_paused)
-        rc = prof_begin(L.name, std::string("conv_f32<") + (L.Cout <= 64 ? "128x64" : "128x128") + ">", 2.0 * macs, bytes,
-                        stream);
-    if (rc != DIR_OK) return rc;
-    rc = conv_f32_launch(a, stream);
-    if (rc != DIR_OK) return rc;
-    return prof_end(stream);
+    return profiled(
+        [&](std::string& name, std::string& kernel) {
+            name = L.name;
+            kernel = std::string("conv_f32<") + (L.Cout <= 64 ? "128x64" : "128x128") + ">";
+        },
+        2.0 * macs, bytes, stream, [&] { return conv_f32_launch(a, stream); });
 }
 
 int dir_engine::forward_f32(const void* img, int B, int H, int W, int fmt, float* desc_out, void* feat_out, int* fh,
@@ -1269,21 +1044,13 @@ int dir_engine::forward_f32(const void* img, int B, int H, int W, int fmt, float
     float* fcout = (float*)(base + p.fcout);
     float* const pp[2] = {(float*)(base + p.bufA), (float*)(base + p.bufB)};
     if (!img) return fail(DIR_ERR_INVALID, "autotune has nothing to choose in the fp32 path");
-    int rc = prof_begin("prep_input", "prep_input_f32", 0,
-                        (double)B * H * W * 3 * (fmt == DIR_IMG_U8_NHWC ? 1 : 4) + (double)B * p.H2 * p.W2 * 64, stream);
-    if (rc != DIR_OK) return rc;
-    rc = prep_input_f32(img, fmt, desc.mean, desc.std, s2d, B, H, W, stream);
-    if (rc != DIR_OK) return rc;
-    if ((rc = prof_end(stream)) != DIR_OK) return rc;
-    rc = run_conv_f32(convs[0], s2d, nullptr, stem, B, p.H2, p.W2, p.OH1, p.OW1, stream);
-    if (rc != DIR_OK) return rc;
+    DIR_CHECK(profiled("prep_input", "prep_input_f32", 0,
+                       (double)B * H * W * 3 * (fmt == DIR_IMG_U8_NHWC ? 1 : 4) + (double)B * p.H2 * p.W2 * 64, stream,
+                       [&] { return prep_input_f32(img, fmt, desc.mean, desc.std, s2d, B, H, W, stream); }));
+    DIR_CHECK(run_conv_f32(convs[0], s2d, nullptr, stem, B, p.H2, p.W2, p.OH1, p.OW1, stream));
     float* cur = pp[0];
-    rc = prof_begin("maxpool", "maxpool_f32", 0, 4.0 * ((double)B * p.OH1 * p.OW1 * 64 + (double)B * p.PH * p.PW * 64),
-                    stream);
-    if (rc != DIR_OK) return rc;
-    rc = maxpool_3x3s2_f32(stem, cur, B, p.OH1, p.OW1, 64, stream);
-    if (rc != DIR_OK) return rc;
-    if ((rc = prof_end(stream)) != DIR_OK) return rc;
+    DIR_CHECK(profiled("maxpool", "maxpool_f32", 0, 4.0 * ((double)B * p.OH1 * p.OW1 * 64 + (double)B * p.PH * p.PW * 64), stream,
+                       [&] { return maxpool_3x3s2_f32(stem, cur, B, p.OH1, p.OW1, 64, stream); }));
 
     float* x4 = nullptr;
     int h = p.PH, w = p.PW, h4 = 0, w4 = 0;
@@ -1294,22 +1061,16 @@ int dir_engine::forward_f32(const void* img, int B, int H, int W, int fmt, float
         float* nxt = keep ? (float*)(base + p.x4) : (cur == pp[0] ? pp[1] : pp[0]);
         const float* resid = cur;
         if (bd.down >= 0) {
-            rc = run_conv_f32(convs[bd.down], cur, nullptr, ds, B, h, w, oh, ow, stream);
-            if (rc != DIR_OK) return rc;
+            DIR_CHECK(run_conv_f32(convs[bd.down], cur, nullptr, ds, B, h, w, oh, ow, stream));
             resid = ds;
         }
         if (desc.bottleneck) {
-            rc = run_conv_f32(convs[bd.conv1], cur, nullptr, t1, B, h, w, h, w, stream);
-            if (rc != DIR_OK) return rc;
-            rc = run_conv_f32(convs[bd.conv2], t1, nullptr, t2, B, h, w, oh, ow, stream);
-            if (rc != DIR_OK) return rc;
-            rc = run_conv_f32(convs[bd.conv3], t2, resid, nxt, B, oh, ow, oh, ow, stream);
-            if (rc != DIR_OK) return rc;
+            DIR_CHECK(run_conv_f32(convs[bd.conv1], cur, nullptr, t1, B, h, w, h, w, stream));
+            DIR_CHECK(run_conv_f32(convs[bd.conv2], t1, nullptr, t2, B, h, w, oh, ow, stream));
+            DIR_CHECK(run_conv_f32(convs[bd.conv3], t2, resid, nxt, B, oh, ow, oh, ow, stream));
         } else {
-            rc = run_conv_f32(convs[bd.conv1], cur, nullptr, t1, B, h, w, oh, ow, stream);
-            if (rc != DIR_OK) return rc;
-            rc = run_conv_f32(convs[bd.conv2], t1, resid, nxt, B, oh, ow, oh, ow, stream);
-            if (rc != DIR_OK) return rc;
+            DIR_CHECK(run_conv_f32(convs[bd.conv1], cur, nullptr, t1, B, h, w, oh, ow, stream));
+            DIR_CHECK(run_conv_f32(convs[bd.conv2], t1, resid, nxt, B, oh, ow, oh, ow, stream));
         }
         cur = nxt;
         h = oh;
@@ -1334,45 +1095,18 @@ int dir_engine::forward_f32(const void* img, int B, int H, int W, int fmt, float
         const float* c4 = x4;
         if (conv1x5 >= 0) {
             float* sum = cur == pp[0] ? pp[1] : pp[0];
-            rc = run_conv_f32(convs[conv1x5], cur, nullptr, t1, B, h, w, h, w, stream);
-            if (rc != DIR_OK) return rc;
-            rc = upsample_add_f32(x4, t1, sum, B, h4, w4, h, w, x4_dim, stream);
-            if (rc != DIR_OK) return rc;
-            rc = run_conv_f32(convs[conv3c4], sum, nullptr, t2, B, h4, w4, h4, w4, stream);
-            if (rc != DIR_OK) return rc;
+            DIR_CHECK(run_conv_f32(convs[conv1x5], cur, nullptr, t1, B, h, w, h, w, stream));
+            DIR_CHECK(upsample_add_f32(x4, t1, sum, B, h4, w4, h, w, x4_dim, stream));
+            DIR_CHECK(run_conv_f32(convs[conv3c4], sum, nullptr, t2, B, h4, w4, h4, w4, stream));
             c4 = t2;
         }
-        rc = global_pool_f32(c4, pooled, head_dim, B, h4, w4, x4_dim, DIR_POOL_GEM, gem_p4, 1e-6f, 0.f, stream);
-        if (rc != DIR_OK) return rc;
+        DIR_CHECK(global_pool_f32(c4, pooled, head_dim, B, h4, w4, x4_dim, DIR_POOL_GEM, gem_p4, 1e-6f, 0.f, stream));
     }
-    rc = prof_begin(fpn ? "adpoolx5" : "adpool", "global_pool_f32", 0,
-                    (double)B * h * w * feat_dim * 4 + (double)B * feat_dim * 4, stream);
-    if (rc != DIR_OK) return rc;
-    rc = global_pool_f32(cur, pooled + (fpn ? x4_dim : 0), head_dim, B, h, w, feat_dim,
-                         classifier ? DIR_POOL_AVG : desc.pooling, gem_p, 1e-6f,
-                         (fpn || classifier) ? 0.f : desc.center_bias, stream);
-    if (rc != DIR_OK) return rc;
-    if ((rc = prof_end(stream)) != DIR_OK) return rc;
-    if (desc.norm_features && !classifier) {
-        rc = l2norm_rows(pooled, B, head_dim, 1e-12f, stream);
-        if (rc != DIR_OK) return rc;
-    }
-    const int D = desc.without_fc ? head_dim : desc.out_dim;
-    if (!desc.without_fc) {
-        rc = prof_begin("fc", "gemm_nt_f32", 2.0 * B * head_dim * (double)D,
-                        4.0 * ((double)D * head_dim + (double)B * (head_dim + D)), stream);
-        if (rc != DIR_OK) return rc;
-        rc = gemm_nt_f32(d_fc_w, head_dim, pooled, head_dim, fcout, D, D, B, head_dim, nullptr, d_fc_b, nullptr, stream,
-                         splitk_scratch, kSplitKMaxBytes);
-        if (rc != DIR_OK) return rc;
-        if ((rc = prof_end(stream)) != DIR_OK) return rc;
-    } else {
-        fcout = pooled;
-    }
-    if (!classifier) {
-        rc = l2norm_rows(fcout, B, D, 1e-12f, stream);
-        if (rc != DIR_OK) return rc;
-    }
-    DIR_HIP_CHECK(hipMemcpyAsync(desc_out, fcout, (size_t)B * D * 4, hipMemcpyDeviceToDevice, stream));
-    return DIR_OK;
+    DIR_CHECK(profiled(fpn ? "adpoolx5" : "adpool", "global_pool_f32", 0, (double)B * h * w * feat_dim * 4 + (double)B * feat_dim * 4,
+                       stream, [&] {
+                           return global_pool_f32(cur, pooled + (fpn ? x4_dim : 0), head_dim, B, h, w, feat_dim,
+                                                  classifier ? DIR_POOL_AVG : desc.pooling, gem_p, 1e-6f,
+                                                  (fpn || classifier) ? 0.f : desc.center_bias, stream);
+                       }));
+    return finish_descriptor(pooled, fcout, B, desc_out, stream);
 }
