@@ -778,6 +778,19 @@ int dir_revisitop_ap(const int* probe_idx, int Q, int P, const int* counts, cons
     DIR_CATCH
 }
 
+int dir_label_rank(const float* scores, int lds, int Q, int N, const int* labels, const int* class_off,
+                   const int* class_members, int C, const int* qclass, const int* qself, double* ap, int* best_rank,
+                   void* stream) {
+    DIR_TRY
+    if (Q < 0 || N < 0 || C < 0) return fail(DIR_ERR_INVALID, "label_rank: negative size");
+    if (Q == 0) return DIR_OK;
+    if (!class_off || !qclass || !qself || !ap || !best_rank || (N > 0 && (!scores || !labels || !class_members)))
+        return fail(DIR_ERR_INVALID, "label_rank: null pointer");
+    return label_rank(scores, lds, Q, N, labels, class_off, class_members, C, qclass, qself, ap, best_rank,
+                      (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_expand_descriptors(const float* descs, int n, const float* db, int m, int D, int k, float alpha,
                            int self_set, float* out, float* sim, size_t sim_bytes, void* stream) {
     DIR_TRY

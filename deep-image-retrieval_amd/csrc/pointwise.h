@@ -46,6 +46,10 @@ int rank_counts(const float* scores, int lds, int Q, int N, const int* probe_idx
 int revisitop_ap(const int* probe_idx, int Q, int P, const int* counts, const float* pscores, const int* pos_off,
                  const int* pos_list, const int* junk_off, const int* junk_list, int modes, double* terms,
                  double* ap_out, hipStream_t stream);
+// class-labelled datasets (label_rank.hip): sklearn AP and the best rank of a same-class image, per query
+int label_rank(const float* scores, int lds, int Q, int N, const int* labels, const int* class_off,
+               const int* class_members, int C, const int* qclass, const int* qself, double* ap, int* best_rank,
+               hipStream_t stream);
 int expand_descriptors(const float* descs, int n, const float* db, int m, int D, int k, float alpha,
                        int self_set, float* out, float* sim, size_t sim_bytes, hipStream_t stream);
 // scratch (optional): fp32 workspace for the split-K partial sums of shapes with few output tiles; without one

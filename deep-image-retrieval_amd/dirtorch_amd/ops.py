@@ -368,6 +368,36 @@ def revisitop_ap(probe_idx, counts, pscores, pos_off, pos_list, junk_off, junk_l
     return ap
 
 
+def label_rank(scores, labels, class_off, class_members, qclass, qself):
+    """Class-labelled ranking of a block of score rows (dir_label_rank, csrc/label_rank.hip) -> (ap [Q] float64,
+    best_rank [Q] int32), both CUDA.  scores [Q,N] fp32 with unit column stride and any row pitch >= N; labels [N],
+    class_off [C+1], class_members [N], qclass [Q], qself [Q] int32 CUDA (ranking.build_label_tables).  ap = sklearn's
+    average_precision_score over every image but qself (-1 without a positive, NaN for a row with a non-finite kept
+    score), best_rank = position of the best same-class image under np.argsort(-scores, kind='stable') (N when the
+    class has no image).  Tables that do not fit together raise DirError; the call synchronises the stream once."""
+    tables = (labels, class_off, class_members, qclass, qself)
+    for t in (scores,) + tables:
+        if not t.is_cuda:
+            raise ValueError('device tensor expected')
+    if scores.dtype != torch.float32 or scores.dim() != 2 or any(t.dtype != torch.int32 for t in tables):
+        raise TypeError('float32 scores [Q,N] and int32 tables expected')
+    if any(t.dim() != 1 or not t.is_contiguous() for t in tables):
+        raise ValueError('contiguous 1-D tables expected')
+    Q, N = scores.shape
+    if Q > 1 and (scores.stride(1) != 1 or scores.stride(0) < N) or (Q <= 1 and not scores.is_contiguous()):
+        scores = scores.contiguous()
+    lds = int(scores.stride(0)) if Q > 1 else N
+    C = int(class_off.numel()) - 1
+    if C < 0 or labels.numel() != N or class_members.numel() != N or qclass.numel() != Q or qself.numel() != Q:
+        raise ValueError('labels [N], class_off [C+1], class_members [N], qclass [Q], qself [Q] expected for scores [Q,N]')
+    ap = torch.empty(Q, dtype=torch.float64, device=scores.device)
+    best = torch.empty(Q, dtype=torch.int32, device=scores.device)
+    if Q:
+        call('dir_label_rank', ptr(scores), lds, Q, N, ptr(labels), ptr(class_off), ptr(class_members), C, ptr(qclass),
+             ptr(qself), ptr(ap), ptr(best), stream_ptr())
+    return ap, best
+
+
 def expand_descriptors(descs, db=None, alpha=0.0, k=0, scratch_bytes=256 << 20):
     """alpha-QE / DBA on the device (dir_expand_descriptors): descs [n,D], db [m,D] fp32 CUDA (db None =
     expand the set against itself, a row never being its own neighbour) -> [n,D] fp32 CUDA."""

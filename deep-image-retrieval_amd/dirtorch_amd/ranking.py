@@ -1,4 +1,5 @@
-"""Device-side ranking + AP for revisitop-style datasets.
+"""Device-side ranking + AP for revisitop-style datasets and, further down, for class-labelled ones
+(build_label_tables / eval_labelled_device: sklearn AP and top-k hits, the score matrix made and ranked in row chunks).
 
 Same numbers as `[db.eval_query_AP(q, s) for q, s in enumerate(scores)]`
 (dirtorch/test_dir.py:153, dirtorch/datasets/generic.py:196-224) without downloading the Q x N score
@@ -127,3 +128,70 @@ def eval_aps_device(db, scores, tables=None):
         return [0.0 if a == -1 else float(a) for a in ap[:, 0]]     # classic protocol has no -1 (generic.py:199-208)
     return [{'easy': float(a[0]) if a[0] != -1 else -1, 'medium': float(a[1]) if a[1] != -1 else -1,
              'hard': float(a[2]) if a[2] != -1 else -1} for a in ap]
+
+
+# ---- class-labelled datasets: ImageListLabels / ImageListLabelsQ ----------------------------------------------------
+def build_label_tables(db):
+    """Host-side tables for eval_labelled_device, built once per dataset from db.labels / db.c_relevant_idx and
+    db.get_query_db() (dirtorch/datasets/dataset.py:70-101) - plain Python and numpy, no GPU:
+        labels [N]          class id of every database image (classes numbered in order of first appearance)
+        class_off [C+1], class_members [N]   CSR of the database indices of every class, shared by all its queries
+        qclass [Q]          class id of the query's label, -1 when no database image carries it
+        qself [Q]           the query's own database index when the queries ARE the database, else -1
+    all int32 ndarrays; plus C and same_set."""
+    query_db = db.get_query_db()
+    same_set = query_db is db
+    N = len(db.labels)
+    cid = {label: c for c, label in enumerate(db.c_relevant_idx)}
+    labels = np.fromiter((cid[l] for l in db.labels), dtype=np.int32, count=N)
+    sizes = [len(db.c_relevant_idx[label]) for label in cid]
+    class_off = np.zeros(len(cid) + 1, dtype=np.int32)
+    class_off[1:] = np.cumsum(sizes)
+    class_members = np.fromiter((i for label in cid for i in db.c_relevant_idx[label]), dtype=np.int32, count=N)
+    Q = len(query_db)
+    qclass = np.fromiter((cid.get(query_db.get_label(q), -1) for q in range(Q)), dtype=np.int32, count=Q)
+    qself = np.arange(Q, dtype=np.int32) if same_set else -np.ones(Q, dtype=np.int32)
+    return dict(labels=labels, class_off=class_off, class_members=class_members, qclass=qclass, qself=qself,
+                C=len(cid), same_set=same_set)
+
+
+def eval_labelled_device(db, qdescs, bdescs, tables=None, k=(1, 5, 10, 20, 50, 100), scratch_bytes=256 << 20):
+    """(aps, tops) of a class-labelled dataset: the lists `[db.eval_query_AP(q, s) ...]` and `[db.eval_query_top(q, s, k)
+    ...]` build from the rows s of the score matrix (dirtorch/test_dir.py:153-178) - floats with -1 for a query without
+    positives, and one {k_: 0.0 / 1.0} dict per query over the k_ < N - without that matrix: the queries are scored
+    (similarity_device's kernels) and ranked (ops.label_rank) in row chunks of scratch_bytes, each chunk dropped before
+    the next, and 12 bytes per query come back.  Ties at a top-k boundary break by ascending index (a stable argsort).
+    A chunk's scores are what ops.similarity gives for that block of queries: the fp32 GEMM starts every tile's sum at
+    its own K slab (csrc/gemm_f32.hip), so against the whole-matrix call the last bits of a score can differ once K has
+    more than two slabs of 32, and two near-equal neighbours can swap (one AP moved by 6.9e-5, the mAP by 3.3e-9, at Q = N = 20000, D = 2048 in six chunks).
+    A row with a NaN or infinite kept score raises ValueError, as sklearn does on the host path."""
+    from .utils.common import _dev
+    t = tables if tables is not None else build_label_tables(db)
+    q, b = _dev(qdescs), _dev(bdescs)
+    Q, N = q.shape[0], b.shape[0]
+    assert Q == len(t['qclass']) and N == len(t['labels']), "descriptors should have %d and %d rows" % (
+        len(t['qclass']), len(t['labels']))
+    if Q == 0:
+        return [], []
+    dev = {name: torch.as_tensor(t[name], dtype=torch.int32).to(b.device)
+           for name in ('labels', 'class_off', 'class_members', 'qclass', 'qself')}
+    # one verdict for every chunk (similarity_device's rule), so that a chunk's scores do not depend on the chunking
+    owned = b is bdescs
+    unit = bool(N >= UNIT_RANGE_MIN_ROWS and (database_is_unit_range(b) if owned else is_unit_range(b))
+                and is_unit_range(q))
+    rows = int(max(1, min(Q, scratch_bytes // max(4 * N, 1))))
+    ap = torch.empty(Q, dtype=torch.float64, device=b.device)
+    best = torch.empty(Q, dtype=torch.int32, device=b.device)
+    for r0 in range(0, Q, rows):
+        r1 = min(Q, r0 + rows)
+        scores = ops.similarity(q[r0:r1], b, unit_range=unit)
+        ap[r0:r1], best[r0:r1] = ops.label_rank(scores, dev['labels'], dev['class_off'], dev['class_members'],
+                                                dev['qclass'][r0:r1], dev['qself'][r0:r1])
+        del scores
+    ap, best = ap.cpu().numpy(), best.cpu().numpy()
+    bad = np.flatnonzero(np.isnan(ap))
+    if len(bad):
+        raise ValueError('query %d: its scores contain NaN or infinity' % int(bad[0]))
+    aps = [-1 if a == -1 else float(a) for a in ap]
+    tops = [{k_: float(r < k_) for k_ in k if k_ < N} for r in best.tolist()]
+    return aps, tops

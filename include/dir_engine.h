@@ -425,6 +425,25 @@ int dir_rank_counts(const float* scores, int lds, int Q, int N, const int* probe
 int dir_revisitop_ap(const int* probe_idx, int Q, int P, const int* counts, const float* probe_scores,
                      const int* pos_off, const int* pos_list, const int* junk_off, const int* junk_list,
                      int modes, double* terms, double* ap_out, void* stream);
+/* N1 for class-labelled datasets (ImageListLabels / ImageListLabelsQ): replaces, per query, get_query_groundtruth +
+ * sklearn's average_precision_score (dirtorch/datasets/dataset.py:70-101, dirtorch/utils/evaluation.py:41-43) and the
+ * argsort of eval_query_top (dirtorch/test_dir.py:153-178), without a sort of the score row.
+ *   scores [Q][lds] fp32, lds >= N; labels [N] = class id of every database image; class_off [C+1] / class_members [N] =
+ *   CSR of the database indices of every class (shared by all queries); qclass [Q] = the query's class, -1 when no
+ *   database image carries it; qself [Q] = the query's own database index when the queries ARE the database, else -1.
+ *   ap[q]        = (1/n_pos) sum over positives p of pos_ge(s_p) / all_ge(s_p), counted over the kept items (all but
+ *                  qself): sklearn's value - tied scores share one threshold, -0 == +0 - summed in fp64 in a fixed order;
+ *                  -1 when no kept item is positive; NaN when a kept score of the row is NaN or +-inf (sklearn raises)
+ *   best_rank[q] = position of the best-placed image of the class under np.argsort(-scores, kind='stable') (score
+ *                  descending, index ascending on ties, NaN last; qself is NOT left out): correct[:k].any() is
+ *                  best_rank < k; N when the class has no image
+ * The tables are checked on the device before anything indexes with them and the call waits for the verdict (one
+ * stream synchronisation per call): lds < N, a class_off that is no CSR from 0 to N, a class_members entry outside [0, N),
+ * filed under another class than labels gives it or listed twice (class_members is a permutation of the database
+ * indices), qclass outside [-1, C) or qself outside [-1, N) fail with DIR_ERR_INVALID and launch nothing else.  One workgroup per query; each score is read once per 4096 class members. */
+int dir_label_rank(const float* scores, int lds, int Q, int N, const int* labels, const int* class_off,
+                   const int* class_members, int C, const int* qclass, const int* qself, double* ap, int* best_rank,
+                   void* stream);
 /* N3: alpha query expansion / database augmentation, expand_descriptors of
  * dirtorch/test_dir.py:24-44.  out[i] = normalize(mean(descs[i], sim[i][j]^alpha * db[j] for the k
  * rows j of db most similar to descs[i])), sim = descs . db^T in fp32; self_set != 0 (db == descs,

@@ -187,6 +187,8 @@ def bench_kernel_name(k):
             'gemm_nt_small_kernel': 'gemm_nt_f32', 'gemm_nt_f32_kernel': 'gemm_nt_f32',
             # the PCA fit's Gram product and its slice reduction (csrc/cov_f32.hip; no timed bench.py step launches them)
             'cov_gram_kernel': 'gemm_nt_f32', 'cov_reduce_kernel': 'gemm_splitk_finalize_kernel',
+            # the class-labelled ranking and its table check (csrc/label_rank.hip; no timed bench.py step launches them)
+            'label_rank_kernel': 'rank_hist_kernel', 'label_check_kernel': 'rank_sort_kernel',
             'maxpool_kernel': 'maxpool_3x3s2', 'upsample_add_kernel': 'upsample_add',
             'prep_input_f32_kernel': 'prep_input_f32', 'maxpool_f32_kernel': 'maxpool_f32',
             'global_pool_f32_kernel': 'global_pool_f32', 'upsample_add_f32_kernel': 'upsample_add_f32',
