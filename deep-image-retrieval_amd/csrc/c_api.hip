@@ -791,6 +791,38 @@ int dir_label_rank(const float* scores, int lds, int Q, int N, const int* labels
     DIR_CATCH
 }
 
+int dir_topk_max_k(void) { return topk_max_k(); }
+
+static int topk_check_sizes(int Q, int N, int k) {
+    if (Q < 0 || N < 0) return fail(DIR_ERR_INVALID, "topk: negative size");
+    if (k < 1) return fail(DIR_ERR_INVALID, "topk: k < 1");
+    if (k > N || k > topk_max_k()) return fail(DIR_ERR_INVALID, "topk: k exceeds min(N, dir_topk_max_k())");
+    return DIR_OK;
+}
+
+int dir_topk_workspace_bytes(int Q, int N, int k, size_t* bytes) {
+    DIR_TRY
+    if (!bytes) return fail(DIR_ERR_INVALID, "topk_workspace_bytes: null pointer");
+    DIR_CHECK(topk_check_sizes(Q, N, k));
+    *bytes = topk_workspace_bytes(Q, N, k);
+    return DIR_OK;
+    DIR_CATCH
+}
+
+int dir_topk(const float* scores, int lds, int Q, int N, int k, const int* ids, const int* exclude, int* out_idx,
+             float* out_score, void* workspace, size_t workspace_bytes, void* stream) {
+    DIR_TRY
+    DIR_CHECK(topk_check_sizes(Q, N, k));
+    if (lds < N) return fail(DIR_ERR_INVALID, "topk: lds < N");
+    if (Q == 0) return DIR_OK;
+    if (!scores || !out_idx || !out_score) return fail(DIR_ERR_INVALID, "topk: null pointer");
+    const size_t need = topk_workspace_bytes(Q, N, k);
+    if (workspace_bytes < need || (need > 0 && !workspace))
+        return fail(DIR_ERR_INVALID, "topk: workspace smaller than dir_topk_workspace_bytes");
+    return topk(scores, lds, Q, N, k, ids, exclude, out_idx, out_score, workspace, workspace_bytes, (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_expand_descriptors(const float* descs, int n, const float* db, int m, int D, int k, float alpha,
                            int self_set, float* out, float* sim, size_t sim_bytes, void* stream) {
     DIR_TRY

@@ -50,6 +50,11 @@ int revisitop_ap(const int* probe_idx, int Q, int P, const int* counts, const fl
 int label_rank(const float* scores, int lds, int Q, int N, const int* labels, const int* class_off,
                const int* class_members, int C, const int* qclass, const int* qself, double* ap, int* best_rank,
                hipStream_t stream);
+// ranked neighbour lists (topk.hip): the k best items of every row under the order rank_counts counts in
+int topk_max_k();
+size_t topk_workspace_bytes(int Q, int N, int k);
+int topk(const float* scores, int lds, int Q, int N, int k, const int* ids, const int* exclude, int* out_idx,
+         float* out_score, void* workspace, size_t workspace_bytes, hipStream_t stream);
 int expand_descriptors(const float* descs, int n, const float* db, int m, int D, int k, float alpha,
                        int self_set, float* out, float* sim, size_t sim_bytes, hipStream_t stream);
 // scratch (optional): fp32 workspace for the split-K partial sums of shapes with few output tiles; without one

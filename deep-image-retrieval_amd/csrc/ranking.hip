@@ -10,6 +10,7 @@
 // only the few hundred listed images of the query (revisitop_ap_kernel at the end of this file).
 #include "dir_common.h"
 #include "pointwise.h"
+#include "rank_key.h"
 
 #include <algorithm>
 
@@ -34,10 +35,7 @@ constexpr int kMaxProbes = 4096;   // probes per query per launch (keys 32 KiB +
 constexpr uint64_t kKeyMax = ~0ull;
 
 __device__ __forceinline__ uint64_t rank_key(float s, int idx) {
-    if (s == 0.f) s = 0.f;                               // -0 -> +0: they compare equal
-    const uint32_t b = __builtin_bit_cast(uint32_t, s);
-    const uint32_t u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);   // order-preserving for every non-NaN float
-    return ((uint64_t)u << 32) | (uint32_t)idx;
+    return ((uint64_t)score_key_u32(s) << 32) | (uint32_t)idx;   // order-preserving for every non-NaN float, -0 == +0
 }
 
 // probe_idx / perm_out point at the slice: [Q][ldp] rows, P (<= kMaxProbes) columns in use, P2 = pow2 >= P.

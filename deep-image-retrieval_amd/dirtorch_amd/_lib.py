@@ -120,6 +120,10 @@ SIGNATURES = {
                                  c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'dir_label_rank': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p]),
+    'dir_topk_max_k': (c_int, []),
+    'dir_topk_workspace_bytes': (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    'dir_topk': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                         c_size_t, c_void_p]),
     'dir_expand_descriptors': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_int,
                                        c_void_p, c_void_p, c_size_t, c_void_p]),
     'dir_comm_init_all': (c_int, [c_int, POINTER(c_int), POINTER(c_void_p)]),

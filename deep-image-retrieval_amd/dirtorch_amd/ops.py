@@ -398,6 +398,53 @@ def label_rank(scores, labels, class_off, class_members, qclass, qself):
     return ap, best
 
 
+def topk_max_k():
+    """The largest k ops.topk takes (dir_topk_max_k; host-only)."""
+    return int(_lib.load().dir_topk_max_k())
+
+
+def topk(scores, k, exclude=None, ids=None):
+    """Ranked neighbour lists of a block of score rows (dir_topk, csrc/topk.hip) -> (idx [Q,k] int32, vals [Q,k] float32),
+    both CUDA: the k best items of every row, best first - score descending, larger id first among equal scores (-0 == +0),
+    NaN after every number; on a NaN-free row np.argsort(row, kind='stable')[::-1][:k].  scores [Q,N] fp32 with unit column
+    stride and any row pitch >= N; 1 <= k <= min(N, topk_max_k()).  ids [Q,N] int32 (same layout rules; None = the column
+    is the id): the id of every column, distinct within a row, -1 = an empty column - the form that merges lists.
+    exclude [Q] int32: the id left out of each row (-1 = none).  A row with fewer than k kept items ends in (-1, NaN)
+    slots; vals carries the stored bits of the picked scores.  The workspace is allocated here."""
+    tables = tuple(t for t in (exclude, ids) if t is not None)
+    for t in (scores,) + tables:
+        if not t.is_cuda:
+            raise ValueError('device tensor expected')
+    if scores.dtype != torch.float32 or scores.dim() != 2 or any(t.dtype != torch.int32 for t in tables):
+        raise TypeError('float32 scores [Q,N] and int32 tables expected')
+    Q, N = scores.shape
+    k = int(k)
+    if k < 1 or k > min(N, topk_max_k()):
+        raise ValueError('1 <= k <= min(N, %d) expected, got k = %d for N = %d' % (topk_max_k(), k, N))
+    if ids is not None and tuple(ids.shape) != (Q, N):
+        raise ValueError('ids [Q,N] expected for scores [Q,N]')
+    if exclude is not None and (exclude.dim() != 1 or exclude.numel() != Q or not exclude.is_contiguous()):
+        raise ValueError('contiguous exclude [Q] expected for scores [Q,N]')
+    if Q > 1 and (scores.stride(1) != 1 or scores.stride(0) < N) or (Q <= 1 and not scores.is_contiguous()):
+        scores = scores.contiguous()
+    lds = int(scores.stride(0)) if Q > 1 else N
+    if ids is not None:
+        # the library reads ids at the pitch of scores
+        if Q > 1 and (ids.stride(1) != 1 or ids.stride(0) != lds) or (Q <= 1 and not ids.is_contiguous()):
+            if lds != N:
+                scores, lds = scores.contiguous(), N
+            ids = ids.contiguous()
+    idx = torch.empty(Q, k, dtype=torch.int32, device=scores.device)
+    vals = torch.empty(Q, k, dtype=torch.float32, device=scores.device)
+    if Q:
+        need = ctypes.c_size_t(0)
+        call('dir_topk_workspace_bytes', Q, N, k, ctypes.byref(need))
+        ws = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=scores.device)
+        call('dir_topk', ptr(scores), lds, Q, N, k, ptr(ids), ptr(exclude), ptr(idx), ptr(vals), ptr(ws),
+             int(need.value), stream_ptr())
+    return idx, vals
+
+
 def expand_descriptors(descs, db=None, alpha=0.0, k=0, scratch_bytes=256 << 20):
     """alpha-QE / DBA on the device (dir_expand_descriptors): descs [n,D], db [m,D] fp32 CUDA (db None =
     expand the set against itself, a row never being its own neighbour) -> [n,D] fp32 CUDA."""

@@ -195,3 +195,54 @@ def eval_labelled_device(db, qdescs, bdescs, tables=None, k=(1, 5, 10, 20, 50, 1
     aps = [-1 if a == -1 else float(a) for a in ap]
     tops = [{k_: float(r < k_) for k_ in k if k_ < N} for r in best.tolist()]
     return aps, tops
+
+
+# ---- ranked neighbour lists -----------------------------------------------------------------------------------------
+def retrieve_device(qdescs, bdescs, k, same_set=False, scratch_bytes=256 << 20, db_rows=None):
+    """(idx [Q,k] int32, vals [Q,k] float32), both CUDA: the k best database rows of every query, best first, and their
+    scores - np.argsort(scores[q], kind='stable')[::-1][:k] of the rows of qdescs . bdescs^T (ops.topk's order: larger
+    index first among equal scores, NaN last) - without the Q x N matrix: the queries are scored (similarity_device's
+    kernels) and ranked (ops.topk) in row chunks of scratch_bytes, each chunk dropped before the next -
+    eval_labelled_device's loop, with its single unit-range verdict for all chunks.  1 <= k <= min(N, ops.topk_max_k()).
+    same_set=True (the queries ARE the database): row q's own index is left out, and a list of k = N ends in (-1, NaN).
+    db_rows: walk the database in blocks of that many rows as well; a block's k best are merged into the running list
+    through ops.topk's id table (the list and the block's candidates, 2k columns), so the scratch holds rows x db_rows
+    scores.  Lists of database shards merge the same way: concatenate (vals, idx + shard offset) and call ops.topk with
+    ids.  The lists depend on the scores alone; a score's last bits can depend on the chunking (eval_labelled_device)."""
+    from .utils.common import _dev
+    q, b = _dev(qdescs), _dev(bdescs)
+    Q, N = q.shape[0], b.shape[0]
+    k = int(k)
+    if k < 1 or k > min(N, ops.topk_max_k()):
+        raise ValueError('1 <= k <= min(N, %d) expected, got k = %d for N = %d' % (ops.topk_max_k(), k, N))
+    if same_set and Q != N:
+        raise ValueError('same_set: the queries are the database, got %d and %d rows' % (Q, N))
+    block = N if db_rows is None else int(max(k, min(N, db_rows)))     # (a block offers k candidates: at least k rows)
+    idx = torch.empty(Q, k, dtype=torch.int32, device=b.device)
+    vals = torch.empty(Q, k, dtype=torch.float32, device=b.device)
+    if Q == 0:
+        return idx, vals
+    owned = b is bdescs
+    unit = bool(N >= UNIT_RANGE_MIN_ROWS and (database_is_unit_range(b) if owned else is_unit_range(b))
+                and is_unit_range(q))
+    rows = int(max(1, min(Q, scratch_bytes // max(4 * block, 1))))
+    for r0 in range(0, Q, rows):
+        r1 = min(Q, r0 + rows)
+        own = torch.arange(r0, r1, dtype=torch.int32, device=b.device) if same_set else None
+        run_i = run_v = None
+        for b0 in range(0, N, block):
+            b1 = min(N, b0 + block)
+            scores = ops.similarity(q[r0:r1], b[b0:b1], unit_range=unit)
+            if b0 == 0 and b1 == N:
+                run_i, run_v = ops.topk(scores, k, exclude=own)
+                break
+            kb = min(k, b1 - b0)                                   # (only a ragged last block is shorter than k)
+            bi, bv = ops.topk(scores, kb, exclude=None if own is None else own - b0)
+            del scores
+            bi = torch.where(bi >= 0, bi + b0, bi)                 # block columns -> database rows; -1 stays a hole
+            if run_i is None:                                      # (the first block has at least k rows)
+                run_i, run_v = bi, bv
+            else:
+                run_i, run_v = ops.topk(torch.cat([run_v, bv], dim=1), k, ids=torch.cat([run_i, bi], dim=1))
+        idx[r0:r1], vals[r0:r1] = run_i, run_v
+    return idx, vals

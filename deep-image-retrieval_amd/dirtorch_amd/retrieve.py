@@ -1,0 +1,79 @@
+"""Ranked neighbour lists: the k best database images of every query, written to a file.
+
+    python -m dirtorch_amd.retrieve --dataset 'ImageList("db.txt")' --checkpoint X.pt --topk 20 --output pairs.txt
+
+Takes the flags of dirtorch_amd.eval_dir and prepares the descriptors the way it does (eval_dir.descriptors: extracted
+or --load-feats, pooled, L2-normalised, whitened, expanded); the lists come from ranking.retrieve_device, so the Q x N
+score matrix is never built or downloaded.  --output PATH:
+    PATH ending in .npz   arrays `idx` [Q,k] int32 (database index, -1 = no such neighbour) and `scores` [Q,k] float32
+    anything else         text: a `# query_image, map_image, score` header, then one `query_key, db_key, score` line
+                          per pair, best first, scores as %.9g (enough digits to give the float32 back)
+When the query set is the database itself a query is not its own neighbour.  Written on rank 0 only.
+"""
+import sys
+
+import numpy as np
+
+from . import datasets, eval_dir, ranking, test_dir
+from . import distributed as ddist
+from .utils.convenient import mkdir
+
+
+def query_keys(db):
+    """[key of query q] - get_query_key where the dataset has one, else the key inside its query dataset."""
+    query_db = db.get_query_db()
+    n = len(query_db)
+    try:
+        return [db.get_query_key(q) for q in range(n)]
+    except (AttributeError, NotImplementedError):
+        return [query_db.get_key(q) for q in range(n)]
+
+
+def write_lists(path, db, idx, scores):
+    """idx / scores: [Q,k] ndarrays of retrieve_device."""
+    mkdir(path, isfile=True)
+    if path.endswith('.npz'):
+        np.savez(path, idx=idx, scores=scores)
+        return
+    qkeys = query_keys(db)
+    with open(path, 'w') as f:
+        f.write('# query_image, map_image, score\n')
+        for q, (row_i, row_s) in enumerate(zip(idx, scores)):
+            for i, s in zip(row_i.tolist(), row_s.tolist()):
+                if i >= 0:
+                    f.write('%s, %s, %.9g\n' % (qkeys[q], db.get_key(i), s))
+
+
+def main(argv=None):
+    args = test_dir.build_parser(description='Write the top-k database images of every query', extra=[
+        (('--save-feats',), dict(type=str, default='', help='path to output features')),
+        (('--load-feats',), dict(type=str, default='', help='path to load features from')),
+        (('--gpu',), dict(type=int, default=0, nargs='+', help='GPU ids')),
+        (('--whiten',), dict(type=str, default='Landmarks_clean', help='applies whitening')),
+        (('--aqe',), dict(type=int, nargs='+', help='alpha-query expansion paramenters')),
+        (('--adba',), dict(type=int, nargs='+', help='alpha-database augmentation paramenters')),
+        (('--whitenp',), dict(type=float, default=0.25, help='whitening power, default is 0.5 (i.e., the sqrt)')),
+        (('--topk',), dict(type=int, default=20, help='neighbours per query')),
+        (('--output',), dict(type=str, required=True, help='path of the list: .npz, or text')),
+    ]).parse_args(argv)
+    iscuda = test_dir.setup_devices(args.gpu)
+    qe = {name: (None if val is None else {'k': val[0], 'alpha': val[1]})
+          for name, val in (('aqe', args.aqe), ('adba', args.adba))}
+    dataset = datasets.create(args.dataset)
+    print("Dataset:", dataset)
+    net = test_dir.load_model(args.checkpoint, iscuda)
+    whiten = test_dir.select_whitening(net, args)
+    qdescs, bdescs = eval_dir.descriptors(dataset, net, args.trfs, pooling=args.pooling, gemp=args.gemp, whiten=whiten,
+                                          aqe=qe['aqe'], adba=qe['adba'], threads=args.threads,
+                                          save_feats=args.save_feats, load_feats=args.load_feats)
+    same_set = dataset.get_query_db() is dataset
+    idx, vals = ranking.retrieve_device(qdescs, bdescs, args.topk, same_set=same_set)
+    idx, vals = idx.cpu().numpy(), vals.cpu().numpy()
+    if ddist.rank() == 0:
+        write_lists(args.output, dataset, idx, vals)
+        print("saved %d x %d neighbours to %s" % (idx.shape[0], idx.shape[1], args.output))
+    return idx, vals
+
+
+if __name__ == '__main__':
+    main(sys.argv[1:])

@@ -444,6 +444,31 @@ int dir_revisitop_ap(const int* probe_idx, int Q, int P, const int* counts, cons
 int dir_label_rank(const float* scores, int lds, int Q, int N, const int* labels, const int* class_off,
                    const int* class_members, int C, const int* qclass, const int* qself, double* ap, int* best_rank,
                    void* stream);
+/* Ranked neighbour lists: the k best database items of every query, in order, without a sort of the score row - what
+ * np.argsort(scores[q])[::-1][:k] (dirtorch/datasets/generic.py:207-208) and the np.argpartition of expand_descriptors
+ * (dirtorch/test_dir.py:24-44) give on the host after downloading the Q x N matrix.
+ *   scores [Q][lds] fp32, lds >= N.  ids NULL: an item's id is its column; else ids [Q][lds] int32 gives the id of every
+ *   column (distinct within a row - the caller's duty), -1 = an empty column that is skipped: the form that merges
+ *   per-shard or per-database-block lists, or a running list with a new block's candidates.  exclude NULL or [Q]: the item
+ *   with id exclude[q] is left out of row q (-1: nothing) - a query is not its own neighbour.
+ *   Order (dir_rank_counts' order): item j before item p when s_j > s_p, or s_j == s_p and id_j > id_p - on a NaN-free row
+ *   np.argsort(row, kind='stable')[::-1]; -0 == +0, +-inf are ordinary values; a NaN ranks after every number, -inf
+ *   included, and among NaNs the larger id comes first.
+ *   out_idx [Q][k] = the ids, best first; out_score [Q][k] = the stored bits of their scores (-0, a NaN's payload).  A row
+ *   with fewer than k kept items ends in (idx -1, score NaN) slots.
+ * 1 <= k <= min(N, dir_topk_max_k()) (host-only query; 2048).  workspace: at least dir_topk_workspace_bytes(Q, N, k)
+ * (host-only; monotone in each argument; 0 for rows of one slice, where workspace may be NULL).  k outside that range,
+ * lds < N, a null scores / out_idx / out_score or a short workspace fail with DIR_ERR_INVALID before anything is launched;
+ * Q == 0 is DIR_OK and launches nothing.
+ * topk.hip: one workgroup per (slice of 16384 columns, query) reads its scores once (N * 4 B per query, like
+ * rank_hist_kernel), radix-selects the slice's k best from keys held in registers and writes them to the workspace as a shorter row with an id
+ * table; the same kernel reduces that row until one slice is left, whose k survivors are sorted in LDS.  The 64-bit keys
+ * (score key : id) are distinct, so the output is bitwise reproducible: it does not depend on the slice size, the grid,
+ * workgroup scheduling or the arrival order of the (LDS, integer) atomics. */
+int dir_topk_max_k(void);
+int dir_topk_workspace_bytes(int Q, int N, int k, size_t* bytes);
+int dir_topk(const float* scores, int lds, int Q, int N, int k, const int* ids, const int* exclude, int* out_idx,
+             float* out_score, void* workspace, size_t workspace_bytes, void* stream);
 /* N3: alpha query expansion / database augmentation, expand_descriptors of
  * dirtorch/test_dir.py:24-44.  out[i] = normalize(mean(descs[i], sim[i][j]^alpha * db[j] for the k
  * rows j of db most similar to descs[i])), sim = descs . db^T in fp32; self_set != 0 (db == descs,

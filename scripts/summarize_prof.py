@@ -189,6 +189,8 @@ def bench_kernel_name(k):
             'cov_gram_kernel': 'gemm_nt_f32', 'cov_reduce_kernel': 'gemm_splitk_finalize_kernel',
             # the class-labelled ranking and its table check (csrc/label_rank.hip; no timed bench.py step launches them)
             'label_rank_kernel': 'rank_hist_kernel', 'label_check_kernel': 'rank_sort_kernel',
+            # the top-k selection, both forms (csrc/topk.hip; no timed bench.py step launches it either)
+            'topk_select_kernel': 'rank_hist_kernel',
             'maxpool_kernel': 'maxpool_3x3s2', 'upsample_add_kernel': 'upsample_add',
             'prep_input_f32_kernel': 'prep_input_f32', 'maxpool_f32_kernel': 'maxpool_f32',
             'global_pool_f32_kernel': 'global_pool_f32', 'upsample_add_f32_kernel': 'upsample_add_f32',
