@@ -791,6 +791,57 @@ int dir_label_rank(const float* scores, int lds, int Q, int N, const int* labels
     DIR_CATCH
 }
 
+int dir_index_i8_max_dim(void) { return index_i8_max_dim(); }
+
+static int index_check_dim(const char* who, int D) {
+    if (D < 1) return fail(DIR_ERR_INVALID, std::string(who) + ": D < 1");
+    if (D > index_i8_max_dim()) return fail(DIR_ERR_INVALID, std::string(who) + ": D exceeds dir_index_i8_max_dim()");
+    return DIR_OK;
+}
+
+int dir_quantize_rows_i8(const float* X, int ldx, int N, int D, int8_t* codes, int ldc, float* scales, void* stream) {
+    DIR_TRY
+    if (N < 0) return fail(DIR_ERR_INVALID, "quantize_rows_i8: negative size");
+    DIR_CHECK(index_check_dim("quantize_rows_i8", D));
+    if (ldx < D) return fail(DIR_ERR_INVALID, "quantize_rows_i8: ldx < D");
+    if (ldc < ((D + 63) & ~63)) return fail(DIR_ERR_INVALID, "quantize_rows_i8: ldc < D rounded up to a multiple of 64");
+    if (N == 0) return DIR_OK;
+    if (!X || !codes || !scales) return fail(DIR_ERR_INVALID, "quantize_rows_i8: null pointer");
+    if ((ldc & 3) != 0 || ((uintptr_t)codes & 3) != 0)
+        return fail(DIR_ERR_INVALID, "quantize_rows_i8: ldc % 4 == 0 and 4-byte aligned codes");
+    return quantize_rows_i8(X, ldx, N, D, codes, ldc, scales, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, const int8_t* bcodes, int ldb,
+                      const float* bscales, int N, int D, float* scores, int lds, void* stream) {
+    DIR_TRY
+    if (Q < 0 || N < 0) return fail(DIR_ERR_INVALID, "similarity_i8: negative size");
+    DIR_CHECK(index_check_dim("similarity_i8", D));
+    if (ldq < D) return fail(DIR_ERR_INVALID, "similarity_i8: ldq < D");
+    if (ldb < ((D + 63) & ~63)) return fail(DIR_ERR_INVALID, "similarity_i8: ldb < D rounded up to a multiple of 64");
+    if (lds < N) return fail(DIR_ERR_INVALID, "similarity_i8: lds < N");
+    if (Q == 0 || N == 0) return DIR_OK;
+    if (!qcodes || !qscales || !bcodes || !bscales || !scores) return fail(DIR_ERR_INVALID, "similarity_i8: null pointer");
+    if (!similarity_i8_admissible(bcodes, ldb, D))
+        return fail(DIR_ERR_INVALID, "similarity_i8: ldb % 16 == 0, ldb < 2^23 and 16-byte aligned bcodes");
+    return similarity_i8(qcodes, ldq, qscales, Q, bcodes, ldb, bscales, N, D, scores, lds, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_gather_scores(const float* queries, int ldq, int Q, const float* database, int ldb, int N, int D, const int* cand,
+                      int ldcand, int R, float* scores, int ldsc, void* stream) {
+    DIR_TRY
+    if (Q < 0 || N < 0 || R < 0) return fail(DIR_ERR_INVALID, "gather_scores: negative size");
+    if (D < 1) return fail(DIR_ERR_INVALID, "gather_scores: D < 1");
+    if (ldq < D || ldb < D) return fail(DIR_ERR_INVALID, "gather_scores: ldq, ldb < D");
+    if (ldcand < R || ldsc < R) return fail(DIR_ERR_INVALID, "gather_scores: ldcand, ldsc < R");
+    if (Q == 0 || N == 0 || R == 0) return DIR_OK;
+    if (!queries || !database || !cand || !scores) return fail(DIR_ERR_INVALID, "gather_scores: null pointer");
+    return gather_scores(queries, ldq, Q, database, ldb, D, cand, ldcand, R, scores, ldsc, (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_topk_max_k(void) { return topk_max_k(); }
 
 static int topk_check_sizes(int Q, int N, int k) {

@@ -55,6 +55,14 @@ int topk_max_k();
 size_t topk_workspace_bytes(int Q, int N, int k);
 int topk(const float* scores, int lds, int Q, int N, int k, const int* ids, const int* exclude, int* out_idx,
          float* out_score, void* workspace, size_t workspace_bytes, hipStream_t stream);
+// the int8 descriptor index (index_i8.hip): per-row codes + scales, the scan on the int8 matrix cores, the shortlist re-score
+int index_i8_max_dim();
+int quantize_rows_i8(const float* X, int ldx, int N, int D, int8_t* codes, int ldc, float* scales, hipStream_t stream);
+bool similarity_i8_admissible(const int8_t* bcodes, int ldb, int D);
+int similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, const int8_t* bcodes, int ldb,
+                  const float* bscales, int N, int D, float* scores, int lds, hipStream_t stream);
+int gather_scores(const float* queries, int ldq, int Q, const float* database, int ldb, int D, const int* cand, int ldcand,
+                  int R, float* scores, int ldsc, hipStream_t stream);
 int expand_descriptors(const float* descs, int n, const float* db, int m, int D, int k, float alpha,
                        int self_set, float* out, float* sim, size_t sim_bytes, hipStream_t stream);
 // scratch (optional): fp32 workspace for the split-K partial sums of shapes with few output tiles; without one

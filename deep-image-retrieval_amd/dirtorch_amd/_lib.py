@@ -124,6 +124,12 @@ SIGNATURES = {
     'dir_topk_workspace_bytes': (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     'dir_topk': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_size_t, c_void_p]),
+    'dir_index_i8_max_dim': (c_int, []),
+    'dir_quantize_rows_i8': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    'dir_similarity_i8': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                                  c_int, c_void_p]),
+    'dir_gather_scores': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                  c_void_p, c_int, c_void_p]),
     'dir_expand_descriptors': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_int,
                                        c_void_p, c_void_p, c_size_t, c_void_p]),
     'dir_comm_init_all': (c_int, [c_int, POINTER(c_int), POINTER(c_void_p)]),

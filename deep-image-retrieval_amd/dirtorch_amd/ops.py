@@ -445,6 +445,106 @@ def topk(scores, k, exclude=None, ids=None):
     return idx, vals
 
 
+# ---- the int8 descriptor index (csrc/index_i8.hip) ---------------------------------------------------------------------
+def index_i8_max_dim():
+    """The widest row the int8 index takes (dir_index_i8_max_dim; host-only)."""
+    return int(_lib.load().dir_index_i8_max_dim())
+
+
+def _rows_pitch(t, width):
+    """t [n, >= width] with unit column stride -> (t, row pitch in elements); copies what the library cannot address."""
+    n = t.shape[0]
+    if n > 1 and (t.stride(1) != 1 or t.stride(0) < width) or (n <= 1 and not t.is_contiguous()):
+        t = t.contiguous()
+    return t, (int(t.stride(0)) if n > 1 else int(t.shape[1]))
+
+
+def quantize_rows(X):
+    """fp32 rows -> (codes int8 [N, ldc], scales fp32 [N]), both CUDA (dir_quantize_rows_i8; include/dir_engine.h gives
+    the definition): ldc = D rounded up to a multiple of 64, the padding bytes zero.  X [N,D] fp32 CUDA with unit column
+    stride and any row pitch."""
+    if not X.is_cuda:
+        raise ValueError('device tensor expected')
+    if X.dtype != torch.float32 or X.dim() != 2:
+        raise TypeError('float32 rows [N,D] expected')
+    N, D = X.shape
+    if D < 1 or D > index_i8_max_dim():
+        raise ValueError('1 <= D <= %d expected, got %d' % (index_i8_max_dim(), D))
+    X, ldx = _rows_pitch(X, D)
+    ldc = (D + 63) // 64 * 64
+    codes = torch.empty(N, ldc, dtype=torch.int8, device=X.device)
+    scales = torch.empty(N, dtype=torch.float32, device=X.device)
+    if N:
+        call('dir_quantize_rows_i8', ptr(X), ldx, N, D, ptr(codes), ldc, ptr(scales), stream_ptr())
+    return codes, scales
+
+
+def similarity_i8(qcodes, qscales, bcodes, bscales, D, out=None):
+    """scores [Q,N] fp32 CUDA of two coded sets (dir_similarity_i8): ((float)int32 dot * qscales[q]) * bscales[n], one
+    defined fp32 number per pair.  qcodes [Q,ldc] / bcodes [N,ldc] int8 and qscales [Q] / bscales [N] fp32 as
+    quantize_rows gives them (row slices included), D the width the codes were made from.  out: a [Q, >= N] fp32 CUDA
+    tensor with unit column stride to write into (its first N columns are returned)."""
+    for t in (qcodes, qscales, bcodes, bscales) + ((out,) if out is not None else ()):
+        if not t.is_cuda:
+            raise ValueError('device tensor expected')
+    if qcodes.dtype != torch.int8 or bcodes.dtype != torch.int8 or qcodes.dim() != 2 or bcodes.dim() != 2:
+        raise TypeError('int8 codes [rows, ldc] expected')
+    if qscales.dtype != torch.float32 or bscales.dtype != torch.float32:
+        raise TypeError('float32 scales expected')
+    D = int(D)
+    Q, N = qcodes.shape[0], bcodes.shape[0]
+    ldc = (D + 63) // 64 * 64
+    if D < 1 or D > index_i8_max_dim() or qcodes.shape[1] < ldc or bcodes.shape[1] < ldc:
+        raise ValueError('codes of a width of at least D rounded up to 64 expected, 1 <= D <= %d' % index_i8_max_dim())
+    if qscales.dim() != 1 or bscales.dim() != 1 or qscales.numel() != Q or bscales.numel() != N:
+        raise ValueError('scales [Q] and [N] expected for codes of Q and N rows')
+    qcodes, ldq = _rows_pitch(qcodes, ldc)
+    bcodes, ldb = _rows_pitch(bcodes, ldc)
+    if ldb % 16 or bcodes.data_ptr() % 16:
+        bcodes = bcodes[:, :ldc].contiguous()
+        ldb = ldc
+    qscales, bscales = qscales.contiguous(), bscales.contiguous()
+    if out is None:
+        out = torch.empty(Q, N, dtype=torch.float32, device=bcodes.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != Q or out.shape[1] < N or (
+            Q > 1 and (out.stride(1) != 1 or out.stride(0) < N)) or (Q <= 1 and not out.is_contiguous()):
+        raise ValueError('out: float32 [Q, >= N] with unit column stride expected')
+    lds = int(out.stride(0)) if Q > 1 else int(out.shape[1])
+    if Q and N:
+        call('dir_similarity_i8', ptr(qcodes), ldq, ptr(qscales), Q, ptr(bcodes), ldb, ptr(bscales), N, D, ptr(out), lds,
+             stream_ptr())
+    return out[:, :N]
+
+
+def gather_scores(queries, database, cand):
+    """scores [Q,R] fp32 CUDA, scores[q][r] = <queries[q], database[cand[q][r]]> (dir_gather_scores): the re-score of a
+    shortlist.  queries [Q,D], database [N,D] fp32 CUDA, cand [Q,R] int32 CUDA with entries in [-1, N) - the caller's
+    duty, as ids in ops.topk; -1 gives NaN.  Unit column strides, any row pitch."""
+    for t in (queries, database, cand):
+        if not t.is_cuda:
+            raise ValueError('device tensor expected')
+    if queries.dtype != torch.float32 or database.dtype != torch.float32 or cand.dtype != torch.int32:
+        raise TypeError('float32 queries / database and int32 cand expected')
+    if queries.dim() != 2 or database.dim() != 2 or cand.dim() != 2:
+        raise ValueError('queries [Q,D], database [N,D], cand [Q,R] expected')
+    Q, D = queries.shape
+    N, D2 = database.shape
+    R = cand.shape[1]
+    if D != D2 or D < 1 or cand.shape[0] != Q:
+        raise ValueError('queries [Q,D], database [N,D], cand [Q,R] expected')
+    queries, ldq = _rows_pitch(queries, D)
+    database, ldb = _rows_pitch(database, D)
+    cand, ldcand = _rows_pitch(cand, R) if R else (cand, 0)
+    scores = torch.empty(Q, R, dtype=torch.float32, device=queries.device)
+    if Q and R:
+        if N == 0:
+            scores.fill_(float('nan'))
+        else:
+            call('dir_gather_scores', ptr(queries), ldq, Q, ptr(database), ldb, N, D, ptr(cand), ldcand, R, ptr(scores), R,
+                 stream_ptr())
+    return scores
+
+
 def expand_descriptors(descs, db=None, alpha=0.0, k=0, scratch_bytes=256 << 20):
     """alpha-QE / DBA on the device (dir_expand_descriptors): descs [n,D], db [m,D] fp32 CUDA (db None =
     expand the set against itself, a row never being its own neighbour) -> [n,D] fp32 CUDA."""

@@ -9,6 +9,9 @@ score matrix is never built or downloaded.  --output PATH:
     anything else         text: a `# query_image, map_image, score` header, then one `query_key, db_key, score` line
                           per pair, best first, scores as %.9g (enough digits to give the float32 back)
 When the query set is the database itself a query is not its own neighbour.  Written on rank 0 only.
+--index int8: the database descriptors go through an index.Int8Index (int8 codes, a quarter of the bytes) and the lists are
+ranked by the quantised scores; --rerank R also re-scores the R best of every query against the fp32 descriptors and keeps
+the --topk best of those, with their fp32 scores.
 """
 import sys
 
@@ -55,7 +58,11 @@ def main(argv=None):
         (('--whitenp',), dict(type=float, default=0.25, help='whitening power, default is 0.5 (i.e., the sqrt)')),
         (('--topk',), dict(type=int, default=20, help='neighbours per query')),
         (('--output',), dict(type=str, required=True, help='path of the list: .npz, or text')),
+        (('--index',), dict(type=str, default='', choices=['', 'int8'], help='scan a quantised copy of the database')),
+        (('--rerank',), dict(type=int, default=0, help='with --index: shortlist size re-scored in fp32 (0 = none)')),
     ]).parse_args(argv)
+    if args.rerank and not args.index:
+        raise SystemExit('--rerank needs --index')
     iscuda = test_dir.setup_devices(args.gpu)
     qe = {name: (None if val is None else {'k': val[0], 'alpha': val[1]})
           for name, val in (('aqe', args.aqe), ('adba', args.adba))}
@@ -67,7 +74,12 @@ def main(argv=None):
                                           aqe=qe['aqe'], adba=qe['adba'], threads=args.threads,
                                           save_feats=args.save_feats, load_feats=args.load_feats)
     same_set = dataset.get_query_db() is dataset
-    idx, vals = ranking.retrieve_device(qdescs, bdescs, args.topk, same_set=same_set)
+    if args.index:
+        from .index import Int8Index
+        idx, vals = Int8Index(bdescs.shape[1]).add(bdescs).search(
+            qdescs, args.topk, rerank=args.rerank, source=bdescs if args.rerank else None, same_set=same_set)
+    else:
+        idx, vals = ranking.retrieve_device(qdescs, bdescs, args.topk, same_set=same_set)
     idx, vals = idx.cpu().numpy(), vals.cpu().numpy()
     if ddist.rank() == 0:
         write_lists(args.output, dataset, idx, vals)

@@ -469,6 +469,38 @@ int dir_topk_max_k(void);
 int dir_topk_workspace_bytes(int Q, int N, int k, size_t* bytes);
 int dir_topk(const float* scores, int lds, int Q, int N, int k, const int* ids, const int* exclude, int* out_idx,
              float* out_score, void* workspace, size_t workspace_bytes, void* stream);
+/* The int8 descriptor index (index_i8.hip): a compact database, the scan that scores it and the re-score of a shortlist.
+ * The quantisation of a row x of D fp32 values, every step a single IEEE fp32 operation rounded to nearest:
+ *     amax  = max_k |x_k|                                  (exact)
+ *     scale = amax / 127          inv = 127 / amax         (two divisions)
+ *     code_k = clamp(rint(x_k * inv), -127, 127) as int8   (one multiply, then round-half-even; -128 never occurs)
+ *   a row whose inv is not finite (amax zero, or so small that 127 / amax overflows) has all-zero codes and scale 0;
+ *   a row that holds a NaN or an infinity has all-zero codes and scale NaN (all its scores are NaN: dir_topk ranks them last).
+ *   Codes are stored as [rows][ldc] int8, ldc >= D rounded up to a multiple of 64; bytes D .. that multiple of every row are
+ *   written as zero, so a scan has no K tail.
+ * dir_index_i8_max_dim (host-only; 131072): the widest row.  |code| <= 127, so a dot product of that width is at most
+ *   2 114 060 288 < 2^31: the int32 accumulator of the scan cannot wrap.
+ * dir_quantize_rows_i8: X [N][ldx] fp32 (ldx >= D, any pitch) -> codes [N][ldc] (4-byte aligned, ldc % 4 == 0) and scales [N].
+ *   One wave per row; a row of up to 2048 values is read once (32 floats per lane), a wider one twice.
+ * dir_similarity_i8: scores[q][n] = ((float)dot_i32 * qscales[q]) * bscales[n], dot_i32 = sum_k qcodes[q][k] * bcodes[n][k]
+ *   in int32 (exact), the conversion rounded to nearest, the two fp32 multiplies in that order - ONE defined fp32 number,
+ *   independent of tiling, K order, chunking and sharding.  qcodes [Q][ldq] (ldq >= D), bcodes [N][ldb] (16-byte aligned,
+ *   ldb % 16 == 0, ldb >= D rounded up to 64: that many bytes of every row are read; what they hold past D does not
+ *   matter), scores [Q][lds] fp32, lds >= N.  v_mfma_i32_32x32x32_i8 on sim_split.hip's work split: 256 database rows per
+ *   workgroup brought in once by LDS-DMA, the query block (96 rows) as a prepared image of the LDS stage, K slabs of 128.
+ *   The query image lives in stream-ordered scratch (no workspace argument).
+ * dir_gather_scores: scores[q][r] = <queries[q], database[cand[q][r]]> in fp32 - the re-score of a shortlist.  queries
+ *   [Q][ldq], database [N][ldb] fp32, cand [Q][ldcand] int32, scores [Q][ldsc]; an entry -1 gives a NaN score, an entry
+ *   outside [-1, N) is undefined (the caller's duty, as ids in dir_topk).  fp32 products and fp32 sums in an unspecified
+ *   order: each score is within (D + 2) * 2^-24 * sum_k |q_k b_k| of the exact sum.  One wave per (query, candidate).
+ * All three: a negative count, D < 1 (or above the max dim), a pitch below its minimum, lds < N or a null pointer fail with
+ * DIR_ERR_INVALID before anything is launched; Q == 0 or N == 0 (or R == 0) is DIR_OK and launches nothing. */
+int dir_index_i8_max_dim(void);
+int dir_quantize_rows_i8(const float* X, int ldx, int N, int D, int8_t* codes, int ldc, float* scales, void* stream);
+int dir_similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, const int8_t* bcodes, int ldb,
+                      const float* bscales, int N, int D, float* scores, int lds, void* stream);
+int dir_gather_scores(const float* queries, int ldq, int Q, const float* database, int ldb, int N, int D, const int* cand,
+                      int ldcand, int R, float* scores, int ldsc, void* stream);
 /* N3: alpha query expansion / database augmentation, expand_descriptors of
  * dirtorch/test_dir.py:24-44.  out[i] = normalize(mean(descs[i], sim[i][j]^alpha * db[j] for the k
  * rows j of db most similar to descs[i])), sim = descs . db^T in fp32; self_set != 0 (db == descs,

@@ -191,6 +191,9 @@ def bench_kernel_name(k):
             'label_rank_kernel': 'rank_hist_kernel', 'label_check_kernel': 'rank_sort_kernel',
             # the top-k selection, both forms (csrc/topk.hip; no timed bench.py step launches it either)
             'topk_select_kernel': 'rank_hist_kernel',
+            # the int8 index: quantiser, query image, scan and shortlist re-score (csrc/index_i8.hip; no timed bench.py step launches them)
+            'quantize_rows_i8_kernel': 'l2norm_rows_kernel', 'code_image_kernel': 'split_queries_kernel',
+            'sim_i8_kernel': 'sim_split_lc_kernel', 'gather_scores_kernel': 'expand_rows_kernel',
             'maxpool_kernel': 'maxpool_3x3s2', 'upsample_add_kernel': 'upsample_add',
             'prep_input_f32_kernel': 'prep_input_f32', 'maxpool_f32_kernel': 'maxpool_f32',
             'global_pool_f32_kernel': 'global_pool_f32', 'upsample_add_f32_kernel': 'upsample_add_f32',
