@@ -842,6 +842,42 @@ int dir_gather_scores(const float* queries, int ldq, int Q, const float* databas
     DIR_CATCH
 }
 
+int dir_segment_sums(const float* X, int ldx, int N, int D, const int* order, const int* seg_off, int S, float* sums,
+                     int lds, void* stream) {
+    DIR_TRY
+    if (N < 0 || S < 0) return fail(DIR_ERR_INVALID, "segment_sums: negative size");
+    if (D < 1) return fail(DIR_ERR_INVALID, "segment_sums: D < 1");
+    if (ldx < D || lds < D) return fail(DIR_ERR_INVALID, "segment_sums: ldx, lds < D");
+    if (S == 0) return DIR_OK;
+    if (!seg_off || !sums || (N > 0 && (!X || !order))) return fail(DIR_ERR_INVALID, "segment_sums: null pointer");
+    return segment_sums(X, ldx, N, D, order, seg_off, S, sums, lds, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, const int8_t* bcodes, int ldb,
+                    const float* bscales, const int* ids, int N, int D, const int* list_off, int nlist, const int* pair_off,
+                    const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
+                    int lds, int width, void* stream) {
+    DIR_TRY
+    if (Q < 0 || N < 0 || nlist < 0 || items < 0 || width < 0) return fail(DIR_ERR_INVALID, "ivf_scan_i8: negative size");
+    DIR_CHECK(index_check_dim("ivf_scan_i8", D));
+    if (ldq < ((D + 63) & ~63) || ldb < ((D + 63) & ~63))
+        return fail(DIR_ERR_INVALID, "ivf_scan_i8: ldq, ldb < D rounded up to a multiple of 64");
+    if (lds < width) return fail(DIR_ERR_INVALID, "ivf_scan_i8: lds < width");
+    if (Q == 0 || width == 0) return DIR_OK;
+    if (!scores || !out_ids) return fail(DIR_ERR_INVALID, "ivf_scan_i8: null pointer");
+    if (items > 0 && N > 0) {
+        if (nlist < 1) return fail(DIR_ERR_INVALID, "ivf_scan_i8: items without a list");
+        if (!qcodes || !qscales || !bcodes || !bscales || !ids || !list_off || !pair_off || !pair_q || !pair_col || !item_off)
+            return fail(DIR_ERR_INVALID, "ivf_scan_i8: null pointer");
+        if (!ivf_scan_i8_admissible(qcodes, ldq, Q, bcodes, ldb))
+            return fail(DIR_ERR_INVALID, "ivf_scan_i8: ldq, ldb % 16 == 0, ldb < 2^23, Q * ldq < 2^31 and 16-byte aligned codes");
+    }
+    return ivf_scan_i8(qcodes, ldq, qscales, Q, bcodes, ldb, bscales, ids, N, D, list_off, nlist, pair_off, pair_q, pair_col,
+                       item_off, items, scores, out_ids, lds, width, (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_topk_max_k(void) { return topk_max_k(); }
 
 static int topk_check_sizes(int Q, int N, int k) {

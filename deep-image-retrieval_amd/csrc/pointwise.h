@@ -63,6 +63,14 @@ int similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, co
                   const float* bscales, int N, int D, float* scores, int lds, hipStream_t stream);
 int gather_scores(const float* queries, int ldq, int Q, const float* database, int ldb, int D, const int* cand, int ldcand,
                   int R, float* scores, int ldsc, hipStream_t stream);
+// the inverted-file int8 index (ivf.hip): the sums of a k-means step, the scan of the probed lists
+int segment_sums(const float* X, int ldx, int N, int D, const int* order, const int* seg_off, int S, float* sums, int lds,
+                 hipStream_t stream);
+bool ivf_scan_i8_admissible(const int8_t* qcodes, int ldq, int Q, const int8_t* bcodes, int ldb);
+int ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, const int8_t* bcodes, int ldb,
+                const float* bscales, const int* ids, int N, int D, const int* list_off, int nlist, const int* pair_off,
+                const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
+                int lds, int width, hipStream_t stream);
 int expand_descriptors(const float* descs, int n, const float* db, int m, int D, int k, float alpha,
                        int self_set, float* out, float* sim, size_t sim_bytes, hipStream_t stream);
 // scratch (optional): fp32 workspace for the split-K partial sums of shapes with few output tiles; without one

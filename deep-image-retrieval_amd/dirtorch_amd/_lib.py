@@ -130,6 +130,10 @@ SIGNATURES = {
                                   c_int, c_void_p]),
     'dir_gather_scores': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int,
                                   c_void_p, c_int, c_void_p]),
+    'dir_segment_sums': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    'dir_ivf_scan_i8': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                c_int, c_void_p]),
     'dir_expand_descriptors': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_int,
                                        c_void_p, c_void_p, c_size_t, c_void_p]),
     'dir_comm_init_all': (c_int, [c_int, POINTER(c_int), POINTER(c_void_p)]),

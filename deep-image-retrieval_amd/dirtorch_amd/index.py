@@ -9,6 +9,17 @@ bytes), scanned on the int8 matrix cores and, on request, re-ranked with the ful
 include/dir_engine.h defines the quantisation and the quantised score; an int8 dot product accumulated in int32 is exact,
 so a quantised score is one defined fp32 number and the lists of a scan do not depend on scratch_bytes, db_rows or on how
 many add() calls built the database.
+
+The inverted file reads only the lists a query falls into instead of the whole database:
+
+    index = IVFInt8Index(D, nlist=1024)
+    index.train(bdescs)                                      # spherical k-means on (a sample of) the descriptors
+    index.add(bdescs)                                        # quantised, assigned to a list, stored list-major
+    idx, vals = index.search(qdescs, 10, nprobe=8)           # the 8 best lists of every query are scanned
+    idx, vals = index.search(qdescs, 10, nprobe=8, rerank=40, source=bdescs)
+
+Its assignment, probing and scores are defined through the quantised score as well (include/dir_engine.h), so with
+nprobe = nlist it returns Int8Index's lists bit for bit, and with fewer lists those of tests/ivf_ref.py.
 """
 import numpy as np
 import torch
@@ -33,8 +44,17 @@ def _upload(x):
     return x.to(device='cuda', dtype=torch.float32).contiguous()
 
 
-class Int8Index:
-    """codes [N, ldc] int8 (ldc = D rounded up to 64, padding zero) and scales [N] fp32, both CUDA."""
+def _quantize_chunks(descs, D):
+    """(codes, scales) of the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap), one chunk of
+    ADD_CHUNK_BYTES at a time, so a database that lives in a host file is never resident on the device as fp32."""
+    rows = max(1, ADD_CHUNK_BYTES // (4 * D))
+    for r0 in range(0, int(descs.shape[0]), rows):
+        yield ops.quantize_rows(_upload(descs[r0:r0 + rows]))
+
+
+class _CodedIndex:
+    """What the flat and the inverted index share: codes [N, ldc] int8 (ldc = D rounded up to 64, padding zero) and scales
+    [N] fp32, both CUDA; the argument checks of search and the fp32 re-rank of a shortlist."""
 
     def __init__(self, D):
         D = int(D)
@@ -47,21 +67,74 @@ class Int8Index:
     def __len__(self):
         return int(self.codes.shape[0])
 
+    def _check_rows(self, descs):
+        if descs.ndim != 2 or descs.shape[1] != self.D:
+            raise ValueError('descriptors [n, %d] expected' % self.D)
+
+    def _check_search(self, q, k, R, source, same_set):
+        """the arguments of search; returns the empty result for an empty query set, else None"""
+        Q, N = q.shape[0], len(self)
+        if q.dim() != 2 or q.shape[1] != self.D:
+            raise ValueError('queries [Q, %d] expected' % self.D)
+        kmax = min(N, ops.topk_max_k())
+        if k < 1 or k > kmax:
+            raise ValueError('1 <= k <= min(N, %d) expected, got k = %d for N = %d' % (ops.topk_max_k(), k, N))
+        if R and (R < k or R > kmax):
+            raise ValueError('k <= rerank <= min(N, %d) expected, got rerank = %d for k = %d, N = %d' % (
+                ops.topk_max_k(), R, k, N))
+        if R and source is None:
+            raise ValueError('rerank needs the fp32 database as `source`')
+        if R and (source.ndim != 2 or tuple(source.shape) != (N, self.D)):
+            raise ValueError('source [%d, %d] expected' % (N, self.D))
+        if same_set and Q != N:
+            raise ValueError('same_set: the queries are the database, got %d and %d rows' % (Q, N))
+        if Q == 0:
+            return (torch.empty(0, k, dtype=torch.int32, device='cuda'),
+                    torch.empty(0, k, dtype=torch.float32, device='cuda'))
+        return None
+
+    def _rerank(self, q, cand, vals, k, R, source, scratch_bytes):
+        """the lists of a scan that kept R or k candidates per query: as they are, or the k best by fp32 score"""
+        if not R:
+            return cand, vals
+        return ops.topk(self._rescore(q, cand, source, scratch_bytes), k, ids=cand)
+
+    def _rescore(self, q, cand, source, scratch_bytes):
+        """fp32 scores [Q, R] of the candidates against the rows of source"""
+        if not _is_host(source):
+            return ops.gather_scores(q, source.to(dtype=torch.float32), cand)
+        if torch.is_tensor(source):
+            source = source.numpy()
+        Q, R = cand.shape
+        out = torch.empty(Q, R, dtype=torch.float32, device='cuda')
+        rows = int(max(1, min(Q, scratch_bytes // max(4 * R * self.D, 1))))
+        for r0 in range(0, Q, rows):
+            r1 = min(Q, r0 + rows)
+            c = cand[r0:r1].cpu().numpy()
+            used = np.unique(c[c >= 0])                                   # sorted: one pass over a memmap
+            picked = _upload(source[used]) if len(used) else torch.zeros(1, self.D, device='cuda')
+            local = np.where(c >= 0, np.searchsorted(used, c), -1).astype(np.int32)
+            out[r0:r1] = ops.gather_scores(q[r0:r1], picked, torch.from_numpy(local).cuda())
+        return out
+
+
+class Int8Index(_CodedIndex):
+    """codes [N, ldc] int8 (ldc = D rounded up to 64, padding zero) and scales [N] fp32, both CUDA."""
+
     def add(self, descs):
         """Append the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap).  They are quantised in
         chunks of ADD_CHUNK_BYTES, so a database that lives in a host file is never resident on the device as fp32."""
-        if descs.ndim != 2 or descs.shape[1] != self.D:
-            raise ValueError('descriptors [n, %d] expected' % self.D)
+        self._check_rows(descs)
         n, N = int(descs.shape[0]), len(self)
         if n == 0:
             return self
         codes = torch.empty(N + n, self.codes.shape[1], dtype=torch.int8, device='cuda')
         scales = torch.empty(N + n, dtype=torch.float32, device='cuda')
         codes[:N], scales[:N] = self.codes, self.scales
-        rows = max(1, ADD_CHUNK_BYTES // (4 * self.D))
-        for r0 in range(0, n, rows):
-            r1 = min(n, r0 + rows)
-            codes[N + r0:N + r1], scales[N + r0:N + r1] = ops.quantize_rows(_upload(descs[r0:r1]))
+        r0 = N
+        for c, s in _quantize_chunks(descs, self.D):
+            codes[r0:r0 + len(s)], scales[r0:r0 + len(s)] = c, s
+            r0 += len(s)
         self.codes, self.scales = codes, scales
         return self
 
@@ -93,24 +166,6 @@ class Int8Index:
             idx[r0:r1], vals[r0:r1] = run_i, run_v
         return idx, vals
 
-    def _rescore(self, q, cand, source, scratch_bytes):
-        """fp32 scores [Q, R] of the candidates against the rows of source"""
-        if not _is_host(source):
-            return ops.gather_scores(q, source.to(dtype=torch.float32), cand)
-        if torch.is_tensor(source):
-            source = source.numpy()
-        Q, R = cand.shape
-        out = torch.empty(Q, R, dtype=torch.float32, device='cuda')
-        rows = int(max(1, min(Q, scratch_bytes // max(4 * R * self.D, 1))))
-        for r0 in range(0, Q, rows):
-            r1 = min(Q, r0 + rows)
-            c = cand[r0:r1].cpu().numpy()
-            used = np.unique(c[c >= 0])                                   # sorted: one pass over a memmap
-            picked = _upload(source[used]) if len(used) else torch.zeros(1, self.D, device='cuda')
-            local = np.where(c >= 0, np.searchsorted(used, c), -1).astype(np.int32)
-            out[r0:r1] = ops.gather_scores(q[r0:r1], picked, torch.from_numpy(local).cuda())
-        return out
-
     def search(self, qdescs, k, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20, db_rows=None):
         """(idx [Q,k] int32, vals [Q,k] float32), both CUDA, under ranking.retrieve_device's contract (its order, same_set
         leaving a query out of its own list, (-1, NaN) where a row runs short).  rerank = 0: ranked by the quantised
@@ -120,30 +175,13 @@ class Int8Index:
         scores of the k best of them."""
         from .utils.common import _dev
         q = _dev(qdescs)
-        Q, N = q.shape[0], len(self)
         k, R = int(k), int(rerank)
-        if q.dim() != 2 or q.shape[1] != self.D:
-            raise ValueError('queries [Q, %d] expected' % self.D)
-        kmax = min(N, ops.topk_max_k())
-        if k < 1 or k > kmax:
-            raise ValueError('1 <= k <= min(N, %d) expected, got k = %d for N = %d' % (ops.topk_max_k(), k, N))
-        if R and (R < k or R > kmax):
-            raise ValueError('k <= rerank <= min(N, %d) expected, got rerank = %d for k = %d, N = %d' % (
-                ops.topk_max_k(), R, k, N))
-        if R and source is None:
-            raise ValueError('rerank needs the fp32 database as `source`')
-        if R and (source.ndim != 2 or tuple(source.shape) != (N, self.D)):
-            raise ValueError('source [%d, %d] expected' % (N, self.D))
-        if same_set and Q != N:
-            raise ValueError('same_set: the queries are the database, got %d and %d rows' % (Q, N))
-        if Q == 0:
-            return (torch.empty(0, k, dtype=torch.int32, device='cuda'),
-                    torch.empty(0, k, dtype=torch.float32, device='cuda'))
+        empty = self._check_search(q, k, R, source, same_set)
+        if empty is not None:
+            return empty
         qc, qs = ops.quantize_rows(q)
         cand, vals = self._scan(qc, qs, R or k, same_set, scratch_bytes, db_rows)
-        if not R:
-            return cand, vals
-        return ops.topk(self._rescore(q, cand, source, scratch_bytes), k, ids=cand)
+        return self._rerank(q, cand, vals, k, R, source, scratch_bytes)
 
     def save(self, path):
         """One .npz: `codes` [N, D] int8 (without the padding), `scales` [N] float32, `D`."""
@@ -160,4 +198,165 @@ class Int8Index:
         index.codes = torch.zeros(len(codes), _pad64(index.D), dtype=torch.int8, device='cuda')
         index.codes[:, :index.D] = torch.from_numpy(codes).cuda()
         index.scales = torch.from_numpy(scales.astype(np.float32)).cuda()
+        return index
+
+
+class IVFInt8Index(_CodedIndex):
+    """The inverted-file int8 index (include/dir_engine.h gives the definitions).  All CUDA: centroids [nlist, D] fp32 with
+    their codes `ccodes` and scales `cscales`; the database LIST-MAJOR - codes [N, ldc] int8, scales [N] fp32, ids [N] int32
+    (a row's number in add order: what Int8Index reports) - and list_off [nlist+1] int32, a CSR from 0 to N; inside a list
+    the rows are in ascending id."""
+
+    def __init__(self, D, nlist):
+        super().__init__(D)
+        nlist = int(nlist)
+        if nlist < 1 or nlist > 65535:
+            raise ValueError('1 <= nlist <= 65535 expected, got %d' % nlist)
+        self.nlist = nlist
+        self.centroids = self.ccodes = self.cscales = None
+        self.ids = torch.empty(0, dtype=torch.int32, device='cuda')
+        self.list_off = torch.zeros(nlist + 1, dtype=torch.int32, device='cuda')
+        self._lens = np.zeros(nlist, np.int64)           # host copy of the list lengths: sizes search's chunks
+
+    def _set_centroids(self, centroids):
+        self.centroids = centroids
+        self.ccodes, self.cscales = ops.quantize_rows(centroids)
+
+    def _assign(self, codes, scales, scratch_bytes=256 << 20):
+        """the list of every coded row [n] int32: the best centroid by quantised score under ops.topk's order"""
+        n = codes.shape[0]
+        out = torch.empty(n, dtype=torch.int32, device='cuda')
+        rows = int(max(1, min(1 << 22, scratch_bytes // (4 * self.nlist))))     # (similarity_i8 takes 65535 * 96 rows a call)
+        for r0 in range(0, n, rows):
+            scores = ops.similarity_i8(codes[r0:r0 + rows], scales[r0:r0 + rows], self.ccodes, self.cscales, self.D)
+            out[r0:r0 + rows] = ops.topk(scores, 1)[0][:, 0]
+        return out
+
+    def train(self, x, iters=10, seed=0, max_rows=None):
+        """Spherical Lloyd iterations on the rows of x [n, D] (any kind add takes), or on a sorted
+        np.random.RandomState(seed).choice sample of max_rows of them (default 256 * nlist) when x has more.  The initial
+        centroids are the rows np.sort(RandomState(seed).choice(n, nlist, replace=False)) of the sample; an iteration
+        assigns every row to its list, sums each list's members in fp32 (ops.segment_sums) and L2-normalises the sums;
+        an empty list keeps its centroid.  Bitwise reproducible.  Rows already added are not re-assigned: train first."""
+        self._check_rows(x)
+        if len(self):
+            raise ValueError('train before add: the rows already stored were assigned to the old centroids')
+        n = int(x.shape[0])
+        max_rows = 256 * self.nlist if max_rows is None else int(max_rows)
+        if n < self.nlist or max_rows < self.nlist:
+            raise ValueError('at least nlist = %d training rows expected, got %d' % (self.nlist, min(n, max_rows)))
+        if n > max_rows:
+            pick = np.sort(np.random.RandomState(seed).choice(n, max_rows, replace=False))
+            x = x[torch.from_numpy(pick).to(x.device)] if torch.is_tensor(x) else x[pick]
+            n = max_rows
+        x = _upload(x)
+        if not bool(torch.isfinite(x).all()):
+            raise ValueError('training data with a non-finite value')
+        first = np.sort(np.random.RandomState(seed).choice(n, self.nlist, replace=False))
+        centroids = x[torch.from_numpy(first).cuda()].clone()
+        codes, scales = ops.quantize_rows(x)
+        bounds = torch.arange(self.nlist + 1, device='cuda')
+        for _ in range(int(iters)):
+            self._set_centroids(centroids)
+            lists, order = torch.sort(self._assign(codes, scales).long(), stable=True)
+            seg_off = torch.searchsorted(lists, bounds).to(torch.int32)
+            sums = ops.segment_sums(x, order.to(torch.int32), seg_off)
+            ops.l2norm_rows_(sums)
+            empty = (seg_off[1:] == seg_off[:-1])[:, None]
+            centroids = torch.where(empty, centroids, sums)
+        self._set_centroids(centroids)
+        return self
+
+    def add(self, descs):
+        """Append the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap), quantised in chunks of
+        ADD_CHUNK_BYTES as Int8Index.add does; their ids continue the count.  The store is regrouped by a stable integer
+        sort of the list indices (old rows first, so ids ascend inside a list): what the index holds does not depend on
+        how the rows were cut into calls.  The regrouping copies the codes once (twice the index's bytes for a moment)
+        and reads the list lengths back to the host."""
+        self._check_rows(descs)
+        if self.centroids is None:
+            raise ValueError('add before train')
+        n, N = int(descs.shape[0]), len(self)
+        if n == 0:
+            return self
+        new = [(c, s, self._assign(c, s)) for c, s in _quantize_chunks(descs, self.D)]
+        old_lists = torch.searchsorted(self.list_off[1:].long(), torch.arange(N, device='cuda'), right=True)
+        lists = torch.cat([old_lists] + [l.long() for _, _, l in new])
+        lists, order = torch.sort(lists, stable=True)
+        self.codes = torch.cat([self.codes] + [c for c, _, _ in new])[order]
+        self.scales = torch.cat([self.scales] + [s for _, s, _ in new])[order]
+        self.ids = torch.cat([self.ids, torch.arange(N, N + n, dtype=torch.int32, device='cuda')])[order]
+        self.list_off = torch.searchsorted(lists, torch.arange(self.nlist + 1, device='cuda')).to(torch.int32)
+        self._lens = np.diff(self.list_off.cpu().numpy().astype(np.int64))
+        return self
+
+    def probe(self, qc, qs, nprobe):
+        """the lists of every coded query [Q, nprobe] int32, best first"""
+        return ops.topk(ops.similarity_i8(qc, qs, self.ccodes, self.cscales, self.D), nprobe)[0]
+
+    def search(self, qdescs, k, nprobe=1, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20):
+        """Int8Index.search's contract over the rows of the nprobe best lists of every query (1 <= nprobe <= nlist): a
+        query whose lists hold fewer than k rows ends in (-1, NaN).  The queries go in chunks whose score and id rows
+        (8 bytes per column; the nprobe longest lists bound the width) fit scratch_bytes; every chunk synchronises with
+        the host once, inside ops.ivf_scan, to learn its grid and its width."""
+        from .utils.common import _dev
+        if self.centroids is None:
+            raise ValueError('search before train')
+        nprobe = int(nprobe)
+        if nprobe < 1 or nprobe > self.nlist:
+            raise ValueError('1 <= nprobe <= nlist = %d expected, got %d' % (self.nlist, nprobe))
+        q = _dev(qdescs)
+        k, R = int(k), int(rerank)
+        empty = self._check_search(q, k, R, source, same_set)
+        if empty is not None:
+            return empty
+        Q, keep = q.shape[0], R or k
+        qc, qs = ops.quantize_rows(q)
+        probe = self.probe(qc, qs, nprobe)
+        lens = (self.list_off[1:] - self.list_off[:-1])[probe.long()]
+        ends = torch.cumsum(lens, dim=1, dtype=torch.int32)
+        col_off = ends - lens
+        bound = max(int(np.sort(self._lens)[-nprobe:].sum()), keep)
+        rows = int(max(1, min(Q, scratch_bytes // (8 * bound))))
+        cand = torch.empty(Q, keep, dtype=torch.int32, device='cuda')
+        vals = torch.empty(Q, keep, dtype=torch.float32, device='cuda')
+        for r0 in range(0, Q, rows):
+            r1 = min(Q, r0 + rows)
+            scores, ids = ops.ivf_scan(qc[r0:r1], qs[r0:r1], self.codes, self.scales, self.ids, self.list_off,
+                                       probe[r0:r1], col_off[r0:r1], self.D)
+            if scores.shape[1] < keep:       # every row of the chunk runs short: top-k wants keep columns, the rest are empty
+                wide = torch.full((r1 - r0, keep), -1, dtype=torch.int32, device='cuda')
+                wide[:, :ids.shape[1]] = ids
+                ids, scores = wide, torch.cat([scores, scores.new_zeros(r1 - r0, keep - scores.shape[1])], dim=1)
+            own = torch.arange(r0, r1, dtype=torch.int32, device='cuda') if same_set else None
+            cand[r0:r1], vals[r0:r1] = ops.topk(scores, keep, ids=ids, exclude=own)
+        return self._rerank(q, cand, vals, k, R, source, scratch_bytes)
+
+    def save(self, path):
+        """One .npz: `centroids` [nlist, D] float32, `codes` [N, D] int8 (without the padding), `scales` [N] float32, `ids`
+        [N] int32, `list_off` [nlist+1] int32, `D`, `nlist`."""
+        if self.centroids is None:
+            raise ValueError('save before train')
+        np.savez(path, centroids=self.centroids.cpu().numpy(), codes=self.codes[:, :self.D].cpu().numpy(),
+                 scales=self.scales.cpu().numpy(), ids=self.ids.cpu().numpy(), list_off=self.list_off.cpu().numpy(),
+                 D=np.int64(self.D), nlist=np.int64(self.nlist))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as f:
+            index = cls(int(f['D']), int(f['nlist']))
+            centroids, codes, scales, ids, list_off = (f[name] for name in ('centroids', 'codes', 'scales', 'ids', 'list_off'))
+        N = len(codes)
+        if codes.dtype != np.int8 or codes.ndim != 2 or codes.shape[1] != index.D or scales.shape != (N,) or ids.shape != (N,):
+            raise ValueError('%s: codes [N, D] int8, scales [N] and ids [N] expected' % path)
+        if centroids.shape != (index.nlist, index.D) or list_off.shape != (index.nlist + 1,) or list_off[0] != 0 or (
+                list_off[-1] != N or (np.diff(list_off.astype(np.int64)) < 0).any()):
+            raise ValueError('%s: centroids [nlist, D] and a list_off [nlist+1] from 0 to N expected' % path)
+        index._set_centroids(torch.from_numpy(centroids.astype(np.float32)).cuda())
+        index.codes = torch.zeros(N, _pad64(index.D), dtype=torch.int8, device='cuda')
+        index.codes[:, :index.D] = torch.from_numpy(codes).cuda()
+        index.scales = torch.from_numpy(scales.astype(np.float32)).cuda()
+        index.ids = torch.from_numpy(ids.astype(np.int32)).cuda()
+        index.list_off = torch.from_numpy(list_off.astype(np.int32)).cuda()
+        index._lens = np.diff(list_off.astype(np.int64))
         return index

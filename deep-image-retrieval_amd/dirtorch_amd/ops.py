@@ -545,6 +545,125 @@ def gather_scores(queries, database, cand):
     return scores
 
 
+# ---- the inverted-file int8 index (csrc/ivf.hip) -----------------------------------------------------------------------
+def segment_sums(X, order, seg_off):
+    """sums [S,D] fp32 CUDA, sums[s] = the rows X[order[seg_off[s] : seg_off[s+1]]] added up in fp32 in a fixed order
+    (dir_segment_sums): bitwise reproducible, an empty segment gives zeros.  X [N,D] fp32 CUDA with unit column stride
+    and any row pitch; order int32 CUDA with entries in [0, N); seg_off [S+1] int32 CUDA, ascending from 0 to at most
+    len(order) - the caller's duty, as ids in ops.topk."""
+    for t in (X, order, seg_off):
+        if not t.is_cuda:
+            raise ValueError('device tensor expected')
+    if X.dtype != torch.float32 or X.dim() != 2 or order.dtype != torch.int32 or seg_off.dtype != torch.int32:
+        raise TypeError('float32 rows [N,D] and int32 order / seg_off expected')
+    if order.dim() != 1 or seg_off.dim() != 1 or seg_off.numel() < 1:
+        raise ValueError('order [n] and seg_off [S+1] expected')
+    N, D = X.shape
+    S = int(seg_off.numel()) - 1
+    if D < 1:
+        raise ValueError('D >= 1 expected')
+    X, ldx = _rows_pitch(X, D)
+    order, seg_off = order.contiguous(), seg_off.contiguous()
+    sums = torch.empty(S, D, dtype=torch.float32, device=X.device)
+    if S:
+        call('dir_segment_sums', ptr(X), ldx, N, D, ptr(order), ptr(seg_off), S, ptr(sums), D, stream_ptr())
+    return sums
+
+
+def ivf_probe_tables(list_off, probe, col_off):
+    """The probe table of a scan by list - what dir_ivf_scan_i8 walks (include/dir_engine.h) - built with integer torch
+    operations on the device: (pair_off [nlist+1], pair_q [pairs], pair_col [pairs], item_off [nlist+1], items, reach),
+    int32 CUDA tensors and two host integers: the workgroups of the scan and the largest col_off + list length.  Reading
+    those two back is the ONE host synchronisation of a scan."""
+    nlist, nprobe = int(list_off.numel()) - 1, int(probe.shape[1])
+    # pairs (query, slot) in a stable order of their lists, empty slots last (key nlist)
+    flat = probe.reshape(-1).long()
+    key, order = torch.sort(torch.where(flat < 0, torch.full_like(flat, nlist), flat), stable=True)
+    pair_off = torch.searchsorted(key, torch.arange(nlist + 1, device=probe.device)).to(torch.int32)
+    pair_q = (order // max(nprobe, 1)).to(torch.int32)
+    pair_col = col_off.reshape(-1)[order].contiguous()
+    lens = (list_off[1:] - list_off[:-1]).long()
+    pairs = (pair_off[1:] - pair_off[:-1]).long()
+    per_list = ((lens + 255) // 256) * ((pairs + 31) // 32)
+    item_off = torch.cat([per_list.new_zeros(1), torch.cumsum(per_list, 0)])
+    ends = col_off.long() + torch.where(probe >= 0, lens[probe.long().clamp(min=0)], lens.new_zeros(()))
+    reach = ends.max().reshape(1) if ends.numel() else item_off[:1]
+    items, reach = torch.cat([item_off[-1:], reach]).tolist()             # the one synchronisation
+    if items > 0x7fffffff:
+        raise ValueError('more than 2^31 - 1 workgroups in one scan: cut the queries')
+    return pair_off, pair_q, pair_col, item_off.to(torch.int32), int(items), int(reach)
+
+
+def ivf_scan(qcodes, qscales, codes, scales, ids, list_off, probe, col_off, D, width=None, out=None, tables=None):
+    """The quantised scores of every query against the rows of the lists it probes (dir_ivf_scan_i8) -> (scores [Q,width]
+    fp32, out_ids [Q,width] int32), both CUDA.  qcodes [Q,ldc] / qscales [Q] as quantize_rows gives them (zero padding
+    included); codes [N,ldc] int8, scales [N] fp32, ids [N] int32, list_off [nlist+1] int32: a list-major database
+    (index.IVFInt8Index); probe [Q,nprobe] int32: the lists of every query, -1 = an empty slot; col_off [Q,nprobe] int32:
+    the first output column of every slot.  For r < len(list probe[q][p]), column col_off[q][p] + r carries the score
+    ((float)int32 dot * qscales[q]) * scales[n] and the id of row n = list_off[probe[q][p]] + r; a column no slot covers
+    carries id -1.  The tables are the caller's duty, as ids in ops.topk: lists in [-1, nlist), slots of a query that do
+    not overlap and end at or below width.  width None: the largest col_off + list length of the call.
+    out: (scores, out_ids) [Q, >= width] with unit column stride and ONE row pitch to write into; columns at or past
+    width keep what they hold.
+    The inverted probe table the kernel walks (pairs grouped by list, workgroups per list) comes from ivf_probe_tables,
+    which synchronises with the host ONCE, to learn the grid and the width; tables: its result for these list_off, probe
+    and col_off, when the caller has it already (the call then does not synchronise)."""
+    tensors = (qcodes, qscales, codes, scales, ids, list_off, probe, col_off) + (tuple(out) if out is not None else ())
+    for t in tensors:
+        if not t.is_cuda:
+            raise ValueError('device tensor expected')
+    if qcodes.dtype != torch.int8 or codes.dtype != torch.int8 or qcodes.dim() != 2 or codes.dim() != 2:
+        raise TypeError('int8 codes [rows, ldc] expected')
+    if qscales.dtype != torch.float32 or scales.dtype != torch.float32:
+        raise TypeError('float32 scales expected')
+    if any(t.dtype != torch.int32 for t in (ids, list_off, probe, col_off)):
+        raise TypeError('int32 ids, list_off, probe and col_off expected')
+    D = int(D)
+    Q, N = qcodes.shape[0], codes.shape[0]
+    ldc = (D + 63) // 64 * 64
+    if D < 1 or D > index_i8_max_dim() or qcodes.shape[1] < ldc or codes.shape[1] < ldc:
+        raise ValueError('codes of a width of at least D rounded up to 64 expected, 1 <= D <= %d' % index_i8_max_dim())
+    if qscales.dim() != 1 or scales.dim() != 1 or ids.dim() != 1 or qscales.numel() != Q or scales.numel() != N or ids.numel() != N:
+        raise ValueError('qscales [Q], scales [N] and ids [N] expected for codes of Q and N rows')
+    if list_off.dim() != 1 or list_off.numel() < 2:
+        raise ValueError('list_off [nlist+1] expected')
+    nlist = int(list_off.numel()) - 1
+    if probe.dim() != 2 or probe.shape[0] != Q or tuple(col_off.shape) != tuple(probe.shape):
+        raise ValueError('probe [Q,nprobe] and col_off [Q,nprobe] expected')
+
+    def aligned(c):
+        c, ld = _rows_pitch(c, ldc)
+        if ld % 16 or c.data_ptr() % 16:
+            c, ld = c[:, :ldc].contiguous(), ldc
+        return c, ld
+    qcodes, ldq = aligned(qcodes)
+    codes, ldb = aligned(codes)
+    qscales, scales, ids, list_off = qscales.contiguous(), scales.contiguous(), ids.contiguous(), list_off.contiguous()
+    dev = codes.device
+    pair_off, pair_q, pair_col, item_off, items, reach = tables if tables is not None else ivf_probe_tables(list_off, probe, col_off)
+    width = reach if width is None else int(width)
+    if out is None:
+        scores = torch.empty(Q, width, dtype=torch.float32, device=dev)
+        out_ids = torch.empty(Q, width, dtype=torch.int32, device=dev)
+        lds = width
+    else:
+        scores, out_ids = out
+        if scores.dtype != torch.float32 or out_ids.dtype != torch.int32:
+            raise TypeError('out: float32 scores and int32 ids expected')
+        for t in (scores, out_ids):
+            if t.dim() != 2 or t.shape[0] != Q or t.shape[1] < width or (Q > 1 and (t.stride(1) != 1 or t.stride(0) < width)) or (
+                    Q <= 1 and not t.is_contiguous()):
+                raise ValueError('out: [Q, >= width] tensors with unit column stride expected')
+        if Q > 1 and scores.stride(0) != out_ids.stride(0) or (Q <= 1 and scores.shape[1] != out_ids.shape[1]):
+            raise ValueError('out: scores and ids of one row pitch expected')
+        lds = int(scores.stride(0)) if Q > 1 else int(scores.shape[1])
+    if Q and width:
+        call('dir_ivf_scan_i8', ptr(qcodes), ldq, ptr(qscales), Q, ptr(codes), ldb, ptr(scales), ptr(ids), N, D, ptr(list_off),
+             nlist, ptr(pair_off), ptr(pair_q), ptr(pair_col), ptr(item_off), items, ptr(scores),
+             ptr(out_ids), lds, width, stream_ptr())
+    return scores[:, :width], out_ids[:, :width]
+
+
 def expand_descriptors(descs, db=None, alpha=0.0, k=0, scratch_bytes=256 << 20):
     """alpha-QE / DBA on the device (dir_expand_descriptors): descs [n,D], db [m,D] fp32 CUDA (db None =
     expand the set against itself, a row never being its own neighbour) -> [n,D] fp32 CUDA."""

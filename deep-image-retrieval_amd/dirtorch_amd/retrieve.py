@@ -12,6 +12,8 @@ When the query set is the database itself a query is not its own neighbour.  Wri
 --index int8: the database descriptors go through an index.Int8Index (int8 codes, a quarter of the bytes) and the lists are
 ranked by the quantised scores; --rerank R also re-scores the R best of every query against the fp32 descriptors and keeps
 the --topk best of those, with their fp32 scores.
+--index ivf --nlist L --nprobe P: an index.IVFInt8Index trained on the database descriptors themselves (L k-means lists);
+every query scans its P best lists only, --rerank as above.  With P = L the lists are those of --index int8.
 """
 import sys
 
@@ -58,11 +60,15 @@ def main(argv=None):
         (('--whitenp',), dict(type=float, default=0.25, help='whitening power, default is 0.5 (i.e., the sqrt)')),
         (('--topk',), dict(type=int, default=20, help='neighbours per query')),
         (('--output',), dict(type=str, required=True, help='path of the list: .npz, or text')),
-        (('--index',), dict(type=str, default='', choices=['', 'int8'], help='scan a quantised copy of the database')),
+        (('--index',), dict(type=str, default='', choices=['', 'int8', 'ivf'], help='scan a quantised copy of the database')),
+        (('--nlist',), dict(type=int, default=0, help='with --index ivf: the number of k-means lists')),
+        (('--nprobe',), dict(type=int, default=1, help='with --index ivf: lists scanned per query')),
         (('--rerank',), dict(type=int, default=0, help='with --index: shortlist size re-scored in fp32 (0 = none)')),
     ]).parse_args(argv)
     if args.rerank and not args.index:
         raise SystemExit('--rerank needs --index')
+    if args.index == 'ivf' and args.nlist < 1:
+        raise SystemExit('--index ivf needs --nlist')
     iscuda = test_dir.setup_devices(args.gpu)
     qe = {name: (None if val is None else {'k': val[0], 'alpha': val[1]})
           for name, val in (('aqe', args.aqe), ('adba', args.adba))}
@@ -74,7 +80,12 @@ def main(argv=None):
                                           aqe=qe['aqe'], adba=qe['adba'], threads=args.threads,
                                           save_feats=args.save_feats, load_feats=args.load_feats)
     same_set = dataset.get_query_db() is dataset
-    if args.index:
+    if args.index == 'ivf':
+        from .index import IVFInt8Index
+        idx, vals = IVFInt8Index(bdescs.shape[1], args.nlist).train(bdescs).add(bdescs).search(
+            qdescs, args.topk, nprobe=args.nprobe, rerank=args.rerank, source=bdescs if args.rerank else None,
+            same_set=same_set)
+    elif args.index:
         from .index import Int8Index
         idx, vals = Int8Index(bdescs.shape[1]).add(bdescs).search(
             qdescs, args.topk, rerank=args.rerank, source=bdescs if args.rerank else None, same_set=same_set)

@@ -501,6 +501,58 @@ int dir_similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q
                       const float* bscales, int N, int D, float* scores, int lds, void* stream);
 int dir_gather_scores(const float* queries, int ldq, int Q, const float* database, int ldb, int N, int D, const int* cand,
                       int ldcand, int R, float* scores, int ldsc, void* stream);
+/* The inverted-file int8 index (ivf.hip; dirtorch_amd/index.py IVFInt8Index; numpy restatement: tests/ivf_ref.py).
+ * An index of width D with nlist lists holds
+ *     centroids [nlist][D] fp32 with their codes and scales (dir_quantize_rows_i8),
+ *     the database in LIST-MAJOR storage: codes [N][ldc] int8, scales [N] fp32, ids [N] int32 - the id of a row is its number
+ *       in the order the rows were added (the number the flat int8 index reports),
+ *     list_off [nlist + 1] int32, a CSR from 0 to N: list l is rows list_off[l] .. list_off[l + 1), in ascending id.
+ * Assignment: a row belongs to the list whose centroid has the best QUANTISED score under dir_topk's order, i.e.
+ *   dir_topk(dir_similarity_i8(row codes, row scale, centroid codes, centroid scales), k = 1): score descending, the
+ *   larger list index among equal scores, NaN last.  A zero row (every score 0) and a non-finite row (every score NaN)
+ *   therefore belong to list nlist - 1; that is the rule, not a special case.  The contents of an index do not depend on
+ *   how the rows were cut into calls or chunks.
+ * Probing: the lists of query q are dir_topk(dir_similarity_i8(q codes, q scale, centroid codes, centroid scales), nprobe),
+ *   in that order.
+ * Search: the candidates of q are the rows of its probed lists, their scores dir_similarity_i8's numbers
+ *   ((float)dot_i32 * qscales[q]) * bscales[n], the result dir_topk of those with the rows' ids as ids (exclude for a query
+ *   set that is the database); a query with fewer than k candidates ends in (-1, NaN) slots.  With a re-rank of R: the R
+ *   best are kept, re-scored with dir_gather_scores against the fp32 rows addressed by id, and ranked again.
+ * Training: spherical Lloyd iterations.  The initial centroids are nlist rows of the training sample; an iteration assigns
+ *   every row by the rule above, sums the members of each list in fp32 (dir_segment_sums) and L2-normalises the sums
+ *   (dir_l2norm_rows); an empty list keeps its centroid.  Bitwise reproducible from call to call.
+ *
+ * dir_segment_sums: sums[s][k] = sum of X[order[i]][k] over i in [seg_off[s], seg_off[s + 1]), fp32 accumulation in a fixed
+ *   order (a function of the segment's length alone; no float atomics), so results are bitwise reproducible; each sum is
+ *   within n_s * 2^-24 * sum |x| of the exact one (n_s rows; n_s / 16 + 4 additions on the longest path).  X [N][ldx] fp32
+ *   (ldx >= D, any pitch), order [seg_off[S]] int32 with entries in [0, N) (an entry outside adds nothing), seg_off
+ *   [S + 1] int32 ascending, sums [S][lds] fp32 (lds >= D); an empty segment gives zeros.  S <= 65535.
+ * dir_ivf_scan_i8: the scores of every query against the rows of the lists it probes.  The probe table arrives INVERTED -
+ *   by list, which is how the scan is cut (a workgroup multiplies up to 256 rows of one list with up to 32 of the queries
+ *   that probe it: queries that share a list read it once) - and is the caller's duty, as ids are in dir_topk
+ *   (dirtorch_amd/ops.py ivf_probe_tables builds it on the device from probe [Q][nprobe] and col_off [Q][nprobe]):
+ *     a pair is one (query q, slot p) with probe[q][p] = l >= 0; the pairs are grouped by list,
+ *     pair_off [nlist + 1]  CSR of the pairs by list,
+ *     pair_q [pairs], pair_col [pairs]  the query of a pair and col_off[q][p], the first output column of the slot,
+ *     item_off [nlist + 1]  CSR of the workgroups by list: list l takes ceil(len_l / 256) * ceil(pairs_l / 32) of them
+ *                           (0 when either is 0), items = item_off[nlist] - the grid.
+ *   For every pair and r < len_l: scores[q][col + r] = the quantised score of q against row list_off[l] + r, and
+ *   out_ids[q][col + r] = ids[list_off[l] + r].  out_ids[q][0 .. width) is pre-filled with -1 BY THIS CALL (a fill kernel
+ *   ahead of the scan), so a column no slot covers carries id -1 (its score is unspecified); columns at or past `width`
+ *   of the [Q][lds] rows are not touched, and a pair whose columns would pass `width`, or whose query is outside [0, Q),
+ *   stores nothing there.  qcodes [Q][ldq] and bcodes [N][ldb]: 16-byte aligned, pitches % 16 == 0 and >= D rounded up
+ *   to 64, Q * ldq < 2^31; the query codes must be ZERO in bytes D .. D rounded up to 64 (dir_quantize_rows_i8 writes them
+ *   so; both operands are read in 16-byte pieces and what the database holds there does not matter).  The slots of one
+ *   query must not overlap.  Otherwise sim_i8_kernel's pipeline: LDS-DMA loaders (the query rows of a group gathered by
+ *   a per-lane offset), v_mfma_i32_32x32x32_i8, K slabs of 128, four stages.
+ * Both: a negative count, D < 1, a pitch below its minimum or a null pointer fail with DIR_ERR_INVALID before anything is
+ *   launched; S == 0, Q == 0 or width == 0 is DIR_OK and launches nothing. */
+int dir_segment_sums(const float* X, int ldx, int N, int D, const int* order, const int* seg_off, int S, float* sums,
+                     int lds, void* stream);
+int dir_ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, const int8_t* bcodes, int ldb,
+                    const float* bscales, const int* ids, int N, int D, const int* list_off, int nlist, const int* pair_off,
+                    const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
+                    int lds, int width, void* stream);
 /* N3: alpha query expansion / database augmentation, expand_descriptors of
  * dirtorch/test_dir.py:24-44.  out[i] = normalize(mean(descs[i], sim[i][j]^alpha * db[j] for the k
  * rows j of db most similar to descs[i])), sim = descs . db^T in fp32; self_set != 0 (db == descs,

@@ -194,6 +194,9 @@ def bench_kernel_name(k):
             # the int8 index: quantiser, query image, scan and shortlist re-score (csrc/index_i8.hip; no timed bench.py step launches them)
             'quantize_rows_i8_kernel': 'l2norm_rows_kernel', 'code_image_kernel': 'split_queries_kernel',
             'sim_i8_kernel': 'sim_split_lc_kernel', 'gather_scores_kernel': 'expand_rows_kernel',
+            # the inverted file: the sums of a k-means step, the id pre-fill and the scan of the probed lists (csrc/ivf.hip; no timed bench.py step launches them)
+            'segment_sums_kernel': 'expand_rows_kernel', 'fill_ids_kernel': 'fill_noise_kernel',
+            'ivf_scan_i8_kernel': 'sim_split_lc_kernel',
             'maxpool_kernel': 'maxpool_3x3s2', 'upsample_add_kernel': 'upsample_add',
             'prep_input_f32_kernel': 'prep_input_f32', 'maxpool_f32_kernel': 'maxpool_f32',
             'global_pool_f32_kernel': 'global_pool_f32', 'upsample_add_f32_kernel': 'upsample_add_f32',
