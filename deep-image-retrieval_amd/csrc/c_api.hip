@@ -804,7 +804,7 @@ int dir_quantize_rows_i8(const float* X, int ldx, int N, int D, int8_t* codes, i
     if (N < 0) return fail(DIR_ERR_INVALID, "quantize_rows_i8: negative size");
     DIR_CHECK(index_check_dim("quantize_rows_i8", D));
     if (ldx < D) return fail(DIR_ERR_INVALID, "quantize_rows_i8: ldx < D");
-    if (ldc < ((D + 63) & ~63)) return fail(DIR_ERR_INVALID, "quantize_rows_i8: ldc < D rounded up to a multiple of 64");
+    if (ldc < pad64(D)) return fail(DIR_ERR_INVALID, "quantize_rows_i8: ldc < D rounded up to a multiple of 64");
     if (N == 0) return DIR_OK;
     if (!X || !codes || !scales) return fail(DIR_ERR_INVALID, "quantize_rows_i8: null pointer");
     if ((ldc & 3) != 0 || ((uintptr_t)codes & 3) != 0)
@@ -819,7 +819,7 @@ int dir_similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q
     if (Q < 0 || N < 0) return fail(DIR_ERR_INVALID, "similarity_i8: negative size");
     DIR_CHECK(index_check_dim("similarity_i8", D));
     if (ldq < D) return fail(DIR_ERR_INVALID, "similarity_i8: ldq < D");
-    if (ldb < ((D + 63) & ~63)) return fail(DIR_ERR_INVALID, "similarity_i8: ldb < D rounded up to a multiple of 64");
+    if (ldb < pad64(D)) return fail(DIR_ERR_INVALID, "similarity_i8: ldb < D rounded up to a multiple of 64");
     if (lds < N) return fail(DIR_ERR_INVALID, "similarity_i8: lds < N");
     if (Q == 0 || N == 0) return DIR_OK;
     if (!qcodes || !qscales || !bcodes || !bscales || !scores) return fail(DIR_ERR_INVALID, "similarity_i8: null pointer");
@@ -861,7 +861,7 @@ int dir_ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, 
     DIR_TRY
     if (Q < 0 || N < 0 || nlist < 0 || items < 0 || width < 0) return fail(DIR_ERR_INVALID, "ivf_scan_i8: negative size");
     DIR_CHECK(index_check_dim("ivf_scan_i8", D));
-    if (ldq < ((D + 63) & ~63) || ldb < ((D + 63) & ~63))
+    if (ldq < pad64(D) || ldb < pad64(D))
         return fail(DIR_ERR_INVALID, "ivf_scan_i8: ldq, ldb < D rounded up to a multiple of 64");
     if (lds < width) return fail(DIR_ERR_INVALID, "ivf_scan_i8: lds < width");
     if (Q == 0 || width == 0) return DIR_OK;

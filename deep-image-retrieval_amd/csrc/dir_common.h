@@ -17,6 +17,8 @@ typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
+typedef __attribute__((ext_vector_type(4))) int i32x4_t;
+typedef __attribute__((ext_vector_type(16))) int i32x16_t;
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
@@ -159,6 +161,15 @@ __device__ inline u32x4_t gload16(const void* p) {
 __device__ inline void gstore16(void* p, u32x4_t v) {
     *(DIR_GLOBAL u32x4_t*)p = v;
 }
+// row[k .. k+3] of a row of D floats, zeros past D; `vec`: every row is 16-byte aligned (k % 4 == 0)
+__device__ __forceinline__ f32x4_t load4_guarded(const float* __restrict__ row, int k, int D, bool vec) {
+    f32x4_t v = {0.f, 0.f, 0.f, 0.f};
+    if (vec && k + 3 < D) return *(const f32x4_t*)(row + k);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (k + e < D) v[e] = row[k + e];
+    return v;
+}
 
 // ---- fp16 overflow tripwire -----------------------------------------------------------------------
 // The reference computes in fp32 and cannot overflow (dirtorch/nets/backbones/resnet.py:67-87); fp16 storage
@@ -225,6 +236,8 @@ __device__ inline int xcd_remap(int bid, int nwg) {
 }
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+// the row length of an int8 code matrix: D rounded up to a multiple of 64
+__host__ __device__ inline int pad64(int D) { return (D + 63) & ~63; }
 
 // CU count of the current device, cached per device: hipGetDeviceProperties costs tens of microseconds, far too
 // much for a launcher that runs 100+ times per batch-1 forward.

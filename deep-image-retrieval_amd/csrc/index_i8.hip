@@ -8,51 +8,32 @@
 // come out of a scan cannot depend on how the caller cut the work.  Search then takes the usual two steps: the scan keeps
 // a shortlist per query (topk.hip), gather_scores re-scores the shortlist against the fp32 rows.
 //
-// sim_i8_kernel is sim_split_lc_kernel<PAIR>'s work split with codes in the stages (same stage geometry, byte for byte):
-// one 768-thread workgroup per 256 database rows; waves 0-7 multiply (a 32-row strip each against a block of 96 query
-// rows, three int32 accumulator blocks of v_mfma_i32_32x32x32_i8), waves 8-11 only issue LDS-DMA.  A 128-byte stage row
-// holds 128 k, so a K slab is 128 wide: 32 KB of database codes (each byte used by exactly one wave: HBM -> LDS raw) + the
+// sim_i8_kernel runs strip_stream.h's pipeline with codes in the stages: one 768-thread workgroup per 256 database rows;
+// the consumer waves multiply a 32-row strip each against a block of 96 query rows (three int32 accumulator blocks of
+// v_mfma_i32_32x32x32_i8).  A 128-byte stage row holds 128 k, so a K slab is 128 wide: 32 KB of database codes + the
 // 12 KB query image of the slab, prepared once by code_image_kernel as an image of the LDS stage and re-streamed from
-// L2.  Three stages, two in flight, one barrier per slab; further query blocks on grid.y.  Both operands of an MFMA step
-// are the same 16 consecutive bytes of a row per lane, so whatever k order the instruction gives the 16 bytes of a lane
-// half is the same on both sides.  Bytes per launch: N * ldb (codes, once per query block) + Q * N * 4 (scores).
+// L2.  Three stages, two in flight; further query blocks on grid.y.  Rows are padded to 64 and not to a slab, hence the
+// loader's half-slab cut.  Bytes per launch: N * ldb (codes, once per query block) + Q * N * 4 (scores).
 #include "dir_common.h"
-#include "conv_device.h"
+#include "strip_stream.h"
 #include "pointwise.h"
 
 #pragma clang fp contract(off)   // the definition is in single IEEE operations: nothing here may fuse
 
 namespace dir {
 
-typedef __attribute__((ext_vector_type(4))) int i32x4_t;
-typedef __attribute__((ext_vector_type(16))) int i32x16_t;
-
 static constexpr int kI8MaxDim = 131072;          // 127 * 127 * 131072 = 2 114 060 288 < 2^31
 static constexpr int kI8QB = 96;                  // query rows per block
-static constexpr int kI8Rows = 256;               // database rows per workgroup
-static constexpr int kI8SlabK = 128;              // k per slab = bytes per stage row
-static constexpr int kI8SlabP = kI8Rows * 128;    // 32768
-static constexpr int kI8SlabQ = kI8QB * 128;      // 12288
-static constexpr int kI8Stage = kI8SlabP + kI8SlabQ;
+static constexpr int kI8SlabQ = kI8QB * kStripRow;    // 12288
+static constexpr int kI8Stage = kStripSlab + kI8SlabQ;
 static constexpr int kI8Stages = 3;
 static constexpr int kI8Lds = kI8Stages * kI8Stage;   // 135168 of 163840
-
-static inline int pad64(int D) { return (D + 63) & ~63; }
 
 int index_i8_max_dim() { return kI8MaxDim; }
 
 // ---- quantisation ------------------------------------------------------------------------------------------------------
 // One wave per row, a lane owns quads of consecutive k: quad (c * 8 + i) * 64 + lane of chunk c (2048 values).  A row of
 // up to 2048 values stays in registers between the amax pass and the rounding pass; a wider row is read twice.
-__device__ __forceinline__ f32x4_t quant_load4(const float* __restrict__ row, int k, int D, bool vec) {
-    f32x4_t v = {0.f, 0.f, 0.f, 0.f};
-    if (vec && k + 3 < D) return *(const f32x4_t*)(row + k);
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (k + e < D) v[e] = row[k + e];
-    return v;
-}
-
 __global__ void __launch_bounds__(256) quantize_rows_i8_kernel(const float* __restrict__ X, int ldx, int N, int D,
                                                              int8_t* __restrict__ codes, int ldc,
                                                              float* __restrict__ scales) {
@@ -61,7 +42,7 @@ __global__ void __launch_bounds__(256) quantize_rows_i8_kernel(const float* __re
     if (n >= N) return;
     const float* row = X + (size_t)n * ldx;
     const bool vec = (ldx & 3) == 0 && (((uintptr_t)X) & 15) == 0;
-    const int Dp = (D + 63) & ~63;
+    const int Dp = pad64(D);
     const int chunks = (D + 2047) >> 11;
     f32x4_t v[8];
     float amax = 0.f;
@@ -69,7 +50,7 @@ __global__ void __launch_bounds__(256) quantize_rows_i8_kernel(const float* __re
     for (int c = 0; c < chunks; ++c) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            v[i] = quant_load4(row, ((c * 8 + i) * 64 + lane) * 4, D, vec);
+            v[i] = load4_guarded(row, ((c * 8 + i) * 64 + lane) * 4, D, vec);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float xe = v[i][e];     // (a copy: __builtin_bit_cast of a vector ELEMENT reads element 0)
@@ -92,7 +73,7 @@ __global__ void __launch_bounds__(256) quantize_rows_i8_kernel(const float* __re
         for (int i = 0; i < 8; ++i) {
             const int k = ((c * 8 + i) * 64 + lane) * 4;
             if (k >= Dp) continue;
-            if (chunks > 1) v[i] = quant_load4(row, k, D, vec);
+            if (chunks > 1) v[i] = load4_guarded(row, k, D, vec);
             uint32_t w = 0;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -125,9 +106,9 @@ __global__ void __launch_bounds__(256) code_image_kernel(const int8_t* __restric
     int8_t* dst = img + ((size_t)qb * T + t) * kI8SlabQ;
     for (int item = threadIdx.x; item < kI8QB * 8; item += 256) {
         const int row = item >> 3, pos = item & 7;
-        const int chunk = pos ^ ((row >> 1) & 7);
+        const int chunk = strip_chunk(pos, row);
         const int q = qb * kI8QB + row;
-        const int k0 = t * kI8SlabK + chunk * 16;
+        const int k0 = t * kStripRow + chunk * 16;
         u32x4_t w = {0u, 0u, 0u, 0u};
         if (q < Q) {
             const int8_t* src = qcodes + (size_t)q * ldq + k0;
@@ -147,86 +128,31 @@ __global__ void __launch_bounds__(768) sim_i8_kernel(const int8_t* __restrict__ 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tile = blockIdx.x, qb = blockIdx.y;
-    const int i0 = tile * kI8Rows;
-    const int rows = min(kI8Rows, NP - i0);
-    // every workgroup walks K from its own starting slab (see sim_split_kernel; an integer sum has no order)
-    const int rot = (int)(((unsigned)tile * 7u) % (unsigned)T);
+    const int i0 = tile * kStripRows;
+    const int rows = min(kStripRows, NP - i0);
+    const int rot = strip_rot(tile, T);
 
     if (wave >= 8) {
-        // ================================ loaders ==============================================================
         const int lw = wave - 8;
         // one descriptor per workgroup, based at its rows: Kp = D rounded up to 64 bytes of every row are readable
         const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (uint32_t)(((size_t)rows - 1) * ldp + Kp));
         const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc(img + (size_t)qb * T * kI8SlabQ, (uint32_t)(T * kI8SlabQ));
-        // database piece j = lw * 8 + i covers rows 8j .. 8j+7 (8 lanes x 16 bytes = one 128-byte run per row)
-        uint32_t pvoff[8];
-        uint32_t upper = 0;      // bit i: this lane's chunk of piece i lies in the upper 64 bytes of a slab
+        const StripLoader<true> db(lw, lane, (uint32_t)ldp, Kp, T);
+        strip_load<kI8Stage, kI8Stages, 11>(smem, T, rot, [&](char* stage, int u) __attribute__((always_inline)) {
+            db.issue(rsrc_p, stage, u);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int row = (lw * 8 + i) * 8 + (lane >> 3);
-            const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-            pvoff[i] = (uint32_t)row * (uint32_t)ldp + (uint32_t)chunk * 16u;   // rows past `rows`: out of range -> 0
-            upper |= (uint32_t)(chunk >= 4) << i;
-        }
-        // Kp % 128 == 64: the upper half of the last slab lies past Kp.  The scalar offset takes no part in the range
-        // check, so those lanes ask for an address that is out of range by itself.
-        const bool half = (Kp & 64) != 0;
-        auto issue = [&](int t) __attribute__((always_inline)) {
-            int u = t + rot;
-            u = u >= T ? u - T : u;
-            char* stage = smem + (t % kI8Stages) * kI8Stage;
-            const bool cut = half && u == T - 1;
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                dma16(rsrc_p, stage + (lw * 8 + i) * 1024, (cut && ((upper >> i) & 1u)) ? kOOB : pvoff[i], u * kI8SlabK);
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-                dma16(rsrc_q, stage + kI8SlabP + (lw * 3 + i) * 1024, (uint32_t)((lw * 3 + i) * 1024 + lane * 16), u * kI8SlabQ);
-        };
-        issue(0);
-        if (T > 1) issue(1);
-        for (int t = 0; t < T; ++t) {
-            // this wave's part of slab t has landed; its newest 11 ops (slab t + 1) may stay in flight
-            if (t + 1 < T)
-                asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-            else
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            ring_barrier();   // hand-off t: slab t is complete; the consumers have left slab t - 1
-            if (t + 2 < T) issue(t + 2);
-        }
+            for (int i = 0; i < 3; ++i) strip_image_piece(rsrc_q, stage, lw * 3 + i, lane, u * kI8SlabQ);
+        });
         return;
     }
 
-    // ==================================== consumers =============================================================
-    const int lrow = lane & 31, lhi = lane >> 5;
-    i32x16_t acc[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[j][e] = 0;
-    const int swz = (lrow >> 1) & 7;          // (the same for query row 32 j + lrow)
-    const int boff = (wave * 32 + lrow) * 128;
-    const int aoff = kI8SlabP + lrow * 128;
+    const StripLane L(wave, lane);
+    i32x16_t acc[3] = {};
+    strip_consume<kI8Stage, kI8Stages>(smem, T, rot, [&](const char* stage, int) __attribute__((always_inline)) {
+        code_slab_mma<3>(L, stage, acc);
+    });
 
-    int cur = 0;
-    for (int t = 0; t < T; ++t) {
-        ring_barrier();   // hand-off t (see the loaders)
-        const char* stage = smem + cur * kI8Stage;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {         // k = 128 u + 32 s + 16 lhi + 0..15
-            const int ch = (((s * 2 + lhi) ^ swz) << 4);
-            const i32x4_t b = *(const i32x4_t*)(stage + boff + ch);
-            i32x4_t a[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) a[j] = *(const i32x4_t*)(stage + aoff + j * 4096 + ch);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[j], b, acc[j], 0, 0, 0);
-        }
-        cur = cur + 1 == kI8Stages ? 0 : cur + 1;
-    }
-
-    // D[i][j]: lane holds database row j = lane & 31 of the strip, query rows i = 32 jb + 8 g + 4 (lane >> 5) + e
-    const int n = i0 + wave * 32 + lrow;
+    const int n = i0 + wave * 32 + L.lrow;
     if (n < NP) {
         const float sb = bscales[n];
 #pragma unroll
@@ -235,7 +161,7 @@ __global__ void __launch_bounds__(768) sim_i8_kernel(const int8_t* __restrict__ 
             for (int g = 0; g < 4; ++g)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const int q = qb * kI8QB + j * 32 + 8 * g + 4 * lhi + e;
+                    const int q = qb * kI8QB + L.qrow(j, g) + e;
                     if (q < NQ) out[(size_t)q * ldo + n] = __fmul_rn(__fmul_rn((float)acc[j][4 * g + e], qscales[q]), sb);
                 }
     }
@@ -244,7 +170,7 @@ __global__ void __launch_bounds__(768) sim_i8_kernel(const int8_t* __restrict__ 
 int similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, const int8_t* bcodes, int ldb,
                   const float* bscales, int N, int D, float* scores, int lds, hipStream_t stream) {
     if (Q <= 0 || N <= 0) return DIR_OK;
-    const int Kp = pad64(D), T = ceil_div(Kp, kI8SlabK), qblocks = ceil_div(Q, kI8QB);
+    const int Kp = pad64(D), T = ceil_div(Kp, kStripRow), qblocks = ceil_div(Q, kI8QB);
     if (qblocks > 65535) return fail(DIR_ERR_INVALID, "similarity_i8: more than 65535 * 96 queries in one call");
     static std::atomic<uint64_t> attr_done{0};
     DIR_HIP_CHECK(ensure_dynamic_lds((const void*)sim_i8_kernel, kI8Lds, attr_done));
@@ -257,7 +183,7 @@ int similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, co
     hipLaunchKernelGGL(code_image_kernel, dim3(T, qblocks), dim3(256), 0, stream, qcodes, ldq, Q, D, img);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(sim_i8_kernel, dim3(ceil_div(N, kI8Rows), qblocks), dim3(768), kI8Lds, stream, bcodes, ldb, N, Kp,
+        hipLaunchKernelGGL(sim_i8_kernel, dim3(ceil_div(N, kStripRows), qblocks), dim3(768), kI8Lds, stream, bcodes, ldb, N, Kp,
                            (const int8_t*)img, qscales, bscales, scores, lds, Q, T);
         e = hipGetLastError();
     }
@@ -269,8 +195,8 @@ int similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, co
 
 // the scan's admission rules beyond the sizes (c_api.hip reports them): 16-byte pieces, one 2 GB descriptor per tile
 bool similarity_i8_admissible(const int8_t* bcodes, int ldb, int D) {
-    return (ldb & 15) == 0 && (((uintptr_t)bcodes) & 15) == 0 && (size_t)ldb * kI8Rows < (1ull << 31) &&
-           (size_t)ceil_div(pad64(D), kI8SlabK) * kI8SlabQ < (1ull << 31);
+    return (ldb & 15) == 0 && (((uintptr_t)bcodes) & 15) == 0 && (size_t)ldb * kStripRows < (1ull << 31) &&
+           (size_t)ceil_div(pad64(D), kStripRow) * kI8SlabQ < (1ull << 31);
 }
 
 // ---- re-scoring a shortlist --------------------------------------------------------------------------------------------

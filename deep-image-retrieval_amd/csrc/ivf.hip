@@ -7,8 +7,8 @@
 // segment_sums_kernel - the sums of a Lloyd iteration: sums[s] = the rows order[seg_off[s] .. seg_off[s+1]) of X added up
 //   in fp32 in a FIXED order (no atomics: their arrival order would make a training run irreproducible).
 //
-// ivf_scan_i8_kernel - sim_i8_kernel's pipeline (LDS-DMA loader waves, consumer waves on v_mfma_i32_32x32x32_i8, K slabs of
-//   128, int32 accumulators, the same two-multiply epilogue: the scores are dir_similarity_i8's numbers) cut LIST-MAJOR: a
+// ivf_scan_i8_kernel - strip_stream.h's pipeline as sim_i8_kernel runs it (K slabs of 128 codes, int32 accumulators, the
+//   same two-multiply epilogue: the scores are dir_similarity_i8's numbers) with FOUR stages and cut LIST-MAJOR: a
 //   workgroup takes up to 256 consecutive rows of ONE list and multiplies them against a group of up to 32 of the queries
 //   that probe that list, so a batch of queries that share a list reads it once.  (Cut query-major, one workgroup per
 //   (query, list), a batch reads Q * nprobe / nlist of the database: at 70 queries and 16 of 1024 lists more bytes than the
@@ -21,15 +21,12 @@
 //   from the pair table, out-of-range for the empty rows of a group - the way the database pieces are addressed; no stage
 //   image is written per list.
 #include "dir_common.h"
-#include "conv_device.h"
+#include "strip_stream.h"
 #include "pointwise.h"
 
 #pragma clang fp contract(off)   // the score is defined in single IEEE operations: nothing here may fuse
 
 namespace dir {
-
-typedef __attribute__((ext_vector_type(4))) int i32x4_t;
-typedef __attribute__((ext_vector_type(16))) int i32x16_t;
 
 // ---- segment sums ------------------------------------------------------------------------------------------------------
 // One workgroup of four waves per (256 columns, segment); a lane owns four consecutive columns.  Wave w adds the rows
@@ -37,15 +34,6 @@ typedef __attribute__((ext_vector_type(16))) int i32x16_t;
 // (c0 + c1) + (c2 + c3), and the four waves' partial sums are folded the same way through LDS: the order is a function
 // of the segment's length alone.  n / 16 + 4 additions on the longest path.
 static constexpr int kSegCols = 256;
-
-__device__ __forceinline__ f32x4_t seg_load4(const float* __restrict__ row, int k, int D, bool vec) {
-    f32x4_t v = {0.f, 0.f, 0.f, 0.f};
-    if (vec && k + 3 < D) return *(const f32x4_t*)(row + k);
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (k + e < D) v[e] = row[k + e];
-    return v;
-}
 
 __global__ void __launch_bounds__(256) segment_sums_kernel(const float* __restrict__ X, int ldx, int N, int D,
                                                          const int* __restrict__ order, const int* __restrict__ seg_off,
@@ -66,7 +54,7 @@ __global__ void __launch_bounds__(256) segment_sums_kernel(const float* __restri
                 const int ii = i + 4 * j;
                 if (ii < i1) {
                     const int r = order[ii];
-                    if ((unsigned)r < (unsigned)N) c[j] += seg_load4(X + (size_t)r * ldx, k, D, vec);
+                    if ((unsigned)r < (unsigned)N) c[j] += load4_guarded(X + (size_t)r * ldx, k, D, vec);
                 }
             }
         }
@@ -94,11 +82,7 @@ int segment_sums(const float* X, int ldx, int N, int D, const int* order, const 
 
 // ---- the scan of the probed lists --------------------------------------------------------------------------------------
 static constexpr int kIvfQG = 32;                   // query rows per group = one 32 x 32 accumulator block
-static constexpr int kIvfRows = 256;                // database rows per workgroup
-static constexpr int kIvfSlabK = 128;               // k per slab = bytes per stage row
-static constexpr int kIvfSlabP = kIvfRows * 128;    // 32768
-static constexpr int kIvfSlabQ = kIvfQG * 128;      // 4096
-static constexpr int kIvfStage = kIvfSlabP + kIvfSlabQ;
+static constexpr int kIvfStage = kStripSlab + kIvfQG * kStripRow;   // 36864
 static constexpr int kIvfStages = 4;                // three slabs in flight, one being multiplied
 static constexpr int kIvfLds = kIvfStages * kIvfStage;   // 147456 of 163840
 
@@ -133,91 +117,41 @@ __global__ void __launch_bounds__(768) ivf_scan_i8_kernel(const int8_t* __restri
     const int local = bid - item_off[l];
     if (groups <= 0 || local < 0) return;
     const int tile = local / groups, grp = local - tile * groups;
-    const int i0 = list_off[l] + tile * kIvfRows;
+    const int i0 = list_off[l] + tile * kStripRows;
     const int iend = min(list_off[l + 1], NP);
-    const int rows = min(kIvfRows, iend - i0);
+    const int rows = min(kStripRows, iend - i0);
     const int pbase = p0 + grp * kIvfQG;
     if (i0 < 0 || rows <= 0) return;
-    const int rot = (int)(((unsigned)bid * 7u) % (unsigned)T);
+    const int rot = strip_rot(bid, T);
 
     if (wave >= 8) {
-        // ================================ loaders ==============================================================
         const int lw = wave - 8;
         const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (uint32_t)(((size_t)rows - 1) * ldp + Kp));
         const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc(qcodes, (uint32_t)(((size_t)Q - 1) * ldq + Kp));
-        uint32_t pvoff[8];
-        uint32_t upper = 0;      // bit i: this lane's chunk of piece i lies in the upper 64 bytes of a slab
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int row = (lw * 8 + i) * 8 + (lane >> 3);
-            const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-            pvoff[i] = (uint32_t)row * (uint32_t)ldp + (uint32_t)chunk * 16u;   // rows past `rows`: out of range -> 0
-            upper |= (uint32_t)(chunk >= 4) << i;
-        }
+        const StripLoader<true> db(lw, lane, (uint32_t)ldp, Kp, T);
         // query piece lw = rows 8 lw .. 8 lw + 7 of the group: row r is the query of pair pbase + r, gathered where it lies
-        const int qrow = lw * 8 + (lane >> 3);
-        const int qchunk = (lane & 7) ^ ((qrow >> 1) & 7);
+        const int qrow = strip_piece_row(lw, lane), qchunk = strip_piece_chunk(lw, lane);
         uint32_t qvoff = kOOB;                                                 // an empty row of the group reads zeros
         if (pbase + qrow < p1) {
             const int q = pair_q[pbase + qrow];
             if ((unsigned)q < (unsigned)Q) qvoff = (uint32_t)q * (uint32_t)ldq + (uint32_t)qchunk * 16u;
         }
         const bool qupper = qchunk >= 4;
-        // Kp % 128 == 64: the upper half of the last slab lies past Kp.  The scalar offset takes no part in the range
-        // check, so those lanes ask for an address that is out of range by itself.
-        const bool half = (Kp & 64) != 0;
-        auto issue = [&](int t) __attribute__((always_inline)) {
-            int u = t + rot;
-            u = u >= T ? u - T : u;
-            char* stage = smem + (t % kIvfStages) * kIvfStage;
-            const bool cut = half && u == T - 1;
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                dma16(rsrc_p, stage + (lw * 8 + i) * 1024, (cut && ((upper >> i) & 1u)) ? kOOB : pvoff[i], u * kIvfSlabK);
-            dma16(rsrc_q, stage + kIvfSlabP + lw * 1024, (cut && qupper) ? kOOB : qvoff, u * kIvfSlabK);
-        };
-        issue(0);
-        if (T > 1) issue(1);
-        if (T > 2) issue(2);
-        for (int t = 0; t < T; ++t) {
-            // this wave's part of slab t has landed; the 9 ops of each newer slab may stay in flight
-            if (t + 2 < T)
-                asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-            else if (t + 1 < T)
-                asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-            else
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            ring_barrier();   // hand-off t: slab t is complete; the consumers have left slab t - 1
-            if (t + 3 < T) issue(t + 3);
-        }
+        strip_load<kIvfStage, kIvfStages, 9>(smem, T, rot, [&](char* stage, int u) __attribute__((always_inline)) {
+            db.issue(rsrc_p, stage, u);
+            dma16(rsrc_q, stage + kStripSlab + lw * kStripPiece, (db.cut(u) && qupper) ? kOOB : qvoff, u * kStripRow);
+        });
         return;
     }
 
-    // ==================================== consumers =============================================================
-    const int lrow = lane & 31, lhi = lane >> 5;
-    i32x16_t acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0;
-    const int swz = (lrow >> 1) & 7;          // (the same for database row 32 wave + lrow and query row lrow)
-    const int boff = (wave * 32 + lrow) * 128;
-    const int aoff = kIvfSlabP + lrow * 128;
+    const StripLane L(wave, lane);
+    i32x16_t acc[1] = {};
+    strip_consume<kIvfStage, kIvfStages>(smem, T, rot, [&](const char* stage, int) __attribute__((always_inline)) {
+        code_slab_mma<1>(L, stage, acc);
+    });
 
-    int cur = 0;
-    for (int t = 0; t < T; ++t) {
-        ring_barrier();   // hand-off t (see the loaders)
-        const char* stage = smem + cur * kIvfStage;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {         // k = 128 u + 32 s + 16 lhi + 0..15
-            const int ch = (((s * 2 + lhi) ^ swz) << 4);
-            const i32x4_t b = *(const i32x4_t*)(stage + boff + ch);
-            const i32x4_t a = *(const i32x4_t*)(stage + aoff + ch);
-            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc, 0, 0, 0);
-        }
-        cur = cur + 1 == kIvfStages ? 0 : cur + 1;
-    }
-
-    // D[i][j]: lane holds database row j = lane & 31 of the strip, group rows i = 8 g + 4 (lane >> 5) + e
-    const int r = tile * kIvfRows + wave * 32 + lrow;      // the row's place in its list
+    // scattered epilogue: the lane's 16 pairs are the group rows L.qrow(0, g) + e
+    const int r = tile * kStripRows + wave * 32 + L.lrow;    // the row's place in its list
     const int n = list_off[l] + r;
     if (n < iend) {
         const float sb = bscales[n];
@@ -228,7 +162,7 @@ __global__ void __launch_bounds__(768) ivf_scan_i8_kernel(const int8_t* __restri
         float sq[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-            const int pi = pbase + 8 * (j >> 2) + 4 * lhi + (j & 3);
+            const int pi = pbase + L.qrow(0, j >> 2) + (j & 3);
             const bool ok = pi < p1;
             qv[j] = ok ? pair_q[pi] : -1;
             cv[j] = ok ? (long)pair_col[pi] + r : -1;
@@ -241,7 +175,7 @@ __global__ void __launch_bounds__(768) ivf_scan_i8_kernel(const int8_t* __restri
 #pragma unroll
         for (int j = 0; j < 16; ++j)
             if (cv[j] >= 0) {
-                out[(size_t)qv[j] * ldo + cv[j]] = __fmul_rn(__fmul_rn((float)acc[j], sq[j]), sb);
+                out[(size_t)qv[j] * ldo + cv[j]] = __fmul_rn(__fmul_rn((float)acc[0][j], sq[j]), sb);
                 out_ids[(size_t)qv[j] * ldo + cv[j]] = id;
             }
     }
@@ -250,7 +184,7 @@ __global__ void __launch_bounds__(768) ivf_scan_i8_kernel(const int8_t* __restri
 // the scan's admission rules beyond the sizes (c_api.hip reports them): 16-byte pieces, one 2 GB descriptor per operand
 bool ivf_scan_i8_admissible(const int8_t* qcodes, int ldq, int Q, const int8_t* bcodes, int ldb) {
     return ((ldq | ldb) & 15) == 0 && ((((uintptr_t)qcodes) | ((uintptr_t)bcodes)) & 15) == 0 &&
-           (size_t)ldb * kIvfRows < (1ull << 31) && (size_t)ldq * (size_t)(Q > 0 ? Q : 1) < (1ull << 31);
+           (size_t)ldb * kStripRows < (1ull << 31) && (size_t)ldq * (size_t)(Q > 0 ? Q : 1) < (1ull << 31);
 }
 
 int ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, const int8_t* bcodes, int ldb,
@@ -262,7 +196,7 @@ int ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, cons
     hipLaunchKernelGGL(fill_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, out_ids, lds, width, total);
     DIR_HIP_CHECK(hipGetLastError());
     if (items <= 0 || N <= 0) return DIR_OK;
-    const int Kp = (D + 63) & ~63, T = ceil_div(Kp, kIvfSlabK);
+    const int Kp = pad64(D), T = ceil_div(Kp, kStripRow);
     static std::atomic<uint64_t> attr_done{0};
     DIR_HIP_CHECK(ensure_dynamic_lds((const void*)ivf_scan_i8_kernel, kIvfLds, attr_done));
     hipLaunchKernelGGL(ivf_scan_i8_kernel, dim3((unsigned)items), dim3(768), kIvfLds, stream, qcodes, ldq, qscales, Q, bcodes,

@@ -26,50 +26,22 @@
 // precision problem in reverse (5 exponent bits): the 2^10 scale puts unit-vector entries (~2^-6) in the middle of the
 // range, values of magnitude >= 64 overflow h to inf and the scores come out non-finite - loudly wrong, never silently.
 //
-// Work split: one 512-thread workgroup per 256 database rows, one 32-row strip per wave against all 96 query rows
-// (3 accumulator blocks).  The database is used by exactly one wave, so it goes HBM -> LDS as raw fp32 by LDS-DMA
-// (128-byte pieces, XOR-swizzled rows) and is split in registers right before the MFMAs; the query planes are split
-// once by split_queries_kernel into an image that is byte-for-byte the LDS layout of every K slab (18 KB per 32
-// k), so their re-streaming from L2 is a linear copy.  Three stages of (32 KB database + 18 KB query planes) in LDS,
-// two in flight; one barrier per K slab.  Algorithmic bytes per launch: N*K*4 (database, once) + Q*N*4 (scores).
-#include "dir_common.h"
-#include "conv_device.h"
+// Work split: strip_stream.h's pipeline (256 database rows per workgroup, a 32-row strip per wave against all 96 query
+// rows, the database HBM -> LDS as raw fp32 by LDS-DMA, one barrier per K slab) - the stage geometry, the loader and
+// consumer loops and the plane arithmetic live there.  Here: the database is split in registers right before the
+// MFMAs; the query planes are split once by split_queries_kernel into an image that is byte-for-byte the LDS layout
+// of every K slab (18 KB per 32 k), so their re-streaming from L2 is a linear copy.  Three stages of (32 KB database +
+// 18 KB query planes) in LDS, two in flight.  Algorithmic bytes per launch: N*K*4 (database, once) + Q*N*4 (scores).
+#include "strip_stream.h"
 
 namespace dir {
 
-static constexpr int kQB = 96;                    // query rows per block (3 MFMA row blocks)
-static constexpr int kPlane = kQB * 64;           // bytes of one bf16 plane of a 32-wide K slab
-static constexpr int kSlabQ = 3 * kPlane;         // 18432
-static constexpr int kRowsP = 256;                // database rows per workgroup
-static constexpr int kSlabP = kRowsP * 128;       // 32768
-static constexpr int kStage = kSlabP + kSlabQ;    // 51200
 static constexpr int kStages = 3;
-static constexpr int kLds = kStages * kStage;     // 153600 of 163840
-// PAIR form: two fp16 planes
-static constexpr int kSlabQ2 = 2 * kPlane;        // 12288
-static constexpr int kStage2 = kSlabP + kSlabQ2;  // 45056
-static constexpr int kLds2 = kStages * kStage2;   // 135168
-static constexpr float kPairScale = 1024.f;       // 2^10: |x| < 64 stays finite in fp16, unit-vector entries mid-range
-
-// x0, x1 -> packed bf16 planes (low half = x0)
-__device__ __forceinline__ void split2(float x0, float x1, uint32_t& h, uint32_t& m, uint32_t& l) {
-    float a, b;
-    h = BF16::pack(x0, x1);
-    BF16::unpack(h, a, b);
-    x0 -= a, x1 -= b;
-    m = BF16::pack(x0, x1);
-    BF16::unpack(m, a, b);
-    x0 -= a, x1 -= b;
-    l = BF16::pack(x0, x1);
-}
-
-// x0, x1 (already scaled) -> packed fp16 planes
-__device__ __forceinline__ void split2h(float x0, float x1, uint32_t& h, uint32_t& l) {
-    float a, b;
-    h = FP16::pack(x0, x1);
-    FP16::unpack(h, a, b);
-    l = FP16::pack(x0 - a, x1 - b);
-}
+static constexpr int kSlabQ = plane_slab(false);          // 18432
+static constexpr int kStage = plane_stage(false);         // 51200
+static constexpr int kLds = kStages * kStage;             // 153600 of 163840
+static constexpr int kSlabQ2 = plane_slab(true);          // 12288: PAIR form, two fp16 planes
+static constexpr int kLds2 = kStages * plane_stage(true); // 3 x 45056 = 135168
 
 // Query planes as an image of the LDS stages: [query block][K slab of 32][plane h, m, l][96 rows][64 bytes], the
 // four 16-byte chunks of a row XOR-swizzled by (row >> 2) & 3.  Rows past NQ and k past K are zero.
@@ -78,7 +50,7 @@ template <bool PAIR>
 __global__ void __launch_bounds__(256) split_queries_kernel(const float* __restrict__ Q, int ldq, int NQ, int K,
                                                            uint16_t* __restrict__ img) {
     const int t = blockIdx.x, qb = blockIdx.y, T = gridDim.x;
-    char* dst = (char*)img + ((size_t)qb * T + t) * (PAIR ? kSlabQ2 : kSlabQ);
+    char* dst = (char*)img + ((size_t)qb * T + t) * plane_slab(PAIR);
     for (int item = threadIdx.x; item < kQB * 4; item += 256) {
         const int row = item >> 2, pos = item & 3;
         const int chunk = pos ^ ((row >> 2) & 3);
@@ -102,122 +74,74 @@ __global__ void __launch_bounds__(256) split_queries_kernel(const float* __restr
     }
 }
 
+// scores of database row n against the 96 query rows from q0, row-major; PAIR: the 2^-20 of the two plane scales
+template <bool PAIR>
+__device__ __forceinline__ void store_scores(const StripLane& L, const f32x16_t (&acc)[3], const f32x16_t (&lo)[3],
+                                             float* __restrict__ out, int ldo, int n, int NP, int q0, int NQ) {
+    if (n >= NP) return;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int q = q0 + L.qrow(j, g) + e;
+                const float v = acc[j][4 * g + e] + lo[j][4 * g + e];
+                if (q < NQ) out[(size_t)q * ldo + n] = PAIR ? v * (1.f / (kPairScale * kPairScale)) : v;
+            }
+}
+
+// ---- one-role form (DIRTORCH_AMD_SIM_V1: A/B and bisecting) --------------------------------------------------------------
+// Eight waves, each of which both loads and multiplies: wave w brings database pieces w, 8 + w, 16 + w, 24 + w and an
+// eighth of the query image of every slab, then multiplies its strip.  Two slabs in flight.
 __global__ void __launch_bounds__(512) sim_split_kernel(const float* __restrict__ P, int ldp, int NP, int K,
                                                        const uint16_t* __restrict__ img, float* __restrict__ out,
                                                        int ldo, int NQ, int T) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lrow = lane & 31, lhi = lane >> 5;
     const int tile = blockIdx.x, qb = blockIdx.y;
-    const int i0 = tile * kRowsP;
-    const int rows = min(kRowsP, NP - i0);
+    const int i0 = tile * kStripRows;
+    const int rows = min(kStripRows, NP - i0);
 
     // the database can exceed the 4 GB a buffer descriptor spans: one descriptor per workgroup, based at its rows
     const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (int)((((size_t)rows - 1) * ldp + K) * 4));
     const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc((const char*)img + (size_t)qb * T * kSlabQ, T * kSlabQ);
 
-    // database: instruction j = i * 8 + wave covers rows 8j .. 8j+7 (8 lanes x 16 bytes = one 128-byte piece)
     uint32_t pvoff[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = (i * 8 + wave) * 8 + (lane >> 3);
-        const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-        pvoff[i] = (uint32_t)row * (uint32_t)ldp * 4u + (uint32_t)chunk * 16u;   // rows past `rows`: out of range -> 0
-    }
+    for (int i = 0; i < 4; ++i) pvoff[i] = strip_piece_voff(i * 8 + wave, lane, (uint32_t)ldp * 4u);
     const uint32_t qvoff = (uint32_t)(wave * (kSlabQ / 8) + lane * 16);          // 2304 bytes per wave: 2 + 1/4 instr.
 
     auto issue = [&](int u, char* stage) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) dma16(rsrc_p, stage + (i * 8 + wave) * 1024, pvoff[i], (uint32_t)u * 128u);
-        char* qd = stage + kSlabP + wave * (kSlabQ / 8);
+        for (int i = 0; i < 4; ++i) dma16(rsrc_p, stage + (i * 8 + wave) * kStripPiece, pvoff[i], u * kStripRow);
+        char* qd = stage + kStripSlab + wave * (kSlabQ / 8);
         dma16(rsrc_q, qd, qvoff, (uint32_t)u * kSlabQ);
         dma16(rsrc_q, qd + 1024, qvoff + 1024, (uint32_t)u * kSlabQ);
         if (lane < 16) dma16(rsrc_q, qd + 2048, qvoff + 2048, (uint32_t)u * kSlabQ);
     };
     constexpr int kOps = 7;   // LDS-DMA instructions per wave per stage
 
-    f32x16_t acc[3], lo[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f, lo[j][e] = 0.f;
-
-    const int boff = (wave * 32 + lrow) * 128, bswz = (lrow >> 1) & 7;
-    const int aoff = kSlabP + lrow * 64, aswz = (lrow >> 2) & 3;
-
-    auto compute = [&](const char* stage) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const int c0 = s * 4 + lhi * 2;
-            const f32x4_t b0 = *(const f32x4_t*)(stage + boff + ((c0 ^ bswz) << 4));
-            const f32x4_t b1 = *(const f32x4_t*)(stage + boff + (((c0 + 1) ^ bswz) << 4));
-            u32x4_t ah[3], am[3], al[3];
-            const int ach = ((s * 2 + lhi) ^ aswz) << 4;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                ah[j] = *(const u32x4_t*)(stage + aoff + 0 * kPlane + j * 2048 + ach);
-                am[j] = *(const u32x4_t*)(stage + aoff + 1 * kPlane + j * 2048 + ach);
-                al[j] = *(const u32x4_t*)(stage + aoff + 2 * kPlane + j * 2048 + ach);
-            }
-            u32x4_t bh, bm, bl;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                uint32_t h, m, l;
-                split2(e < 2 ? b0[2 * e] : b1[2 * e - 4], e < 2 ? b0[2 * e + 1] : b1[2 * e - 3], h, m, l);
-                bh[e] = h, bm[e] = m, bl[e] = l;
-            }
-#define DIR_MM(ACC, A, B)                                                                                   \
-    _Pragma("unroll") for (int j = 0; j < 3; ++j) ACC[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(         \
-        __builtin_bit_cast(bf16x8_t, A[j]), __builtin_bit_cast(bf16x8_t, B), ACC[j], 0, 0, 0)
-            // the five correction products (weight <= 2^-8) have their own accumulator: the leading sum then sees
-            // K/16 roundings instead of 6K/16, and the corrections round at 2^-8 of its scale
-            DIR_MM(lo, al, bh);
-            DIR_MM(lo, ah, bl);
-            DIR_MM(lo, am, bm);
-            DIR_MM(lo, am, bh);
-            DIR_MM(lo, ah, bm);
-            DIR_MM(acc, ah, bh);
-#undef DIR_MM
-        }
-    };
-
-    // every workgroup walks K from its own starting slab: with an 8 KiB row pitch workgroups in lock-step would
-    // all be on the same few HBM channels at any instant (same rotation as gemm_nt_f32_kernel; the sum is the same)
-    const int rot = (int)(((unsigned)tile * 7u) % (unsigned)T);
-    auto slab = [&](int t) {
-        int u = t + rot;
-        return u >= T ? u - T : u;
-    };
-    issue(slab(0), smem);
-    if (T > 1) issue(slab(1), smem + kStage);
+    const StripLane L(wave, lane);
+    f32x16_t acc[3] = {}, lo[3] = {};
+    const int rot = strip_rot(tile, T);
+    issue(strip_slab(0, rot, T), smem);
+    if (T > 1) issue(strip_slab(1, rot, T), smem + kStage);
     int cur = 0;
     for (int t = 0; t < T; ++t) {
         if (t + 1 < T)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"i"(kOps) : "memory");
+            wait_vmcnt<kOps>();
         else
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
         ring_barrier();   // slab t landed everywhere; everyone is past slab t-1, whose slot is free
         int nxt = cur + 2;
         if (nxt >= kStages) nxt -= kStages;
-        if (t + 2 < T) issue(slab(t + 2), smem + nxt * kStage);
-        compute(smem + cur * kStage);
+        if (t + 2 < T) issue(strip_slab(t + 2, rot, T), smem + nxt * kStage);
+        plane_slab_mma<false>(L, smem + cur * kStage, 0, PairScale<false>(), acc, lo);
         cur = cur + 1 == kStages ? 0 : cur + 1;
     }
-
-    // D[i][j]: lane holds database row j = lane & 31 of the strip, query rows i = 8g + 4(lane >> 5) + e
-    const int n = i0 + wave * 32 + lrow;
-    if (n < NP) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int q = qb * kQB + j * 32 + 8 * g + 4 * lhi + e;
-                    if (q < NQ) out[(size_t)q * ldo + n] = acc[j][4 * g + e] + lo[j][4 * g + e];
-                }
-    }
+    store_scores<false>(L, acc, lo, out, ldo, i0 + wave * 32 + L.lrow, NP, qb * kQB, NQ);
 }
 
 // Timing-only experiment builds (scripts/exp_abl.sh sim_split DIR_SIM_ABL <bits>): -DDIR_SIM_ABL=<bits> - 1 = no database DMA, 2 = no query DMA,
@@ -231,149 +155,45 @@ __global__ void __launch_bounds__(512) sim_split_kernel(const float* __restrict_
 // wave role: on a memory-bound CU the request queue is full, every LDS-DMA instruction holds its wave at issue until the
 // queue drains, and in the kernel above the eight waves that issue the next slab are the eight waves that should be
 // splitting and multiplying this one - the two phases serialise (the same finding as conv_ring.hip,
-// profiles/r03_ring_ablation.txt).  Here a workgroup has TWELVE waves (148 VGPRs: three waves per SIMD fit): waves 0-7
-// are the consumers of the old kernel (one 32-row strip each, no memory ops until the final score store), waves 8-11
-// only issue LDS-DMA - 8 database pieces + 4 or 5 KB of the query image per slab each - and wait for it.  One
-// s_barrier per K slab is the hand-off both ways (slab t landed / slot of slab t - 1 is free).
+// profiles/r03_ring_ablation.txt).  Here the twelve waves of strip_stream.h (three per SIMD: at most 168 VGPRs): a
+// loader brings 8 database pieces + 4 or 5 KB of the query image per slab.
 template <bool PAIR>
 __global__ void __launch_bounds__(768) sim_split_lc_kernel(const float* __restrict__ P, int ldp, int NP, int K,
                                                           const uint16_t* __restrict__ img, float* __restrict__ out,
                                                           int ldo, int NQ, int T) {
-    constexpr int kSlabQ = PAIR ? dir::kSlabQ2 : dir::kSlabQ;     // (shadow the three-plane constants)
-    constexpr int kStage = PAIR ? dir::kStage2 : dir::kStage;
+    constexpr int kSlabQ = plane_slab(PAIR), kStage = plane_stage(PAIR);     // (shadow the three-plane constants)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tile = blockIdx.x, qb = blockIdx.y;
-    const int i0 = tile * kRowsP;
-    const int rows = min(kRowsP, NP - i0);
-    // every workgroup walks K from its own starting slab (see sim_split_kernel)
-    const int rot = (int)(((unsigned)tile * 7u) % (unsigned)T);
+    const int i0 = tile * kStripRows;
+    const int rows = min(kStripRows, NP - i0);
+    const int rot = strip_rot(tile, T);
 
     if (wave >= 8) {
-        // ================================ loaders ==============================================================
         const int lw = wave - 8;
         const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (int)((((size_t)rows - 1) * ldp + K) * 4));
         const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc((const char*)img + (size_t)qb * T * kSlabQ, T * kSlabQ);
-        // database piece j = lw * 8 + i covers rows 8j .. 8j+7 (8 lanes x 16 bytes = one 128-byte run per row)
-        uint32_t pvoff[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int row = (lw * 8 + i) * 8 + (lane >> 3);
-            const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-            pvoff[i] = (uint32_t)row * (uint32_t)ldp * 4u + (uint32_t)chunk * 16u;   // rows past `rows`: out of range -> 0
-        }
+        const StripLoader<false> db(lw, lane, (uint32_t)ldp * 4u);
         // query image of a slab: 18 pieces of 1 KiB; loaders 0 / 1 take 5, loaders 2 / 3 take 4 (PAIR: 12 pieces, 3 each)
         const int q0 = PAIR ? lw * 3 : (lw < 2 ? lw * 5 : 10 + (lw - 2) * 4);
         const bool five = !PAIR && lw < 2;
-        auto issue = [&](int t) __attribute__((always_inline)) {
-            int u = t + rot;
-            u = u >= T ? u - T : u;
-            char* stage = smem + (t % kStages) * kStage;
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (!(DIR_SIM_ABL & 1)) dma16(rsrc_p, stage + (lw * 8 + i) * 1024, pvoff[i], (uint32_t)u * 128u);
+        strip_load<kStage, kStages, PAIR ? 11 : 12, PAIR ? 11 : 13>(smem, T, rot, [&](char* stage, int u) __attribute__((always_inline)) {
+            if (!(DIR_SIM_ABL & 1)) db.issue(rsrc_p, stage, u);
 #pragma unroll
             for (int i = 0; i < (PAIR ? 3 : 4); ++i)
-                if (!(DIR_SIM_ABL & 2))
-                    dma16(rsrc_q, stage + kSlabP + (q0 + i) * 1024, (uint32_t)((q0 + i) * 1024 + lane * 16), (uint32_t)u * kSlabQ);
-            if (five && !(DIR_SIM_ABL & 2)) dma16(rsrc_q, stage + kSlabP + (q0 + 4) * 1024, (uint32_t)((q0 + 4) * 1024 + lane * 16), (uint32_t)u * kSlabQ);
-        };
-        issue(0);
-        if (T > 1) issue(1);
-        for (int t = 0; t < T; ++t) {
-            // this wave's part of slab t has landed; its newest 12 / 13 ops (slab t + 1) may stay in flight
-            if (t + 1 < T) {
-                if (PAIR) {
-                    asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-                } else if (five) {
-                    asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
-                } else {
-                    asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-                }
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            ring_barrier();   // hand-off t: slab t is complete; the consumers have left slab t - 1
-            if (t + 2 < T) issue(t + 2);
-        }
+                if (!(DIR_SIM_ABL & 2)) strip_image_piece(rsrc_q, stage, q0 + i, lane, u * kSlabQ);
+            if (five && !(DIR_SIM_ABL & 2)) strip_image_piece(rsrc_q, stage, q0 + 4, lane, u * kSlabQ);
+        }, five);
         return;
     }
 
-    // ==================================== consumers =============================================================
-    const int lrow = lane & 31, lhi = lane >> 5;
-    f32x16_t acc[3], lo[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f, lo[j][e] = 0.f;
-    const int boff = (wave * 32 + lrow) * 128, bswz = (lrow >> 1) & 7;
-    const int aoff = kSlabP + lrow * 64, aswz = (lrow >> 2) & 3;
-
-    int cur = 0;
-    for (int t = 0; t < T; ++t) {
-        ring_barrier();   // hand-off t (see the loaders)
-        const char* stage = smem + cur * kStage;
-#pragma unroll
-        for (int s = 0; s < ((DIR_SIM_ABL & 4) ? 0 : 2); ++s) {
-            const int c0 = s * 4 + lhi * 2;
-            const f32x4_t b0 = *(const f32x4_t*)(stage + boff + ((c0 ^ bswz) << 4));
-            const f32x4_t b1 = *(const f32x4_t*)(stage + boff + (((c0 + 1) ^ bswz) << 4));
-            u32x4_t ah[3], am[3], al[3];
-            const int ach = ((s * 2 + lhi) ^ aswz) << 4;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                ah[j] = *(const u32x4_t*)(stage + aoff + 0 * kPlane + j * 2048 + ach);
-                am[j] = *(const u32x4_t*)(stage + aoff + 1 * kPlane + j * 2048 + ach);
-                if (!PAIR) al[j] = *(const u32x4_t*)(stage + aoff + 2 * kPlane + j * 2048 + ach);
-            }
-            u32x4_t bh, bm, bl;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                uint32_t h, m, l = 0;
-                const float x0 = e < 2 ? b0[2 * e] : b1[2 * e - 4], x1 = e < 2 ? b0[2 * e + 1] : b1[2 * e - 3];
-                if (PAIR)
-                    split2h(x0 * kPairScale, x1 * kPairScale, h, m);
-                else
-                    split2(x0, x1, h, m, l);
-                bh[e] = h, bm[e] = m, bl[e] = l;
-            }
-            if (PAIR) {   // planes (h, m) = (hi, lo) of fp16: leading product + the two corrections
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    lo[j] = FP16::mfma32(__builtin_bit_cast(f16x8_t, am[j]), __builtin_bit_cast(f16x8_t, bh), lo[j]);
-                    lo[j] = FP16::mfma32(__builtin_bit_cast(f16x8_t, ah[j]), __builtin_bit_cast(f16x8_t, bm), lo[j]);
-                    acc[j] = FP16::mfma32(__builtin_bit_cast(f16x8_t, ah[j]), __builtin_bit_cast(f16x8_t, bh), acc[j]);
-                }
-                continue;
-            }
-#define DIR_MM(ACC, A, B)                                                                                   \
-    _Pragma("unroll") for (int j = 0; j < 3; ++j) ACC[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(         \
-        __builtin_bit_cast(bf16x8_t, A[j]), __builtin_bit_cast(bf16x8_t, B), ACC[j], 0, 0, 0)
-            DIR_MM(lo, al, bh);     // same order of products and accumulators as sim_split_kernel
-            DIR_MM(lo, ah, bl);
-            DIR_MM(lo, am, bm);
-            DIR_MM(lo, am, bh);
-            DIR_MM(lo, ah, bm);
-            DIR_MM(acc, ah, bh);
-#undef DIR_MM
-        }
-        cur = cur + 1 == kStages ? 0 : cur + 1;
-    }
-
-    const int n = i0 + wave * 32 + lrow;
-    if (n < NP) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int q = qb * kQB + j * 32 + 8 * g + 4 * lhi + e;
-                    const float v = acc[j][4 * g + e] + lo[j][4 * g + e];
-                    if (q < NQ) out[(size_t)q * ldo + n] = PAIR ? v * (1.f / (kPairScale * kPairScale)) : v;
-                }
-    }
+    const StripLane L(wave, lane);
+    f32x16_t acc[3] = {}, lo[3] = {};
+    strip_consume<kStage, kStages>(smem, T, rot, [&](const char* stage, int u) __attribute__((always_inline)) {
+        if (!(DIR_SIM_ABL & 4)) plane_slab_mma<PAIR>(L, stage, u, PairScale<PAIR>(), acc, lo);
+    });
+    store_scores<PAIR>(L, acc, lo, out, ldo, i0 + wave * 32 + L.lrow, NP, qb * kQB, NQ);
 }
 
 // ---- PCA whitening of a LARGE descriptor set on the same machinery -------------------------------------------------------
@@ -385,7 +205,7 @@ __global__ void __launch_bounds__(768) sim_split_lc_kernel(const float* __restri
 // fp32 accumulation.  What differs from sim_split_lc_kernel<true>:
 //   * X takes the database's place (streamed once per component block by LDS-DMA as raw fp32, 256 rows per workgroup) and the
 //     mean is subtracted in fp32 right before the split, as the reference subtracts it before its GEMM (no cancellation between
-//     two large dot products); the mean vector lives in LDS (K floats);
+//     two large dot products); the mean vector lives in LDS (K floats), so the loaders' wait also covers lgkmcnt;
 //   * the components take the queries' place (their plane image: split_queries_kernel<true>), 96 rows per block - but there are
 //     v / 96 = 22 blocks, not one, so the grid is 1-D with an XCD-aware decode: the 22 workgroups that share an X tile run on the
 //     SAME XCD at the same time and walk K in the same rotated order - one of them misses to HBM, 21 hit that XCD's L2;
@@ -396,8 +216,7 @@ __global__ void __launch_bounds__(768) whiten_split_kernel(const float* __restri
                                                           const uint16_t* __restrict__ img, const float* __restrict__ mean,
                                                           const float* __restrict__ alpha, float* __restrict__ out, int ldo,
                                                           int NQ, int T, int tiles, int qblocks) {
-    constexpr int kSlabQ = dir::kSlabQ2;
-    constexpr int kStage = dir::kStage2;
+    constexpr int kSlabQ = plane_slab(true), kStage = plane_stage(true);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* lmean = (float*)(smem + kStages * kStage);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -406,105 +225,44 @@ __global__ void __launch_bounds__(768) whiten_split_kernel(const float* __restri
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int tile = (slot / qblocks) * 8 + xcd, qb = slot % qblocks;
     if (tile >= tiles) return;
-    const int i0 = tile * kRowsP;
-    const int rows = min(kRowsP, NP - i0);
-    const int rot = (int)(((unsigned)tile * 7u) % (unsigned)T);
+    const int i0 = tile * kStripRows;
+    const int rows = min(kStripRows, NP - i0);
+    const int rot = strip_rot(tile, T);
     if (HAS_MEAN)   // the table holds 2^10 mean: (x - mean) 2^10 is then ONE fma per value, bit-identical (a power-of-two scale commutes with rounding)
         for (int i = tid; i < K; i += 768) lmean[i] = mean[i] * kPairScale;
 
     if (wave >= 8) {
-        // ================================ loaders (as sim_split_lc_kernel<true>) ================================
         const int lw = wave - 8;
         const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (int)((((size_t)rows - 1) * ldp + K) * 4));
         const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc((const char*)img + (size_t)qb * T * kSlabQ, T * kSlabQ);
-        uint32_t pvoff[8];
+        const StripLoader<false> db(lw, lane, (uint32_t)ldp * 4u);
+        // (the first hand-off also publishes this wave's share of the mean table)
+        strip_load<kStage, kStages, 11, 11, true>(smem, T, rot, [&](char* stage, int u) __attribute__((always_inline)) {
+            db.issue(rsrc_p, stage, u);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int row = (lw * 8 + i) * 8 + (lane >> 3);
-            const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-            pvoff[i] = (uint32_t)row * (uint32_t)ldp * 4u + (uint32_t)chunk * 16u;   // rows past `rows`: out of range -> 0
-        }
-        const int q0 = lw * 3;
-        auto issue = [&](int t) __attribute__((always_inline)) {
-            int u = t + rot;
-            u = u >= T ? u - T : u;
-            char* stage = smem + (t % kStages) * kStage;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) dma16(rsrc_p, stage + (lw * 8 + i) * 1024, pvoff[i], (uint32_t)u * 128u);
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-                dma16(rsrc_q, stage + kSlabP + (q0 + i) * 1024, (uint32_t)((q0 + i) * 1024 + lane * 16), (uint32_t)u * kSlabQ);
-        };
-        issue(0);
-        if (T > 1) issue(1);
-        for (int t = 0; t < T; ++t) {
-            if (t + 1 < T)
-                asm volatile("s_waitcnt vmcnt(11) lgkmcnt(0)" ::: "memory");
-            else
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            ring_barrier();   // hand-off t: slab t is complete (and, at t = 0, the mean table); the consumers have left slab t - 1
-            if (t + 2 < T) issue(t + 2);
-        }
+            for (int i = 0; i < 3; ++i) strip_image_piece(rsrc_q, stage, lw * 3 + i, lane, u * kSlabQ);
+        });
         return;
     }
 
-    // ==================================== consumers =============================================================
-    const int lrow = lane & 31, lhi = lane >> 5;
-    f32x16_t acc[3], lo[3];
+    const StripLane L(wave, lane);
+    f32x16_t acc[3] = {}, lo[3] = {};
+    auto center = [&](f32x4_t& b0, f32x4_t& b1, int u, int c0) __attribute__((always_inline)) {
+        if (HAS_MEAN) {   // k = 32 u + 4 c0 + 0..7
+            const f32x4_t m0 = *(const f32x4_t*)(lmean + u * 32 + c0 * 4), m1 = *(const f32x4_t*)(lmean + u * 32 + c0 * 4 + 4);
 #pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f, lo[j][e] = 0.f;
-    const int boff = (wave * 32 + lrow) * 128, bswz = (lrow >> 1) & 7;
-    const int aoff = kSlabP + lrow * 64, aswz = (lrow >> 2) & 3;
-
-    int cur = 0;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (this wave's share of the mean table is written)
-    for (int t = 0; t < T; ++t) {
-        ring_barrier();   // hand-off t (see the loaders)
-        const char* stage = smem + cur * kStage;
-        int u = t + rot;
-        u = u >= T ? u - T : u;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const int c0 = s * 4 + lhi * 2;
-            f32x4_t b0 = *(const f32x4_t*)(stage + boff + ((c0 ^ bswz) << 4));
-            f32x4_t b1 = *(const f32x4_t*)(stage + boff + (((c0 + 1) ^ bswz) << 4));
-            if (HAS_MEAN) {   // k = 32 u + 16 s + 8 lhi + 0..7
-                const f32x4_t m0 = *(const f32x4_t*)(lmean + u * 32 + c0 * 4), m1 = *(const f32x4_t*)(lmean + u * 32 + c0 * 4 + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) b0[e] = __builtin_fmaf(b0[e], kPairScale, -m0[e]), b1[e] = __builtin_fmaf(b1[e], kPairScale, -m1[e]);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) b0[e] *= kPairScale, b1[e] *= kPairScale;
-            }
-            u32x4_t ah[3], al[3];
-            const int ach = ((s * 2 + lhi) ^ aswz) << 4;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                ah[j] = *(const u32x4_t*)(stage + aoff + 0 * kPlane + j * 2048 + ach);
-                al[j] = *(const u32x4_t*)(stage + aoff + 1 * kPlane + j * 2048 + ach);
-            }
-            u32x4_t bh, bl;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                uint32_t h, l;
-                const float x0 = e < 2 ? b0[2 * e] : b1[2 * e - 4], x1 = e < 2 ? b0[2 * e + 1] : b1[2 * e - 3];
-                split2h(x0, x1, h, l);      // (already scaled by 2^10)
-                bh[e] = h, bl[e] = l;
-            }
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                lo[j] = FP16::mfma32(__builtin_bit_cast(f16x8_t, al[j]), __builtin_bit_cast(f16x8_t, bh), lo[j]);
-                lo[j] = FP16::mfma32(__builtin_bit_cast(f16x8_t, ah[j]), __builtin_bit_cast(f16x8_t, bl), lo[j]);
-                acc[j] = FP16::mfma32(__builtin_bit_cast(f16x8_t, ah[j]), __builtin_bit_cast(f16x8_t, bh), acc[j]);
-            }
+            for (int e = 0; e < 4; ++e) b0[e] = __builtin_fmaf(b0[e], kPairScale, -m0[e]), b1[e] = __builtin_fmaf(b1[e], kPairScale, -m1[e]);
+        } else {
+            PairScale<true>()(b0, b1, u, c0);
         }
-        cur = cur + 1 == kStages ? 0 : cur + 1;
-    }
+    };
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (this wave's share of the mean table is written)
+    strip_consume<kStage, kStages>(smem, T, rot, [&](const char* stage, int u) __attribute__((always_inline)) {
+        plane_slab_mma<true>(L, stage, u, center, acc, lo);
+    });
 
-    // D[i][j]: lane holds X row lrow of the strip and component rows i = 32 j + 8 g + 4 lhi + e: four consecutive outputs of row n
-    const int n = i0 + wave * 32 + lrow;
+    // a lane holds X row lrow of the strip and four consecutive component rows per (j, g): 16-byte stores of row n
+    const int n = i0 + wave * 32 + L.lrow;
     if (n < NP) {
         float* orow = out + (size_t)n * ldo;
         const bool vec = (ldo & 3) == 0 && (((uintptr_t)out) & 15) == 0;
@@ -512,7 +270,7 @@ __global__ void __launch_bounds__(768) whiten_split_kernel(const float* __restri
         for (int j = 0; j < 3; ++j)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int q = qb * kQB + j * 32 + 8 * g + 4 * lhi;
+                const int q = qb * kQB + L.qrow(j, g);
                 if (q >= NQ) continue;
                 f32x4_t v;
 #pragma unroll
@@ -535,8 +293,8 @@ size_t whiten_split_workspace_bytes(int v, int K) { return (size_t)ceil_div(v, k
 
 bool whiten_split_admissible(const float* X, int ldx, int N, int K, int v) {
     return N > 0 && v > 0 && K > 0 && (K % 32) == 0 && (ldx % 4) == 0 && ((uintptr_t)X & 15) == 0 && ldx >= K &&
-           (size_t)ldx * 4 * kRowsP < (1ull << 31) && (size_t)ceil_div(K, 32) * kSlabQ2 < (1ull << 31) &&
-           kLds2 + (size_t)K * 4 <= 160 * 1024 && (size_t)ceil_div(N, kRowsP) * ceil_div(v, kQB) < (1ull << 30);
+           (size_t)ldx * 4 * kStripRows < (1ull << 31) && (size_t)ceil_div(K, 32) * kSlabQ2 < (1ull << 31) &&
+           kLds2 + (size_t)K * 4 <= 160 * 1024 && (size_t)ceil_div(N, kStripRows) * ceil_div(v, kQB) < (1ull << 30);
 }
 
 // X [N, K] (row stride ldx), components [v, K] (row stride ldc), mean [K] or null, alpha [v] or null -> out [N, v] (row stride ldo).
@@ -549,7 +307,7 @@ int whiten_split(const float* X, int ldx, int N, const float* comps, int ldc, in
     if (!workspace || workspace_bytes < whiten_split_workspace_bytes(v, K))
         return fail(DIR_ERR_WORKSPACE, "whiten_split: workspace too small");
     if (((uintptr_t)workspace & 15) != 0) return fail(DIR_ERR_INVALID, "whiten_split: workspace must be 16-byte aligned");
-    const int T = K / 32, qblocks = ceil_div(v, kQB), tiles = ceil_div(N, kRowsP);
+    const int T = K / 32, qblocks = ceil_div(v, kQB), tiles = ceil_div(N, kStripRows);
     const int lds = kLds2 + K * 4;
     static std::atomic<uint64_t> attr_m{0}, attr_n{0};
     DIR_HIP_CHECK(ensure_dynamic_lds((const void*)whiten_split_kernel<true>, 160 * 1024, attr_m));
@@ -573,7 +331,7 @@ size_t similarity_split_workspace_bytes(int NQ, int K) {
 bool similarity_split_admissible(const float* P, int ldp, const float* Q, int ldq, int NP, int NQ, int K) {
     (void)Q, (void)ldq;
     return NP > 0 && NQ > 0 && K > 0 && (K % 32) == 0 && (ldp % 4) == 0 && ((uintptr_t)P & 15) == 0 &&
-           (size_t)ldp * 4 * kRowsP < (1ull << 31) && (size_t)ceil_div(K, 32) * kSlabQ < (1ull << 31) &&
+           (size_t)ldp * 4 * kStripRows < (1ull << 31) && (size_t)ceil_div(K, 32) * kSlabQ < (1ull << 31) &&
            ceil_div(NQ, kQB) < 65536;
 }
 
@@ -593,17 +351,17 @@ int similarity_split(const float* P, int ldp, const float* Q, int ldq, float* ou
     const int T = K / 32, qblocks = ceil_div(NQ, kQB);
     if (unit_range && !v1) {   // operands in (-64, 64): two fp16 planes, three products
         hipLaunchKernelGGL(split_queries_kernel<true>, dim3(T, qblocks), dim3(256), 0, stream, Q, ldq, NQ, K, (uint16_t*)workspace);
-        hipLaunchKernelGGL(sim_split_lc_kernel<true>, dim3(ceil_div(NP, kRowsP), qblocks), dim3(768), kLds2, stream, P, ldp, NP, K,
+        hipLaunchKernelGGL(sim_split_lc_kernel<true>, dim3(ceil_div(NP, kStripRows), qblocks), dim3(768), kLds2, stream, P, ldp, NP, K,
                            (const uint16_t*)workspace, out, ldo, NQ, T);
         DIR_HIP_CHECK(hipGetLastError());
         return DIR_OK;
     }
     hipLaunchKernelGGL(split_queries_kernel<false>, dim3(T, qblocks), dim3(256), 0, stream, Q, ldq, NQ, K, (uint16_t*)workspace);
     if (v1)
-        hipLaunchKernelGGL(sim_split_kernel, dim3(ceil_div(NP, kRowsP), qblocks), dim3(512), kLds, stream, P, ldp, NP, K,
+        hipLaunchKernelGGL(sim_split_kernel, dim3(ceil_div(NP, kStripRows), qblocks), dim3(512), kLds, stream, P, ldp, NP, K,
                            (const uint16_t*)workspace, out, ldo, NQ, T);
     else
-        hipLaunchKernelGGL(sim_split_lc_kernel<false>, dim3(ceil_div(NP, kRowsP), qblocks), dim3(768), kLds, stream, P, ldp, NP, K,
+        hipLaunchKernelGGL(sim_split_lc_kernel<false>, dim3(ceil_div(NP, kStripRows), qblocks), dim3(768), kLds, stream, P, ldp, NP, K,
                            (const uint16_t*)workspace, out, ldo, NQ, T);
     DIR_HIP_CHECK(hipGetLastError());
     return DIR_OK;

@@ -106,12 +106,12 @@ def _codes(r, n, D, junk=False):
     return c
 
 
-@pytest.mark.parametrize('D', [1, 64, 65, 129, 200, 320, 2048])
+@pytest.mark.parametrize('D', [1, 64, 65, 129, 200, 320, 448, 640, 2048])
 def test_similarity_i8_is_the_restatement(D):
     """One launch form: grid = (database tiles of 256 rows, query blocks of 96 rows), K slabs of 128 over D rounded up to
     64.  Q = 1 / 33 / 96 | 97 / 200: a partial block, a full one, one block plus a row, three blocks; N on both sides of a
     tile and twelve tiles (every rotation of the slab walk); D = 64, 129, 320: the last slab is half a slab, D = 65, 200:
-    ragged, 2048: sixteen slabs.  The database codes carry noise in their padding (it must not count)."""
+    ragged, 448: four slabs, the last a half (the three-stage ring reuses its first slot), 640: five, 2048: sixteen slabs.  The database codes carry noise in their padding (it must not count)."""
     from dirtorch_amd import ops
     r = np.random.RandomState(100 + D)
     cq, cb = _codes(r, 200, D), _codes(r, 3000, D, junk=True)

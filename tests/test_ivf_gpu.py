@@ -149,12 +149,13 @@ def _check_scan(dev, D, want, ids, probe):
     assert torch.equal(again_i, got_i) and torch.equal(again_s.view(torch.int32)[again_i >= 0], got_s.view(torch.int32)[got_i >= 0])
 
 
-@pytest.mark.parametrize('D', [1, 64, 65, 200, 320, 2048])
+@pytest.mark.parametrize('D', [1, 64, 65, 200, 320, 448, 640, 2048])
 def test_ivf_scan_is_the_restatement(D):
     """Hand-made lists, no training: every covered column carries index_ref.score's bits and its row's id, every other
     column id -1, and nothing past the width is written.  Q = 1 / 33 / 97 / 200 queries with 1 / 3 / 9 distinct random
     lists each (-1 in some slots); 200 queries that all probe the 700-row list (seven groups of 32 per tile); a table
-    that leaves lists out; one NaN scale on each side; noise in the padding of the database codes."""
+    that leaves lists out; one NaN scale on each side; noise in the padding of the database codes.  D = 448: four slabs,
+    the last a half (the first re-issue of the four-stage ring), 640: five slabs (the ring wraps)."""
     r = np.random.RandomState(180 + D)
     cq, cb = _codes(r, 200, D), _codes(r, NROWS, D, junk=True)
     sq = np.exp(r.uniform(-8, 2, 200)).astype(np.float32)
