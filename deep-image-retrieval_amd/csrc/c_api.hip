@@ -910,6 +910,53 @@ int dir_topk(const float* scores, int lds, int Q, int N, int k, const int* ids, 
     DIR_CATCH
 }
 
+int dir_pq_max_m(void) { return pq_max_m(); }
+
+// D and M of a product quantiser: 1 <= M <= dir_pq_max_m(), M divides D, D within the int8 index's widest row
+static int pq_check_dims(const char* who, int D, int M) {
+    DIR_CHECK(index_check_dim(who, D));
+    if (M < 1 || M > pq_max_m()) return fail(DIR_ERR_INVALID, std::string(who) + ": M outside 1 .. dir_pq_max_m()");
+    if (D % M != 0) return fail(DIR_ERR_INVALID, std::string(who) + ": M does not divide D");
+    return DIR_OK;
+}
+
+int dir_pq_encode(const float* X, int ldx, int N, int D, int M, const float* codebooks, uint8_t* codes, int ldc, void* stream) {
+    DIR_TRY
+    if (N < 0) return fail(DIR_ERR_INVALID, "pq_encode: negative size");
+    DIR_CHECK(pq_check_dims("pq_encode", D, M));
+    if (ldx < D) return fail(DIR_ERR_INVALID, "pq_encode: ldx < D");
+    if (ldc < M || ldc % 4 != 0) return fail(DIR_ERR_INVALID, "pq_encode: ldc < M or ldc % 4 != 0");
+    if (N == 0) return DIR_OK;
+    if (!X || !codebooks || !codes) return fail(DIR_ERR_INVALID, "pq_encode: null pointer");
+    return pq_encode(X, ldx, N, D, M, codebooks, codes, ldc, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_pq_lut(const float* queries, int ldq, int Q, int D, int M, const float* codebooks, float* lut, void* stream) {
+    DIR_TRY
+    if (Q < 0) return fail(DIR_ERR_INVALID, "pq_lut: negative size");
+    DIR_CHECK(pq_check_dims("pq_lut", D, M));
+    if (ldq < D) return fail(DIR_ERR_INVALID, "pq_lut: ldq < D");
+    if (Q == 0) return DIR_OK;
+    if (!queries || !codebooks || !lut) return fail(DIR_ERR_INVALID, "pq_lut: null pointer");
+    return pq_lut(queries, ldq, Q, D, M, codebooks, lut, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_pq_scan(const float* lut, int Q, int M, const uint8_t* codes, int ldc, int N, float* scores, int lds, void* stream) {
+    DIR_TRY
+    if (Q < 0 || N < 0) return fail(DIR_ERR_INVALID, "pq_scan: negative size");
+    if (M < 1 || M > pq_max_m()) return fail(DIR_ERR_INVALID, "pq_scan: M outside 1 .. dir_pq_max_m()");
+    if (ldc < M || ldc % 4 != 0) return fail(DIR_ERR_INVALID, "pq_scan: ldc < M or ldc % 4 != 0");
+    if (lds < N) return fail(DIR_ERR_INVALID, "pq_scan: lds < N");
+    if (Q == 0 || N == 0) return DIR_OK;
+    if (!lut || !codes || !scores) return fail(DIR_ERR_INVALID, "pq_scan: null pointer");
+    if ((((uintptr_t)lut) & 15) != 0 || (((uintptr_t)codes) & 3) != 0)
+        return fail(DIR_ERR_INVALID, "pq_scan: a 16-byte aligned lut and 4-byte aligned codes expected");
+    return pq_scan(lut, Q, M, codes, ldc, N, scores, lds, (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_expand_descriptors(const float* descs, int n, const float* db, int m, int D, int k, float alpha,
                            int self_set, float* out, float* sim, size_t sim_bytes, void* stream) {
     DIR_TRY

@@ -71,6 +71,11 @@ int ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, cons
                 const float* bscales, const int* ids, int N, int D, const int* list_off, int nlist, const int* pair_off,
                 const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
                 int lds, int width, hipStream_t stream);
+// the product-quantised index (pq.hip): 8-bit codes per sub-space, the tables of a query, the scan that adds their entries
+int pq_max_m();
+int pq_encode(const float* X, int ldx, int N, int D, int M, const float* codebooks, uint8_t* codes, int ldc, hipStream_t stream);
+int pq_lut(const float* queries, int ldq, int Q, int D, int M, const float* codebooks, float* lut, hipStream_t stream);
+int pq_scan(const float* lut, int Q, int M, const uint8_t* codes, int ldc, int N, float* scores, int lds, hipStream_t stream);
 int expand_descriptors(const float* descs, int n, const float* db, int m, int D, int k, float alpha,
                        int self_set, float* out, float* sim, size_t sim_bytes, hipStream_t stream);
 // scratch (optional): fp32 workspace for the split-K partial sums of shapes with few output tiles; without one

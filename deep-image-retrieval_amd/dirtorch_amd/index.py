@@ -20,6 +20,18 @@ The inverted file reads only the lists a query falls into instead of the whole d
 
 Its assignment, probing and scores are defined through the quantised score as well (include/dir_engine.h), so with
 nprobe = nlist it returns Int8Index's lists bit for bit, and with fewer lists those of tests/ivf_ref.py.
+
+The product-quantised index keeps M bytes per row instead of D - a row is the numbers of its nearest of 256 centroids in
+each of M sub-spaces - and scores a query through M tables of 256 inner products:
+
+    index = PQIndex(D, M)                                    # M divides D, 1 <= M <= ops.pq_max_m()
+    index.train(bdescs)                                      # Lloyd iterations per sub-space on (a sample of) the descriptors
+    index.add(bdescs)                                        # encoded in row chunks
+    idx, vals = index.search(qdescs, 10)                     # lists by table score
+    idx, vals = index.search(qdescs, 10, rerank=40, source=bdescs)
+
+Codes, tables and scores are chains of single fp32 operations in a fixed order (include/dir_engine.h): the lists are those
+of tests/pq_ref.py bit for bit and do not depend on scratch_bytes, db_rows or on how many add() calls built the database.
 """
 import numpy as np
 import torch
@@ -93,6 +105,37 @@ class _CodedIndex:
                     torch.empty(0, k, dtype=torch.float32, device='cuda'))
         return None
 
+    def _scan_blocks(self, Q, keep, same_set, scratch_bytes, db_rows, scorer, row_bytes=0):
+        """ranking.retrieve_device's loop on a coded database: the `keep` best rows of every query.  scorer(r0, r1) -> a
+        function (b0, b1) -> the scores [r1 - r0, b1 - b0] of queries r0 .. r1 against rows b0 .. b1.  The queries go in
+        chunks whose score rows (and row_bytes more per query: what a scorer holds for its chunk) fit scratch_bytes."""
+        N = len(self)
+        block = N if db_rows is None else int(max(keep, min(N, db_rows)))
+        idx = torch.empty(Q, keep, dtype=torch.int32, device='cuda')
+        vals = torch.empty(Q, keep, dtype=torch.float32, device='cuda')
+        rows = int(max(1, min(Q, scratch_bytes // max(4 * block + row_bytes, 1))))
+        for r0 in range(0, Q, rows):
+            r1 = min(Q, r0 + rows)
+            own = torch.arange(r0, r1, dtype=torch.int32, device='cuda') if same_set else None
+            score = scorer(r0, r1)
+            run_i = run_v = None
+            for b0 in range(0, N, block):
+                b1 = min(N, b0 + block)
+                scores = score(b0, b1)
+                if b0 == 0 and b1 == N:
+                    run_i, run_v = ops.topk(scores, keep, exclude=own)
+                    break
+                kb = min(keep, b1 - b0)
+                bi, bv = ops.topk(scores, kb, exclude=None if own is None else own - b0)
+                del scores
+                bi = torch.where(bi >= 0, bi + b0, bi)
+                if run_i is None:
+                    run_i, run_v = bi, bv
+                else:
+                    run_i, run_v = ops.topk(torch.cat([run_v, bv], dim=1), keep, ids=torch.cat([run_i, bi], dim=1))
+            idx[r0:r1], vals[r0:r1] = run_i, run_v
+        return idx, vals
+
     def _rerank(self, q, cand, vals, k, R, source, scratch_bytes):
         """the lists of a scan that kept R or k candidates per query: as they are, or the k best by fp32 score"""
         if not R:
@@ -139,32 +182,10 @@ class Int8Index(_CodedIndex):
         return self
 
     def _scan(self, qc, qs, keep, same_set, scratch_bytes, db_rows):
-        """ranking.retrieve_device's loop on the coded sets: the `keep` best rows of every query by quantised score."""
-        Q, N = qc.shape[0], len(self)
-        block = N if db_rows is None else int(max(keep, min(N, db_rows)))
-        idx = torch.empty(Q, keep, dtype=torch.int32, device='cuda')
-        vals = torch.empty(Q, keep, dtype=torch.float32, device='cuda')
-        rows = int(max(1, min(Q, scratch_bytes // max(4 * block, 1))))
-        for r0 in range(0, Q, rows):
-            r1 = min(Q, r0 + rows)
-            own = torch.arange(r0, r1, dtype=torch.int32, device='cuda') if same_set else None
-            run_i = run_v = None
-            for b0 in range(0, N, block):
-                b1 = min(N, b0 + block)
-                scores = ops.similarity_i8(qc[r0:r1], qs[r0:r1], self.codes[b0:b1], self.scales[b0:b1], self.D)
-                if b0 == 0 and b1 == N:
-                    run_i, run_v = ops.topk(scores, keep, exclude=own)
-                    break
-                kb = min(keep, b1 - b0)
-                bi, bv = ops.topk(scores, kb, exclude=None if own is None else own - b0)
-                del scores
-                bi = torch.where(bi >= 0, bi + b0, bi)
-                if run_i is None:
-                    run_i, run_v = bi, bv
-                else:
-                    run_i, run_v = ops.topk(torch.cat([run_v, bv], dim=1), keep, ids=torch.cat([run_i, bi], dim=1))
-            idx[r0:r1], vals[r0:r1] = run_i, run_v
-        return idx, vals
+        """the `keep` best rows of every coded query by quantised score"""
+        def scorer(r0, r1):
+            return lambda b0, b1: ops.similarity_i8(qc[r0:r1], qs[r0:r1], self.codes[b0:b1], self.scales[b0:b1], self.D)
+        return self._scan_blocks(qc.shape[0], keep, same_set, scratch_bytes, db_rows, scorer)
 
     def search(self, qdescs, k, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20, db_rows=None):
         """(idx [Q,k] int32, vals [Q,k] float32), both CUDA, under ranking.retrieve_device's contract (its order, same_set
@@ -359,4 +380,118 @@ class IVFInt8Index(_CodedIndex):
         index.ids = torch.from_numpy(ids.astype(np.int32)).cuda()
         index.list_off = torch.from_numpy(list_off.astype(np.int32)).cuda()
         index._lens = np.diff(list_off.astype(np.int64))
+        return index
+
+
+class PQIndex(_CodedIndex):
+    """The product-quantised index (include/dir_engine.h gives the definitions).  All CUDA: codebooks [M, 256, D / M] fp32
+    (None until train or load) and codes [N, ldc] uint8, ldc = M rounded up to a multiple of 4, the padding zero."""
+
+    def __init__(self, D, M):
+        super().__init__(D)
+        M = int(M)
+        if M < 1 or M > ops.pq_max_m() or self.D % M:
+            raise ValueError('1 <= M <= %d dividing D = %d expected, got %d' % (ops.pq_max_m(), self.D, M))
+        self.M, self.dsub = M, self.D // M
+        self.codebooks = None
+        self.codes = torch.empty(0, (M + 3) // 4 * 4, dtype=torch.uint8, device='cuda')
+        self.scales = None
+
+    def nbytes(self):
+        """the bytes the database rows take on the device (the codebooks, 1024 * D bytes, not counted)"""
+        return len(self) * int(self.codes.shape[1])
+
+    def train(self, x, iters=10, seed=0, max_rows=None):
+        """Lloyd iterations per sub-space on the rows of x [n, D] (any kind add takes), or on a sorted
+        np.random.RandomState(seed).choice sample of max_rows of them (default 256 * 256) when x has more.  The initial
+        centroids are the rows np.sort(RandomState(seed).choice(n, 256, replace=False)) of the sample, sub-space m taking
+        its columns of them; an iteration encodes the sample (ops.pq_encode is the assignment), sums each centroid's
+        members in fp32 (ops.segment_sums on the sub-space's columns) and divides by their number; a centroid without
+        members keeps its value.  Bitwise reproducible.  Rows already added are not re-encoded: train first."""
+        self._check_rows(x)
+        if len(self):
+            raise ValueError('train before add: the rows already stored were encoded with the old codebooks')
+        n = int(x.shape[0])
+        max_rows = 256 * 256 if max_rows is None else int(max_rows)
+        if n < 256 or max_rows < 256:
+            raise ValueError('at least 256 training rows expected, got %d' % min(n, max_rows))
+        if n > max_rows:
+            pick = np.sort(np.random.RandomState(seed).choice(n, max_rows, replace=False))
+            x = x[torch.from_numpy(pick).to(x.device)] if torch.is_tensor(x) else x[pick]
+            n = max_rows
+        x = _upload(x)
+        if not bool(torch.isfinite(x).all()):
+            raise ValueError('training data with a non-finite value')
+        first = np.sort(np.random.RandomState(seed).choice(n, 256, replace=False))
+        codebooks = x[torch.from_numpy(first).cuda()].view(256, self.M, self.dsub).permute(1, 0, 2).contiguous()
+        bounds = torch.arange(257, device='cuda')
+        for _ in range(int(iters)):
+            codes = ops.pq_encode(x, codebooks)
+            for m in range(self.M):
+                col, order = torch.sort(codes[:, m].long(), stable=True)
+                seg_off = torch.searchsorted(col, bounds).to(torch.int32)
+                sums = ops.segment_sums(x[:, m * self.dsub:(m + 1) * self.dsub], order.to(torch.int32), seg_off)
+                count = (seg_off[1:] - seg_off[:-1])[:, None]
+                codebooks[m] = torch.where(count > 0, sums / count.to(torch.float32), codebooks[m])
+        self.codebooks = codebooks
+        return self
+
+    def add(self, descs):
+        """Append the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap), encoded in chunks of
+        ADD_CHUNK_BYTES as Int8Index.add quantises them."""
+        self._check_rows(descs)
+        if self.codebooks is None:
+            raise ValueError('add before train')
+        n, N = int(descs.shape[0]), len(self)
+        if n == 0:
+            return self
+        codes = torch.empty(N + n, self.codes.shape[1], dtype=torch.uint8, device='cuda')
+        codes[:N] = self.codes
+        rows = max(1, ADD_CHUNK_BYTES // (4 * self.D))
+        for r0 in range(0, n, rows):
+            codes[N + r0:N + min(n, r0 + rows)] = ops.pq_encode(_upload(descs[r0:r0 + rows]), self.codebooks)
+        self.codes = codes
+        return self
+
+    def _scan(self, q, keep, same_set, scratch_bytes, db_rows):
+        """the `keep` best rows of every query by table score; a chunk of queries holds its tables, 1024 * M bytes each"""
+        def scorer(r0, r1):
+            lut = ops.pq_lut(q[r0:r1], self.codebooks)
+            return lambda b0, b1: ops.pq_scan(lut, self.codes[b0:b1])
+        return self._scan_blocks(q.shape[0], keep, same_set, scratch_bytes, db_rows, scorer, row_bytes=1024 * self.M)
+
+    def search(self, qdescs, k, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20, db_rows=None):
+        """Int8Index.search's contract with the table scores in place of the quantised ones: (idx [Q,k] int32, vals [Q,k]
+        float32), both CUDA, in ops.topk's order, same_set leaving a query out of its own list, (-1, NaN) where a row runs
+        short; rerank = R re-scores the R best against `source` (CUDA tensor, host array or memmap) in fp32."""
+        from .utils.common import _dev
+        if self.codebooks is None:
+            raise ValueError('search before train')
+        q = _dev(qdescs)
+        k, R = int(k), int(rerank)
+        empty = self._check_search(q, k, R, source, same_set)
+        if empty is not None:
+            return empty
+        cand, vals = self._scan(q, R or k, same_set, scratch_bytes, db_rows)
+        return self._rerank(q, cand, vals, k, R, source, scratch_bytes)
+
+    def save(self, path):
+        """One .npz: `codebooks` [M, 256, D / M] float32, `codes` [N, M] uint8 (without the padding), `D`, `M`."""
+        if self.codebooks is None:
+            raise ValueError('save before train')
+        np.savez(path, codebooks=self.codebooks.cpu().numpy(), codes=self.codes[:, :self.M].cpu().numpy(),
+                 D=np.int64(self.D), M=np.int64(self.M))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as f:
+            index = cls(int(f['D']), int(f['M']))
+            codebooks, codes = f['codebooks'], f['codes']
+        if codes.dtype != np.uint8 or codes.ndim != 2 or codes.shape[1] != index.M:
+            raise ValueError('%s: codes [N, M] uint8 expected' % path)
+        if codebooks.shape != (index.M, 256, index.dsub) or codebooks.dtype.kind != 'f':
+            raise ValueError('%s: codebooks [M, 256, D / M] float32 expected' % path)
+        index.codebooks = torch.from_numpy(np.ascontiguousarray(codebooks, dtype=np.float32)).cuda()
+        index.codes = torch.zeros(len(codes), (index.M + 3) // 4 * 4, dtype=torch.uint8, device='cuda')
+        index.codes[:, :index.M] = torch.from_numpy(codes).cuda()
         return index

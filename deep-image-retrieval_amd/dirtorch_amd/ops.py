@@ -664,6 +664,97 @@ def ivf_scan(qcodes, qscales, codes, scales, ids, list_off, probe, col_off, D, w
     return scores[:, :width], out_ids[:, :width]
 
 
+# ---- the product-quantised index (csrc/pq.hip) -------------------------------------------------------------------------
+def pq_max_m():
+    """The largest number of sub-spaces a product quantiser takes (dir_pq_max_m; host-only)."""
+    return int(_lib.load().dir_pq_max_m())
+
+
+def _pq_codebooks(codebooks, D=None):
+    """codebooks [M, 256, dsub] fp32 CUDA, contiguous -> (codebooks, M, D)"""
+    if not codebooks.is_cuda:
+        raise ValueError('device tensor expected')
+    if codebooks.dtype != torch.float32 or codebooks.dim() != 3 or codebooks.shape[1] != 256 or codebooks.shape[2] < 1:
+        raise TypeError('float32 codebooks [M, 256, dsub] expected')
+    M = int(codebooks.shape[0])
+    if M < 1 or M > pq_max_m():
+        raise ValueError('1 <= M <= %d expected, got %d' % (pq_max_m(), M))
+    if D is not None and int(D) != M * int(codebooks.shape[2]):
+        raise ValueError('rows of M * dsub = %d values expected, got %d' % (M * int(codebooks.shape[2]), D))
+    return codebooks.contiguous(), M, M * int(codebooks.shape[2])
+
+
+def pq_encode(X, codebooks):
+    """fp32 rows -> codes uint8 [N, ldc] CUDA (dir_pq_encode; include/dir_engine.h gives the definition): byte m of a row
+    is its nearest of the 256 centroids of sub-space m, ldc = M rounded up to a multiple of 4, the padding bytes zero.
+    X [N,D] fp32 CUDA with unit column stride and any row pitch; codebooks [M, 256, D / M] fp32 CUDA."""
+    if not X.is_cuda:
+        raise ValueError('device tensor expected')
+    if X.dtype != torch.float32 or X.dim() != 2:
+        raise TypeError('float32 rows [N,D] expected')
+    N, D = X.shape
+    codebooks, M, _ = _pq_codebooks(codebooks, D)
+    if D > index_i8_max_dim():
+        raise ValueError('D <= %d expected, got %d' % (index_i8_max_dim(), D))
+    X, ldx = _rows_pitch(X, D)
+    ldc = (M + 3) // 4 * 4
+    codes = torch.empty(N, ldc, dtype=torch.uint8, device=X.device)
+    if N:
+        call('dir_pq_encode', ptr(X), ldx, N, D, M, ptr(codebooks), ptr(codes), ldc, stream_ptr())
+    return codes
+
+
+def pq_lut(queries, codebooks):
+    """The tables of every query, lut [Q, M, 256] fp32 CUDA (dir_pq_lut): lut[q][m][j] = <sub-vector m of query q,
+    centroid j of sub-space m>, accumulated in fp32 in column order.  queries [Q,D] fp32 CUDA with unit column stride."""
+    if not queries.is_cuda:
+        raise ValueError('device tensor expected')
+    if queries.dtype != torch.float32 or queries.dim() != 2:
+        raise TypeError('float32 queries [Q,D] expected')
+    Q, D = queries.shape
+    codebooks, M, _ = _pq_codebooks(codebooks, D)
+    if D > index_i8_max_dim():
+        raise ValueError('D <= %d expected, got %d' % (index_i8_max_dim(), D))
+    queries, ldq = _rows_pitch(queries, D)
+    lut = torch.empty(Q, M, 256, dtype=torch.float32, device=queries.device)
+    if Q:
+        call('dir_pq_lut', ptr(queries), ldq, Q, D, M, ptr(codebooks), ptr(lut), stream_ptr())
+    return lut
+
+
+def pq_scan(lut, codes, out=None):
+    """scores [Q,N] fp32 CUDA (dir_pq_scan): scores[q][n] = the entries lut[q][m][codes[n][m]] added up in fp32 in the
+    order m = 0 .. M - 1, one defined number per pair.  lut [Q, M, 256] fp32 CUDA as pq_lut gives it; codes [N, >= M]
+    uint8 CUDA as pq_encode gives them (row slices included).  out: a [Q, >= N] fp32 CUDA tensor with unit column stride
+    to write into (its first N columns are returned; the others keep what they hold)."""
+    for t in (lut, codes) + ((out,) if out is not None else ()):
+        if not t.is_cuda:
+            raise ValueError('device tensor expected')
+    if lut.dtype != torch.float32 or lut.dim() != 3 or lut.shape[2] != 256:
+        raise TypeError('float32 lut [Q, M, 256] expected')
+    if codes.dtype != torch.uint8 or codes.dim() != 2:
+        raise TypeError('uint8 codes [N, ldc] expected')
+    Q, M = int(lut.shape[0]), int(lut.shape[1])
+    N = int(codes.shape[0])
+    if M < 1 or M > pq_max_m() or codes.shape[1] < M:
+        raise ValueError('codes of at least M bytes a row expected, 1 <= M <= %d' % pq_max_m())
+    lut = lut.contiguous()
+    codes, ldc = _rows_pitch(codes, M)
+    if ldc % 4 or codes.data_ptr() % 4:
+        padded = torch.zeros(N, (M + 3) // 4 * 4, dtype=torch.uint8, device=codes.device)
+        padded[:, :M] = codes[:, :M]
+        codes, ldc = padded, int(padded.shape[1])
+    if out is None:
+        out = torch.empty(Q, N, dtype=torch.float32, device=codes.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != Q or out.shape[1] < N or (
+            Q > 1 and (out.stride(1) != 1 or out.stride(0) < N)) or (Q <= 1 and not out.is_contiguous()):
+        raise ValueError('out: float32 [Q, >= N] with unit column stride expected')
+    lds = int(out.stride(0)) if Q > 1 else int(out.shape[1])
+    if Q and N:
+        call('dir_pq_scan', ptr(lut), Q, M, ptr(codes), ldc, N, ptr(out), lds, stream_ptr())
+    return out[:, :N]
+
+
 def expand_descriptors(descs, db=None, alpha=0.0, k=0, scratch_bytes=256 << 20):
     """alpha-QE / DBA on the device (dir_expand_descriptors): descs [n,D], db [m,D] fp32 CUDA (db None =
     expand the set against itself, a row never being its own neighbour) -> [n,D] fp32 CUDA."""

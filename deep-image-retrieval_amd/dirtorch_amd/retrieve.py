@@ -14,6 +14,8 @@ ranked by the quantised scores; --rerank R also re-scores the R best of every qu
 the --topk best of those, with their fp32 scores.
 --index ivf --nlist L --nprobe P: an index.IVFInt8Index trained on the database descriptors themselves (L k-means lists);
 every query scans its P best lists only, --rerank as above.  With P = L the lists are those of --index int8.
+--index pq --pq-m M: an index.PQIndex trained on the database descriptors themselves (M bytes per image, M dividing the
+descriptor width; at least 256 database images); the lists are ranked by the table scores, --rerank as above.
 """
 import sys
 
@@ -60,15 +62,18 @@ def main(argv=None):
         (('--whitenp',), dict(type=float, default=0.25, help='whitening power, default is 0.5 (i.e., the sqrt)')),
         (('--topk',), dict(type=int, default=20, help='neighbours per query')),
         (('--output',), dict(type=str, required=True, help='path of the list: .npz, or text')),
-        (('--index',), dict(type=str, default='', choices=['', 'int8', 'ivf'], help='scan a quantised copy of the database')),
+        (('--index',), dict(type=str, default='', choices=['', 'int8', 'ivf', 'pq'], help='scan a quantised copy of the database')),
         (('--nlist',), dict(type=int, default=0, help='with --index ivf: the number of k-means lists')),
         (('--nprobe',), dict(type=int, default=1, help='with --index ivf: lists scanned per query')),
+        (('--pq-m',), dict(type=int, default=0, help='with --index pq: bytes (sub-spaces) per database image')),
         (('--rerank',), dict(type=int, default=0, help='with --index: shortlist size re-scored in fp32 (0 = none)')),
     ]).parse_args(argv)
     if args.rerank and not args.index:
         raise SystemExit('--rerank needs --index')
     if args.index == 'ivf' and args.nlist < 1:
         raise SystemExit('--index ivf needs --nlist')
+    if args.index == 'pq' and args.pq_m < 1:
+        raise SystemExit('--index pq needs --pq-m')
     iscuda = test_dir.setup_devices(args.gpu)
     qe = {name: (None if val is None else {'k': val[0], 'alpha': val[1]})
           for name, val in (('aqe', args.aqe), ('adba', args.adba))}
@@ -85,6 +90,12 @@ def main(argv=None):
         idx, vals = IVFInt8Index(bdescs.shape[1], args.nlist).train(bdescs).add(bdescs).search(
             qdescs, args.topk, nprobe=args.nprobe, rerank=args.rerank, source=bdescs if args.rerank else None,
             same_set=same_set)
+    elif args.index == 'pq':
+        from .index import PQIndex
+        if bdescs.shape[1] % args.pq_m:
+            raise SystemExit('--pq-m %d does not divide the descriptor width %d' % (args.pq_m, bdescs.shape[1]))
+        idx, vals = PQIndex(bdescs.shape[1], args.pq_m).train(bdescs).add(bdescs).search(
+            qdescs, args.topk, rerank=args.rerank, source=bdescs if args.rerank else None, same_set=same_set)
     elif args.index:
         from .index import Int8Index
         idx, vals = Int8Index(bdescs.shape[1]).add(bdescs).search(

@@ -553,6 +553,42 @@ int dir_ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, 
                     const float* bscales, const int* ids, int N, int D, const int* list_off, int nlist, const int* pair_off,
                     const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
                     int lds, int width, void* stream);
+/* The product-quantised index (pq.hip; dirtorch_amd/index.py PQIndex; numpy restatement: tests/pq_ref.py).
+ * A row of D fp32 values is cut into M sub-vectors of dsub = D / M values (M divides D, 1 <= M <= dir_pq_max_m(), D <=
+ * dir_index_i8_max_dim()); sub-vector m is replaced by the number of one of the 256 centroids of sub-space m, so a row is
+ * M bytes.  codebooks [M][256][dsub] fp32, contiguous.  Every number below is a chain of single IEEE fp32 operations
+ * rounded to nearest (no fused multiply-add), in the stated order: it does not depend on tiling, chunking or the number
+ * of calls, and a numpy float32 restatement reproduces it bit for bit.
+ *   Encoding of row x, sub-space m:  dist_j = (((+0 + t_0 * t_0) + t_1 * t_1) + ...), t_d = x[m * dsub + d] - c[m][j][d],
+ *     d = 0 .. dsub - 1.  code_m = the result of  best = 0; for j = 1 .. 255: if dist_j < dist_best, or dist_best is a NaN
+ *     and dist_j is not: best = j  - the smallest distance, the smaller j among equal distances, a NaN distance never
+ *     chosen over a number; a row that holds a NaN has code 0 in the sub-spaces the NaN falls into.
+ *   Table of query q:  lut[q][m][j] = (((+0 + q_0 * c_0) + q_1 * c_1) + ...) over the dsub values of sub-space m.
+ *   Score:  score[q][n] = (((+0 + lut[q][0][code[n][0]]) + lut[q][1][code[n][1]]) + ...), m = 0 .. M - 1: the inner
+ *     product of the query with the row's centroids (asymmetric distance computation), one defined fp32 number per pair.
+ * dir_pq_max_m (host-only; 128): the largest M - one query's table, M KiB, has to fit the 160 KiB of LDS.
+ * dir_pq_encode: X [N][ldx] fp32 (ldx >= D, any pitch) -> codes [N][ldc] uint8, ldc >= M and ldc % 4 == 0.  Bytes M .. M
+ *   rounded up to a multiple of 4 of every row are written as zero; bytes past that are not touched.  One workgroup per
+ *   (sub-space, 256 rows): thread j holds centroid j's distances to 32 rows at a time, the arg-min is a minimum of
+ *   (distance bits, j) keys.  At most 2^31 - 1 workgroups: N * M / 256 rows of them.
+ * dir_pq_lut: queries [Q][ldq] fp32 (ldq >= D) -> lut [Q][M][256] fp32, contiguous.
+ * dir_pq_scan: lut [Q][M][256] (16-byte aligned), codes [N][ldc] uint8 (4-byte aligned, ldc >= M, ldc % 4 == 0; what the
+ *   bytes past M hold does not matter) -> scores [Q][lds] fp32, lds >= N; columns at or past N are not touched.  A
+ *   workgroup of 1024 threads keeps the codes of a tile of 2048 rows (1024 for M > 64) in registers and walks the
+ *   queries two at a time, their tables interleaved in LDS (64 sub-spaces at a time for M > 64).
+ * All three: a negative count, D < 1 or above the max dim, M outside 1 .. dir_pq_max_m(), M not dividing D, a pitch below
+ *   its minimum, ldc % 4 != 0, a misaligned lut / codes or a null pointer fail with DIR_ERR_INVALID before anything is
+ *   launched; Q == 0 or N == 0 is DIR_OK and launches nothing.
+ * Training (PQIndex.train): Lloyd iterations per sub-space.  The initial centroids are 256 rows of the training sample,
+ *   sub-space m taking columns m * dsub .. of them; an iteration encodes the sample (dir_pq_encode is the assignment), sums
+ *   the members of every centroid in fp32 (dir_segment_sums on the sub-space's columns, members in ascending row order)
+ *   and divides each sum by the member count (one fp32 division); a centroid without members keeps its value.
+ * Search: dir_topk of the scores, exactly as the flat int8 index ranks its own; with a re-rank of R the R best are
+ *   re-scored with dir_gather_scores against the fp32 rows and ranked again. */
+int dir_pq_max_m(void);
+int dir_pq_encode(const float* X, int ldx, int N, int D, int M, const float* codebooks, uint8_t* codes, int ldc, void* stream);
+int dir_pq_lut(const float* queries, int ldq, int Q, int D, int M, const float* codebooks, float* lut, void* stream);
+int dir_pq_scan(const float* lut, int Q, int M, const uint8_t* codes, int ldc, int N, float* scores, int lds, void* stream);
 /* N3: alpha query expansion / database augmentation, expand_descriptors of
  * dirtorch/test_dir.py:24-44.  out[i] = normalize(mean(descs[i], sim[i][j]^alpha * db[j] for the k
  * rows j of db most similar to descs[i])), sim = descs . db^T in fp32; self_set != 0 (db == descs,

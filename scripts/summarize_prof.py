@@ -197,6 +197,8 @@ def bench_kernel_name(k):
             # the inverted file: the sums of a k-means step, the id pre-fill and the scan of the probed lists (csrc/ivf.hip; no timed bench.py step launches them)
             'segment_sums_kernel': 'expand_rows_kernel', 'fill_ids_kernel': 'fill_noise_kernel',
             'ivf_scan_i8_kernel': 'sim_split_lc_kernel',
+            # the product-quantised index: encoder, query tables and the table scan (csrc/pq.hip; no timed bench.py step launches them)
+            'pq_encode_kernel': 'expand_rows_kernel', 'pq_lut_kernel': 'expand_rows_kernel', 'pq_scan_kernel': 'rank_hist_kernel',
             'maxpool_kernel': 'maxpool_3x3s2', 'upsample_add_kernel': 'upsample_add',
             'prep_input_f32_kernel': 'prep_input_f32', 'maxpool_f32_kernel': 'maxpool_f32',
             'global_pool_f32_kernel': 'global_pool_f32', 'upsample_add_f32_kernel': 'upsample_add_f32',
