@@ -957,6 +957,39 @@ int dir_pq_scan(const float* lut, int Q, int M, const uint8_t* codes, int ldc, i
     DIR_CATCH
 }
 
+int dir_ivfpq_scan_cols(void) { return ivfpq_scan_cols(); }
+
+int dir_ivfpq_base(const float* queries, int ldq, int Q, const float* centroids, int ldc, int nlist, int D, int M,
+                   const int* probe, int nprobe, float* base, void* stream) {
+    DIR_TRY
+    if (Q < 0 || nlist < 0 || nprobe < 0) return fail(DIR_ERR_INVALID, "ivfpq_base: negative size");
+    DIR_CHECK(pq_check_dims("ivfpq_base", D, M));
+    if (ldq < D || ldc < D) return fail(DIR_ERR_INVALID, "ivfpq_base: ldq, ldc < D");
+    if (Q == 0 || nprobe == 0) return DIR_OK;
+    if (!queries || !probe || !base || (nlist > 0 && !centroids)) return fail(DIR_ERR_INVALID, "ivfpq_base: null pointer");
+    return ivfpq_base(queries, ldq, Q, centroids, ldc, nlist, D, M, probe, nprobe, base, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_ivfpq_scan(const float* lut, const float* base, int Q, int M, const uint8_t* codes, int ldc, const int* ids, int N,
+                   const int* list_off, int nlist, const int* probe, const int* col_off, int nprobe, float* scores,
+                   int* out_ids, int lds, int width, void* stream) {
+    DIR_TRY
+    if (Q < 0 || N < 0 || nlist < 0 || nprobe < 0 || width < 0) return fail(DIR_ERR_INVALID, "ivfpq_scan: negative size");
+    if (M < 1 || M > pq_max_m()) return fail(DIR_ERR_INVALID, "ivfpq_scan: M outside 1 .. dir_pq_max_m()");
+    if (ldc < M || ldc % 4 != 0) return fail(DIR_ERR_INVALID, "ivfpq_scan: ldc < M or ldc % 4 != 0");
+    if (lds < width) return fail(DIR_ERR_INVALID, "ivfpq_scan: lds < width");
+    if (Q == 0 || width == 0) return DIR_OK;
+    if (!lut || !scores || !out_ids) return fail(DIR_ERR_INVALID, "ivfpq_scan: null pointer");
+    if (nprobe > 0 && (!base || !probe || !col_off)) return fail(DIR_ERR_INVALID, "ivfpq_scan: null pointer");
+    if (nprobe > 0 && nlist > 0 && N > 0 && (!codes || !ids || !list_off)) return fail(DIR_ERR_INVALID, "ivfpq_scan: null pointer");
+    if ((((uintptr_t)lut) & 15) != 0 || (((uintptr_t)codes) & 3) != 0)
+        return fail(DIR_ERR_INVALID, "ivfpq_scan: a 16-byte aligned lut and 4-byte aligned codes expected");
+    return ivfpq_scan(lut, base, Q, M, codes, ldc, ids, N, list_off, nlist, probe, col_off, nprobe, scores, out_ids, lds, width,
+                      (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_expand_descriptors(const float* descs, int n, const float* db, int m, int D, int k, float alpha,
                            int self_set, float* out, float* sim, size_t sim_bytes, void* stream) {
     DIR_TRY

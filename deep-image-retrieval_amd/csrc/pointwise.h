@@ -76,6 +76,13 @@ int pq_max_m();
 int pq_encode(const float* X, int ldx, int N, int D, int M, const float* codebooks, uint8_t* codes, int ldc, hipStream_t stream);
 int pq_lut(const float* queries, int ldq, int Q, int D, int M, const float* codebooks, float* lut, hipStream_t stream);
 int pq_scan(const float* lut, int Q, int M, const uint8_t* codes, int ldc, int N, float* scores, int lds, hipStream_t stream);
+// the IVF-PQ index (ivfpq.hip): the coarse terms of the probed lists, the query-major scan of their residual codes
+int ivfpq_scan_cols();
+int ivfpq_base(const float* queries, int ldq, int Q, const float* centroids, int ldc, int nlist, int D, int M, const int* probe,
+               int nprobe, float* base, hipStream_t stream);
+int ivfpq_scan(const float* lut, const float* base, int Q, int M, const uint8_t* codes, int ldc, const int* ids, int N,
+               const int* list_off, int nlist, const int* probe, const int* col_off, int nprobe, float* scores, int* out_ids,
+               int lds, int width, hipStream_t stream);
 int expand_descriptors(const float* descs, int n, const float* db, int m, int D, int k, float alpha,
                        int self_set, float* out, float* sim, size_t sim_bytes, hipStream_t stream);
 // scratch (optional): fp32 workspace for the split-K partial sums of shapes with few output tiles; without one

@@ -138,6 +138,11 @@ SIGNATURES = {
     'dir_pq_encode': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     'dir_pq_lut': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'dir_pq_scan': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'dir_ivfpq_scan_cols': (c_int, []),
+    'dir_ivfpq_base': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                               c_void_p]),
+    'dir_ivfpq_scan': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                               c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'dir_expand_descriptors': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_int,
                                        c_void_p, c_void_p, c_size_t, c_void_p]),
     'dir_comm_init_all': (c_int, [c_int, POINTER(c_int), POINTER(c_void_p)]),

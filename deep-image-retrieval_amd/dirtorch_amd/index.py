@@ -32,6 +32,18 @@ each of M sub-spaces - and scores a query through M tables of 256 inner products
 
 Codes, tables and scores are chains of single fp32 operations in a fixed order (include/dir_engine.h): the lists are those
 of tests/pq_ref.py bit for bit and do not depend on scratch_bytes, db_rows or on how many add() calls built the database.
+
+IVF-PQ puts the two together: the inverted file's lists hold M-byte codes of the RESIDUAL of a row to the centroid of its
+list, and a query reads the codes of its probed lists only:
+
+    index = IVFPQIndex(D, nlist=1024, M=64)
+    index.train(bdescs)                                      # the inverted file's k-means, then PQ codebooks on the residuals
+    index.add(bdescs)                                        # assigned as IVFInt8Index does, residuals encoded, stored list-major
+    idx, vals = index.search(qdescs, 10, nprobe=8)
+    idx, vals = index.search(qdescs, 10, nprobe=8, rerank=40, source=bdescs)
+
+A row lands in the list IVFInt8Index puts it in; the score is the coarse term <q, centroid> plus the row's table entries,
+one chain of fp32 additions (include/dir_engine.h), and the lists are those of tests/ivfpq_ref.py bit for bit.
 """
 import numpy as np
 import torch
@@ -64,9 +76,43 @@ def _quantize_chunks(descs, D):
         yield ops.quantize_rows(_upload(descs[r0:r0 + rows]))
 
 
+def _training_rows(x, seed, max_rows, least, least_name):
+    """The training sample of a train() call as a contiguous fp32 CUDA tensor: the rows of x, or the sorted
+    np.random.RandomState(seed).choice sample of max_rows of them when x has more; at least `least` finite rows."""
+    n = int(x.shape[0])
+    if n < least or max_rows < least:
+        raise ValueError('at least %s training rows expected, got %d' % (least_name, min(n, max_rows)))
+    if n > max_rows:
+        pick = np.sort(np.random.RandomState(seed).choice(n, max_rows, replace=False))
+        x = x[torch.from_numpy(pick).to(x.device)] if torch.is_tensor(x) else x[pick]
+    x = _upload(x)
+    if not bool(torch.isfinite(x).all()):
+        raise ValueError('training data with a non-finite value')
+    return x
+
+
+def _lloyd_codebooks(x, M, iters, seed):
+    """PQIndex.train's iterations on the sample x [n, D] (fp32 CUDA, n >= 256) -> codebooks [M, 256, D / M]"""
+    n, dsub = int(x.shape[0]), int(x.shape[1]) // M
+    first = np.sort(np.random.RandomState(seed).choice(n, 256, replace=False))
+    codebooks = x[torch.from_numpy(first).cuda()].view(256, M, dsub).permute(1, 0, 2).contiguous()
+    bounds = torch.arange(257, device='cuda')
+    for _ in range(int(iters)):
+        codes = ops.pq_encode(x, codebooks)
+        for m in range(M):
+            col, order = torch.sort(codes[:, m].long(), stable=True)
+            seg_off = torch.searchsorted(col, bounds).to(torch.int32)
+            sums = ops.segment_sums(x[:, m * dsub:(m + 1) * dsub], order.to(torch.int32), seg_off)
+            count = (seg_off[1:] - seg_off[:-1])[:, None]
+            codebooks[m] = torch.where(count > 0, sums / count.to(torch.float32), codebooks[m])
+    return codebooks
+
+
 class _CodedIndex:
-    """What the flat and the inverted index share: codes [N, ldc] int8 (ldc = D rounded up to 64, padding zero) and scales
-    [N] fp32, both CUDA; the argument checks of search and the fp32 re-rank of a shortlist."""
+    """What every index shares: `codes` [N, ldc], one row per database row, CUDA - int8 with ldc = D rounded up to 64 (padding
+    zero) and `scales` [N] fp32 for the int8 indexes, which is what the constructor makes; uint8 with ldc = M rounded up to 4
+    and scales None for the product-quantised ones, which replace both - the argument checks of search, the blocked scan
+    loop and the fp32 re-rank of a shortlist."""
 
     def __init__(self, D):
         D = int(D)
@@ -222,14 +268,12 @@ class Int8Index(_CodedIndex):
         return index
 
 
-class IVFInt8Index(_CodedIndex):
-    """The inverted-file int8 index (include/dir_engine.h gives the definitions).  All CUDA: centroids [nlist, D] fp32 with
-    their codes `ccodes` and scales `cscales`; the database LIST-MAJOR - codes [N, ldc] int8, scales [N] fp32, ids [N] int32
-    (a row's number in add order: what Int8Index reports) - and list_off [nlist+1] int32, a CSR from 0 to N; inside a list
-    the rows are in ascending id."""
+class _InvertedLists:
+    """What the two inverted files share - the coarse quantiser and the list-major bookkeeping: centroids [nlist, D] fp32
+    with their codes `ccodes` and scales `cscales`, ids [N] int32, list_off [nlist+1] int32 and `_lens`, the host copy of
+    the list lengths; assignment, probing, the spherical Lloyd iterations and the regrouping of a store after an add."""
 
-    def __init__(self, D, nlist):
-        super().__init__(D)
+    def _init_lists(self, nlist):
         nlist = int(nlist)
         if nlist < 1 or nlist > 65535:
             raise ValueError('1 <= nlist <= 65535 expected, got %d' % nlist)
@@ -253,27 +297,9 @@ class IVFInt8Index(_CodedIndex):
             out[r0:r0 + rows] = ops.topk(scores, 1)[0][:, 0]
         return out
 
-    def train(self, x, iters=10, seed=0, max_rows=None):
-        """Spherical Lloyd iterations on the rows of x [n, D] (any kind add takes), or on a sorted
-        np.random.RandomState(seed).choice sample of max_rows of them (default 256 * nlist) when x has more.  The initial
-        centroids are the rows np.sort(RandomState(seed).choice(n, nlist, replace=False)) of the sample; an iteration
-        assigns every row to its list, sums each list's members in fp32 (ops.segment_sums) and L2-normalises the sums;
-        an empty list keeps its centroid.  Bitwise reproducible.  Rows already added are not re-assigned: train first."""
-        self._check_rows(x)
-        if len(self):
-            raise ValueError('train before add: the rows already stored were assigned to the old centroids')
-        n = int(x.shape[0])
-        max_rows = 256 * self.nlist if max_rows is None else int(max_rows)
-        if n < self.nlist or max_rows < self.nlist:
-            raise ValueError('at least nlist = %d training rows expected, got %d' % (self.nlist, min(n, max_rows)))
-        if n > max_rows:
-            pick = np.sort(np.random.RandomState(seed).choice(n, max_rows, replace=False))
-            x = x[torch.from_numpy(pick).to(x.device)] if torch.is_tensor(x) else x[pick]
-            n = max_rows
-        x = _upload(x)
-        if not bool(torch.isfinite(x).all()):
-            raise ValueError('training data with a non-finite value')
-        first = np.sort(np.random.RandomState(seed).choice(n, self.nlist, replace=False))
+    def _lloyd_centroids(self, x, iters, seed):
+        """IVFInt8Index.train's iterations on the sample x [n, D] (fp32 CUDA, n >= nlist); sets the centroids"""
+        first = np.sort(np.random.RandomState(seed).choice(int(x.shape[0]), self.nlist, replace=False))
         centroids = x[torch.from_numpy(first).cuda()].clone()
         codes, scales = ops.quantize_rows(x)
         bounds = torch.arange(self.nlist + 1, device='cuda')
@@ -286,6 +312,51 @@ class IVFInt8Index(_CodedIndex):
             empty = (seg_off[1:] == seg_off[:-1])[:, None]
             centroids = torch.where(empty, centroids, sums)
         self._set_centroids(centroids)
+
+    def _regroup(self, new_lists, stores):
+        """After n rows were appended: new_lists, their lists (int32 tensors, in add order); stores, the per-row tensors
+        with the new rows appended [N + n, ...].  A stable integer sort of the list indices, old rows first, so ids ascend
+        inside a list; sets ids, list_off and _lens (one read-back) and returns the regrouped stores."""
+        N = int(self.ids.numel())
+        n = sum(int(l.numel()) for l in new_lists)
+        old_lists = torch.searchsorted(self.list_off[1:].long(), torch.arange(N, device='cuda'), right=True)
+        lists, order = torch.sort(torch.cat([old_lists] + [l.long() for l in new_lists]), stable=True)
+        self.ids = torch.cat([self.ids, torch.arange(N, N + n, dtype=torch.int32, device='cuda')])[order]
+        self.list_off = torch.searchsorted(lists, torch.arange(self.nlist + 1, device='cuda')).to(torch.int32)
+        self._lens = np.diff(self.list_off.cpu().numpy().astype(np.int64))
+        return [s[order] for s in stores]
+
+    def probe(self, qc, qs, nprobe):
+        """the lists of every coded query [Q, nprobe] int32, best first"""
+        return ops.topk(ops.similarity_i8(qc, qs, self.ccodes, self.cscales, self.D), nprobe)[0]
+
+    def _slots(self, probe):
+        """col_off [Q, nprobe] int32: the probed lists of a query side by side, in probe order"""
+        lens = (self.list_off[1:] - self.list_off[:-1])[probe.long()]
+        return torch.cumsum(lens, dim=1, dtype=torch.int32) - lens
+
+
+class IVFInt8Index(_InvertedLists, _CodedIndex):
+    """The inverted-file int8 index (include/dir_engine.h gives the definitions).  All CUDA: centroids [nlist, D] fp32 with
+    their codes `ccodes` and scales `cscales`; the database LIST-MAJOR - codes [N, ldc] int8, scales [N] fp32, ids [N] int32
+    (a row's number in add order: what Int8Index reports) - and list_off [nlist+1] int32, a CSR from 0 to N; inside a list
+    the rows are in ascending id."""
+
+    def __init__(self, D, nlist):
+        _CodedIndex.__init__(self, D)
+        self._init_lists(nlist)
+
+    def train(self, x, iters=10, seed=0, max_rows=None):
+        """Spherical Lloyd iterations on the rows of x [n, D] (any kind add takes), or on a sorted
+        np.random.RandomState(seed).choice sample of max_rows of them (default 256 * nlist) when x has more.  The initial
+        centroids are the rows np.sort(RandomState(seed).choice(n, nlist, replace=False)) of the sample; an iteration
+        assigns every row to its list, sums each list's members in fp32 (ops.segment_sums) and L2-normalises the sums;
+        an empty list keeps its centroid.  Bitwise reproducible.  Rows already added are not re-assigned: train first."""
+        self._check_rows(x)
+        if len(self):
+            raise ValueError('train before add: the rows already stored were assigned to the old centroids')
+        max_rows = 256 * self.nlist if max_rows is None else int(max_rows)
+        self._lloyd_centroids(_training_rows(x, seed, max_rows, self.nlist, 'nlist = %d' % self.nlist), iters, seed)
         return self
 
     def add(self, descs):
@@ -297,23 +368,12 @@ class IVFInt8Index(_CodedIndex):
         self._check_rows(descs)
         if self.centroids is None:
             raise ValueError('add before train')
-        n, N = int(descs.shape[0]), len(self)
-        if n == 0:
+        if int(descs.shape[0]) == 0:
             return self
         new = [(c, s, self._assign(c, s)) for c, s in _quantize_chunks(descs, self.D)]
-        old_lists = torch.searchsorted(self.list_off[1:].long(), torch.arange(N, device='cuda'), right=True)
-        lists = torch.cat([old_lists] + [l.long() for _, _, l in new])
-        lists, order = torch.sort(lists, stable=True)
-        self.codes = torch.cat([self.codes] + [c for c, _, _ in new])[order]
-        self.scales = torch.cat([self.scales] + [s for _, s, _ in new])[order]
-        self.ids = torch.cat([self.ids, torch.arange(N, N + n, dtype=torch.int32, device='cuda')])[order]
-        self.list_off = torch.searchsorted(lists, torch.arange(self.nlist + 1, device='cuda')).to(torch.int32)
-        self._lens = np.diff(self.list_off.cpu().numpy().astype(np.int64))
+        self.codes, self.scales = self._regroup([l for _, _, l in new], [torch.cat([self.codes] + [c for c, _, _ in new]),
+                                                                         torch.cat([self.scales] + [s for _, s, _ in new])])
         return self
-
-    def probe(self, qc, qs, nprobe):
-        """the lists of every coded query [Q, nprobe] int32, best first"""
-        return ops.topk(ops.similarity_i8(qc, qs, self.ccodes, self.cscales, self.D), nprobe)[0]
 
     def search(self, qdescs, k, nprobe=1, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20):
         """Int8Index.search's contract over the rows of the nprobe best lists of every query (1 <= nprobe <= nlist): a
@@ -334,9 +394,7 @@ class IVFInt8Index(_CodedIndex):
         Q, keep = q.shape[0], R or k
         qc, qs = ops.quantize_rows(q)
         probe = self.probe(qc, qs, nprobe)
-        lens = (self.list_off[1:] - self.list_off[:-1])[probe.long()]
-        ends = torch.cumsum(lens, dim=1, dtype=torch.int32)
-        col_off = ends - lens
+        col_off = self._slots(probe)
         bound = max(int(np.sort(self._lens)[-nprobe:].sum()), keep)
         rows = int(max(1, min(Q, scratch_bytes // (8 * bound))))
         cand = torch.empty(Q, keep, dtype=torch.int32, device='cuda')
@@ -411,29 +469,8 @@ class PQIndex(_CodedIndex):
         self._check_rows(x)
         if len(self):
             raise ValueError('train before add: the rows already stored were encoded with the old codebooks')
-        n = int(x.shape[0])
         max_rows = 256 * 256 if max_rows is None else int(max_rows)
-        if n < 256 or max_rows < 256:
-            raise ValueError('at least 256 training rows expected, got %d' % min(n, max_rows))
-        if n > max_rows:
-            pick = np.sort(np.random.RandomState(seed).choice(n, max_rows, replace=False))
-            x = x[torch.from_numpy(pick).to(x.device)] if torch.is_tensor(x) else x[pick]
-            n = max_rows
-        x = _upload(x)
-        if not bool(torch.isfinite(x).all()):
-            raise ValueError('training data with a non-finite value')
-        first = np.sort(np.random.RandomState(seed).choice(n, 256, replace=False))
-        codebooks = x[torch.from_numpy(first).cuda()].view(256, self.M, self.dsub).permute(1, 0, 2).contiguous()
-        bounds = torch.arange(257, device='cuda')
-        for _ in range(int(iters)):
-            codes = ops.pq_encode(x, codebooks)
-            for m in range(self.M):
-                col, order = torch.sort(codes[:, m].long(), stable=True)
-                seg_off = torch.searchsorted(col, bounds).to(torch.int32)
-                sums = ops.segment_sums(x[:, m * self.dsub:(m + 1) * self.dsub], order.to(torch.int32), seg_off)
-                count = (seg_off[1:] - seg_off[:-1])[:, None]
-                codebooks[m] = torch.where(count > 0, sums / count.to(torch.float32), codebooks[m])
-        self.codebooks = codebooks
+        self.codebooks = _lloyd_codebooks(_training_rows(x, seed, max_rows, 256, '256'), self.M, iters, seed)
         return self
 
     def add(self, descs):
@@ -494,4 +531,132 @@ class PQIndex(_CodedIndex):
         index.codebooks = torch.from_numpy(np.ascontiguousarray(codebooks, dtype=np.float32)).cuda()
         index.codes = torch.zeros(len(codes), (index.M + 3) // 4 * 4, dtype=torch.uint8, device='cuda')
         index.codes[:, :index.M] = torch.from_numpy(codes).cuda()
+        return index
+
+
+class IVFPQIndex(_InvertedLists, _CodedIndex):
+    """The IVF-PQ index (include/dir_engine.h gives the definitions).  All CUDA: the coarse quantiser of IVFInt8Index
+    (centroids [nlist, D] fp32, `ccodes`, `cscales`), codebooks [M, 256, D / M] fp32 trained on residuals, and the database
+    LIST-MAJOR - codes [N, ldc] uint8 (ldc = M rounded up to a multiple of 4, the padding zero): the codes of the row's
+    residual to the fp32 centroid of its list; ids [N] int32; list_off [nlist+1] int32, a CSR from 0 to N; inside a list
+    the rows are in ascending id."""
+
+    def __init__(self, D, nlist, M):
+        _CodedIndex.__init__(self, D)
+        self._init_lists(nlist)
+        M = int(M)
+        if M < 1 or M > ops.pq_max_m() or self.D % M:
+            raise ValueError('1 <= M <= %d dividing D = %d expected, got %d' % (ops.pq_max_m(), self.D, M))
+        self.M, self.dsub = M, self.D // M
+        self.codebooks = None
+        self.codes = torch.empty(0, (M + 3) // 4 * 4, dtype=torch.uint8, device='cuda')
+        self.scales = None
+
+    def nbytes(self):
+        """the bytes the database rows take on the device: codes and ids (centroids and codebooks not counted)"""
+        return len(self) * (int(self.codes.shape[1]) + 4)
+
+    def _residuals(self, x, lists):
+        """x [n, D] fp32 CUDA minus the fp32 centroid of every row's list: one subtraction per element"""
+        return x - self.centroids[lists.long()]
+
+    def train(self, x, iters=10, seed=0, max_rows=None):
+        """Two steps on the rows of x [n, D] (any kind add takes), or on IVFInt8Index.train's sample of max_rows of them
+        (default 256 * nlist) when x has more; at least max(nlist, 256) rows.  1. the coarse centroids exactly as
+        IVFInt8Index.train finds them.  2. the codebooks exactly as PQIndex.train finds them (same seed, same iterations),
+        but on the residuals of that sample to the final centroids of the lists its rows are assigned to.  Bitwise
+        reproducible.  Rows already added are neither re-assigned nor re-encoded: train first."""
+        self._check_rows(x)
+        if len(self):
+            raise ValueError('train before add: the rows already stored were assigned and encoded with the old centroids')
+        max_rows = 256 * self.nlist if max_rows is None else int(max_rows)
+        least = max(self.nlist, 256)
+        x = _training_rows(x, seed, max_rows, least, 'max(nlist, 256) = %d' % least)
+        self._lloyd_centroids(x, iters, seed)
+        self.codebooks = _lloyd_codebooks(self._residuals(x, self._assign(*ops.quantize_rows(x))), self.M, iters, seed)
+        return self
+
+    def add(self, descs):
+        """Append the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap) in chunks of ADD_CHUNK_BYTES:
+        a chunk is quantised and assigned as IVFInt8Index.add does, its residuals are encoded (ops.pq_encode), and the
+        store is regrouped by that class's stable integer sort, so what the index holds does not depend on how the rows
+        were cut into calls."""
+        self._check_rows(descs)
+        if self.centroids is None or self.codebooks is None:
+            raise ValueError('add before train')
+        n = int(descs.shape[0])
+        if n == 0:
+            return self
+        rows = max(1, ADD_CHUNK_BYTES // (4 * self.D))
+        new = []
+        for r0 in range(0, n, rows):
+            x = _upload(descs[r0:r0 + rows])
+            lists = self._assign(*ops.quantize_rows(x))
+            new.append((ops.pq_encode(self._residuals(x, lists), self.codebooks), lists))
+        self.codes, = self._regroup([l for _, l in new], [torch.cat([self.codes] + [c for c, _ in new])])
+        return self
+
+    def search(self, qdescs, k, nprobe=1, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20):
+        """IVFInt8Index.search's contract over the rows of the nprobe best lists of every query (1 <= nprobe <= nlist), with
+        the score  <q, centroid of the list> + the row's table entries  in place of the quantised one; a query whose lists
+        hold fewer than k rows ends in (-1, NaN).  The queries go in chunks whose score and id rows (8 bytes per column;
+        the nprobe longest lists give the width) and tables (1024 * M bytes per query) fit scratch_bytes.  The width comes
+        from the host's copy of the list lengths: a search does not synchronise with the host."""
+        from .utils.common import _dev
+        if self.centroids is None or self.codebooks is None:
+            raise ValueError('search before train')
+        nprobe = int(nprobe)
+        if nprobe < 1 or nprobe > self.nlist:
+            raise ValueError('1 <= nprobe <= nlist = %d expected, got %d' % (self.nlist, nprobe))
+        q = _dev(qdescs)
+        k, R = int(k), int(rerank)
+        empty = self._check_search(q, k, R, source, same_set)
+        if empty is not None:
+            return empty
+        Q, keep = q.shape[0], R or k
+        probe = self.probe(*ops.quantize_rows(q), nprobe)
+        col_off = self._slots(probe)
+        width = max(int(np.sort(self._lens)[-nprobe:].sum()), keep)
+        rows = int(max(1, min(Q, scratch_bytes // (8 * width + 1024 * self.M))))
+        cand = torch.empty(Q, keep, dtype=torch.int32, device='cuda')
+        vals = torch.empty(Q, keep, dtype=torch.float32, device='cuda')
+        for r0 in range(0, Q, rows):
+            r1 = min(Q, r0 + rows)
+            lut = ops.pq_lut(q[r0:r1], self.codebooks)
+            base = ops.ivfpq_base(q[r0:r1], self.centroids, probe[r0:r1], self.M)
+            scores, ids = ops.ivfpq_scan(lut, base, self.codes, self.ids, self.list_off, probe[r0:r1], col_off[r0:r1],
+                                         width=width)
+            own = torch.arange(r0, r1, dtype=torch.int32, device='cuda') if same_set else None
+            cand[r0:r1], vals[r0:r1] = ops.topk(scores, keep, ids=ids, exclude=own)
+        return self._rerank(q, cand, vals, k, R, source, scratch_bytes)
+
+    def save(self, path):
+        """One .npz: `centroids` [nlist, D] float32, `codebooks` [M, 256, D / M] float32, `codes` [N, M] uint8 (without the
+        padding), `ids` [N] int32, `list_off` [nlist+1] int32, `D`, `nlist`, `M`."""
+        if self.centroids is None or self.codebooks is None:
+            raise ValueError('save before train')
+        np.savez(path, centroids=self.centroids.cpu().numpy(), codebooks=self.codebooks.cpu().numpy(),
+                 codes=self.codes[:, :self.M].cpu().numpy(), ids=self.ids.cpu().numpy(), list_off=self.list_off.cpu().numpy(),
+                 D=np.int64(self.D), nlist=np.int64(self.nlist), M=np.int64(self.M))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as f:
+            index = cls(int(f['D']), int(f['nlist']), int(f['M']))
+            centroids, codebooks, codes, ids, list_off = (f[name] for name in ('centroids', 'codebooks', 'codes', 'ids', 'list_off'))
+        N = len(codes)
+        if codes.dtype != np.uint8 or codes.ndim != 2 or codes.shape[1] != index.M or ids.shape != (N,):
+            raise ValueError('%s: codes [N, M] uint8 and ids [N] expected' % path)
+        if codebooks.shape != (index.M, 256, index.dsub) or codebooks.dtype.kind != 'f':
+            raise ValueError('%s: codebooks [M, 256, D / M] float32 expected' % path)
+        if centroids.shape != (index.nlist, index.D) or list_off.shape != (index.nlist + 1,) or list_off[0] != 0 or (
+                list_off[-1] != N or (np.diff(list_off.astype(np.int64)) < 0).any()):
+            raise ValueError('%s: centroids [nlist, D] and a list_off [nlist+1] from 0 to N expected' % path)
+        index._set_centroids(torch.from_numpy(centroids.astype(np.float32)).cuda())
+        index.codebooks = torch.from_numpy(np.ascontiguousarray(codebooks, dtype=np.float32)).cuda()
+        index.codes = torch.zeros(N, (index.M + 3) // 4 * 4, dtype=torch.uint8, device='cuda')
+        index.codes[:, :index.M] = torch.from_numpy(codes).cuda()
+        index.ids = torch.from_numpy(ids.astype(np.int32)).cuda()
+        index.list_off = torch.from_numpy(list_off.astype(np.int32)).cuda()
+        index._lens = np.diff(list_off.astype(np.int64))
         return index

@@ -755,6 +755,112 @@ def pq_scan(lut, codes, out=None):
     return out[:, :N]
 
 
+# ---- the IVF-PQ index (csrc/ivfpq.hip) ----------------------------------------------------------------------------------
+def ivfpq_scan_cols():
+    """The output columns a workgroup of the IVF-PQ scan owns (dir_ivfpq_scan_cols; host-only)."""
+    return int(_lib.load().dir_ivfpq_scan_cols())
+
+
+def ivfpq_base(queries, centroids, probe, M):
+    """The coarse term of every probed list, base [Q,nprobe] fp32 CUDA (dir_ivfpq_base): base[q][p] = <q, centroids[probe
+    [q][p]]> as M partial sums - the chain over the D / M columns of sub-space m, in column order - added in the order
+    m = 0 .. M - 1 (include/dir_engine.h); NaN for a slot of -1.  queries [Q,D] and centroids [nlist,D] fp32 CUDA with unit
+    column stride and any row pitch; probe [Q,nprobe] int32 CUDA with entries in [-1, nlist)."""
+    for t in (queries, centroids, probe):
+        if not t.is_cuda:
+            raise ValueError('device tensor expected')
+    if queries.dtype != torch.float32 or centroids.dtype != torch.float32 or queries.dim() != 2 or centroids.dim() != 2:
+        raise TypeError('float32 queries [Q,D] and centroids [nlist,D] expected')
+    if probe.dtype != torch.int32:
+        raise TypeError('int32 probe expected')
+    Q, D = queries.shape
+    M = int(M)
+    if centroids.shape[1] != D or D < 1 or D > index_i8_max_dim():
+        raise ValueError('queries and centroids of one width D expected, 1 <= D <= %d' % index_i8_max_dim())
+    if M < 1 or M > pq_max_m() or D % M:
+        raise ValueError('1 <= M <= %d dividing D = %d expected, got %d' % (pq_max_m(), D, M))
+    if probe.dim() != 2 or probe.shape[0] != Q:
+        raise ValueError('probe [Q,nprobe] expected')
+    nlist, nprobe = int(centroids.shape[0]), int(probe.shape[1])
+    queries, ldq = _rows_pitch(queries, D)
+    centroids, ldc = _rows_pitch(centroids, D)
+    probe = probe.contiguous()
+    base = torch.empty(Q, nprobe, dtype=torch.float32, device=queries.device)
+    if Q and nprobe:
+        call('dir_ivfpq_base', ptr(queries), ldq, Q, ptr(centroids), ldc, nlist, D, M, ptr(probe), nprobe, ptr(base),
+             stream_ptr())
+    return base
+
+
+def ivfpq_scan(lut, base, codes, ids, list_off, probe, col_off, width=None, out=None):
+    """The scores of every query against the rows of the lists it probes (dir_ivfpq_scan) -> (scores [Q,width] fp32,
+    out_ids [Q,width] int32), both CUDA.  lut [Q, M, 256] fp32 as pq_lut gives it; base [Q,nprobe] fp32 as ivfpq_base gives
+    it; codes [N, >= M] uint8, ids [N] int32, list_off [nlist+1] int32: a list-major database (index.IVFPQIndex); probe
+    [Q,nprobe] int32: the lists of every query, -1 = an empty slot; col_off [Q,nprobe] int32: the first output column of
+    every slot.  For r < len(list probe[q][p]), column col_off[q][p] + r carries (((base[q][p] + lut[q][0][code[n][0]]) +
+    lut[q][1][code[n][1]]) + ...) and the id of row n = list_off[probe[q][p]] + r; a column no slot covers carries id -1.
+    The tables are the caller's duty, as ids in ops.topk: lists in [-1, nlist), slots of a query that do not overlap; a
+    slot stores nothing at or past width.  width None: the largest col_off + list length of the call, which is read back
+    from the device (the one host synchronisation; a caller that knows its width passes it and has none).
+    out: (scores, out_ids) [Q, >= width] with unit column stride and ONE row pitch to write into; columns at or past
+    width keep what they hold."""
+    tensors = (lut, base, codes, ids, list_off, probe, col_off) + (tuple(out) if out is not None else ())
+    for t in tensors:
+        if not t.is_cuda:
+            raise ValueError('device tensor expected')
+    if lut.dtype != torch.float32 or lut.dim() != 3 or lut.shape[2] != 256:
+        raise TypeError('float32 lut [Q, M, 256] expected')
+    if codes.dtype != torch.uint8 or codes.dim() != 2:
+        raise TypeError('uint8 codes [N, ldc] expected')
+    if base.dtype != torch.float32:
+        raise TypeError('float32 base expected')
+    if any(t.dtype != torch.int32 for t in (ids, list_off, probe, col_off)):
+        raise TypeError('int32 ids, list_off, probe and col_off expected')
+    Q, M = int(lut.shape[0]), int(lut.shape[1])
+    N = int(codes.shape[0])
+    if M < 1 or M > pq_max_m() or codes.shape[1] < M:
+        raise ValueError('codes of at least M bytes a row expected, 1 <= M <= %d' % pq_max_m())
+    if ids.dim() != 1 or ids.numel() != N:
+        raise ValueError('ids [N] expected for codes of N rows')
+    if list_off.dim() != 1 or list_off.numel() < 2:
+        raise ValueError('list_off [nlist+1] expected')
+    nlist = int(list_off.numel()) - 1
+    if probe.dim() != 2 or probe.shape[0] != Q or tuple(col_off.shape) != tuple(probe.shape) or tuple(base.shape) != tuple(probe.shape):
+        raise ValueError('probe, col_off and base [Q,nprobe] expected')
+    nprobe = int(probe.shape[1])
+    lut = lut.contiguous()
+    codes, ldc = _rows_pitch(codes, M)
+    if ldc % 4 or codes.data_ptr() % 4:
+        padded = torch.zeros(N, (M + 3) // 4 * 4, dtype=torch.uint8, device=codes.device)
+        padded[:, :M] = codes[:, :M]
+        codes, ldc = padded, int(padded.shape[1])
+    base, ids, list_off, probe, col_off = (t.contiguous() for t in (base, ids, list_off, probe, col_off))
+    if width is None:
+        lens = (list_off[1:] - list_off[:-1]).long()
+        ends = col_off.long() + torch.where(probe >= 0, lens[probe.long().clamp(min=0)], lens.new_zeros(()))
+        width = int(ends.max()) if ends.numel() else 0
+    width = max(int(width), 0)
+    if out is None:
+        scores = torch.empty(Q, width, dtype=torch.float32, device=codes.device)
+        out_ids = torch.empty(Q, width, dtype=torch.int32, device=codes.device)
+        lds = width
+    else:
+        scores, out_ids = out
+        if scores.dtype != torch.float32 or out_ids.dtype != torch.int32:
+            raise TypeError('out: float32 scores and int32 ids expected')
+        for t in (scores, out_ids):
+            if t.dim() != 2 or t.shape[0] != Q or t.shape[1] < width or (Q > 1 and (t.stride(1) != 1 or t.stride(0) < width)) or (
+                    Q <= 1 and not t.is_contiguous()):
+                raise ValueError('out: [Q, >= width] tensors with unit column stride expected')
+        if Q > 1 and scores.stride(0) != out_ids.stride(0) or (Q <= 1 and scores.shape[1] != out_ids.shape[1]):
+            raise ValueError('out: scores and ids of one row pitch expected')
+        lds = int(scores.stride(0)) if Q > 1 else int(scores.shape[1])
+    if Q and width:
+        call('dir_ivfpq_scan', ptr(lut), ptr(base), Q, M, ptr(codes), ldc, ptr(ids), N, ptr(list_off), nlist, ptr(probe),
+             ptr(col_off), nprobe, ptr(scores), ptr(out_ids), lds, width, stream_ptr())
+    return scores[:, :width], out_ids[:, :width]
+
+
 def expand_descriptors(descs, db=None, alpha=0.0, k=0, scratch_bytes=256 << 20):
     """alpha-QE / DBA on the device (dir_expand_descriptors): descs [n,D], db [m,D] fp32 CUDA (db None =
     expand the set against itself, a row never being its own neighbour) -> [n,D] fp32 CUDA."""

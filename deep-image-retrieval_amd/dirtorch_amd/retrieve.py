@@ -16,6 +16,9 @@ the --topk best of those, with their fp32 scores.
 every query scans its P best lists only, --rerank as above.  With P = L the lists are those of --index int8.
 --index pq --pq-m M: an index.PQIndex trained on the database descriptors themselves (M bytes per image, M dividing the
 descriptor width; at least 256 database images); the lists are ranked by the table scores, --rerank as above.
+--index ivfpq --nlist L --nprobe P --pq-m M: an index.IVFPQIndex trained on the database descriptors themselves (L k-means
+lists holding M-byte codes of the residuals; at least max(L, 256) database images); every query scans its P best lists
+only, --rerank as above.
 """
 import sys
 
@@ -62,18 +65,18 @@ def main(argv=None):
         (('--whitenp',), dict(type=float, default=0.25, help='whitening power, default is 0.5 (i.e., the sqrt)')),
         (('--topk',), dict(type=int, default=20, help='neighbours per query')),
         (('--output',), dict(type=str, required=True, help='path of the list: .npz, or text')),
-        (('--index',), dict(type=str, default='', choices=['', 'int8', 'ivf', 'pq'], help='scan a quantised copy of the database')),
-        (('--nlist',), dict(type=int, default=0, help='with --index ivf: the number of k-means lists')),
-        (('--nprobe',), dict(type=int, default=1, help='with --index ivf: lists scanned per query')),
-        (('--pq-m',), dict(type=int, default=0, help='with --index pq: bytes (sub-spaces) per database image')),
+        (('--index',), dict(type=str, default='', choices=['', 'int8', 'ivf', 'pq', 'ivfpq'], help='scan a quantised copy of the database')),
+        (('--nlist',), dict(type=int, default=0, help='with --index ivf / ivfpq: the number of k-means lists')),
+        (('--nprobe',), dict(type=int, default=1, help='with --index ivf / ivfpq: lists scanned per query')),
+        (('--pq-m',), dict(type=int, default=0, help='with --index pq / ivfpq: bytes (sub-spaces) per database image')),
         (('--rerank',), dict(type=int, default=0, help='with --index: shortlist size re-scored in fp32 (0 = none)')),
     ]).parse_args(argv)
     if args.rerank and not args.index:
         raise SystemExit('--rerank needs --index')
-    if args.index == 'ivf' and args.nlist < 1:
-        raise SystemExit('--index ivf needs --nlist')
-    if args.index == 'pq' and args.pq_m < 1:
-        raise SystemExit('--index pq needs --pq-m')
+    if args.index in ('ivf', 'ivfpq') and args.nlist < 1:
+        raise SystemExit('--index %s needs --nlist' % args.index)
+    if args.index in ('pq', 'ivfpq') and args.pq_m < 1:
+        raise SystemExit('--index %s needs --pq-m' % args.index)
     iscuda = test_dir.setup_devices(args.gpu)
     qe = {name: (None if val is None else {'k': val[0], 'alpha': val[1]})
           for name, val in (('aqe', args.aqe), ('adba', args.adba))}
@@ -96,6 +99,13 @@ def main(argv=None):
             raise SystemExit('--pq-m %d does not divide the descriptor width %d' % (args.pq_m, bdescs.shape[1]))
         idx, vals = PQIndex(bdescs.shape[1], args.pq_m).train(bdescs).add(bdescs).search(
             qdescs, args.topk, rerank=args.rerank, source=bdescs if args.rerank else None, same_set=same_set)
+    elif args.index == 'ivfpq':
+        from .index import IVFPQIndex
+        if bdescs.shape[1] % args.pq_m:
+            raise SystemExit('--pq-m %d does not divide the descriptor width %d' % (args.pq_m, bdescs.shape[1]))
+        idx, vals = IVFPQIndex(bdescs.shape[1], args.nlist, args.pq_m).train(bdescs).add(bdescs).search(
+            qdescs, args.topk, nprobe=args.nprobe, rerank=args.rerank, source=bdescs if args.rerank else None,
+            same_set=same_set)
     elif args.index:
         from .index import Int8Index
         idx, vals = Int8Index(bdescs.shape[1]).add(bdescs).search(

@@ -589,6 +589,55 @@ int dir_pq_max_m(void);
 int dir_pq_encode(const float* X, int ldx, int N, int D, int M, const float* codebooks, uint8_t* codes, int ldc, void* stream);
 int dir_pq_lut(const float* queries, int ldq, int Q, int D, int M, const float* codebooks, float* lut, void* stream);
 int dir_pq_scan(const float* lut, int Q, int M, const uint8_t* codes, int ldc, int N, float* scores, int lds, void* stream);
+/* The IVF-PQ index (ivfpq.hip; dirtorch_amd/index.py IVFPQIndex; numpy restatement: tests/ivfpq_ref.py): the inverted file
+ * above with M-byte product-quantiser codes of RESIDUALS in its lists.  The house rule holds: every number is a chain of
+ * single IEEE fp32 operations in the stated order (no fused multiply-add).  An index of width D, nlist lists and M
+ * sub-spaces (M divides D, 1 <= M <= dir_pq_max_m(), dsub = D / M) holds
+ *     the coarse quantiser of the inverted int8 index, unchanged: centroids [nlist][D] fp32 with their int8 codes and
+ *       scales.  ASSIGNMENT and PROBING are the rules written there (dir_topk of dir_similarity_i8 against the quantised
+ *       centroids): a row lands in the same list in both indexes,
+ *     codebooks [M][256][dsub] fp32,
+ *     the database LIST-MAJOR: codes [N][ldc] uint8 (ldc = M rounded up to 4, the padding zero), ids [N] int32, list_off
+ *       [nlist + 1] int32; rows ascend in id inside a list, and the store does not depend on how the rows were cut into
+ *       add calls.
+ *   Residual of row x in list l:  r_d = x_d - centroids[l][d], one fp32 subtraction per element against the fp32 centroid
+ *     (not its dequantised code).  The codes of the row are dir_pq_encode of r.
+ *   Coarse term of query q and list l:  s_m = (((+0 + q_{m,0} c_{m,0}) + q_{m,1} c_{m,1}) + ...) over the dsub columns of
+ *     sub-space m of centroids[l], in column order;  base[q][l] = (((+0 + s_0) + s_1) + ... + s_{M-1}).
+ *   Score of q against row n of a probed list l:  (((base[q][l] + lut[q][0][code[n][0]]) + lut[q][1][code[n][1]]) + ...),
+ *     m ascending, lut = dir_pq_lut(q, codebooks): for inner products the table does not depend on the list, and the
+ *     chain starts at the coarse term instead of +0.
+ *   Search: the candidates of q are the rows of its nprobe probed lists, the result dir_topk of their scores with the rows'
+ *     ids as ids (exclude for a query set that is the database); a row that runs short ends in (-1, NaN).  With a re-rank of
+ *     R the R best are re-scored with dir_gather_scores against the fp32 rows addressed by id and ranked again.
+ *   Training: 1. the coarse centroids exactly as the inverted int8 index trains them (same sample, same start rows, same
+ *     iterations); 2. the codebooks exactly as the product-quantised index trains them, on the residuals of that same
+ *     sample to the final centroids of the lists its rows are assigned to.  Bitwise reproducible from call to call.
+ *
+ * dir_ivfpq_scan_cols (host-only; 1024): the output columns a workgroup of the scan owns.
+ * dir_ivfpq_base: queries [Q][ldq] fp32 (ldq >= D), centroids [nlist][ldc] fp32 (ldc >= D), probe [Q][nprobe] int32 ->
+ *   base [Q][nprobe] fp32, contiguous: the coarse term of every slot; a slot outside [0, nlist) (-1 = empty) stores a NaN.
+ *   One workgroup per slot, one thread per sub-space chain, then the M partial sums added in order.
+ * dir_ivfpq_scan: lut [Q][M][256] (16-byte aligned), base, probe, col_off [Q][nprobe] (contiguous), codes [N][ldc] uint8
+ *   (4-byte aligned, ldc >= M, ldc % 4 == 0; what the bytes past M hold does not matter), ids [N], list_off [nlist + 1] ->
+ *   scores [Q][lds] fp32 and out_ids [Q][lds] int32 over `width` columns, with dir_ivf_scan_i8's output contract: for every
+ *   slot p of query q with l = probe[q][p] >= 0 and r < len_l, column col_off[q][p] + r carries the score of row list_off[l]
+ *   + r and ids[list_off[l] + r]; a column of [0, width) that no slot covers carries id -1 (its score is unspecified);
+ *   columns at or past `width` are not touched, and a slot stores nothing there.  The slots of one query must not overlap;
+ *   a list outside [0, nlist) is an empty slot, and rows at or past N are not read.  Cut QUERY-major - the expensive operand
+ *   is the query's table, M KiB of LDS, not the M-byte rows: a workgroup of 1024 threads owns one query and 1024 consecutive
+ *   output columns, stages the table once, finds the slot of each column from the col_off row and adds the entries of the
+ *   row's codes (held in registers) in the order m = 0 .. M - 1 starting from base.  No inverted probe table, no sort, no
+ *   fill kernel and no host synchronisation: the grid is Q * ceil(width / 1024).
+ * Both: a negative count, a bad D or M (as dir_pq_lut), a pitch below its minimum, ldc % 4 != 0, lds < width, a misaligned
+ *   lut / codes or a null pointer fail with DIR_ERR_INVALID before anything is launched; Q == 0, nprobe == 0 (base) or
+ *   width == 0 (scan) is DIR_OK and launches nothing. */
+int dir_ivfpq_scan_cols(void);
+int dir_ivfpq_base(const float* queries, int ldq, int Q, const float* centroids, int ldc, int nlist, int D, int M,
+                   const int* probe, int nprobe, float* base, void* stream);
+int dir_ivfpq_scan(const float* lut, const float* base, int Q, int M, const uint8_t* codes, int ldc, const int* ids, int N,
+                   const int* list_off, int nlist, const int* probe, const int* col_off, int nprobe, float* scores,
+                   int* out_ids, int lds, int width, void* stream);
 /* N3: alpha query expansion / database augmentation, expand_descriptors of
  * dirtorch/test_dir.py:24-44.  out[i] = normalize(mean(descs[i], sim[i][j]^alpha * db[j] for the k
  * rows j of db most similar to descs[i])), sim = descs . db^T in fp32; self_set != 0 (db == descs,
