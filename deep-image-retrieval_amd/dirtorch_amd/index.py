@@ -49,12 +49,13 @@ import numpy as np
 import torch
 
 from . import ops
+from .utils.common import _dev
 
 ADD_CHUNK_BYTES = 256 << 20     # fp32 bytes of a database that are on the device at a time while it is quantised
 
 
-def _pad64(D):
-    return (D + 63) // 64 * 64
+def _round_up(n, to):
+    return (n + to - 1) // to * to
 
 
 def _is_host(x):
@@ -68,12 +69,26 @@ def _upload(x):
     return x.to(device='cuda', dtype=torch.float32).contiguous()
 
 
-def _quantize_chunks(descs, D):
-    """(codes, scales) of the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap), one chunk of
-    ADD_CHUNK_BYTES at a time, so a database that lives in a host file is never resident on the device as fp32."""
+def _row_chunks(descs, D):
+    """The rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap) as contiguous fp32 CUDA tensors, one chunk
+    of ADD_CHUNK_BYTES at a time, so a database that lives in a host file is never resident on the device as fp32."""
     rows = max(1, ADD_CHUNK_BYTES // (4 * D))
     for r0 in range(0, int(descs.shape[0]), rows):
-        yield ops.quantize_rows(_upload(descs[r0:r0 + rows]))
+        yield _upload(descs[r0:r0 + rows])
+
+
+def _appended(stores, descs, D, encode):
+    """The flat stores [N, ...] of an index, each grown by the rows of descs [n, D]: copied once, then filled chunk by
+    chunk with encode(x) -> one tensor per store for the rows of the chunk x."""
+    n, r0 = int(descs.shape[0]), len(stores[0])
+    out = [torch.empty((r0 + n,) + tuple(s.shape[1:]), dtype=s.dtype, device='cuda') for s in stores]
+    for o, s in zip(out, stores):
+        o[:r0] = s
+    for x in _row_chunks(descs, D):
+        for o, part in zip(out, encode(x)):
+            o[r0:r0 + len(x)] = part
+        r0 += len(x)
+    return out
 
 
 def _training_rows(x, seed, max_rows, least, least_name):
@@ -91,46 +106,71 @@ def _training_rows(x, seed, max_rows, least, least_name):
     return x
 
 
-def _lloyd_codebooks(x, M, iters, seed):
-    """PQIndex.train's iterations on the sample x [n, D] (fp32 CUDA, n >= 256) -> codebooks [M, 256, D / M]"""
-    n, dsub = int(x.shape[0]), int(x.shape[1]) // M
-    first = np.sort(np.random.RandomState(seed).choice(n, 256, replace=False))
-    codebooks = x[torch.from_numpy(first).cuda()].view(256, M, dsub).permute(1, 0, 2).contiguous()
-    bounds = torch.arange(257, device='cuda')
-    for _ in range(int(iters)):
-        codes = ops.pq_encode(x, codebooks)
-        for m in range(M):
-            col, order = torch.sort(codes[:, m].long(), stable=True)
-            seg_off = torch.searchsorted(col, bounds).to(torch.int32)
-            sums = ops.segment_sums(x[:, m * dsub:(m + 1) * dsub], order.to(torch.int32), seg_off)
-            count = (seg_off[1:] - seg_off[:-1])[:, None]
-            codebooks[m] = torch.where(count > 0, sums / count.to(torch.float32), codebooks[m])
-    return codebooks
+def _segment_sums(x, assign, bounds):
+    """The step the two Lloyd loops share.  assign [n]: the segment of every row of x [n, d]; bounds: arange(S + 1) on the
+    device.  -> (seg_off [S+1] int32, sums [S, d] fp32): a stable sort of the assignment, so a segment adds its rows up in
+    ascending row order (ops.segment_sums); an empty segment has seg_off[s] == seg_off[s+1] and sums to zero."""
+    key, order = torch.sort(assign.long(), stable=True)
+    seg_off = torch.searchsorted(key, bounds).to(torch.int32)
+    return seg_off, ops.segment_sums(x, order.to(torch.int32), seg_off)
+
+
+def _read_npz(path):
+    with np.load(path) as f:
+        return {name: f[name] for name in f.files}
+
+
+def _padded_codes(path, codes, width, dtype, pitch):
+    """a saved code matrix [N, width] -> the device store [N, width rounded up to pitch], the padding zero"""
+    if codes.dtype != dtype or codes.ndim != 2 or codes.shape[1] != width:
+        raise ValueError('%s: codes [N, %d] %s expected' % (path, width, np.dtype(dtype).name))
+    codes = torch.from_numpy(codes).cuda()
+    store = torch.zeros(len(codes), _round_up(width, pitch), dtype=codes.dtype, device='cuda')
+    store[:, :width] = codes
+    return store
 
 
 class _CodedIndex:
     """What every index shares: `codes` [N, ldc], one row per database row, CUDA - int8 with ldc = D rounded up to 64 (padding
-    zero) and `scales` [N] fp32 for the int8 indexes, which is what the constructor makes; uint8 with ldc = M rounded up to 4
-    and scales None for the product-quantised ones, which replace both - the argument checks of search, the blocked scan
-    loop and the fp32 re-rank of a shortlist."""
+    zero) and `scales` [N] fp32 for the int8 indexes, which is what the constructor makes, with their half of save and load;
+    uint8 with ldc = M rounded up to 4 and scales None for the product-quantised ones, which replace both - what a search
+    does around its scan (the argument checks, the fp32 re-rank of a shortlist) and the blocked scan loop."""
 
     def __init__(self, D):
         D = int(D)
         if D < 1 or D > ops.index_i8_max_dim():
             raise ValueError('1 <= D <= %d expected, got %d' % (ops.index_i8_max_dim(), D))
         self.D = D
-        self.codes = torch.empty(0, _pad64(D), dtype=torch.int8, device='cuda')
+        self.codes = torch.empty(0, _round_up(D, 64), dtype=torch.int8, device='cuda')
         self.scales = torch.empty(0, dtype=torch.float32, device='cuda')
 
     def __len__(self):
         return int(self.codes.shape[0])
 
+    def _trained(self):
+        """whether add, search and save have what they need (the mixins below add their conditions)"""
+        return True
+
+    def _need_trained(self, what):
+        if not self._trained():
+            raise ValueError('%s before train' % what)
+
     def _check_rows(self, descs):
         if descs.ndim != 2 or descs.shape[1] != self.D:
             raise ValueError('descriptors [n, %d] expected' % self.D)
 
-    def _check_search(self, q, k, R, source, same_set):
-        """the arguments of search; returns the empty result for an empty query set, else None"""
+    def _check_train(self, x):
+        self._check_rows(x)
+        if len(self):
+            raise ValueError('train before add: the rows already stored were coded with the old centroids / codebooks')
+
+    def _search(self, qdescs, k, rerank, source, same_set, scratch_bytes, scan):
+        """What every search does around its scan: the queries to the device, the argument checks, the empty result of an
+        empty query set, scan(q, keep) -> the (cand, vals) [Q, keep] of the keep = rerank or k best rows of every query,
+        and - with rerank - the k best of those by fp32 score against `source`."""
+        self._need_trained('search')
+        q = _dev(qdescs)
+        k, R = int(k), int(rerank)
         Q, N = q.shape[0], len(self)
         if q.dim() != 2 or q.shape[1] != self.D:
             raise ValueError('queries [Q, %d] expected' % self.D)
@@ -149,7 +189,10 @@ class _CodedIndex:
         if Q == 0:
             return (torch.empty(0, k, dtype=torch.int32, device='cuda'),
                     torch.empty(0, k, dtype=torch.float32, device='cuda'))
-        return None
+        cand, vals = scan(q, R or k)
+        if not R:
+            return cand, vals
+        return ops.topk(self._rescore(q, cand, source, scratch_bytes), k, ids=cand)
 
     def _scan_blocks(self, Q, keep, same_set, scratch_bytes, db_rows, scorer, row_bytes=0):
         """ranking.retrieve_device's loop on a coded database: the `keep` best rows of every query.  scorer(r0, r1) -> a
@@ -182,12 +225,6 @@ class _CodedIndex:
             idx[r0:r1], vals[r0:r1] = run_i, run_v
         return idx, vals
 
-    def _rerank(self, q, cand, vals, k, R, source, scratch_bytes):
-        """the lists of a scan that kept R or k candidates per query: as they are, or the k best by fp32 score"""
-        if not R:
-            return cand, vals
-        return ops.topk(self._rescore(q, cand, source, scratch_bytes), k, ids=cand)
-
     def _rescore(self, q, cand, source, scratch_bytes):
         """fp32 scores [Q, R] of the candidates against the rows of source"""
         if not _is_host(source):
@@ -206,6 +243,16 @@ class _CodedIndex:
             out[r0:r1] = ops.gather_scores(q[r0:r1], picked, torch.from_numpy(local).cuda())
         return out
 
+    def _save_i8(self):
+        """the int8 store's arrays of a .npz: `codes` [N, D] int8 (without the padding), `scales` [N] float32"""
+        return dict(codes=self.codes[:, :self.D].cpu().numpy(), scales=self.scales.cpu().numpy())
+
+    def _load_i8(self, path, f):
+        self.codes = _padded_codes(path, f['codes'], self.D, np.int8, 64)
+        if f['scales'].shape != (len(self),):
+            raise ValueError('%s: scales [N] expected for codes [N, D]' % path)
+        self.scales = torch.from_numpy(f['scales'].astype(np.float32)).cuda()
+
 
 class Int8Index(_CodedIndex):
     """codes [N, ldc] int8 (ldc = D rounded up to 64, padding zero) and scales [N] fp32, both CUDA."""
@@ -214,24 +261,9 @@ class Int8Index(_CodedIndex):
         """Append the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap).  They are quantised in
         chunks of ADD_CHUNK_BYTES, so a database that lives in a host file is never resident on the device as fp32."""
         self._check_rows(descs)
-        n, N = int(descs.shape[0]), len(self)
-        if n == 0:
-            return self
-        codes = torch.empty(N + n, self.codes.shape[1], dtype=torch.int8, device='cuda')
-        scales = torch.empty(N + n, dtype=torch.float32, device='cuda')
-        codes[:N], scales[:N] = self.codes, self.scales
-        r0 = N
-        for c, s in _quantize_chunks(descs, self.D):
-            codes[r0:r0 + len(s)], scales[r0:r0 + len(s)] = c, s
-            r0 += len(s)
-        self.codes, self.scales = codes, scales
+        if int(descs.shape[0]):
+            self.codes, self.scales = _appended([self.codes, self.scales], descs, self.D, ops.quantize_rows)
         return self
-
-    def _scan(self, qc, qs, keep, same_set, scratch_bytes, db_rows):
-        """the `keep` best rows of every coded query by quantised score"""
-        def scorer(r0, r1):
-            return lambda b0, b1: ops.similarity_i8(qc[r0:r1], qs[r0:r1], self.codes[b0:b1], self.scales[b0:b1], self.D)
-        return self._scan_blocks(qc.shape[0], keep, same_set, scratch_bytes, db_rows, scorer)
 
     def search(self, qdescs, k, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20, db_rows=None):
         """(idx [Q,k] int32, vals [Q,k] float32), both CUDA, under ranking.retrieve_device's contract (its order, same_set
@@ -240,38 +272,31 @@ class Int8Index(_CodedIndex):
         they are re-scored against `source` - the fp32 database: a CUDA tensor is gathered on the device, a host array
         or memmap has the candidates' rows gathered on the host in chunks of scratch_bytes - and vals carries the fp32
         scores of the k best of them."""
-        from .utils.common import _dev
-        q = _dev(qdescs)
-        k, R = int(k), int(rerank)
-        empty = self._check_search(q, k, R, source, same_set)
-        if empty is not None:
-            return empty
-        qc, qs = ops.quantize_rows(q)
-        cand, vals = self._scan(qc, qs, R or k, same_set, scratch_bytes, db_rows)
-        return self._rerank(q, cand, vals, k, R, source, scratch_bytes)
+        def scan(q, keep):
+            qc, qs = ops.quantize_rows(q)
+
+            def scorer(r0, r1):
+                return lambda b0, b1: ops.similarity_i8(qc[r0:r1], qs[r0:r1], self.codes[b0:b1], self.scales[b0:b1], self.D)
+            return self._scan_blocks(q.shape[0], keep, same_set, scratch_bytes, db_rows, scorer)
+        return self._search(qdescs, k, rerank, source, same_set, scratch_bytes, scan)
 
     def save(self, path):
         """One .npz: `codes` [N, D] int8 (without the padding), `scales` [N] float32, `D`."""
-        np.savez(path, codes=self.codes[:, :self.D].cpu().numpy(), scales=self.scales.cpu().numpy(),
-                 D=np.int64(self.D))
+        np.savez(path, D=np.int64(self.D), **self._save_i8())
 
     @classmethod
     def load(cls, path):
-        with np.load(path) as f:
-            index = cls(int(f['D']))
-            codes, scales = f['codes'], f['scales']
-        if codes.dtype != np.int8 or codes.ndim != 2 or codes.shape[1] != index.D or scales.shape != (len(codes),):
-            raise ValueError('%s: codes [N, D] int8 and scales [N] expected' % path)
-        index.codes = torch.zeros(len(codes), _pad64(index.D), dtype=torch.int8, device='cuda')
-        index.codes[:, :index.D] = torch.from_numpy(codes).cuda()
-        index.scales = torch.from_numpy(scales.astype(np.float32)).cuda()
+        f = _read_npz(path)
+        index = cls(int(f['D']))
+        index._load_i8(path, f)
         return index
 
 
 class _InvertedLists:
     """What the two inverted files share - the coarse quantiser and the list-major bookkeeping: centroids [nlist, D] fp32
     with their codes `ccodes` and scales `cscales`, ids [N] int32, list_off [nlist+1] int32 and `_lens`, the host copy of
-    the list lengths; assignment, probing, the spherical Lloyd iterations and the regrouping of a store after an add."""
+    the list lengths; assignment, probing, the spherical Lloyd iterations, the regrouping of a store after an add, the
+    probed search loop and their half of save and load."""
 
     def _init_lists(self, nlist):
         nlist = int(nlist)
@@ -282,6 +307,9 @@ class _InvertedLists:
         self.ids = torch.empty(0, dtype=torch.int32, device='cuda')
         self.list_off = torch.zeros(nlist + 1, dtype=torch.int32, device='cuda')
         self._lens = np.zeros(nlist, np.int64)           # host copy of the list lengths: sizes search's chunks
+
+    def _trained(self):
+        return self.centroids is not None and super()._trained()
 
     def _set_centroids(self, centroids):
         self.centroids = centroids
@@ -305,9 +333,7 @@ class _InvertedLists:
         bounds = torch.arange(self.nlist + 1, device='cuda')
         for _ in range(int(iters)):
             self._set_centroids(centroids)
-            lists, order = torch.sort(self._assign(codes, scales).long(), stable=True)
-            seg_off = torch.searchsorted(lists, bounds).to(torch.int32)
-            sums = ops.segment_sums(x, order.to(torch.int32), seg_off)
+            seg_off, sums = _segment_sums(x, self._assign(codes, scales), bounds)
             ops.l2norm_rows_(sums)
             empty = (seg_off[1:] == seg_off[:-1])[:, None]
             centroids = torch.where(empty, centroids, sums)
@@ -335,6 +361,98 @@ class _InvertedLists:
         lens = (self.list_off[1:] - self.list_off[:-1])[probe.long()]
         return torch.cumsum(lens, dim=1, dtype=torch.int32) - lens
 
+    def _search_lists(self, qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, query_bytes):
+        """The search of an inverted file around self._scan_lists(q, qc, qs, probe, col_off, rows, width) -> the (scores,
+        ids) [len(rows), <= width] of the queries of the slice `rows` against the lists they probe: the queries go in
+        chunks whose score and id rows (8 bytes per column; the nprobe longest lists bound the width, by the host's copy
+        of the list lengths) and query_bytes more per query fit scratch_bytes."""
+        nprobe = int(nprobe)
+        if nprobe < 1 or nprobe > self.nlist:
+            raise ValueError('1 <= nprobe <= nlist = %d expected, got %d' % (self.nlist, nprobe))
+
+        def scan(q, keep):
+            Q = q.shape[0]
+            qc, qs = ops.quantize_rows(q)
+            probe = self.probe(qc, qs, nprobe)
+            col_off = self._slots(probe)
+            width = max(int(np.partition(self._lens, -nprobe)[-nprobe:].sum()), keep)     # the nprobe longest lists
+            step = int(max(1, min(Q, scratch_bytes // (8 * width + query_bytes))))
+            cand = torch.empty(Q, keep, dtype=torch.int32, device='cuda')
+            vals = torch.empty(Q, keep, dtype=torch.float32, device='cuda')
+            for r0 in range(0, Q, step):
+                r1 = min(Q, r0 + step)
+                scores, ids = self._scan_lists(q, qc, qs, probe, col_off, slice(r0, r1), width)
+                if scores.shape[1] < keep:   # every row of the chunk runs short: top-k wants keep columns, the rest are empty
+                    wide = torch.full((r1 - r0, keep), -1, dtype=torch.int32, device='cuda')
+                    wide[:, :ids.shape[1]] = ids
+                    ids, scores = wide, torch.cat([scores, scores.new_zeros(r1 - r0, keep - scores.shape[1])], dim=1)
+                own = torch.arange(r0, r1, dtype=torch.int32, device='cuda') if same_set else None
+                cand[r0:r1], vals[r0:r1] = ops.topk(scores, keep, ids=ids, exclude=own)
+            return cand, vals
+        return self._search(qdescs, k, rerank, source, same_set, scratch_bytes, scan)
+
+    def _save_lists(self):
+        """the lists' arrays of a .npz: `centroids` [nlist, D] float32, `ids` [N] int32, `list_off` [nlist+1] int32, `nlist`"""
+        return dict(centroids=self.centroids.cpu().numpy(), ids=self.ids.cpu().numpy(), list_off=self.list_off.cpu().numpy(),
+                    nlist=np.int64(self.nlist))
+
+    def _load_lists(self, path, f):
+        """after the code store is loaded: N is its row count"""
+        N, centroids, ids, list_off = len(self), f['centroids'], f['ids'], f['list_off']
+        if ids.shape != (N,):
+            raise ValueError('%s: ids [N] expected for codes of N rows' % path)
+        if centroids.shape != (self.nlist, self.D) or list_off.shape != (self.nlist + 1,) or list_off[0] != 0 or (
+                list_off[-1] != N or (np.diff(list_off.astype(np.int64)) < 0).any()):
+            raise ValueError('%s: centroids [nlist, D] and a list_off [nlist+1] from 0 to N expected' % path)
+        self._set_centroids(torch.from_numpy(centroids.astype(np.float32)).cuda())
+        self.ids = torch.from_numpy(ids.astype(np.int32)).cuda()
+        self.list_off = torch.from_numpy(list_off.astype(np.int32)).cuda()
+        self._lens = np.diff(list_off.astype(np.int64))
+
+
+class _ProductQuantizer:
+    """What the two product-quantised indexes share: M sub-spaces of dsub = D / M columns, codebooks [M, 256, dsub] fp32
+    (None until train or load), the uint8 code store [N, M rounded up to 4] (padding zero) in place of the int8 one, the
+    Lloyd iterations per sub-space and their half of save and load."""
+
+    def _init_pq(self, M):
+        M = int(M)
+        if M < 1 or M > ops.pq_max_m() or self.D % M:
+            raise ValueError('1 <= M <= %d dividing D = %d expected, got %d' % (ops.pq_max_m(), self.D, M))
+        self.M, self.dsub = M, self.D // M
+        self.codebooks = None
+        self.codes = torch.empty(0, _round_up(M, 4), dtype=torch.uint8, device='cuda')
+        self.scales = None
+
+    def _trained(self):
+        return self.codebooks is not None and super()._trained()
+
+    def _lloyd_codebooks(self, x, iters, seed):
+        """PQIndex.train's iterations on the sample x [n, D] (fp32 CUDA, n >= 256); sets the codebooks"""
+        M, dsub = self.M, self.dsub
+        first = np.sort(np.random.RandomState(seed).choice(int(x.shape[0]), 256, replace=False))
+        codebooks = x[torch.from_numpy(first).cuda()].view(256, M, dsub).permute(1, 0, 2).contiguous()
+        bounds = torch.arange(257, device='cuda')
+        for _ in range(int(iters)):
+            codes = ops.pq_encode(x, codebooks)
+            for m in range(M):
+                seg_off, sums = _segment_sums(x[:, m * dsub:(m + 1) * dsub], codes[:, m], bounds)
+                count = (seg_off[1:] - seg_off[:-1])[:, None]
+                codebooks[m] = torch.where(count > 0, sums / count.to(torch.float32), codebooks[m])
+        self.codebooks = codebooks
+
+    def _save_pq(self):
+        """the quantiser's arrays of a .npz: `codebooks` [M, 256, D / M] float32, `codes` [N, M] uint8 (without the
+        padding), `M`"""
+        return dict(codebooks=self.codebooks.cpu().numpy(), codes=self.codes[:, :self.M].cpu().numpy(), M=np.int64(self.M))
+
+    def _load_pq(self, path, f):
+        codebooks = f['codebooks']
+        if codebooks.shape != (self.M, 256, self.dsub) or codebooks.dtype.kind != 'f':
+            raise ValueError('%s: codebooks [M, 256, D / M] float32 expected' % path)
+        self.codes = _padded_codes(path, f['codes'], self.M, np.uint8, 4)
+        self.codebooks = torch.from_numpy(np.ascontiguousarray(codebooks, dtype=np.float32)).cuda()
+
 
 class IVFInt8Index(_InvertedLists, _CodedIndex):
     """The inverted-file int8 index (include/dir_engine.h gives the definitions).  All CUDA: centroids [nlist, D] fp32 with
@@ -352,9 +470,7 @@ class IVFInt8Index(_InvertedLists, _CodedIndex):
         centroids are the rows np.sort(RandomState(seed).choice(n, nlist, replace=False)) of the sample; an iteration
         assigns every row to its list, sums each list's members in fp32 (ops.segment_sums) and L2-normalises the sums;
         an empty list keeps its centroid.  Bitwise reproducible.  Rows already added are not re-assigned: train first."""
-        self._check_rows(x)
-        if len(self):
-            raise ValueError('train before add: the rows already stored were assigned to the old centroids')
+        self._check_train(x)
         max_rows = 256 * self.nlist if max_rows is None else int(max_rows)
         self._lloyd_centroids(_training_rows(x, seed, max_rows, self.nlist, 'nlist = %d' % self.nlist), iters, seed)
         return self
@@ -366,94 +482,51 @@ class IVFInt8Index(_InvertedLists, _CodedIndex):
         how the rows were cut into calls.  The regrouping copies the codes once (twice the index's bytes for a moment)
         and reads the list lengths back to the host."""
         self._check_rows(descs)
-        if self.centroids is None:
-            raise ValueError('add before train')
+        self._need_trained('add')
         if int(descs.shape[0]) == 0:
             return self
-        new = [(c, s, self._assign(c, s)) for c, s in _quantize_chunks(descs, self.D)]
-        self.codes, self.scales = self._regroup([l for _, _, l in new], [torch.cat([self.codes] + [c for c, _, _ in new]),
-                                                                         torch.cat([self.scales] + [s for _, s, _ in new])])
+        lists, codes, scales = [], [self.codes], [self.scales]
+        for x in _row_chunks(descs, self.D):
+            c, s = ops.quantize_rows(x)
+            lists.append(self._assign(c, s))
+            codes.append(c)
+            scales.append(s)
+        self.codes, self.scales = self._regroup(lists, [torch.cat(codes), torch.cat(scales)])
         return self
+
+    def _scan_lists(self, q, qc, qs, probe, col_off, rows, width):
+        return ops.ivf_scan(qc[rows], qs[rows], self.codes, self.scales, self.ids, self.list_off, probe[rows], col_off[rows],
+                            self.D)
 
     def search(self, qdescs, k, nprobe=1, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20):
         """Int8Index.search's contract over the rows of the nprobe best lists of every query (1 <= nprobe <= nlist): a
         query whose lists hold fewer than k rows ends in (-1, NaN).  The queries go in chunks whose score and id rows
         (8 bytes per column; the nprobe longest lists bound the width) fit scratch_bytes; every chunk synchronises with
         the host once, inside ops.ivf_scan, to learn its grid and its width."""
-        from .utils.common import _dev
-        if self.centroids is None:
-            raise ValueError('search before train')
-        nprobe = int(nprobe)
-        if nprobe < 1 or nprobe > self.nlist:
-            raise ValueError('1 <= nprobe <= nlist = %d expected, got %d' % (self.nlist, nprobe))
-        q = _dev(qdescs)
-        k, R = int(k), int(rerank)
-        empty = self._check_search(q, k, R, source, same_set)
-        if empty is not None:
-            return empty
-        Q, keep = q.shape[0], R or k
-        qc, qs = ops.quantize_rows(q)
-        probe = self.probe(qc, qs, nprobe)
-        col_off = self._slots(probe)
-        bound = max(int(np.sort(self._lens)[-nprobe:].sum()), keep)
-        rows = int(max(1, min(Q, scratch_bytes // (8 * bound))))
-        cand = torch.empty(Q, keep, dtype=torch.int32, device='cuda')
-        vals = torch.empty(Q, keep, dtype=torch.float32, device='cuda')
-        for r0 in range(0, Q, rows):
-            r1 = min(Q, r0 + rows)
-            scores, ids = ops.ivf_scan(qc[r0:r1], qs[r0:r1], self.codes, self.scales, self.ids, self.list_off,
-                                       probe[r0:r1], col_off[r0:r1], self.D)
-            if scores.shape[1] < keep:       # every row of the chunk runs short: top-k wants keep columns, the rest are empty
-                wide = torch.full((r1 - r0, keep), -1, dtype=torch.int32, device='cuda')
-                wide[:, :ids.shape[1]] = ids
-                ids, scores = wide, torch.cat([scores, scores.new_zeros(r1 - r0, keep - scores.shape[1])], dim=1)
-            own = torch.arange(r0, r1, dtype=torch.int32, device='cuda') if same_set else None
-            cand[r0:r1], vals[r0:r1] = ops.topk(scores, keep, ids=ids, exclude=own)
-        return self._rerank(q, cand, vals, k, R, source, scratch_bytes)
+        return self._search_lists(qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, 0)
 
     def save(self, path):
         """One .npz: `centroids` [nlist, D] float32, `codes` [N, D] int8 (without the padding), `scales` [N] float32, `ids`
         [N] int32, `list_off` [nlist+1] int32, `D`, `nlist`."""
-        if self.centroids is None:
-            raise ValueError('save before train')
-        np.savez(path, centroids=self.centroids.cpu().numpy(), codes=self.codes[:, :self.D].cpu().numpy(),
-                 scales=self.scales.cpu().numpy(), ids=self.ids.cpu().numpy(), list_off=self.list_off.cpu().numpy(),
-                 D=np.int64(self.D), nlist=np.int64(self.nlist))
+        self._need_trained('save')
+        np.savez(path, D=np.int64(self.D), **self._save_i8(), **self._save_lists())
 
     @classmethod
     def load(cls, path):
-        with np.load(path) as f:
-            index = cls(int(f['D']), int(f['nlist']))
-            centroids, codes, scales, ids, list_off = (f[name] for name in ('centroids', 'codes', 'scales', 'ids', 'list_off'))
-        N = len(codes)
-        if codes.dtype != np.int8 or codes.ndim != 2 or codes.shape[1] != index.D or scales.shape != (N,) or ids.shape != (N,):
-            raise ValueError('%s: codes [N, D] int8, scales [N] and ids [N] expected' % path)
-        if centroids.shape != (index.nlist, index.D) or list_off.shape != (index.nlist + 1,) or list_off[0] != 0 or (
-                list_off[-1] != N or (np.diff(list_off.astype(np.int64)) < 0).any()):
-            raise ValueError('%s: centroids [nlist, D] and a list_off [nlist+1] from 0 to N expected' % path)
-        index._set_centroids(torch.from_numpy(centroids.astype(np.float32)).cuda())
-        index.codes = torch.zeros(N, _pad64(index.D), dtype=torch.int8, device='cuda')
-        index.codes[:, :index.D] = torch.from_numpy(codes).cuda()
-        index.scales = torch.from_numpy(scales.astype(np.float32)).cuda()
-        index.ids = torch.from_numpy(ids.astype(np.int32)).cuda()
-        index.list_off = torch.from_numpy(list_off.astype(np.int32)).cuda()
-        index._lens = np.diff(list_off.astype(np.int64))
+        f = _read_npz(path)
+        index = cls(int(f['D']), int(f['nlist']))
+        index._load_i8(path, f)
+        index._load_lists(path, f)
         return index
 
 
-class PQIndex(_CodedIndex):
+class PQIndex(_ProductQuantizer, _CodedIndex):
     """The product-quantised index (include/dir_engine.h gives the definitions).  All CUDA: codebooks [M, 256, D / M] fp32
     (None until train or load) and codes [N, ldc] uint8, ldc = M rounded up to a multiple of 4, the padding zero."""
 
     def __init__(self, D, M):
-        super().__init__(D)
-        M = int(M)
-        if M < 1 or M > ops.pq_max_m() or self.D % M:
-            raise ValueError('1 <= M <= %d dividing D = %d expected, got %d' % (ops.pq_max_m(), self.D, M))
-        self.M, self.dsub = M, self.D // M
-        self.codebooks = None
-        self.codes = torch.empty(0, (M + 3) // 4 * 4, dtype=torch.uint8, device='cuda')
-        self.scales = None
+        _CodedIndex.__init__(self, D)
+        self._init_pq(M)
 
     def nbytes(self):
         """the bytes the database rows take on the device (the codebooks, 1024 * D bytes, not counted)"""
@@ -466,75 +539,46 @@ class PQIndex(_CodedIndex):
         its columns of them; an iteration encodes the sample (ops.pq_encode is the assignment), sums each centroid's
         members in fp32 (ops.segment_sums on the sub-space's columns) and divides by their number; a centroid without
         members keeps its value.  Bitwise reproducible.  Rows already added are not re-encoded: train first."""
-        self._check_rows(x)
-        if len(self):
-            raise ValueError('train before add: the rows already stored were encoded with the old codebooks')
+        self._check_train(x)
         max_rows = 256 * 256 if max_rows is None else int(max_rows)
-        self.codebooks = _lloyd_codebooks(_training_rows(x, seed, max_rows, 256, '256'), self.M, iters, seed)
+        self._lloyd_codebooks(_training_rows(x, seed, max_rows, 256, '256'), iters, seed)
         return self
 
     def add(self, descs):
         """Append the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap), encoded in chunks of
         ADD_CHUNK_BYTES as Int8Index.add quantises them."""
         self._check_rows(descs)
-        if self.codebooks is None:
-            raise ValueError('add before train')
-        n, N = int(descs.shape[0]), len(self)
-        if n == 0:
-            return self
-        codes = torch.empty(N + n, self.codes.shape[1], dtype=torch.uint8, device='cuda')
-        codes[:N] = self.codes
-        rows = max(1, ADD_CHUNK_BYTES // (4 * self.D))
-        for r0 in range(0, n, rows):
-            codes[N + r0:N + min(n, r0 + rows)] = ops.pq_encode(_upload(descs[r0:r0 + rows]), self.codebooks)
-        self.codes = codes
+        self._need_trained('add')
+        if int(descs.shape[0]):
+            self.codes, = _appended([self.codes], descs, self.D, lambda x: [ops.pq_encode(x, self.codebooks)])
         return self
-
-    def _scan(self, q, keep, same_set, scratch_bytes, db_rows):
-        """the `keep` best rows of every query by table score; a chunk of queries holds its tables, 1024 * M bytes each"""
-        def scorer(r0, r1):
-            lut = ops.pq_lut(q[r0:r1], self.codebooks)
-            return lambda b0, b1: ops.pq_scan(lut, self.codes[b0:b1])
-        return self._scan_blocks(q.shape[0], keep, same_set, scratch_bytes, db_rows, scorer, row_bytes=1024 * self.M)
 
     def search(self, qdescs, k, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20, db_rows=None):
         """Int8Index.search's contract with the table scores in place of the quantised ones: (idx [Q,k] int32, vals [Q,k]
         float32), both CUDA, in ops.topk's order, same_set leaving a query out of its own list, (-1, NaN) where a row runs
-        short; rerank = R re-scores the R best against `source` (CUDA tensor, host array or memmap) in fp32."""
-        from .utils.common import _dev
-        if self.codebooks is None:
-            raise ValueError('search before train')
-        q = _dev(qdescs)
-        k, R = int(k), int(rerank)
-        empty = self._check_search(q, k, R, source, same_set)
-        if empty is not None:
-            return empty
-        cand, vals = self._scan(q, R or k, same_set, scratch_bytes, db_rows)
-        return self._rerank(q, cand, vals, k, R, source, scratch_bytes)
+        short; rerank = R re-scores the R best against `source` (CUDA tensor, host array or memmap) in fp32.  A chunk of
+        queries holds its tables, 1024 * M bytes each, beside its score rows."""
+        def scan(q, keep):
+            def scorer(r0, r1):
+                lut = ops.pq_lut(q[r0:r1], self.codebooks)
+                return lambda b0, b1: ops.pq_scan(lut, self.codes[b0:b1])
+            return self._scan_blocks(q.shape[0], keep, same_set, scratch_bytes, db_rows, scorer, row_bytes=1024 * self.M)
+        return self._search(qdescs, k, rerank, source, same_set, scratch_bytes, scan)
 
     def save(self, path):
         """One .npz: `codebooks` [M, 256, D / M] float32, `codes` [N, M] uint8 (without the padding), `D`, `M`."""
-        if self.codebooks is None:
-            raise ValueError('save before train')
-        np.savez(path, codebooks=self.codebooks.cpu().numpy(), codes=self.codes[:, :self.M].cpu().numpy(),
-                 D=np.int64(self.D), M=np.int64(self.M))
+        self._need_trained('save')
+        np.savez(path, D=np.int64(self.D), **self._save_pq())
 
     @classmethod
     def load(cls, path):
-        with np.load(path) as f:
-            index = cls(int(f['D']), int(f['M']))
-            codebooks, codes = f['codebooks'], f['codes']
-        if codes.dtype != np.uint8 or codes.ndim != 2 or codes.shape[1] != index.M:
-            raise ValueError('%s: codes [N, M] uint8 expected' % path)
-        if codebooks.shape != (index.M, 256, index.dsub) or codebooks.dtype.kind != 'f':
-            raise ValueError('%s: codebooks [M, 256, D / M] float32 expected' % path)
-        index.codebooks = torch.from_numpy(np.ascontiguousarray(codebooks, dtype=np.float32)).cuda()
-        index.codes = torch.zeros(len(codes), (index.M + 3) // 4 * 4, dtype=torch.uint8, device='cuda')
-        index.codes[:, :index.M] = torch.from_numpy(codes).cuda()
+        f = _read_npz(path)
+        index = cls(int(f['D']), int(f['M']))
+        index._load_pq(path, f)
         return index
 
 
-class IVFPQIndex(_InvertedLists, _CodedIndex):
+class IVFPQIndex(_InvertedLists, _ProductQuantizer, _CodedIndex):
     """The IVF-PQ index (include/dir_engine.h gives the definitions).  All CUDA: the coarse quantiser of IVFInt8Index
     (centroids [nlist, D] fp32, `ccodes`, `cscales`), codebooks [M, 256, D / M] fp32 trained on residuals, and the database
     LIST-MAJOR - codes [N, ldc] uint8 (ldc = M rounded up to a multiple of 4, the padding zero): the codes of the row's
@@ -544,13 +588,7 @@ class IVFPQIndex(_InvertedLists, _CodedIndex):
     def __init__(self, D, nlist, M):
         _CodedIndex.__init__(self, D)
         self._init_lists(nlist)
-        M = int(M)
-        if M < 1 or M > ops.pq_max_m() or self.D % M:
-            raise ValueError('1 <= M <= %d dividing D = %d expected, got %d' % (ops.pq_max_m(), self.D, M))
-        self.M, self.dsub = M, self.D // M
-        self.codebooks = None
-        self.codes = torch.empty(0, (M + 3) // 4 * 4, dtype=torch.uint8, device='cuda')
-        self.scales = None
+        self._init_pq(M)
 
     def nbytes(self):
         """the bytes the database rows take on the device: codes and ids (centroids and codebooks not counted)"""
@@ -566,14 +604,12 @@ class IVFPQIndex(_InvertedLists, _CodedIndex):
         IVFInt8Index.train finds them.  2. the codebooks exactly as PQIndex.train finds them (same seed, same iterations),
         but on the residuals of that sample to the final centroids of the lists its rows are assigned to.  Bitwise
         reproducible.  Rows already added are neither re-assigned nor re-encoded: train first."""
-        self._check_rows(x)
-        if len(self):
-            raise ValueError('train before add: the rows already stored were assigned and encoded with the old centroids')
+        self._check_train(x)
         max_rows = 256 * self.nlist if max_rows is None else int(max_rows)
         least = max(self.nlist, 256)
         x = _training_rows(x, seed, max_rows, least, 'max(nlist, 256) = %d' % least)
         self._lloyd_centroids(x, iters, seed)
-        self.codebooks = _lloyd_codebooks(self._residuals(x, self._assign(*ops.quantize_rows(x))), self.M, iters, seed)
+        self._lloyd_codebooks(self._residuals(x, self._assign(*ops.quantize_rows(x))), iters, seed)
         return self
 
     def add(self, descs):
@@ -582,19 +618,20 @@ class IVFPQIndex(_InvertedLists, _CodedIndex):
         store is regrouped by that class's stable integer sort, so what the index holds does not depend on how the rows
         were cut into calls."""
         self._check_rows(descs)
-        if self.centroids is None or self.codebooks is None:
-            raise ValueError('add before train')
-        n = int(descs.shape[0])
-        if n == 0:
+        self._need_trained('add')
+        if int(descs.shape[0]) == 0:
             return self
-        rows = max(1, ADD_CHUNK_BYTES // (4 * self.D))
-        new = []
-        for r0 in range(0, n, rows):
-            x = _upload(descs[r0:r0 + rows])
-            lists = self._assign(*ops.quantize_rows(x))
-            new.append((ops.pq_encode(self._residuals(x, lists), self.codebooks), lists))
-        self.codes, = self._regroup([l for _, l in new], [torch.cat([self.codes] + [c for c, _ in new])])
+        lists, codes = [], [self.codes]
+        for x in _row_chunks(descs, self.D):
+            lists.append(self._assign(*ops.quantize_rows(x)))
+            codes.append(ops.pq_encode(self._residuals(x, lists[-1]), self.codebooks))
+        self.codes, = self._regroup(lists, [torch.cat(codes)])
         return self
+
+    def _scan_lists(self, q, qc, qs, probe, col_off, rows, width):
+        lut = ops.pq_lut(q[rows], self.codebooks)
+        base = ops.ivfpq_base(q[rows], self.centroids, probe[rows], self.M)
+        return ops.ivfpq_scan(lut, base, self.codes, self.ids, self.list_off, probe[rows], col_off[rows], width=width)
 
     def search(self, qdescs, k, nprobe=1, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20):
         """IVFInt8Index.search's contract over the rows of the nprobe best lists of every query (1 <= nprobe <= nlist), with
@@ -602,61 +639,18 @@ class IVFPQIndex(_InvertedLists, _CodedIndex):
         hold fewer than k rows ends in (-1, NaN).  The queries go in chunks whose score and id rows (8 bytes per column;
         the nprobe longest lists give the width) and tables (1024 * M bytes per query) fit scratch_bytes.  The width comes
         from the host's copy of the list lengths: a search does not synchronise with the host."""
-        from .utils.common import _dev
-        if self.centroids is None or self.codebooks is None:
-            raise ValueError('search before train')
-        nprobe = int(nprobe)
-        if nprobe < 1 or nprobe > self.nlist:
-            raise ValueError('1 <= nprobe <= nlist = %d expected, got %d' % (self.nlist, nprobe))
-        q = _dev(qdescs)
-        k, R = int(k), int(rerank)
-        empty = self._check_search(q, k, R, source, same_set)
-        if empty is not None:
-            return empty
-        Q, keep = q.shape[0], R or k
-        probe = self.probe(*ops.quantize_rows(q), nprobe)
-        col_off = self._slots(probe)
-        width = max(int(np.sort(self._lens)[-nprobe:].sum()), keep)
-        rows = int(max(1, min(Q, scratch_bytes // (8 * width + 1024 * self.M))))
-        cand = torch.empty(Q, keep, dtype=torch.int32, device='cuda')
-        vals = torch.empty(Q, keep, dtype=torch.float32, device='cuda')
-        for r0 in range(0, Q, rows):
-            r1 = min(Q, r0 + rows)
-            lut = ops.pq_lut(q[r0:r1], self.codebooks)
-            base = ops.ivfpq_base(q[r0:r1], self.centroids, probe[r0:r1], self.M)
-            scores, ids = ops.ivfpq_scan(lut, base, self.codes, self.ids, self.list_off, probe[r0:r1], col_off[r0:r1],
-                                         width=width)
-            own = torch.arange(r0, r1, dtype=torch.int32, device='cuda') if same_set else None
-            cand[r0:r1], vals[r0:r1] = ops.topk(scores, keep, ids=ids, exclude=own)
-        return self._rerank(q, cand, vals, k, R, source, scratch_bytes)
+        return self._search_lists(qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, 1024 * self.M)
 
     def save(self, path):
         """One .npz: `centroids` [nlist, D] float32, `codebooks` [M, 256, D / M] float32, `codes` [N, M] uint8 (without the
         padding), `ids` [N] int32, `list_off` [nlist+1] int32, `D`, `nlist`, `M`."""
-        if self.centroids is None or self.codebooks is None:
-            raise ValueError('save before train')
-        np.savez(path, centroids=self.centroids.cpu().numpy(), codebooks=self.codebooks.cpu().numpy(),
-                 codes=self.codes[:, :self.M].cpu().numpy(), ids=self.ids.cpu().numpy(), list_off=self.list_off.cpu().numpy(),
-                 D=np.int64(self.D), nlist=np.int64(self.nlist), M=np.int64(self.M))
+        self._need_trained('save')
+        np.savez(path, D=np.int64(self.D), **self._save_pq(), **self._save_lists())
 
     @classmethod
     def load(cls, path):
-        with np.load(path) as f:
-            index = cls(int(f['D']), int(f['nlist']), int(f['M']))
-            centroids, codebooks, codes, ids, list_off = (f[name] for name in ('centroids', 'codebooks', 'codes', 'ids', 'list_off'))
-        N = len(codes)
-        if codes.dtype != np.uint8 or codes.ndim != 2 or codes.shape[1] != index.M or ids.shape != (N,):
-            raise ValueError('%s: codes [N, M] uint8 and ids [N] expected' % path)
-        if codebooks.shape != (index.M, 256, index.dsub) or codebooks.dtype.kind != 'f':
-            raise ValueError('%s: codebooks [M, 256, D / M] float32 expected' % path)
-        if centroids.shape != (index.nlist, index.D) or list_off.shape != (index.nlist + 1,) or list_off[0] != 0 or (
-                list_off[-1] != N or (np.diff(list_off.astype(np.int64)) < 0).any()):
-            raise ValueError('%s: centroids [nlist, D] and a list_off [nlist+1] from 0 to N expected' % path)
-        index._set_centroids(torch.from_numpy(centroids.astype(np.float32)).cuda())
-        index.codebooks = torch.from_numpy(np.ascontiguousarray(codebooks, dtype=np.float32)).cuda()
-        index.codes = torch.zeros(N, (index.M + 3) // 4 * 4, dtype=torch.uint8, device='cuda')
-        index.codes[:, :index.M] = torch.from_numpy(codes).cuda()
-        index.ids = torch.from_numpy(ids.astype(np.int32)).cuda()
-        index.list_off = torch.from_numpy(list_off.astype(np.int32)).cuda()
-        index._lens = np.diff(list_off.astype(np.int64))
+        f = _read_npz(path)
+        index = cls(int(f['D']), int(f['nlist']), int(f['M']))
+        index._load_pq(path, f)
+        index._load_lists(path, f)
         return index

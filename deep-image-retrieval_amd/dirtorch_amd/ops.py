@@ -5,6 +5,7 @@ kernel of libdir_engine.so.  16-bit activations travel as torch.bfloat16 / torch
 NHWC layout.
 """
 import ctypes
+import functools
 
 import torch
 
@@ -398,6 +399,7 @@ def label_rank(scores, labels, class_off, class_members, qclass, qself):
     return ap, best
 
 
+@functools.lru_cache(maxsize=None)     # a constant of the library: asked once, not in every call of a search
 def topk_max_k():
     """The largest k ops.topk takes (dir_topk_max_k; host-only)."""
     return int(_lib.load().dir_topk_max_k())
@@ -446,6 +448,7 @@ def topk(scores, k, exclude=None, ids=None):
 
 
 # ---- the int8 descriptor index (csrc/index_i8.hip) ---------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)     # a constant of the library: asked once, not in every call of a search
 def index_i8_max_dim():
     """The widest row the int8 index takes (dir_index_i8_max_dim; host-only)."""
     return int(_lib.load().dir_index_i8_max_dim())
@@ -459,12 +462,86 @@ def _rows_pitch(t, width):
     return t, (int(t.stride(0)) if n > 1 else int(t.shape[1]))
 
 
+def _on_device(*ts):
+    """every tensor given (None: an optional one left out) is a device tensor; unlike _need_cuda, of any strides"""
+    for t in ts:
+        if t is not None and not t.is_cuda:
+            raise ValueError('device tensor expected')
+
+
+def _i8_codes(codes, ldc):
+    """int8 codes [n, >= ldc] -> (codes, row pitch) at a 16-byte pitch and address; copies what is not"""
+    codes, ld = _rows_pitch(codes, ldc)
+    if ld % 16 or codes.data_ptr() % 16:
+        codes, ld = codes[:, :ldc].contiguous(), ldc
+    return codes, ld
+
+
+def _u8_codes(codes, M):
+    """uint8 codes [N, >= M] -> (codes, row pitch) at a 4-byte pitch and address; copies (padding zero) what is not"""
+    codes, ldc = _rows_pitch(codes, M)
+    if ldc % 4 or codes.data_ptr() % 4:
+        padded = torch.zeros(codes.shape[0], (M + 3) // 4 * 4, dtype=torch.uint8, device=codes.device)
+        padded[:, :M] = codes[:, :M]
+        codes, ldc = padded, int(padded.shape[1])
+    return codes, ldc
+
+
+def _score_out(out, Q, N, device):
+    """out= of a score block: float32 [Q, >= N] with unit column stride, or None: a new [Q, N] -> (out, its row pitch)"""
+    if out is None:
+        return torch.empty(Q, N, dtype=torch.float32, device=device), N
+    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != Q or out.shape[1] < N or (
+            Q > 1 and (out.stride(1) != 1 or out.stride(0) < N)) or (Q <= 1 and not out.is_contiguous()):
+        raise ValueError('out: float32 [Q, >= N] with unit column stride expected')
+    return out, (int(out.stride(0)) if Q > 1 else int(out.shape[1]))
+
+
+def _scan_out(out, Q, width, device):
+    """out= of a scan by list: (float32 scores, int32 ids), [Q, >= width] with unit column stride and ONE row pitch, or
+    None: a new pair [Q, width] -> (scores, ids, their row pitch)"""
+    if out is None:
+        return (torch.empty(Q, width, dtype=torch.float32, device=device),
+                torch.empty(Q, width, dtype=torch.int32, device=device), width)
+    scores, out_ids = out
+    if scores.dtype != torch.float32 or out_ids.dtype != torch.int32:
+        raise TypeError('out: float32 scores and int32 ids expected')
+    for t in (scores, out_ids):
+        if t.dim() != 2 or t.shape[0] != Q or t.shape[1] < width or (Q > 1 and (t.stride(1) != 1 or t.stride(0) < width)) or (
+                Q <= 1 and not t.is_contiguous()):
+            raise ValueError('out: [Q, >= width] tensors with unit column stride expected')
+    if Q > 1 and scores.stride(0) != out_ids.stride(0) or (Q <= 1 and scores.shape[1] != out_ids.shape[1]):
+        raise ValueError('out: scores and ids of one row pitch expected')
+    return scores, out_ids, (int(scores.stride(0)) if Q > 1 else int(scores.shape[1]))
+
+
+def _list_tables(Q, N, ids, list_off, probe, col_off, base=None):
+    """The tables of a scan by list: ids [N] and list_off [nlist+1] of a list-major database of N rows; probe, col_off and,
+    where there is one, base [Q,nprobe] of Q queries -> nlist"""
+    if base is not None and base.dtype != torch.float32:
+        raise TypeError('float32 base expected')
+    if not ids.dtype == list_off.dtype == probe.dtype == col_off.dtype == torch.int32:
+        raise TypeError('int32 ids, list_off, probe and col_off expected')
+    if ids.dim() != 1 or ids.numel() != N:
+        raise ValueError('ids [N] expected for codes of N rows')
+    if list_off.dim() != 1 or list_off.numel() < 2:
+        raise ValueError('list_off [nlist+1] expected')
+    if probe.dim() != 2 or probe.shape[0] != Q or col_off.shape != probe.shape or (base is not None and base.shape != probe.shape):
+        raise ValueError('probe, col_off and base [Q,nprobe] expected')
+    return int(list_off.numel()) - 1
+
+
+def _slot_ends(lens, probe, col_off):
+    """[Q,nprobe] int64: col_off + the length of the slot's list (lens [nlist] int64; 0 for an empty slot); its largest
+    entry is the reach of the slots, the width a scan by list needs"""
+    return col_off.long() + torch.where(probe >= 0, lens[probe.long().clamp(min=0)], lens.new_zeros(()))
+
+
 def quantize_rows(X):
     """fp32 rows -> (codes int8 [N, ldc], scales fp32 [N]), both CUDA (dir_quantize_rows_i8; include/dir_engine.h gives
     the definition): ldc = D rounded up to a multiple of 64, the padding bytes zero.  X [N,D] fp32 CUDA with unit column
     stride and any row pitch."""
-    if not X.is_cuda:
-        raise ValueError('device tensor expected')
+    _on_device(X)
     if X.dtype != torch.float32 or X.dim() != 2:
         raise TypeError('float32 rows [N,D] expected')
     N, D = X.shape
@@ -484,9 +561,7 @@ def similarity_i8(qcodes, qscales, bcodes, bscales, D, out=None):
     defined fp32 number per pair.  qcodes [Q,ldc] / bcodes [N,ldc] int8 and qscales [Q] / bscales [N] fp32 as
     quantize_rows gives them (row slices included), D the width the codes were made from.  out: a [Q, >= N] fp32 CUDA
     tensor with unit column stride to write into (its first N columns are returned)."""
-    for t in (qcodes, qscales, bcodes, bscales) + ((out,) if out is not None else ()):
-        if not t.is_cuda:
-            raise ValueError('device tensor expected')
+    _on_device(qcodes, qscales, bcodes, bscales, out)
     if qcodes.dtype != torch.int8 or bcodes.dtype != torch.int8 or qcodes.dim() != 2 or bcodes.dim() != 2:
         raise TypeError('int8 codes [rows, ldc] expected')
     if qscales.dtype != torch.float32 or bscales.dtype != torch.float32:
@@ -499,17 +574,9 @@ def similarity_i8(qcodes, qscales, bcodes, bscales, D, out=None):
     if qscales.dim() != 1 or bscales.dim() != 1 or qscales.numel() != Q or bscales.numel() != N:
         raise ValueError('scales [Q] and [N] expected for codes of Q and N rows')
     qcodes, ldq = _rows_pitch(qcodes, ldc)
-    bcodes, ldb = _rows_pitch(bcodes, ldc)
-    if ldb % 16 or bcodes.data_ptr() % 16:
-        bcodes = bcodes[:, :ldc].contiguous()
-        ldb = ldc
+    bcodes, ldb = _i8_codes(bcodes, ldc)
     qscales, bscales = qscales.contiguous(), bscales.contiguous()
-    if out is None:
-        out = torch.empty(Q, N, dtype=torch.float32, device=bcodes.device)
-    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != Q or out.shape[1] < N or (
-            Q > 1 and (out.stride(1) != 1 or out.stride(0) < N)) or (Q <= 1 and not out.is_contiguous()):
-        raise ValueError('out: float32 [Q, >= N] with unit column stride expected')
-    lds = int(out.stride(0)) if Q > 1 else int(out.shape[1])
+    out, lds = _score_out(out, Q, N, bcodes.device)
     if Q and N:
         call('dir_similarity_i8', ptr(qcodes), ldq, ptr(qscales), Q, ptr(bcodes), ldb, ptr(bscales), N, D, ptr(out), lds,
              stream_ptr())
@@ -520,9 +587,7 @@ def gather_scores(queries, database, cand):
     """scores [Q,R] fp32 CUDA, scores[q][r] = <queries[q], database[cand[q][r]]> (dir_gather_scores): the re-score of a
     shortlist.  queries [Q,D], database [N,D] fp32 CUDA, cand [Q,R] int32 CUDA with entries in [-1, N) - the caller's
     duty, as ids in ops.topk; -1 gives NaN.  Unit column strides, any row pitch."""
-    for t in (queries, database, cand):
-        if not t.is_cuda:
-            raise ValueError('device tensor expected')
+    _on_device(queries, database, cand)
     if queries.dtype != torch.float32 or database.dtype != torch.float32 or cand.dtype != torch.int32:
         raise TypeError('float32 queries / database and int32 cand expected')
     if queries.dim() != 2 or database.dim() != 2 or cand.dim() != 2:
@@ -551,9 +616,7 @@ def segment_sums(X, order, seg_off):
     (dir_segment_sums): bitwise reproducible, an empty segment gives zeros.  X [N,D] fp32 CUDA with unit column stride
     and any row pitch; order int32 CUDA with entries in [0, N); seg_off [S+1] int32 CUDA, ascending from 0 to at most
     len(order) - the caller's duty, as ids in ops.topk."""
-    for t in (X, order, seg_off):
-        if not t.is_cuda:
-            raise ValueError('device tensor expected')
+    _on_device(X, order, seg_off)
     if X.dtype != torch.float32 or X.dim() != 2 or order.dtype != torch.int32 or seg_off.dtype != torch.int32:
         raise TypeError('float32 rows [N,D] and int32 order / seg_off expected')
     if order.dim() != 1 or seg_off.dim() != 1 or seg_off.numel() < 1:
@@ -586,7 +649,7 @@ def ivf_probe_tables(list_off, probe, col_off):
     pairs = (pair_off[1:] - pair_off[:-1]).long()
     per_list = ((lens + 255) // 256) * ((pairs + 31) // 32)
     item_off = torch.cat([per_list.new_zeros(1), torch.cumsum(per_list, 0)])
-    ends = col_off.long() + torch.where(probe >= 0, lens[probe.long().clamp(min=0)], lens.new_zeros(()))
+    ends = _slot_ends(lens, probe, col_off)
     reach = ends.max().reshape(1) if ends.numel() else item_off[:1]
     items, reach = torch.cat([item_off[-1:], reach]).tolist()             # the one synchronisation
     if items > 0x7fffffff:
@@ -608,55 +671,25 @@ def ivf_scan(qcodes, qscales, codes, scales, ids, list_off, probe, col_off, D, w
     The inverted probe table the kernel walks (pairs grouped by list, workgroups per list) comes from ivf_probe_tables,
     which synchronises with the host ONCE, to learn the grid and the width; tables: its result for these list_off, probe
     and col_off, when the caller has it already (the call then does not synchronise)."""
-    tensors = (qcodes, qscales, codes, scales, ids, list_off, probe, col_off) + (tuple(out) if out is not None else ())
-    for t in tensors:
-        if not t.is_cuda:
-            raise ValueError('device tensor expected')
+    _on_device(qcodes, qscales, codes, scales, ids, list_off, probe, col_off, *(out or ()))
     if qcodes.dtype != torch.int8 or codes.dtype != torch.int8 or qcodes.dim() != 2 or codes.dim() != 2:
         raise TypeError('int8 codes [rows, ldc] expected')
     if qscales.dtype != torch.float32 or scales.dtype != torch.float32:
         raise TypeError('float32 scales expected')
-    if any(t.dtype != torch.int32 for t in (ids, list_off, probe, col_off)):
-        raise TypeError('int32 ids, list_off, probe and col_off expected')
-    D = int(D)
     Q, N = qcodes.shape[0], codes.shape[0]
+    nlist = _list_tables(Q, N, ids, list_off, probe, col_off)
+    D = int(D)
     ldc = (D + 63) // 64 * 64
     if D < 1 or D > index_i8_max_dim() or qcodes.shape[1] < ldc or codes.shape[1] < ldc:
         raise ValueError('codes of a width of at least D rounded up to 64 expected, 1 <= D <= %d' % index_i8_max_dim())
-    if qscales.dim() != 1 or scales.dim() != 1 or ids.dim() != 1 or qscales.numel() != Q or scales.numel() != N or ids.numel() != N:
-        raise ValueError('qscales [Q], scales [N] and ids [N] expected for codes of Q and N rows')
-    if list_off.dim() != 1 or list_off.numel() < 2:
-        raise ValueError('list_off [nlist+1] expected')
-    nlist = int(list_off.numel()) - 1
-    if probe.dim() != 2 or probe.shape[0] != Q or tuple(col_off.shape) != tuple(probe.shape):
-        raise ValueError('probe [Q,nprobe] and col_off [Q,nprobe] expected')
-
-    def aligned(c):
-        c, ld = _rows_pitch(c, ldc)
-        if ld % 16 or c.data_ptr() % 16:
-            c, ld = c[:, :ldc].contiguous(), ldc
-        return c, ld
-    qcodes, ldq = aligned(qcodes)
-    codes, ldb = aligned(codes)
+    if qscales.dim() != 1 or scales.dim() != 1 or qscales.numel() != Q or scales.numel() != N:
+        raise ValueError('qscales [Q] and scales [N] expected for codes of Q and N rows')
+    qcodes, ldq = _i8_codes(qcodes, ldc)
+    codes, ldb = _i8_codes(codes, ldc)
     qscales, scales, ids, list_off = qscales.contiguous(), scales.contiguous(), ids.contiguous(), list_off.contiguous()
-    dev = codes.device
     pair_off, pair_q, pair_col, item_off, items, reach = tables if tables is not None else ivf_probe_tables(list_off, probe, col_off)
     width = reach if width is None else int(width)
-    if out is None:
-        scores = torch.empty(Q, width, dtype=torch.float32, device=dev)
-        out_ids = torch.empty(Q, width, dtype=torch.int32, device=dev)
-        lds = width
-    else:
-        scores, out_ids = out
-        if scores.dtype != torch.float32 or out_ids.dtype != torch.int32:
-            raise TypeError('out: float32 scores and int32 ids expected')
-        for t in (scores, out_ids):
-            if t.dim() != 2 or t.shape[0] != Q or t.shape[1] < width or (Q > 1 and (t.stride(1) != 1 or t.stride(0) < width)) or (
-                    Q <= 1 and not t.is_contiguous()):
-                raise ValueError('out: [Q, >= width] tensors with unit column stride expected')
-        if Q > 1 and scores.stride(0) != out_ids.stride(0) or (Q <= 1 and scores.shape[1] != out_ids.shape[1]):
-            raise ValueError('out: scores and ids of one row pitch expected')
-        lds = int(scores.stride(0)) if Q > 1 else int(scores.shape[1])
+    scores, out_ids, lds = _scan_out(out, Q, width, codes.device)
     if Q and width:
         call('dir_ivf_scan_i8', ptr(qcodes), ldq, ptr(qscales), Q, ptr(codes), ldb, ptr(scales), ptr(ids), N, D, ptr(list_off),
              nlist, ptr(pair_off), ptr(pair_q), ptr(pair_col), ptr(item_off), items, ptr(scores),
@@ -665,37 +698,37 @@ def ivf_scan(qcodes, qscales, codes, scales, ids, list_off, probe, col_off, D, w
 
 
 # ---- the product-quantised index (csrc/pq.hip) -------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)     # a constant of the library: asked once, not in every call of a search
 def pq_max_m():
     """The largest number of sub-spaces a product quantiser takes (dir_pq_max_m; host-only)."""
     return int(_lib.load().dir_pq_max_m())
 
 
-def _pq_codebooks(codebooks, D=None):
-    """codebooks [M, 256, dsub] fp32 CUDA, contiguous -> (codebooks, M, D)"""
-    if not codebooks.is_cuda:
-        raise ValueError('device tensor expected')
+def _pq_codebooks(codebooks, D):
+    """codebooks [M, 256, dsub] fp32 CUDA for rows of D = M * dsub values, D within the index's bound -> (codebooks,
+    contiguous, M)"""
+    _on_device(codebooks)
     if codebooks.dtype != torch.float32 or codebooks.dim() != 3 or codebooks.shape[1] != 256 or codebooks.shape[2] < 1:
         raise TypeError('float32 codebooks [M, 256, dsub] expected')
     M = int(codebooks.shape[0])
     if M < 1 or M > pq_max_m():
         raise ValueError('1 <= M <= %d expected, got %d' % (pq_max_m(), M))
-    if D is not None and int(D) != M * int(codebooks.shape[2]):
+    if int(D) != M * int(codebooks.shape[2]):
         raise ValueError('rows of M * dsub = %d values expected, got %d' % (M * int(codebooks.shape[2]), D))
-    return codebooks.contiguous(), M, M * int(codebooks.shape[2])
+    if D > index_i8_max_dim():
+        raise ValueError('D <= %d expected, got %d' % (index_i8_max_dim(), D))
+    return codebooks.contiguous(), M
 
 
 def pq_encode(X, codebooks):
     """fp32 rows -> codes uint8 [N, ldc] CUDA (dir_pq_encode; include/dir_engine.h gives the definition): byte m of a row
     is its nearest of the 256 centroids of sub-space m, ldc = M rounded up to a multiple of 4, the padding bytes zero.
     X [N,D] fp32 CUDA with unit column stride and any row pitch; codebooks [M, 256, D / M] fp32 CUDA."""
-    if not X.is_cuda:
-        raise ValueError('device tensor expected')
+    _on_device(X)
     if X.dtype != torch.float32 or X.dim() != 2:
         raise TypeError('float32 rows [N,D] expected')
     N, D = X.shape
-    codebooks, M, _ = _pq_codebooks(codebooks, D)
-    if D > index_i8_max_dim():
-        raise ValueError('D <= %d expected, got %d' % (index_i8_max_dim(), D))
+    codebooks, M = _pq_codebooks(codebooks, D)
     X, ldx = _rows_pitch(X, D)
     ldc = (M + 3) // 4 * 4
     codes = torch.empty(N, ldc, dtype=torch.uint8, device=X.device)
@@ -707,14 +740,11 @@ def pq_encode(X, codebooks):
 def pq_lut(queries, codebooks):
     """The tables of every query, lut [Q, M, 256] fp32 CUDA (dir_pq_lut): lut[q][m][j] = <sub-vector m of query q,
     centroid j of sub-space m>, accumulated in fp32 in column order.  queries [Q,D] fp32 CUDA with unit column stride."""
-    if not queries.is_cuda:
-        raise ValueError('device tensor expected')
+    _on_device(queries)
     if queries.dtype != torch.float32 or queries.dim() != 2:
         raise TypeError('float32 queries [Q,D] expected')
     Q, D = queries.shape
-    codebooks, M, _ = _pq_codebooks(codebooks, D)
-    if D > index_i8_max_dim():
-        raise ValueError('D <= %d expected, got %d' % (index_i8_max_dim(), D))
+    codebooks, M = _pq_codebooks(codebooks, D)
     queries, ldq = _rows_pitch(queries, D)
     lut = torch.empty(Q, M, 256, dtype=torch.float32, device=queries.device)
     if Q:
@@ -727,9 +757,7 @@ def pq_scan(lut, codes, out=None):
     order m = 0 .. M - 1, one defined number per pair.  lut [Q, M, 256] fp32 CUDA as pq_lut gives it; codes [N, >= M]
     uint8 CUDA as pq_encode gives them (row slices included).  out: a [Q, >= N] fp32 CUDA tensor with unit column stride
     to write into (its first N columns are returned; the others keep what they hold)."""
-    for t in (lut, codes) + ((out,) if out is not None else ()):
-        if not t.is_cuda:
-            raise ValueError('device tensor expected')
+    _on_device(lut, codes, out)
     if lut.dtype != torch.float32 or lut.dim() != 3 or lut.shape[2] != 256:
         raise TypeError('float32 lut [Q, M, 256] expected')
     if codes.dtype != torch.uint8 or codes.dim() != 2:
@@ -739,17 +767,8 @@ def pq_scan(lut, codes, out=None):
     if M < 1 or M > pq_max_m() or codes.shape[1] < M:
         raise ValueError('codes of at least M bytes a row expected, 1 <= M <= %d' % pq_max_m())
     lut = lut.contiguous()
-    codes, ldc = _rows_pitch(codes, M)
-    if ldc % 4 or codes.data_ptr() % 4:
-        padded = torch.zeros(N, (M + 3) // 4 * 4, dtype=torch.uint8, device=codes.device)
-        padded[:, :M] = codes[:, :M]
-        codes, ldc = padded, int(padded.shape[1])
-    if out is None:
-        out = torch.empty(Q, N, dtype=torch.float32, device=codes.device)
-    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != Q or out.shape[1] < N or (
-            Q > 1 and (out.stride(1) != 1 or out.stride(0) < N)) or (Q <= 1 and not out.is_contiguous()):
-        raise ValueError('out: float32 [Q, >= N] with unit column stride expected')
-    lds = int(out.stride(0)) if Q > 1 else int(out.shape[1])
+    codes, ldc = _u8_codes(codes, M)
+    out, lds = _score_out(out, Q, N, codes.device)
     if Q and N:
         call('dir_pq_scan', ptr(lut), Q, M, ptr(codes), ldc, N, ptr(out), lds, stream_ptr())
     return out[:, :N]
@@ -766,9 +785,7 @@ def ivfpq_base(queries, centroids, probe, M):
     [q][p]]> as M partial sums - the chain over the D / M columns of sub-space m, in column order - added in the order
     m = 0 .. M - 1 (include/dir_engine.h); NaN for a slot of -1.  queries [Q,D] and centroids [nlist,D] fp32 CUDA with unit
     column stride and any row pitch; probe [Q,nprobe] int32 CUDA with entries in [-1, nlist)."""
-    for t in (queries, centroids, probe):
-        if not t.is_cuda:
-            raise ValueError('device tensor expected')
+    _on_device(queries, centroids, probe)
     if queries.dtype != torch.float32 or centroids.dtype != torch.float32 or queries.dim() != 2 or centroids.dim() != 2:
         raise TypeError('float32 queries [Q,D] and centroids [nlist,D] expected')
     if probe.dtype != torch.int32:
@@ -804,57 +821,25 @@ def ivfpq_scan(lut, base, codes, ids, list_off, probe, col_off, width=None, out=
     from the device (the one host synchronisation; a caller that knows its width passes it and has none).
     out: (scores, out_ids) [Q, >= width] with unit column stride and ONE row pitch to write into; columns at or past
     width keep what they hold."""
-    tensors = (lut, base, codes, ids, list_off, probe, col_off) + (tuple(out) if out is not None else ())
-    for t in tensors:
-        if not t.is_cuda:
-            raise ValueError('device tensor expected')
+    _on_device(lut, base, codes, ids, list_off, probe, col_off, *(out or ()))
     if lut.dtype != torch.float32 or lut.dim() != 3 or lut.shape[2] != 256:
         raise TypeError('float32 lut [Q, M, 256] expected')
     if codes.dtype != torch.uint8 or codes.dim() != 2:
         raise TypeError('uint8 codes [N, ldc] expected')
-    if base.dtype != torch.float32:
-        raise TypeError('float32 base expected')
-    if any(t.dtype != torch.int32 for t in (ids, list_off, probe, col_off)):
-        raise TypeError('int32 ids, list_off, probe and col_off expected')
     Q, M = int(lut.shape[0]), int(lut.shape[1])
     N = int(codes.shape[0])
+    nlist = _list_tables(Q, N, ids, list_off, probe, col_off, base)
     if M < 1 or M > pq_max_m() or codes.shape[1] < M:
         raise ValueError('codes of at least M bytes a row expected, 1 <= M <= %d' % pq_max_m())
-    if ids.dim() != 1 or ids.numel() != N:
-        raise ValueError('ids [N] expected for codes of N rows')
-    if list_off.dim() != 1 or list_off.numel() < 2:
-        raise ValueError('list_off [nlist+1] expected')
-    nlist = int(list_off.numel()) - 1
-    if probe.dim() != 2 or probe.shape[0] != Q or tuple(col_off.shape) != tuple(probe.shape) or tuple(base.shape) != tuple(probe.shape):
-        raise ValueError('probe, col_off and base [Q,nprobe] expected')
     nprobe = int(probe.shape[1])
     lut = lut.contiguous()
-    codes, ldc = _rows_pitch(codes, M)
-    if ldc % 4 or codes.data_ptr() % 4:
-        padded = torch.zeros(N, (M + 3) // 4 * 4, dtype=torch.uint8, device=codes.device)
-        padded[:, :M] = codes[:, :M]
-        codes, ldc = padded, int(padded.shape[1])
+    codes, ldc = _u8_codes(codes, M)
     base, ids, list_off, probe, col_off = (t.contiguous() for t in (base, ids, list_off, probe, col_off))
     if width is None:
-        lens = (list_off[1:] - list_off[:-1]).long()
-        ends = col_off.long() + torch.where(probe >= 0, lens[probe.long().clamp(min=0)], lens.new_zeros(()))
+        ends = _slot_ends((list_off[1:] - list_off[:-1]).long(), probe, col_off)
         width = int(ends.max()) if ends.numel() else 0
     width = max(int(width), 0)
-    if out is None:
-        scores = torch.empty(Q, width, dtype=torch.float32, device=codes.device)
-        out_ids = torch.empty(Q, width, dtype=torch.int32, device=codes.device)
-        lds = width
-    else:
-        scores, out_ids = out
-        if scores.dtype != torch.float32 or out_ids.dtype != torch.int32:
-            raise TypeError('out: float32 scores and int32 ids expected')
-        for t in (scores, out_ids):
-            if t.dim() != 2 or t.shape[0] != Q or t.shape[1] < width or (Q > 1 and (t.stride(1) != 1 or t.stride(0) < width)) or (
-                    Q <= 1 and not t.is_contiguous()):
-                raise ValueError('out: [Q, >= width] tensors with unit column stride expected')
-        if Q > 1 and scores.stride(0) != out_ids.stride(0) or (Q <= 1 and scores.shape[1] != out_ids.shape[1]):
-            raise ValueError('out: scores and ids of one row pitch expected')
-        lds = int(scores.stride(0)) if Q > 1 else int(scores.shape[1])
+    scores, out_ids, lds = _scan_out(out, Q, width, codes.device)
     if Q and width:
         call('dir_ivfpq_scan', ptr(lut), ptr(base), Q, M, ptr(codes), ldc, ptr(ids), N, ptr(list_off), nlist, ptr(probe),
              ptr(col_off), nprobe, ptr(scores), ptr(out_ids), lds, width, stream_ptr())

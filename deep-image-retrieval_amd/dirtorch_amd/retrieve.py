@@ -28,6 +28,10 @@ from . import datasets, eval_dir, ranking, test_dir
 from . import distributed as ddist
 from .utils.convenient import mkdir
 
+# --index kind -> (its class in dirtorch_amd.index, the flags its constructor takes after the width, whether it is trained)
+INDEX_KINDS = {'int8': ('Int8Index', (), False), 'ivf': ('IVFInt8Index', ('nlist',), True),
+               'pq': ('PQIndex', ('pq_m',), True), 'ivfpq': ('IVFPQIndex', ('nlist', 'pq_m'), True)}
+
 
 def query_keys(db):
     """[key of query q] - get_query_key where the dataset has one, else the key inside its query dataset."""
@@ -65,7 +69,7 @@ def main(argv=None):
         (('--whitenp',), dict(type=float, default=0.25, help='whitening power, default is 0.5 (i.e., the sqrt)')),
         (('--topk',), dict(type=int, default=20, help='neighbours per query')),
         (('--output',), dict(type=str, required=True, help='path of the list: .npz, or text')),
-        (('--index',), dict(type=str, default='', choices=['', 'int8', 'ivf', 'pq', 'ivfpq'], help='scan a quantised copy of the database')),
+        (('--index',), dict(type=str, default='', choices=[''] + list(INDEX_KINDS), help='scan a quantised copy of the database')),
         (('--nlist',), dict(type=int, default=0, help='with --index ivf / ivfpq: the number of k-means lists')),
         (('--nprobe',), dict(type=int, default=1, help='with --index ivf / ivfpq: lists scanned per query')),
         (('--pq-m',), dict(type=int, default=0, help='with --index pq / ivfpq: bytes (sub-spaces) per database image')),
@@ -73,10 +77,10 @@ def main(argv=None):
     ]).parse_args(argv)
     if args.rerank and not args.index:
         raise SystemExit('--rerank needs --index')
-    if args.index in ('ivf', 'ivfpq') and args.nlist < 1:
-        raise SystemExit('--index %s needs --nlist' % args.index)
-    if args.index in ('pq', 'ivfpq') and args.pq_m < 1:
-        raise SystemExit('--index %s needs --pq-m' % args.index)
+    class_name, flags, trained = INDEX_KINDS.get(args.index, ('', (), False))
+    for flag in flags:
+        if getattr(args, flag) < 1:
+            raise SystemExit('--index %s needs --%s' % (args.index, flag.replace('_', '-')))
     iscuda = test_dir.setup_devices(args.gpu)
     qe = {name: (None if val is None else {'k': val[0], 'alpha': val[1]})
           for name, val in (('aqe', args.aqe), ('adba', args.adba))}
@@ -88,28 +92,15 @@ def main(argv=None):
                                           aqe=qe['aqe'], adba=qe['adba'], threads=args.threads,
                                           save_feats=args.save_feats, load_feats=args.load_feats)
     same_set = dataset.get_query_db() is dataset
-    if args.index == 'ivf':
-        from .index import IVFInt8Index
-        idx, vals = IVFInt8Index(bdescs.shape[1], args.nlist).train(bdescs).add(bdescs).search(
-            qdescs, args.topk, nprobe=args.nprobe, rerank=args.rerank, source=bdescs if args.rerank else None,
-            same_set=same_set)
-    elif args.index == 'pq':
-        from .index import PQIndex
-        if bdescs.shape[1] % args.pq_m:
+    if args.index:
+        from . import index as index_classes
+        if 'pq_m' in flags and bdescs.shape[1] % args.pq_m:
             raise SystemExit('--pq-m %d does not divide the descriptor width %d' % (args.pq_m, bdescs.shape[1]))
-        idx, vals = PQIndex(bdescs.shape[1], args.pq_m).train(bdescs).add(bdescs).search(
-            qdescs, args.topk, rerank=args.rerank, source=bdescs if args.rerank else None, same_set=same_set)
-    elif args.index == 'ivfpq':
-        from .index import IVFPQIndex
-        if bdescs.shape[1] % args.pq_m:
-            raise SystemExit('--pq-m %d does not divide the descriptor width %d' % (args.pq_m, bdescs.shape[1]))
-        idx, vals = IVFPQIndex(bdescs.shape[1], args.nlist, args.pq_m).train(bdescs).add(bdescs).search(
-            qdescs, args.topk, nprobe=args.nprobe, rerank=args.rerank, source=bdescs if args.rerank else None,
-            same_set=same_set)
-    elif args.index:
-        from .index import Int8Index
-        idx, vals = Int8Index(bdescs.shape[1]).add(bdescs).search(
-            qdescs, args.topk, rerank=args.rerank, source=bdescs if args.rerank else None, same_set=same_set)
+        index = getattr(index_classes, class_name)(bdescs.shape[1], *(getattr(args, flag) for flag in flags))
+        if trained:
+            index.train(bdescs)
+        idx, vals = index.add(bdescs).search(qdescs, args.topk, rerank=args.rerank, source=bdescs if args.rerank else None,
+                                             same_set=same_set, **(dict(nprobe=args.nprobe) if 'nlist' in flags else {}))
     else:
         idx, vals = ranking.retrieve_device(qdescs, bdescs, args.topk, same_set=same_set)
     idx, vals = idx.cpu().numpy(), vals.cpu().numpy()

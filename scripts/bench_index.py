@@ -50,16 +50,37 @@ def event_ms(fn, inner):
     return e0.elapsed_time(e1) / inner
 
 
-def device_ms(fns, inner, repeats):
-    """[(median, min, max)] per function over `repeats` event timings of `inner` calls; the functions alternate."""
-    for fn in fns:
-        fn()
+def wall_ms(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def alternating(fns, repeats, timer):
+    """[(median, min, max, the result of the warm-up call)] per function over `repeats` timings; the functions alternate inside a repeat"""
+    outs = [fn() for fn in fns]
     torch.cuda.synchronize()
     ts = [[] for _ in fns]
     for _ in range(repeats):
         for i, fn in enumerate(fns):
-            ts[i].append(event_ms(fn, inner))
-    return [(statistics.median(t), min(t), max(t)) for t in ts]
+            ts[i].append(timer(fn))
+    return [(statistics.median(t), min(t), max(t), o) for t, o in zip(ts, outs)]
+
+
+def device_ms(fns, inner, repeats):
+    """[(median, min, max)] per function over `repeats` event timings of `inner` calls; the functions alternate."""
+    return [t[:3] for t in alternating(fns, repeats, lambda fn: event_ms(fn, inner))]
+
+
+def recall(got, ref):
+    """the share of ref's list entries that got's list of the same query holds, in chunks of queries"""
+    hits, rows = 0, max(1, (1 << 26) // (got.shape[1] * ref.shape[1]))
+    for r0 in range(0, got.shape[0], rows):
+        g, e = got[r0:r0 + rows], ref[r0:r0 + rows]
+        hits += int(((g.unsqueeze(2) == e.unsqueeze(1)) & (e.unsqueeze(1) >= 0)).any(dim=1).sum())
+    return hits / max(float((ref >= 0).sum()), 1.0)
 
 
 def wall_s(fn, repeats):

@@ -18,35 +18,15 @@ import json
 import os
 import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'deep-image-retrieval_amd'))
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 sys.path.insert(0, os.path.join(ROOT, 'scripts'))
 import torch
-from bench_index import descriptors, event_ms
+from bench_index import alternating, descriptors, event_ms, wall_ms
 from dirtorch_amd import ops
 from dirtorch_amd.index import IVFInt8Index, Int8Index
-
-
-def alternating(fns, repeats, timer):
-    """[(median, min, max, last result)] per function over `repeats` timings; the functions alternate inside a repeat"""
-    outs = [fn() for fn in fns]
-    torch.cuda.synchronize()
-    ts = [[] for _ in fns]
-    for _ in range(repeats):
-        for i, fn in enumerate(fns):
-            ts[i].append(timer(fn))
-    return [(statistics.median(t), min(t), max(t), o) for t, o in zip(ts, outs)]
-
-
-def wall_ms(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
 
 
 def main():

@@ -23,9 +23,7 @@ draw (bench_ivf.py explains why), so they have relatives in it."""
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'deep-image-retrieval_amd'))
@@ -33,37 +31,9 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 sys.path.insert(0, os.path.join(ROOT, 'scripts'))
 import numpy as np
 import torch
-from bench_index import descriptors, event_ms
+from bench_index import alternating, descriptors, event_ms, recall, wall_ms
 from dirtorch_amd import ops, ranking
 from dirtorch_amd.index import IVFInt8Index, IVFPQIndex, PQIndex
-
-
-def wall_ms(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
-
-
-def alternating(fns, repeats, timer):
-    """[(median, min, max, last result)] per function over `repeats` timings; the functions alternate inside a repeat"""
-    outs = [fn() for fn in fns]
-    torch.cuda.synchronize()
-    ts = [[] for _ in fns]
-    for _ in range(repeats):
-        for i, fn in enumerate(fns):
-            ts[i].append(timer(fn))
-    return [(statistics.median(t), min(t), max(t), o) for t, o in zip(ts, outs)]
-
-
-def recall(got, ref):
-    """the share of ref's list entries that got's list of the same query holds, in chunks of queries"""
-    hits, rows = 0, max(1, (1 << 26) // (got.shape[1] * ref.shape[1]))
-    for r0 in range(0, got.shape[0], rows):
-        g, e = got[r0:r0 + rows], ref[r0:r0 + rows]
-        hits += int(((g.unsqueeze(2) == e.unsqueeze(1)) & (e.unsqueeze(1) >= 0)).any(dim=1).sum())
-    return hits / max(float((ref >= 0).sum()), 1.0)
 
 
 def main():

@@ -17,7 +17,6 @@ Every timing is the median (min .. max) of `--repeats` after a warm-up.  The des
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -26,7 +25,7 @@ sys.path.insert(0, os.path.join(ROOT, 'deep-image-retrieval_amd'))
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 sys.path.insert(0, os.path.join(ROOT, 'scripts'))
 import torch
-from bench_index import descriptors, device_ms
+from bench_index import alternating, descriptors, device_ms, recall, wall_ms
 from dirtorch_amd import ops, ranking
 from dirtorch_amd.index import Int8Index, PQIndex
 
@@ -40,26 +39,8 @@ def once_s(fn):
 
 
 def wall_alternating(fns, repeats):
-    """[(median, min, max, last result)] per function; the functions alternate inside every repeat"""
-    outs = [fn() for fn in fns]
-    ts = [[] for _ in fns]
-    for _ in range(repeats):
-        for i, fn in enumerate(fns):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            outs[i] = fn()
-            torch.cuda.synchronize()
-            ts[i].append(time.perf_counter() - t0)
-    return [(statistics.median(t), min(t), max(t), o) for t, o in zip(ts, outs)]
-
-
-def recall(got, ref):
-    """the share of ref's list entries that got's list of the same query holds, in chunks of queries"""
-    hits, rows = 0, max(1, (1 << 26) // (got.shape[1] * ref.shape[1]))
-    for r0 in range(0, got.shape[0], rows):
-        g, e = got[r0:r0 + rows], ref[r0:r0 + rows]
-        hits += int(((g.unsqueeze(2) == e.unsqueeze(1)) & (e.unsqueeze(1) >= 0)).any(dim=1).sum())
-    return hits / float((ref >= 0).sum())
+    """bench_index.alternating on the synchronised wall clock, in seconds"""
+    return alternating(fns, repeats, lambda fn: wall_ms(fn) / 1e3)
 
 
 def main():

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import index_ref
+from index_util import cuda as _cuda, same as _same
 from synth import synth_descriptors
 from topk_ref import bits, topk_ref_rows
 
@@ -20,19 +21,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 QB, ROWS = 96, 256      # csrc/index_i8.hip: query rows per block, database rows per workgroup
 
 
-def _cuda(a, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
-
-
 def _bits_equal(got, want):
     """the same stored bits, a NaN matching any NaN (which NaN a multiply returns is not part of the definition)"""
     return (bits(got) == bits(want)) | (np.isnan(got) & np.isnan(want))
-
-
-def _same(got, want, what=''):
-    got = tuple(t.cpu().numpy() if torch.is_tensor(t) else t for t in got)
-    assert (got[0] == want[0]).all(), (what, np.argwhere(got[0] != want[0])[:5])
-    assert (bits(got[1]) == bits(want[1])).all(), (what, np.argwhere(bits(got[1]) != bits(want[1]))[:5])
 
 
 # ---- quantize_rows -----------------------------------------------------------------------------------------------------

@@ -13,23 +13,13 @@ import torch
 
 import index_ref
 import ivf_ref
+from index_util import cuda as _cuda, same as _same
 from synth import synth_descriptors
 from topk_ref import bits
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _cuda(a, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
-
-
-def _same(got, want, what=''):
-    got = tuple(t.cpu().numpy() if torch.is_tensor(t) else t for t in got)
-    want = tuple(t.cpu().numpy() if torch.is_tensor(t) else t for t in want)
-    assert (got[0] == want[0]).all(), (what, np.argwhere(got[0] != want[0])[:5])
-    assert (bits(got[1]) == bits(want[1])).all(), (what, np.argwhere(bits(got[1]) != bits(want[1]))[:5])
 
 
 # ---- segment_sums ------------------------------------------------------------------------------------------------------
@@ -259,6 +249,27 @@ def test_probed_search_is_the_restatement(sets, nprobe):
     idx = ivf.search(qq, 10, nprobe=nprobe)[0].cpu().numpy()
     want = ivf_ref.search(qq, b, sets['centroids'], 10, nprobe)
     assert (idx == want[0]).all()
+
+
+def test_search_pads_a_chunk_whose_rows_all_run_short():
+    """Forty rows in four hand-set lists of 10, 4, 14 and 12 (no training), k = 40: with one list probed a query has 4 - 14
+    neighbours, with two 14 - 26, so every chunk of queries is narrower than k and search widens it with empty columns
+    before the top-k.  The lists equal ivf_ref's, ids and value bits with their (-1, NaN) tails, in one chunk and in
+    chunks of two queries."""
+    from dirtorch_amd.index import IVFInt8Index
+    b, q = synth_descriptors(6, 3000, 200)[:40], synth_descriptors(5, 33, 200)[:5]
+    c = b[[0, 10, 20, 30]]
+    index = IVFInt8Index(200, 4)
+    index._set_centroids(_cuda(c))
+    index.add(b)
+    assert index._lens.tolist() == [10, 4, 14, 12] == np.diff(ivf_ref.build(b, c)['list_off']).tolist()
+    for nprobe, least, most in ((1, 4, 14), (2, 14, 26)):
+        want = ivf_ref.search(q, b, c, 40, nprobe)
+        found = (want[0] >= 0).sum(axis=1)
+        assert found.min() == least and found.max() == most and most < 40         # every query runs short
+        assert (want[0][:, most:] == -1).all() and np.isnan(want[1][:, most:]).all()
+        for kw in ({}, dict(scratch_bytes=8 * 40 * 2)):                             # 8 bytes a column, 40 columns: two queries
+            _same(index.search(q, 40, nprobe=nprobe, **kw), want, 'nprobe = %d, %r' % (nprobe, kw))
 
 
 def test_rerank_over_probed_lists(sets):

@@ -12,23 +12,13 @@ import torch
 
 import ivfpq_ref
 import pq_ref
+from index_util import cuda as _cuda, same as _same
 from synth import synth_descriptors
 from topk_ref import bits
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _cuda(a, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
-
-
-def _same(got, want, what=''):
-    got = tuple(t.cpu().numpy() if torch.is_tensor(t) else t for t in got)
-    want = tuple(t.cpu().numpy() if torch.is_tensor(t) else t for t in want)
-    assert (got[0] == want[0]).all(), (what, np.argwhere(got[0] != want[0])[:5])
-    assert (bits(got[1]) == bits(want[1])).all(), (what, np.argwhere(bits(got[1]) != bits(want[1]))[:5])
 
 
 def _bits_ok(got, want):

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import pq_ref
+from index_util import cuda as _cuda, same as _same
 from synth import synth_descriptors
 from topk_ref import bits
 
@@ -23,17 +24,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # second short; dsub = 130: five)
 DM = [(8, 1), (12, 3), (64, 8), (200, 8), (2048, 64), (2048, 128), (256, 128), (80, 2), (130, 1)]
 ENC_ROWS = 256            # rows of an encoder workgroup (eight passes of 32)
-
-
-def _cuda(a, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
-
-
-def _same(got, want, what=''):
-    got = tuple(t.cpu().numpy() if torch.is_tensor(t) else t for t in got)
-    want = tuple(t.cpu().numpy() if torch.is_tensor(t) else t for t in want)
-    assert (got[0] == want[0]).all(), (what, np.argwhere(got[0] != want[0])[:5])
-    assert (bits(got[1]) == bits(want[1])).all(), (what, np.argwhere(bits(got[1]) != bits(want[1]))[:5])
 
 
 def _same_bits(got, want, what=''):
