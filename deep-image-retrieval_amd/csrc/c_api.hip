@@ -468,18 +468,35 @@ static int launch_c3c1(const char* who, const ConvArgs& a, int dtype, void* stre
     return DIR_OK;
 }
 
-int dir_conv_c3c1(const void* t2, const void* w3, const float* bias3, const void* res, void* y, const void* w1,
-                  const float* bias1, void* t1, int B, int H, int W, int P, int P2, int relu3, int relu1, int dtype,
-                  void* stream) {
-    DIR_TRY
+// (keep_stride: ConvArgs::y_keep_stride - 0 from the plain entry points, the caller's from the _keep ones)
+static int conv_c3c1_entry(const void* t2, const void* w3, const float* bias3, const void* res, void* y, const void* w1,
+                           const float* bias1, void* t1, int B, int H, int W, int P, int P2, int relu3, int relu1,
+                           int keep_stride, int dtype, void* stream) {
     ConvArgs a;
     DIR_CHECK(fill_conv_args(a, t2, w3, bias3, res, y, B, H, W, P, 4 * P, 1, 1, 1, 0, H, W, relu3));
     if (!w1 || !bias1 || !t1 || !res) return fail(DIR_ERR_INVALID, "conv_c3c1: null pointer");
     if (dtype != DIR_BF16 && dtype != DIR_FP16) return fail(DIR_ERR_INVALID, "conv_c3c1: bad dtype");
+    if (keep_stride < 0) return fail(DIR_ERR_INVALID, "conv_c3c1: negative keep_stride");
     conv_args_next_conv1(a, (const uint16_t*)w1, nullptr, bias1, (uint16_t*)t1, P2, relu1 ? 1 : 0);
+    a.y_keep_stride = keep_stride;
     if (!conv_c3c1_admissible(a))
-        return fail(DIR_ERR_INVALID, "conv_c3c1: planes must be 64, 128 (P2 = P, or 128 after 64) or 256 (P2 = 256, B*H*W % 64 == 0)");
+        return fail(DIR_ERR_INVALID, "conv_c3c1: planes must be 64, 128 (P2 = P, or 128 after 64) or 256 (P2 = 256, B*H*W % 64 == 0; no keep_stride)");
     return launch_c3c1("conv_c3c1", a, dtype, stream, {t2, w3, res, y, w1, t1, bias3, bias1});
+}
+
+int dir_conv_c3c1(const void* t2, const void* w3, const float* bias3, const void* res, void* y, const void* w1,
+                  const float* bias1, void* t1, int B, int H, int W, int P, int P2, int relu3, int relu1, int dtype,
+                  void* stream) {
+    DIR_TRY
+    return conv_c3c1_entry(t2, w3, bias3, res, y, w1, bias1, t1, B, H, W, P, P2, relu3, relu1, 0, dtype, stream);
+    DIR_CATCH
+}
+
+int dir_conv_c3c1_keep(const void* t2, const void* w3, const float* bias3, const void* res, void* y, const void* w1,
+                       const float* bias1, void* t1, int B, int H, int W, int P, int P2, int relu3, int relu1,
+                       int keep_stride, int dtype, void* stream) {
+    DIR_TRY
+    return conv_c3c1_entry(t2, w3, bias3, res, y, w1, bias1, t1, B, H, W, P, P2, relu3, relu1, keep_stride, dtype, stream);
     DIR_CATCH
 }
 
@@ -499,18 +516,35 @@ int dir_conv_c3c1_ds(const void* t2, const void* x, const void* wcat, const floa
     DIR_CATCH
 }
 
+static int conv_c3c1_wpair_entry(const void* t2, const void* w3, const void* w3_lo, const float* bias3, const void* res, void* y,
+                                 const void* w1, const void* w1_lo, const float* bias1, void* t1, int B, int H, int W, int P2,
+                                 int relu3, int relu1, int keep_stride, void* stream) {
+    ConvArgs a;
+    DIR_CHECK(fill_conv_args(a, t2, w3, bias3, res, y, B, H, W, 64, 256, 1, 1, 1, 0, H, W, relu3));
+    if (!w3_lo || !w1 || !bias1 || !t1 || !res) return fail(DIR_ERR_INVALID, "conv_c3c1_wpair: null pointer");
+    if (keep_stride < 0) return fail(DIR_ERR_INVALID, "conv_c3c1_wpair: negative keep_stride");
+    a.w_lo = (const uint16_t*)w3_lo;
+    conv_args_next_conv1(a, (const uint16_t*)w1, (const uint16_t*)w1_lo, bias1, (uint16_t*)t1, P2, relu1 ? 1 : 0);
+    a.y_keep_stride = keep_stride;
+    if (!conv_c3c1_admissible(a))
+        return fail(DIR_ERR_INVALID, "conv_c3c1_wpair: planes 64; P2 = 64 (w1_lo required) or 128 (w1_lo optional)");
+    return launch_c3c1("conv_c3c1_wpair", a, DIR_FP16, stream, {t2, w3, w3_lo, res, y, w1, w1_lo, t1, bias3, bias1});
+}
+
 int dir_conv_c3c1_wpair(const void* t2, const void* w3, const void* w3_lo, const float* bias3, const void* res, void* y,
                         const void* w1, const void* w1_lo, const float* bias1, void* t1, int B, int H, int W, int P2,
                         int relu3, int relu1, void* stream) {
     DIR_TRY
-    ConvArgs a;
-    DIR_CHECK(fill_conv_args(a, t2, w3, bias3, res, y, B, H, W, 64, 256, 1, 1, 1, 0, H, W, relu3));
-    if (!w3_lo || !w1 || !bias1 || !t1 || !res) return fail(DIR_ERR_INVALID, "conv_c3c1_wpair: null pointer");
-    a.w_lo = (const uint16_t*)w3_lo;
-    conv_args_next_conv1(a, (const uint16_t*)w1, (const uint16_t*)w1_lo, bias1, (uint16_t*)t1, P2, relu1 ? 1 : 0);
-    if (!conv_c3c1_admissible(a))
-        return fail(DIR_ERR_INVALID, "conv_c3c1_wpair: planes 64; P2 = 64 (w1_lo required) or 128 (w1_lo optional)");
-    return launch_c3c1("conv_c3c1_wpair", a, DIR_FP16, stream, {t2, w3, w3_lo, res, y, w1, w1_lo, t1, bias3, bias1});
+    return conv_c3c1_wpair_entry(t2, w3, w3_lo, bias3, res, y, w1, w1_lo, bias1, t1, B, H, W, P2, relu3, relu1, 0, stream);
+    DIR_CATCH
+}
+
+int dir_conv_c3c1_wpair_keep(const void* t2, const void* w3, const void* w3_lo, const float* bias3, const void* res, void* y,
+                             const void* w1, const void* w1_lo, const float* bias1, void* t1, int B, int H, int W, int P2,
+                             int relu3, int relu1, int keep_stride, void* stream) {
+    DIR_TRY
+    return conv_c3c1_wpair_entry(t2, w3, w3_lo, bias3, res, y, w1, w1_lo, bias1, t1, B, H, W, P2, relu3, relu1, keep_stride,
+                                 stream);
     DIR_CATCH
 }
 

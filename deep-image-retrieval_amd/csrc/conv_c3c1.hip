@@ -5,8 +5,13 @@
 //
 // Un-fused, the 4P-wide block output is written by conv3 and read back twice (conv1' and, later, the
 // residual of block b+1).  In layer1 / layer2 both 1x1 convs are HBM-bound (AI 60-100 FLOP/B), and the
-// read by conv1' is a quarter of everything the pair moves: t2 (P) + residual (4P) + out (4P) in,
-// out (4P) + t1' (P) back = 14 P bytes per pixel un-fused, 10 P fused.  Here a persistent 8-wave
+// read by conv1' is the part this kernel removes.  Per pixel, in units of P 16-bit values: t2 (1) + residual (4) in, out (4) +
+// t1' (P2 / P) back.  At a stage exit (ConvArgs::y_keep_stride = s: the next block's 1x1 stride-s downsample is the only reader
+// left of `out`, and it reads the pixels on rows and columns that are multiples of s) only those pixels of `out` are stored,
+// at their places in the full-resolution tensor: 4 / s^2 instead of 4, i.e. layer1 -> layer2 moves 1 + 4 + 1 + 2 = 8 P instead
+// of 11 P.  conv1' still sees every pixel (the LDS out-tile is complete).  `out` may be the residual tensor itself (identity
+// blocks in place): a strip's residual is in registers before that strip is stored, and no other workgroup touches the tile.
+// A persistent 8-wave
 // workgroup keeps BOTH weight matrices in registers (W3: 4P x P, W1: P x 4P; 8 + 8 KB per wave at
 // P = 128), streams 64-pixel tiles of t2, and hands the rounded output tile to conv1' through LDS:
 //
@@ -186,6 +191,19 @@ __global__ void __launch_bounds__(512) conv_c3c1_kernel(const ConvArgs a) {
         const int m0 = tile * BM;
         if (!DS) load_res(tile, 1, rres1);
         const char* xb = smem + cur * XBUF;
+        // stage exit (y_keep_stride = s > 1): bit p = pixel m0 + p of this tile sits on a row and a column of its image that
+        // are multiples of s.  One ballot per tile, kept in scalars; phase A's HBM stores of the other pixels are dropped.
+        uint64_t ykeep = ~0ull;
+        if (!DS && a.y_keep_stride > 1) {
+            const uint32_t m = (uint32_t)(m0 + lane);
+            const uint32_t img = fast_div(m, a.div_ohw_mul, a.div_ohw_shr);
+            const uint32_t rem = m - img * (uint32_t)(a.H * a.W);
+            const uint32_t row = fast_div(rem, a.div_ow_mul, a.div_ow_shr);
+            const uint32_t col = rem - row * (uint32_t)a.W;
+            const uint32_t s = (uint32_t)a.y_keep_stride;
+            ykeep = __ballot(fast_div(row, a.div_keep_mul, a.div_keep_shr) * s == row &&
+                             fast_div(col, a.div_keep_mul, a.div_keep_shr) * s == col);
+        }
 
         // ================= phase A: out = relu(t2 . W3^T + bias3 + res) ================================
 #pragma unroll
@@ -243,10 +261,15 @@ __global__ void __launch_bounds__(512) conv_c3c1_kernel(const ConvArgs a) {
                     u32x4_t ov;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) ov[e] = DT::pack(v[2 * e], v[2 * e + 1]);
-                    __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y, row_off(m0 + j * 32 + mrow), i * 64, 0);
+                    const int p = j * 32 + mrow;
+                    // (a dropped pixel's store goes where a row beyond M goes: the descriptor discards it)
+                    const uint32_t keep16 = (uint32_t)(ykeep >> (j * 32 + pass * 16));   // (scalar: this pass's 16 rows)
+                    // (a wave-uniform branch around the store of a pass without a kept row was measured: the branches cost both
+                    // forms of the kernel 5 % - profiles/seam_stores.txt - so every pass issues its store)
+                    __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y, DS || ((keep16 >> erow) & 1) ? row_off(m0 + p) : kOOB, i * 64, 0);
                     ovf.see(ov);
-                    // the same 16 bytes into the out-tile (B operand of phase B)
-                    const int n = n_wave + i * 32 + ecol, p = j * 32 + mrow;
+                    // the same 16 bytes into the out-tile (B operand of phase B), whether stored to HBM or not
+                    const int n = n_wave + i * 32 + ecol;
                     *(u32x4_t*)(otile + (n >> 6) * (BM * 128) + p * 128 + ((((n & 63) >> 3) ^ ((p >> 1) & 7)) << 4)) = ov;
                 }
                 wave_lds_sync();
@@ -342,6 +365,9 @@ bool conv_c3c1_admissible(const ConvArgs& a) {
     // either a tensor (a.res) or - DS form, planes 64 - the 64-channel block input a.x2, whose
     // downsample weights are concatenated to a.w along K ([Cout][64 + 64]) and biases summed in a.bias
     const bool ds = a.x2 != nullptr;
+    // the stage-exit store (y_keep_stride > 1) exists in the register-stationary forms with a residual tensor only: the DS forms
+    // (here and conv_c3c1lc.hip) open a stage, and conv_seam3.hip stores every pixel - refused, not silently stored in full
+    if (a.y_keep_stride < 0 || (a.y_keep_stride > 1 && (ds || a.Cin == 256))) return false;
 #ifdef DIR_EXPERIMENTS
     if (a.Cin == 256) return conv_seam3_admissible(a);     // layer3: the streamed-weights form (conv_seam3.hip, experiments builds)
 #endif
@@ -366,6 +392,11 @@ static hipError_t launch_c3c1(const ConvArgs& a, hipStream_t stream) {
     if (hipError_t e = ensure_dynamic_lds((const void*)kern, LDS, attr_done); e != hipSuccess) return e;
     ConvArgs b = a;
     b.x_bytes = (uint32_t)((size_t)a.M * a.Cin * 2);   // (not conv_fill_extents: the seam reads t2 as the flat [M][Cin] matrix its GEMM walks)
+    if (a.y_keep_stride > 1) {   // pixel index -> (image, row, column), and which rows / columns are multiples of the stride
+        fastdiv_init((uint32_t)(a.H * a.W), b.div_ohw_mul, b.div_ohw_shr);
+        fastdiv_init((uint32_t)a.W, b.div_ow_mul, b.div_ow_shr);
+        fastdiv_init((uint32_t)a.y_keep_stride, b.div_keep_mul, b.div_keep_shr);
+    }
     const int mt = (a.M + 63) / 64;
     const int ncu = cu_count();
     hipLaunchKernelGGL(kern, dim3(mt < ncu ? mt : ncu), dim3(512), LDS, stream, b);

@@ -54,6 +54,11 @@ struct ConvArgs {
     int flat;                                // 1x1, stride 1, no padding: pixel m reads pixel m
     uint32_t div_ohw_mul, div_ohw_shr;       // exact n / (OH*OW) and n / OW for n < 2^31
     uint32_t div_ow_mul, div_ow_shr;
+    // the fused seam at a stage exit (conv_c3c1.hip): s > 1 = y receives only the pixels with row % s == 0 && col % s == 0 of
+    // each image, at their places in the full-resolution layout - all that the next stage's 1x1 stride-s downsample reads of
+    // it; every other element of y is left as it was.  0 or 1 = every pixel is stored.  (y2 is complete either way.)
+    int y_keep_stride;
+    uint32_t div_keep_mul, div_keep_shr;     // filled by the launcher: exact n / y_keep_stride
 };
 
 // ---- launcher prologue (host half of conv_device.h) ----------------------------------------------------------------------

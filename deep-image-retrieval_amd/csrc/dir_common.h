@@ -70,7 +70,8 @@ struct Env {
     int pair_stages = 1;                         // ..._PAIR_STAGES = 1..4 (validated at finalize)
     bool sim_v1 = false, sim_exact = false;      // ..._SIM_V1 (one-role kernel), ..._SIM_EXACT (fp32 MFMA chain at any size)
     bool experiments = false;                    // ..._EXPERIMENTS: opt-in kernels of an experiments build (conv_ring / conv_seam3)
-    bool no_inplace = false;                     // ..._NO_INPLACE: layers 3-4's identity blocks ping-pong again instead of writing their output in place
+    bool no_inplace = false;                     // ..._NO_INPLACE: the identity blocks ping-pong again instead of writing their output in place
+    bool seam_full_store = false;                // ..._SEAM_FULL_STORE: the seam at a stage exit stores every pixel of the block output again, not only those the next stage's strided downsample reads
     bool no_stem_u8 = false;                     // ..._NO_STEM_U8: DIR_FP16P on the uint8 feed takes the generic paired stem (image pair, three MFMAs per term) again
     bool stem_pair_old = false;                  // ..._STEM_PAIR_OLD: the generic paired stem as conv_pair.hip's stem_pool_pair_persist_kernel (3 x 15 pooled tiles through a 64 KB fp32 conv tile)
     bool stem_u8_prep = false;                   // ..._STEM_U8_PREP: stem_u8.hip reads prep_input_u8's space-to-depth plane again instead of the raw image

@@ -154,7 +154,7 @@ struct dir_engine {
     // downsample folded in as extra K), run_seam launches exactly that
     bool pick_seam(const dir::ConvLayer& c3, const dir::ConvLayer& c1, const uint16_t* t2, const uint16_t* res, uint16_t* y,
                    uint16_t* t1, int B, int H, int W, const uint16_t* block_in, const uint16_t* block_in_lo,
-                   dir::ConvArgs* a) const;
+                   dir::ConvArgs* a, int y_keep_stride = 0) const;
     int run_seam(const dir::ConvLayer& c3, const dir::ConvLayer& c1, const dir::ConvArgs& a, hipStream_t stream);
     // conv3 + the block's 1x1 downsample branch as ONE two-source GEMM (conv_persist.hip DUAL form), in two steps:
     // pick_conv_dual builds the launch's arguments and returns the variant that takes them, or -1 when the block keeps the

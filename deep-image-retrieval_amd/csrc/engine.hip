@@ -60,6 +60,7 @@ static Env read_env() {
     e.sim_exact = on("DIRTORCH_AMD_SIM_EXACT");
     e.experiments = on("DIRTORCH_AMD_EXPERIMENTS");
     e.no_inplace = on("DIRTORCH_AMD_NO_INPLACE");
+    e.seam_full_store = on("DIRTORCH_AMD_SEAM_FULL_STORE");
     e.no_stem_u8 = on("DIRTORCH_AMD_NO_STEM_U8");
     e.stem_u8_wg8 = on("DIRTORCH_AMD_STEM_U8_WG8");
     e.stem_u8_prep = on("DIRTORCH_AMD_STEM_U8_PREP");
@@ -748,13 +749,14 @@ static constexpr long kSeam3MinTiles = 768;   // conv_seam3.hip: three 64-pixel 
 // the downsample that the DS form would fold in).
 bool dir_engine::pick_seam(const ConvLayer& c3, const ConvLayer& c1, const uint16_t* t2, const uint16_t* res, uint16_t* y,
                            uint16_t* t1, int B, int H, int W, const uint16_t* block_in, const uint16_t* block_in_lo,
-                           ConvArgs* ap) const {
+                           ConvArgs* ap, int y_keep_stride) const {
     ConvArgs& a = *ap;
     // DIRTORCH_AMD_C3C1: "0" = never (A/B and bisecting), "force" = whenever the shapes qualify, default =
     // when every persistent workgroup gets at least ~8 pixel tiles to amortise loading both weight sets
     if (sw.c3c1_off) return false;
     conv_args_init(a, layer_geom(c3, B, H, W, H, W), t2, c3.dev.w, c3.dev.bias, res, y);
     a.w_lo = c3.dev.w_lo;       // DIR_FP16P: the weights of layer1's 1x1s are pairs (conv_c3c1.hip WP3 / WP1)
+    a.y_keep_stride = y_keep_stride;   // a stage exit: only the pixels the next block's strided downsample reads (forward decides)
     if (block_in) {   // DS form: the residual is the downsample conv of the block input, folded into this GEMM
         if (!c3.dev.w_ds || c3.Cin != 64) return false;   // (the caller checks the downsample's own shape)
         a.w = c3.dev.w_ds;
@@ -779,7 +781,11 @@ bool dir_engine::pick_seam(const ConvLayer& c3, const ConvLayer& c1, const uint1
 int dir_engine::run_seam(const ConvLayer& c3, const ConvLayer& c1, const ConvArgs& a, hipStream_t stream) {
     const bool ds = a.x2 != nullptr;
     const double macs = (double)a.M * ((double)c3.Cout * (c3.Cin + a.Cin2) + (double)c1.Cout * c1.Cin);
-    const double bytes = 2.0 * ((double)a.M * (c3.Cin + a.Cin2 * (a.x2_lo ? 2 : 1) + (ds ? 1.0 : 2.0) * c3.Cout + c1.Cout) +
+    // (block-output pixels actually stored: all of them, or every y_keep_stride-th row and column of each image)
+    const int ks = a.y_keep_stride > 1 ? a.y_keep_stride : 1;
+    const double m_stored = (double)a.B * ((a.H + ks - 1) / ks) * ((a.W + ks - 1) / ks);
+    const double bytes = 2.0 * ((double)a.M * (c3.Cin + a.Cin2 * (a.x2_lo ? 2 : 1) + (ds ? 0.0 : 1.0) * c3.Cout + c1.Cout) +
+                                m_stored * c3.Cout +
                                 (double)c3.Cout * (c3.Cin + a.Cin2) * (a.w_lo ? 2 : 1) + (double)c1.Cout * c1.Cin * (a.w2_lo ? 2 : 1));
     return profiled(
         [&](std::string& name, std::string& kernel) {   // profile row "layerS.J.c3c1": conv3 of block J + conv1 of block J+1
@@ -900,14 +906,18 @@ int dir_engine::forward(const void* img, int B, int H, int W, int fmt, float* de
         const int oh = conv_out(h, 3, bd.stride, 1), ow = conv_out(w, 3, bd.stride, 1);
         const bool keep = (int)bi == x4_block;
         nxt = keep ? (uint16_t*)(base + p.x4) : (cur == pp[0] ? pp[1] : pp[0]);
-        // The identity blocks of layers 3-4 write their output OVER their input (round 5; DIRTORCH_AMD_NO_INPLACE restores the
+        // The identity blocks of layers 2-4 write their output OVER their input (layers 3-4 since round 5; layer2 - its seams and
+        // its last, plain conv3 - since the stage-exit store; DIRTORCH_AMD_NO_INPLACE restores the
         // ping-pong).  Safe and bit-identical: conv3 reads every residual element it adds before it stores that element - conv_wreg
-        // one strip ahead in registers, conv_persist / the tiled kernels the whole tile before the K loop, the split-K finalize
-        // element by element - and no other workgroup touches it (conv3's INPUT is t2).  Found while pricing Infinity-Cache
+        // and the seam (conv_c3c1.hip) one strip ahead in registers, conv_persist / conv_pair / the tiled kernels the whole tile
+        // before the K loop, the split-K finalize
+        // element by element - and no other workgroup touches it (conv3's INPUT is t2).  Layer1's seams were measured in place as
+        // well and gain nothing (0.499-0.501 against 0.496-0.501 ms, profiles/seam_stores.txt): they keep the ping-pong.
+        // Found while pricing Infinity-Cache
         // residency (profiles/r05_mall_probe.txt: the cache itself buys nothing), kept for what it does in HBM: a
         // read-modify-write stream gets 5.6-5.9 TB/s where a copy gets 5.2-5.4 - layer3's conv3 110 -> 104 us, step 14.03 -> 13.96 ms
         // (A/B on one box) - and layer3's footprint in the workspace halves.
-        if (!sw.no_inplace && desc.bottleneck && bd.down < 0 && !keep && !tuning && convs[bd.conv3].Cin >= 256) nxt = cur;
+        if (!sw.no_inplace && desc.bottleneck && bd.down < 0 && !keep && !tuning && convs[bd.conv3].Cin >= 128) nxt = cur;
         const uint16_t* resid = cur;
         // How a first block's downsample runs is decided here, before anything launches.  In layer1 it can ride in the seam
         // kernel as extra K (conv_c3c1.hip, DS form), if pick_seam says that kernel will run for this shape: the next
@@ -916,6 +926,17 @@ int dir_engine::forward(const void* img, int B, int H, int W, int fmt, float* de
         // large for the kernel, which is left to conv_launch's own 2^31-byte error.  Otherwise the downsample joins conv3 in a
         // two-source GEMM (pick_conv_dual), or else runs as its own launch.
         const bool seam_next = desc.bottleneck && bi + 1 < blocks.size() && !tuning;
+        // A stage exit: when the seam produces the next block's conv1, the only reader left of this block's output is that
+        // block's downsample - 1x1, no padding, stride s > 1: pixel (oh * s, ow * s) for output pixel (oh, ow), in every kernel
+        // that can run it (the two-source forms of conv_wregd / conv_persist / conv_persistlc, or its own launch on conv_igemm's
+        // tiles, conv_small or conv_pair).  The seam then stores only those pixels (ConvArgs::y_keep_stride;
+        // DIRTORCH_AMD_SEAM_FULL_STORE: all of them again).  Not when the output is kept for the FPN head; the last block has no seam.
+        int keep_stride = 0;
+        // (planes <= 128: the register-stationary seam; the experiments builds' layer3 seam stores every pixel)
+        if (seam_next && !keep && !sw.seam_full_store && bd.down < 0 && blocks[bi + 1].down >= 0 && convs[bd.conv3].Cin <= 128) {
+            const ConvLayer& nd = convs[blocks[bi + 1].down];
+            if (nd.R == 1 && nd.S == 1 && nd.pad == 0 && nd.stride > 1) keep_stride = nd.stride;
+        }
         ConvArgs seam;
         bool ds_in_seam = false;
         if (bd.down >= 0 && seam_next && !sw.no_ds_seam && convs[bd.down].Cin == 64 && convs[bd.down].stride == 1)
@@ -938,7 +959,7 @@ int dir_engine::forward(const void* img, int B, int H, int W, int fmt, float* de
             if (dual_variant >= 0) {   // (block output written; the next block's conv1 still has to run)
                 DIR_CHECK(run_conv_dual(convs[bd.conv3], convs[bd.down], dual, dual_variant, stream));
             } else if (seam_next && (ds_in_seam || pick_seam(convs[bd.conv3], convs[blocks[bi + 1].conv1], t2, resid, nxt, t1, B, oh,
-                                                             ow, nullptr, nullptr, &seam))) {
+                                                             ow, nullptr, nullptr, &seam, keep_stride))) {
                 // conv3 + the next block's conv1 in one kernel: the block output is not re-read (conv_c3c1.hip)
                 DIR_CHECK(run_seam(convs[bd.conv3], convs[blocks[bi + 1].conv1], seam, stream));
                 t1_ready = true;

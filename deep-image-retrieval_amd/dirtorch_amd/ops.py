@@ -158,6 +158,44 @@ def conv_c3c1_wpair(t2, w3, bias3, res, w1, bias1, relu3=True, relu1=True):
     return y, t1
 
 
+def _seam_y(y, res):
+    """The caller's block-output tensor (res itself = in place), or a fresh one."""
+    if y is None:
+        return torch.empty_like(res)
+    _need_cuda(y)
+    if y.shape != res.shape or y.dtype != res.dtype:
+        raise ValueError('y must have the shape and dtype of res')
+    return y
+
+
+def conv_c3c1_keep(t2, w3, bias3, res, w1, bias1, keep_stride=0, y=None, relu3=True, relu1=True):
+    """conv_c3c1 as the engine launches it at a stage exit / in place (dir_conv_c3c1_keep): keep_stride = s > 1 stores only the
+    pixels of y on rows and columns that are multiples of s (the rest of y is left untouched: pass a pre-filled y to see it);
+    y = res writes the block output over the residual.  Returns (y, t1); t1 is always complete."""
+    _need_cuda(t2, w3, bias3, res, w1, bias1)
+    B, H, W, P = t2.shape
+    P2 = w1.shape[0]
+    y = _seam_y(y, res)
+    t1 = torch.empty(B, H, W, P2, dtype=t2.dtype, device=t2.device)
+    call('dir_conv_c3c1_keep', ptr(t2), ptr(w3), ptr(bias3), ptr(res), ptr(y), ptr(w1), ptr(bias1), ptr(t1), B, H, W, P, P2,
+         int(bool(relu3)), int(bool(relu1)), int(keep_stride), _dtype_code(t2), stream_ptr())
+    return y, t1
+
+
+def conv_c3c1_wpair_keep(t2, w3, bias3, res, w1, bias1, keep_stride=0, y=None, relu3=True, relu1=True):
+    """... and with paired weights (dir_conv_c3c1_wpair_keep; operands as conv_c3c1_wpair)."""
+    (w3h, w3l), (w1h, w1l) = w3, w1
+    _need_cuda(t2, w3h, w3l, bias3, res, w1h, bias1)
+    B, H, W, P = t2.shape
+    P2 = w1h.shape[0]
+    y = _seam_y(y, res)
+    t1 = torch.empty(B, H, W, P2, dtype=t2.dtype, device=t2.device)
+    call('dir_conv_c3c1_wpair_keep', ptr(t2), ptr(w3h), ptr(w3l), ptr(bias3), ptr(res), ptr(y), ptr(w1h),
+         ptr(w1l) if w1l is not None else None, ptr(bias1), ptr(t1), B, H, W, P2, int(bool(relu3)), int(bool(relu1)),
+         int(keep_stride), stream_ptr())
+    return y, t1
+
+
 def conv_c3c1_ds_wpair(t2, x, wcat, bias, w1, bias1, relu3=True, relu1=True):
     """... and its downsample form (dir_conv_c3c1_ds_wpair): x = (hi, lo) [B,H,W,64] the paired block input,
     wcat = (hi, lo) [256, 128] = [w3 | wds], w1 = (hi, lo) [64, 256] -> (y [B,H,W,256], t1 [B,H,W,64])."""

@@ -109,7 +109,7 @@ const char* dir_version(void);
  * dir_engine_create.  A host that changes one of them afterwards (tests, A/B scripts) calls this to re-read them.  Two lifetimes:
  *   per ENGINE (copied at dir_engine_create; an existing engine keeps what it was created with):  _C3C1, _NO_DS_SEAM, _NO_DUAL,
  *       _REV_CONV1 / _REV_CONV3, _UNFUSED_STEM, _PAIR_ACTS, _PAIR_STAGES (the last two take effect at dir_engine_finalize),
- *       _NO_INPLACE, _NO_STEM_U8, _STEM_U8_SEG, _EXPERIMENTS (which kernels a forward may consider)
+ *       _NO_INPLACE, _SEAM_FULL_STORE, _NO_STEM_U8, _STEM_U8_SEG, _EXPERIMENTS (which kernels a forward may consider)
  *   per PROCESS (read from the current snapshot at every launch, by engines and by the per-op entry points alike):  the kernel
  *       pickers' _NO_PATCHLC / _NO_WREG / _NO_WREGD / _NO_SMALLMAP / _SMALL_K2 / _NO_C3C1LC / _LC1X1 / _X3_K2048 / _NO_PATCHS2 / _PATCHW_PACK / _NO_PATCHW_PACK / _NO_PATCHW / _NO_PATCHW_LC / _NO_X3 / _NO_PATCHS / _NO_PAIR_PATCH / _NO_XCDMAP,
  *       _STEM_V1, _STEM_PAIR_OLD, _STEM_U8_PREP, _STEM_U8_WG8, _SIM_V1, _SIM_EXACT
@@ -291,6 +291,17 @@ int dir_conv_c3c1_wpair(const void* t2, const void* w3, const void* w3_lo, const
 int dir_conv_c3c1_ds_wpair(const void* t2, const void* x, const void* x_lo, const void* wcat, const void* wcat_lo,
                            const float* bias, void* y, const void* w1, const void* w1_lo, const float* bias1, void* t1,
                            int B, int H, int W, int relu3, int relu1, void* stream);
+/* dir_conv_c3c1 / dir_conv_c3c1_wpair as the engine launches them at a stage exit and in place:
+ *   keep_stride = s > 1: y receives only the pixels (b, h, w) with h % s == 0 && w % s == 0, at their places in the
+ *       full-resolution [B,H,W,4P] layout - what a following 1x1 stride-s downsample reads; every other element of y is left
+ *       untouched.  t1 is complete.  keep_stride 0 or 1: every pixel, as the entry points above.
+ *   y may be res itself (an identity block written over its input): the result is the same, bit for bit. */
+int dir_conv_c3c1_keep(const void* t2, const void* w3, const float* bias3, const void* res, void* y, const void* w1,
+                       const float* bias1, void* t1, int B, int H, int W, int P, int P2, int relu3, int relu1,
+                       int keep_stride, int dtype, void* stream);
+int dir_conv_c3c1_wpair_keep(const void* t2, const void* w3, const void* w3_lo, const float* bias3, const void* res, void* y,
+                             const void* w1, const void* w1_lo, const float* bias1, void* t1, int B, int H, int W, int P2,
+                             int relu3, int relu1, int keep_stride, void* stream);
 /* Slow, obviously-correct direct convolution with the same contract (device-side checker). */
 int dir_conv_bn_act_naive(const void* x, const void* w, const float* bias, const void* res,
                           void* y, int B, int H, int W, int Cin, int Cout, int R, int S,
