@@ -1034,6 +1034,20 @@ int dir_expand_descriptors(const float* descs, int n, const float* db, int m, in
     DIR_CATCH
 }
 
+int dir_expand_lists(const float* descs, int ldd, int n, const float* db, int ldb, int m, int D, const int* idx,
+                     const float* vals, int ldl, int k, float alpha, float* out, int ldo, void* stream) {
+    DIR_TRY
+    if (n < 0 || m < 0 || k < 0) return fail(DIR_ERR_INVALID, "expand_lists: negative size");
+    if (D < 1) return fail(DIR_ERR_INVALID, "expand_lists: D < 1");
+    if (ldd < D || ldb < D || ldo < D) return fail(DIR_ERR_INVALID, "expand_lists: ldd, ldb, ldo < D");
+    if (ldl < k) return fail(DIR_ERR_INVALID, "expand_lists: ldl < k");
+    if (!(alpha >= 0.f)) return fail(DIR_ERR_INVALID, "expand_lists: alpha must be non-negative");
+    if (n == 0) return DIR_OK;
+    if (!descs || !db || !out || (k > 0 && (!idx || !vals))) return fail(DIR_ERR_INVALID, "expand_lists: null pointer");
+    return expand_lists(descs, ldd, n, db, ldb, D, idx, vals, ldl, k, alpha, out, ldo, (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_multiscale_pool(const float* x, float* out, int S, int N, int D, int mode, float gemp,
                         void* stream) {
     DIR_TRY

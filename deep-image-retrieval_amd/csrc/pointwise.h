@@ -85,6 +85,9 @@ int ivfpq_scan(const float* lut, const float* base, int Q, int M, const uint8_t*
                int lds, int width, hipStream_t stream);
 int expand_descriptors(const float* descs, int n, const float* db, int m, int D, int k, float alpha,
                        int self_set, float* out, float* sim, size_t sim_bytes, hipStream_t stream);
+// the same expansion from neighbour lists (expand_lists.hip): a gather of k + 1 rows per output row, no score matrix
+int expand_lists(const float* descs, int ldd, int n, const float* db, int ldb, int D, const int* idx, const float* vals,
+                 int ldl, int k, float alpha, float* out, int ldo, hipStream_t stream);
 // scratch (optional): fp32 workspace for the split-K partial sums of shapes with few output tiles; without one
 // the partials live in stream-ordered memory (hipMallocAsync)
 constexpr size_t kGemmSplitKMaxBytes = 64u << 20;

@@ -8,6 +8,8 @@ DIRTORCH_AMD_DEVICE_RANK=1, or `auto` (default) from 50 000 images - the switch 
 applies to the revisited Oxford / Paris datasets - is scored and ranked on the GPU in row chunks
 (ranking.eval_labelled_device) instead of downloading the Q x N score matrix, calling sklearn once per query and
 sorting every row (test_dir.py:153-178).  Every other case IS test_dir.eval_model.
+--expand lists (that device route only; default --expand matrix): --aqe / --adba take their neighbours from exact top-k lists
+and a gather (ranking.expand_device) instead of the n x m score matrix of test_dir.expand_descriptors.
 """
 import json
 import os
@@ -30,10 +32,25 @@ def labelled_on_device(db):
                 and getattr(db, 'labels', None))
 
 
+EXPAND_ROUTES = ('matrix', 'lists')
+EXPAND_FLAG = (('--expand',), dict(type=str, default='matrix', choices=list(EXPAND_ROUTES),
+                                   help='--aqe / --adba from the score matrix (default) or from neighbour lists'))
+
+
 def descriptors(db, net, trfs, pooling='mean', gemp=3, whiten=None, aqe=None, adba=None, threads=8, batch_size=16,
-                save_feats=None, load_feats=None):
+                save_feats=None, load_feats=None, expand='matrix', expand_index=None):
     """(qdescs, bdescs) as test_dir.eval_model prepares them before it scores (test_dir.py:104-143): extracted or
-    loaded, pooled over the scales, L2-normalised, saved, whitened, expanded."""
+    loaded, pooled over the scales, L2-normalised, saved, whitened, expanded.
+    expand='matrix': adba / aqe through test_dir.expand_descriptors (the n x m score matrix; ndarrays come back).
+    expand='lists': through ranking.expand_device - neighbour lists, then a gather; the expanded sets come back as CUDA
+    tensors (no round trip of a large database through the host).  expand_index (lists only): None for exact lists, or a
+    callable bdescs -> (index, search_kw) that returns an index of dirtorch_amd.index holding exactly those rows and the
+    keywords of its search (nprobe, rerank); it is called with the un-augmented database for adba (self-set) and with
+    the database as it is scored for aqe."""
+    if expand not in EXPAND_ROUTES:
+        raise ValueError('expand: one of %s expected, got %r' % (', '.join(EXPAND_ROUTES), expand))
+    if expand_index is not None and expand != 'lists':
+        raise ValueError("expand_index needs expand='lists'")
     query_db = db.get_query_db()
     same_set = query_db is db
     if load_feats:
@@ -53,6 +70,17 @@ def descriptors(db, net, trfs, pooling='mean', gemp=3, whiten=None, aqe=None, ad
     if whiten is not None:
         bdescs = common.whiten_features(tonumpy(bdescs), net.pca, **whiten)
         qdescs = common.whiten_features(tonumpy(qdescs), net.pca, **whiten)
+    if expand == 'lists':
+        def lists_kw(rows):
+            if expand_index is None:
+                return {}
+            index, search_kw = expand_index(rows)
+            return dict(search_kw, index=index)
+        if adba is not None:
+            bdescs = ranking.expand_device(bdescs, **adba, **lists_kw(bdescs))
+        if aqe is not None:
+            qdescs = ranking.expand_device(qdescs, db=bdescs, **aqe, **lists_kw(bdescs))
+        return qdescs, bdescs
     if adba is not None:
         bdescs = test_dir.expand_descriptors(bdescs, **adba)
     if aqe is not None:
@@ -61,16 +89,24 @@ def descriptors(db, net, trfs, pooling='mean', gemp=3, whiten=None, aqe=None, ad
 
 
 def eval_model(db, net, trfs, pooling='mean', gemp=3, detailed=False, whiten=None, aqe=None, adba=None, threads=8,
-               batch_size=16, save_feats=None, load_feats=None, dbg=()):
+               batch_size=16, save_feats=None, load_feats=None, dbg=(), expand='matrix'):
     """test_dir.eval_model, except that a class-labelled dataset under the device-rank switch (labelled_on_device) is
-    ranked on the GPU; `mAP`, `APs`, `top<k>` and `tops` are filled as the host branch fills them."""
+    ranked on the GPU; `mAP`, `APs`, `top<k>` and `tops` are filled as the host branch fills them.  expand='lists'
+    (descriptors above) exists on that device route only: test_dir.eval_model has one expansion, the matrix, and asking
+    it for lists raises instead of quietly running the matrix."""
+    if expand not in EXPAND_ROUTES:
+        raise ValueError('expand: one of %s expected, got %r' % (', '.join(EXPAND_ROUTES), expand))
     if not labelled_on_device(db):
+        if expand != 'matrix' and (aqe is not None or adba is not None):
+            raise ValueError("expand='lists' needs the device route of a class-labelled dataset "
+                             '(DIRTORCH_AMD_DEVICE_RANK=1); test_dir.eval_model expands through the score matrix')
         return test_dir.eval_model(db, net, trfs, pooling=pooling, gemp=gemp, detailed=detailed, whiten=whiten, aqe=aqe,
                                    adba=adba, threads=threads, batch_size=batch_size, save_feats=save_feats,
                                    load_feats=load_feats, dbg=dbg)
     print("\n>> Evaluation...")
     qdescs, bdescs = descriptors(db, net, trfs, pooling=pooling, gemp=gemp, whiten=whiten, aqe=aqe, adba=adba,
-                                 threads=threads, batch_size=batch_size, save_feats=save_feats, load_feats=load_feats)
+                                 threads=threads, batch_size=batch_size, save_feats=save_feats, load_feats=load_feats,
+                                 expand=expand)
     aps, tops = ranking.eval_labelled_device(db, qdescs, bdescs)
     res = {}
     test_dir._mean_ap(aps, detailed, res)
@@ -91,6 +127,7 @@ def main(argv=None):
         (('--aqe',), dict(type=int, nargs='+', help='alpha-query expansion paramenters')),
         (('--adba',), dict(type=int, nargs='+', help='alpha-database augmentation paramenters')),
         (('--whitenp',), dict(type=float, default=0.25, help='whitening power, default is 0.5 (i.e., the sqrt)')),
+        EXPAND_FLAG,
     ]).parse_args(argv)
     iscuda = test_dir.setup_devices(args.gpu)
     qe = {name: (None if val is None else {'k': val[0], 'alpha': val[1]})
@@ -101,7 +138,7 @@ def main(argv=None):
     whiten = test_dir.select_whitening(net, args)
     res = eval_model(dataset, net, args.trfs, pooling=args.pooling, gemp=args.gemp, detailed=args.detailed,
                      threads=args.threads, dbg=args.dbg, whiten=whiten, aqe=qe['aqe'], adba=qe['adba'],
-                     save_feats=args.save_feats, load_feats=args.load_feats)
+                     save_feats=args.save_feats, load_feats=args.load_feats, expand=args.expand)
     if ddist.rank() == 0:
         print(' * ' + '\n * '.join('%s = %g' % kv for kv in res.items() if np.isscalar(kv[1])))
         if args.out_json:

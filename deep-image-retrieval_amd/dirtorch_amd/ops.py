@@ -902,6 +902,35 @@ def expand_descriptors(descs, db=None, alpha=0.0, k=0, scratch_bytes=256 << 20):
     return out
 
 
+def expand_lists(descs, db, idx, vals, alpha):
+    """alpha-QE / DBA from neighbour lists (dir_expand_lists, csrc/expand_lists.hip; include/dir_engine.h gives the
+    definition, tests/expand_ref.py restates it) -> [n,D] fp32 CUDA:
+    out[i] = normalize((descs[i] + sum_t vals[i][t]^alpha * db[idx[i][t]]) / (k + 1)), the picks added in list order.
+    descs [n,D], db [m,D] fp32 CUDA (db may BE descs: the self-set); idx / vals [n,k] int32 / fp32 CUDA as ops.topk or an
+    index's search gives them - entries in [-1, m) are the caller's duty, a -1 slot adds nothing and its vals entry is
+    not read.  Unit column strides, any row pitch; k = 0 normalises descs.  alpha >= 0."""
+    _on_device(descs, db, idx, vals)
+    if descs.dtype != torch.float32 or db.dtype != torch.float32 or idx.dtype != torch.int32 or vals.dtype != torch.float32:
+        raise TypeError('float32 descs / db / vals and int32 idx expected')
+    if descs.dim() != 2 or db.dim() != 2 or idx.dim() != 2 or vals.dim() != 2:
+        raise ValueError('descs [n,D], db [m,D], idx and vals [n,k] expected')
+    n, D = descs.shape
+    m, D2 = db.shape
+    k = idx.shape[1]
+    if D != D2 or idx.shape[0] != n or tuple(vals.shape) != (n, k):
+        raise ValueError('descs [n,D], db [m,D], idx and vals [n,k] expected')
+    descs, ldd = _rows_pitch(descs, D)
+    db, ldb = _rows_pitch(db, D)
+    idx, ldi = _rows_pitch(idx, k) if k else (idx, 0)
+    vals, ldv = _rows_pitch(vals, k) if k else (vals, 0)
+    if ldi != ldv:      # (one pitch for both tables in the C ABI)
+        idx, vals, ldi = idx.contiguous(), vals.contiguous(), k
+    out = torch.empty(n, D, dtype=torch.float32, device=descs.device)
+    call('dir_expand_lists', ptr(descs), ldd, n, ptr(db), ldb, m, D, ptr(idx), ptr(vals), ldi, k, float(alpha), ptr(out), D,
+         stream_ptr())
+    return out
+
+
 def stem_pool(s2d, w_packed, bias, out_hw):
     """Fused stem: s2d image [B,H2,W2,16] + packed 4x4x16 filter -> pooled [B,PH,PW,64];
     out_hw = (OH, OW) of the 7x7 s2 convolution."""

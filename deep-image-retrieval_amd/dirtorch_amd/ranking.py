@@ -246,3 +246,46 @@ def retrieve_device(qdescs, bdescs, k, same_set=False, scratch_bytes=256 << 20, 
                 run_i, run_v = ops.topk(torch.cat([run_v, bv], dim=1), k, ids=torch.cat([run_i, bi], dim=1))
         idx[r0:r1], vals[r0:r1] = run_i, run_v
     return idx, vals
+
+
+# ---- alpha query expansion / database augmentation from neighbour lists --------------------------------------------------
+def expand_device(descs, db=None, alpha=0, k=0, index=None, scratch_bytes=256 << 20, **search_kw):
+    """test_dir.expand_descriptors (dirtorch/test_dir.py:24-44) from neighbour LISTS -> CUDA fp32 [n, D]:
+    out[i] = normalize(mean(descs[i], score^alpha * db[j] for the k neighbours j of descs[i])), without the n x m score
+    matrix of the matrix route (ops.expand_descriptors): the lists are made first, then ops.expand_lists gathers k + 1 rows
+    per output row (include/dir_engine.h gives the arithmetic, tests/expand_ref.py restates it).
+    db=None: the set is expanded against itself (DBA) and a row is not its own neighbour (same_set lists).  k == 0 returns
+    `descs` itself, the reference's contract; a negative k or alpha raises ValueError.
+    index=None: exact lists, retrieve_device(descs, db, k, same_set=...).  Otherwise `index` is one of the four classes of
+    dirtorch_amd.index and already holds exactly the rows of db (of descs for the self-set) - len(index) and index.D are
+    checked, the contents are the caller's word - and the lists are index.search(descs, k, same_set=..., **search_kw);
+    search_kw carries nprobe, rerank and source (source defaults to the rows themselves when rerank is given).  With rerank
+    the weights are fp32 scores; without it they are the index's quantised or table scores, and an inverted file probed
+    too narrowly gives lists that end in empty slots, which add nothing (the mean still divides by k + 1).
+    1 <= k <= min(m, ops.topk_max_k()) is inherited from the list makers; the matrix route keeps its "any k".
+    The one semantic difference from the matrix route: the reference zeroes the diagonal of a self-set, so a row can still
+    pick ITSELF, with weight 0^alpha, when fewer than k other rows score above 0; the list route never picks the row
+    itself and takes the k best other rows whatever their sign."""
+    from .utils.common import _dev
+    k = int(k)
+    if k < 0 or alpha < 0:
+        raise ValueError('k and alpha must be non-negative, got k = %d, alpha = %g' % (k, alpha))
+    if k == 0:
+        return descs
+    same_set = db is None
+    x = _dev(descs)
+    pool_ = x if same_set else _dev(db)
+    if x.dim() != 2 or pool_.dim() != 2 or x.shape[1] != pool_.shape[1]:
+        raise ValueError('descs [n, D] and db [m, D] expected')
+    if index is None:
+        if search_kw:
+            raise TypeError('%s only apply to an index' % ', '.join(sorted(search_kw)))
+        idx, vals = retrieve_device(x, pool_, k, same_set=same_set, scratch_bytes=scratch_bytes)
+    else:
+        if len(index) != pool_.shape[0] or index.D != pool_.shape[1]:
+            raise ValueError('an index over the %d x %d rows of db expected, got %d x %d' % (
+                pool_.shape[0], pool_.shape[1], len(index), index.D))
+        if search_kw.get('rerank') and search_kw.get('source') is None:
+            search_kw = dict(search_kw, source=pool_)
+        idx, vals = index.search(x, k, same_set=same_set, scratch_bytes=scratch_bytes, **search_kw)
+    return ops.expand_lists(x, pool_, idx, vals, float(alpha))

@@ -19,6 +19,11 @@ descriptor width; at least 256 database images); the lists are ranked by the tab
 --index ivfpq --nlist L --nprobe P --pq-m M: an index.IVFPQIndex trained on the database descriptors themselves (L k-means
 lists holding M-byte codes of the residuals; at least max(L, 256) database images); every query scans its P best lists
 only, --rerank as above.
+--expand lists: --adba / --aqe take their neighbours from lists (ranking.expand_device) instead of the n x m score matrix;
+the default, --expand matrix, is test_dir.expand_descriptors.  Without --index the lists are exact (retrieve_device); with
+--index KIND they come from indexes of that kind with the same --nlist / --pq-m / --nprobe / --rerank: --adba from one
+trained and filled on the un-augmented database descriptors (self-set), --aqe from the index over the (augmented)
+database that the final search then reuses - it is built once.
 """
 import sys
 
@@ -74,6 +79,7 @@ def main(argv=None):
         (('--nprobe',), dict(type=int, default=1, help='with --index ivf / ivfpq: lists scanned per query')),
         (('--pq-m',), dict(type=int, default=0, help='with --index pq / ivfpq: bytes (sub-spaces) per database image')),
         (('--rerank',), dict(type=int, default=0, help='with --index: shortlist size re-scored in fp32 (0 = none)')),
+        eval_dir.EXPAND_FLAG,
     ]).parse_args(argv)
     if args.rerank and not args.index:
         raise SystemExit('--rerank needs --index')
@@ -88,19 +94,31 @@ def main(argv=None):
     print("Dataset:", dataset)
     net = test_dir.load_model(args.checkpoint, iscuda)
     whiten = test_dir.select_whitening(net, args)
-    qdescs, bdescs = eval_dir.descriptors(dataset, net, args.trfs, pooling=args.pooling, gemp=args.gemp, whiten=whiten,
-                                          aqe=qe['aqe'], adba=qe['adba'], threads=args.threads,
-                                          save_feats=args.save_feats, load_feats=args.load_feats)
-    same_set = dataset.get_query_db() is dataset
     if args.index:
         from . import index as index_classes
-        if 'pq_m' in flags and bdescs.shape[1] % args.pq_m:
-            raise SystemExit('--pq-m %d does not divide the descriptor width %d' % (args.pq_m, bdescs.shape[1]))
-        index = getattr(index_classes, class_name)(bdescs.shape[1], *(getattr(args, flag) for flag in flags))
-        if trained:
-            index.train(bdescs)
-        idx, vals = index.add(bdescs).search(qdescs, args.topk, rerank=args.rerank, source=bdescs if args.rerank else None,
-                                             same_set=same_set, **(dict(nprobe=args.nprobe) if 'nlist' in flags else {}))
+    search_kw = dict(rerank=args.rerank, **(dict(nprobe=args.nprobe) if 'nlist' in flags else {}))
+    built = [None, None]      # the database rows the last index was made from, and that index
+
+    def build_index(rows):
+        """an index of --index's kind over `rows`, trained on them; the one over the same array is handed out again"""
+        if built[0] is not rows:
+            if 'pq_m' in flags and rows.shape[1] % args.pq_m:
+                raise SystemExit('--pq-m %d does not divide the descriptor width %d' % (args.pq_m, rows.shape[1]))
+            index = getattr(index_classes, class_name)(rows.shape[1], *(getattr(args, flag) for flag in flags))
+            if trained:
+                index.train(rows)
+            built[:] = [rows, index.add(rows)]
+        return built[1]
+
+    by_index = args.expand == 'lists' and bool(args.index)
+    qdescs, bdescs = eval_dir.descriptors(dataset, net, args.trfs, pooling=args.pooling, gemp=args.gemp, whiten=whiten,
+                                          aqe=qe['aqe'], adba=qe['adba'], threads=args.threads,
+                                          save_feats=args.save_feats, load_feats=args.load_feats, expand=args.expand,
+                                          expand_index=(lambda rows: (build_index(rows), search_kw)) if by_index else None)
+    same_set = dataset.get_query_db() is dataset
+    if args.index:
+        idx, vals = build_index(bdescs).search(qdescs, args.topk, source=bdescs if args.rerank else None,
+                                               same_set=same_set, **search_kw)
     else:
         idx, vals = ranking.retrieve_device(qdescs, bdescs, args.topk, same_set=same_set)
     idx, vals = idx.cpu().numpy(), vals.cpu().numpy()

@@ -658,6 +658,32 @@ int dir_ivfpq_scan(const float* lut, const float* base, int Q, int M, const uint
  * not finite yields a NaN row (the reference propagates NaN the same way). */
 int dir_expand_descriptors(const float* descs, int n, const float* db, int m, int D, int k, float alpha,
                            int self_set, float* out, float* sim, size_t sim_bytes, void* stream);
+/* The same expansion from neighbour LISTS (expand_lists.hip; dirtorch_amd/ranking.py expand_device; numpy restatement:
+ * tests/expand_ref.py): the k neighbours of every row arrive as dir_topk writes them - exact, or from any of the index
+ * classes - so neither the n x m score matrix nor a selection pass over it exists.  descs [n][ldd], db [m][ldb] and out
+ * [n][ldo] fp32 with any pitch >= D; idx / vals [n][ldl] int32 / fp32, ldl >= k, best first.  The house rule of the index
+ * blocks holds: every number is a chain of single IEEE fp32 operations rounded to nearest, in the stated order (no fused
+ * multiply-add), and a numpy float32 restatement reproduces it bit for bit - except powf, below.
+ *   Weight:  w_t = vals[i][t]^alpha.  alpha an integer in 0 .. 64: w = 1, then alpha times w = w * v (what
+ *     expand_rows_kernel does); otherwise powf(v, alpha), the one step that is not bit-defined.
+ *   Sum:  acc_d = descs[i][d]; for t = 0 .. k - 1 ascending with idx[i][t] >= 0:  acc_d = acc_d + (db[idx[i][t]][d] * w_t),
+ *     the product rounded, then the sum.  A slot with idx < 0 (a list that ran short) contributes nothing and its vals
+ *     entry is not read; an id outside [-1, m) is undefined (the caller's duty, as ids in dir_topk).
+ *   Mean:  acc_d = acc_d * inv, inv = 1.f / (float)(k + 1): the reference's mean over k + 1 rows, however many slots are
+ *     empty.
+ *   Norm:  column d belongs to lane tau = (d mod 1024) / 4 of 256.  p[tau] = the chain p = p + acc_d * acc_d over the lane's
+ *     columns in ascending d, from +0; then for s = 128, 64, .., 1: p[tau] = p[tau] + p[tau + s] for tau < s;
+ *     out[i][d] = acc_d / sqrtf(p[0]), one division.  A NaN weight or row gives a NaN row, as the reference's arithmetic
+ *     does, and touches no other row.
+ * k == 0 is allowed and normalises descs (idx and vals may then be NULL).  out must not overlap descs or db: with db ==
+ * descs (DBA) other rows still read what a row would overwrite.
+ * One workgroup of 256 threads per output row, no scratch and no atomics; a lane reads its four columns of a span as one
+ * 16-byte load when D % 4 == 0 and descs, db and out are 16-byte aligned with pitches % 4 == 0, as four scalars otherwise;
+ * the rows of four picks are requested before the first is added.  It reads (k + 1) * 4 D bytes per output row.
+ * A negative count, D < 1, a pitch below its minimum, ldl < k, alpha < 0 (or NaN) or a null pointer fail with
+ * DIR_ERR_INVALID before anything is launched; n == 0 is DIR_OK and launches nothing. */
+int dir_expand_lists(const float* descs, int ldd, int n, const float* db, int ldb, int m, int D, const int* idx,
+                     const float* vals, int ldl, int k, float alpha, float* out, int ldo, void* stream);
 
 /* ---- the exchange step ------------------------------------------------------------
  * All-gather of per-GPU descriptor blocks over RCCL / xGMI for ONE process driving several GPUs - the

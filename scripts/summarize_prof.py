@@ -201,6 +201,8 @@ def bench_kernel_name(k):
             'pq_encode_kernel': 'expand_rows_kernel', 'pq_lut_kernel': 'expand_rows_kernel', 'pq_scan_kernel': 'rank_hist_kernel',
             # IVF-PQ: the coarse terms and the query-major scan of the probed lists (csrc/ivfpq.hip; no timed bench.py step launches them)
             'ivfpq_base_kernel': 'expand_rows_kernel', 'ivfpq_scan_kernel': 'rank_hist_kernel',
+            # alpha-QE / DBA from neighbour lists: the row gather (csrc/expand_lists.hip; no timed bench.py step launches it)
+            'expand_lists_kernel': 'expand_rows_kernel',
             'maxpool_kernel': 'maxpool_3x3s2', 'upsample_add_kernel': 'upsample_add',
             'prep_input_f32_kernel': 'prep_input_f32', 'maxpool_f32_kernel': 'maxpool_f32',
             'global_pool_f32_kernel': 'global_pool_f32', 'upsample_add_f32_kernel': 'upsample_add_f32',
