@@ -506,218 +506,7 @@ const ConvVariant& conv_variant(int i) { return kVariants[i]; }
 bool conv_variant_admissible(int v, const ConvArgs& a) {
     return v >= 0 && v < kNumVariants && kVariants[v].admissible != nullptr && kVariants[v].admissible(a);
 }
-
-int conv_splitk_factor(int v, const ConvArgs& a);
-
-static int find_variant(const char* name) {
-    for (int v = 0; v < kNumVariants; ++v)
-        if (strcmp(kVariants[v].name, name) == 0) return v;
-    return -1;
-}
-
-// Heuristic used when a shape has not been autotuned (variable-size images, the reference's real
-// workload).  Distilled from the autotuner's choices on ResNet-101 at 1024^2 (profiles/
-// r01_tuned_variants_b32_1024.txt):
-//   * narrow 3x3 layers (Cin 64) take the LDS-patch kernel, K = 64 layers the long 256x64 tile;
-//   * wide outputs with a real K loop (layer3/4 conv1 + conv2) a 256x256 tile: the persistent
-//     kernel for 1x1, the 16-wave form for 3x3;
-//   * wide outputs with a short K loop (the 256 -> 1024 conv3 of layer3, residual + store bound)
-//     and everything with 128/512 outputs (layer2) the 72 KB / 128-VGPR tiles that fit two
-//     workgroups per CU, so that one's epilogue overlaps the other's K loop;
-// each falling back to smaller pixel tiles until about three quarters of the CU slots get a tile.
-int conv_pick_variant(const ConvArgs& a) {
-    {
-        // layer1's 64 -> 64 3x3: filter resident in LDS, loader / consumer waves (DIRTORCH_AMD_NO_PATCHLC: A/B and bisecting)
-        const bool no_lc = env().no_patchlc;
-        const int v = find_variant("256x64_patchlc3x3");
-        if (!no_lc && v >= 0 && conv_variant_admissible(v, a) &&
-            (long)a.B * ((a.OH + 7) / 8) * ((a.OW + 31) / 32) >= 192)
-            return v;
-    }
-    {
-        // 3x3 stride 2 over 128 channels (layer2.0's conv2, bound by its full-resolution input): the patch kernel with even / odd
-        // column runs - 0.222 -> 0.208 ms standalone at batch 32 (gpurun_out/r6s2b).  Not for the 256 / 512-channel ones of
-        // layer3.0 / 4.0: those are matrix-bound, and one plane in flight per CU costs them 15-25 us against the 16-wave tile (0.174
-        // vs 0.149, 0.152 vs 0.135 ms) - the variant stays a tuner candidate there.  DIRTORCH_AMD_NO_PATCHS2: generic tiles again.
-        const int v = find_variant("256x128_patchs2");
-        if (!env().no_patchs2 && v >= 0 && a.Cin <= 128 && conv_variant_admissible(v, a) &&
-            (long)a.B * ((a.OH + 7) / 8) * ((a.OW + 31) / 32) * (a.Cout / 128) >= 192)
-            return v;
-    }
-    for (int v = 0; v < kNumVariants; ++v)
-        if (kVariants[v].launch == conv_patch3x3_launch && a.Cin == 64 && conv_variant_admissible(v, a)) return v;
-    // the residual 1x1 convs with K <= 256 (layer2/3 conv3): weights stationary in registers, as long
-    // as every persistent workgroup gets at least ~4 pixel tiles to amortise loading them
-    {
-        const bool no_wreg = env().no_wreg;   // A/B and bisecting
-        const int v = find_variant("64x512_wreg1x1");
-        if (!no_wreg && v >= 0 && conv_variant_admissible(v, a) &&
-            (long)ceil_div(a.M, 64) * (a.Cout / 512) >= 1024)
-            return v;
-    }
-    const int T = a.Ktot / 64;
-    struct Cand { const char* name; int wg_per_cu; };
-    Cand c[12];
-    int n = 0;
-    {
-        // 3x3 stride 1 over >= 128 channels (conv2 of layer2 / 3 / 4): 512 pixels x 128 channels per workgroup with
-        // double-buffered 32-channel planes (conv_patchw.hip) - A/B at batch 32 (gpurun_out/pw): layer2 175 -> 153 us,
-        // layer3 133 -> 124 us, layer4 121 -> 113 us.  Falls through (like every candidate) when it is not admissible
-        // or leaves CUs without a tile.
-        const bool no_pw = env().no_patchw;   // A/B and bisecting
-        if (!no_pw && a.R * a.S > 1 && a.Cin >= 128) c[n++] = {"512x128_patch3x3w", 1};
-    }
-    if (T <= 1 || a.Cout % 128 != 0) {
-        c[n++] = {"256x64_w4x1", 1}, c[n++] = {"128x64_w2x2", 1}, c[n++] = {"64x64_w2x1", 1};
-    } else if (a.Cout % 256 == 0 && T >= 6) {
-        // 3x3: 16 waves of 64x64; 1x1: the persistent kernel (falls through when not admissible)
-        // 1x1 without a residual and a very long K loop (the 2048 -> 512 conv1 of layer4): the deep-X ring.
-        // A/B at batch 32 (gpurun_out/r2b): 81 -> 71 us there, but 87 -> 90 us on layer3's 1024 -> 256 -
-        // those are not short of HBM requests in flight, so they keep the 2-slot form.
-        const bool no_x3 = env().no_x3;      // A/B and bisecting
-        // Round 6: the tuner's pick flipped on layer3's 1024 -> 256 conv1 (22 launches; in-place identity blocks and the loader /
-        // consumer 3x3 have changed what runs around it since round 2): 88-90 -> 82-84 us per launch, +0.9 % on the step
-        // (gpurun_out/r6tune32).  256-channel outputs take the deep-X ring from K = 1024; DIRTORCH_AMD_X3_K2048 = the old rule.
-        const bool x3 = a.R * a.S == 1 && !a.res && !no_x3 && (T >= 32 || (T >= 16 && a.Cout <= 256 && !env().x3_k2048));
-        // 3x3 over 256 / 512 channels: the plane-at-a-time patch kernel (conv_patch.hip) - falls through to the
-        // 16-wave implicit-GEMM tile where it is not admissible (stride 2, odd widths) or too few tiles
-        const bool no_ps = env().no_patchs;  // A/B and bisecting
-        if (a.R * a.S > 1 && !no_ps) c[n++] = {"256x256_patch3x3s", 1};
-        // (conv_ring.hip's 128x256_ring1x1 - split loader / consumer waves - ties the persistent kernel on these layers
-        // inside the network, gpurun_out/r3f-r3h: it stays a tuner candidate; an experiments build + DIRTORCH_AMD_EXPERIMENTS=1 puts it first, for A/B)
-#ifdef DIR_EXPERIMENTS
-        if (a.R * a.S == 1 && !a.res && env().experiments) c[n++] = {"128x256_ring1x1", 1};
-#endif
-        if (a.R * a.S == 1 && !a.res && env().lc1x1) c[n++] = {"256x256_lc1x1", 1};   // (A/B: DIRTORCH_AMD_LC1X1)
-        c[n++] = {a.R * a.S > 1 ? "256x256_w4x4" : (x3 ? "256x256_persist1x1_x3" : "256x256_persist1x1"), 1};
-        c[n++] = {"256x256_w4x2", 1}, c[n++] = {"128x128_w2x2", 1};
-        // small M (batch 1 at the deep stages): the 4-slot ring hides the fill latency of a long K
-        // loop; with fewer than ~100 tiles even that leaves CUs idle and split-K takes over
-        c[n++] = {"64x128_w2x2_s4", 1}, c[n++] = {"64x128_w2x2", 1};
-    } else if (a.Cout % 256 == 0 && T >= 3) {
-        c[n++] = {"128x256_w2x4_s3_k32", 2}, c[n++] = {"256x256_w4x2", 1}, c[n++] = {"128x128_w2x2", 1};
-        c[n++] = {"128x64_w2x2", 1}, c[n++] = {"64x64_w2x1", 1};   // short K: more, smaller tiles
-    } else {
-        // strided 3x3 (the first conv2 of layer2): the gather touches every other pixel, so the 128-B K rows of
-        // the BK = 64 tile halve the number of requests per byte (A/B gpurun_out/r2t: 273 -> 224 us)
-        if (a.R * a.S > 1 && a.stride > 1) c[n++] = {"256x128_w4x2_s3", 1};
-        c[n++] = {"256x128_w4x2_s3_k32", 2}, c[n++] = {"128x128_w2x2", 1};
-        c[n++] = {T >= 8 ? "64x128_w2x2_s4" : "64x128_w2x2", 1}, c[n++] = {"64x64_w2x1", 1};
-    }
-    // The small-map regime (round 6, distilled from the tuner at batch 1 / batch 4 of 1024^2 and ResNet-50 at 64 x 224^2,
-    // gpurun_out/r6small): when a long-K layer with 256+ outputs cannot fill the chip with 256-wide tiles and 128 x 128 tiles give
-    // it less than two rounds, 64 x 128 tiles (48 KB: two workgroups per CU, one's fill under the other's MFMAs) are 8-10 %
-    // faster (same box: +0.5 % on the whole step at batch 4 and on config A); below ~250 of those, 64 x 64 tiles on a 4-slot ring
-    // (one per CU at 4 096 pixels x 256 channels, 64 KB so that a second stream's workgroup fits beside it).
-    if (!env().no_smallmap && a.Cout % 256 == 0 && T >= 6 && !(a.R * a.S > 1 && a.Cin >= 128 && !env().no_patchw &&
-                                         conv_patch3x3w_admissible(a) && (long)ceil_div(a.M, 512) * (a.Cout / 128) >= 192)) {
-        const long t256 = (long)ceil_div(a.M, 256) * (a.Cout / 256), t128 = (long)ceil_div(a.M, 128) * (a.Cout / 128);
-        const long t64x128 = (long)ceil_div(a.M, 64) * (a.Cout / 128), t64 = (long)ceil_div(a.M, 64) * (a.Cout / 64);
-        if (t256 < 192 && t128 < 512) {
-            const int v1 = find_variant("64x128_w2x2"), v2 = find_variant("64x64_w2x2_s4"), v3 = find_variant("64x64_small_s4k2");
-            const bool ok2 = v2 >= 0 && conv_variant_admissible(v2, a), ok3 = v3 >= 0 && conv_variant_admissible(v3, a);
-            // Long K loops in this regime (the tuner at batch 4 of 1024^2 and ResNet-50 at 64 x 224^2, scripts/exp_tune_any.py):
-            //   * layer4's 3x3 (K = 4608) with 96-191 tiles of 128 x 128: that tile with split-K (4 096 pixels x 512 channels: 62 -> 38 us
-            //     per launch against the 64 x 128 tile, 3 136 pixels: 38 -> 33) - the small tiles stream the 4.7 MB filter once per 64 pixels;
-            //   * layer4's 2048 -> 512 conv1 (32 K-steps): the 64 x 128 tile on its four-slot ring (33 -> 21 us), not the two-slot one.
-            if (a.R * a.S > 1 && T >= 64 && t128 >= 96 && t128 < 192) {
-                const int v4 = find_variant("128x128_w2x2");
-                if (v4 >= 0 && conv_variant_admissible(v4, a)) return v4;
-            }
-            if (a.R * a.S == 1 && t64x128 >= 256 && t64x128 < 384 && T >= 32) {   // (one workgroup per CU: no second one to hide the fill)
-                const int v5 = find_variant("64x128_w2x2_s4");
-                if (v5 >= 0 && conv_variant_admissible(v5, a)) return v5;
-            }
-            //   * 512+ output channels with 1.25+ rounds of 128 x 128 tiles (config A's layer4 1x1 convs, 392-400 tiles: 20-32 -> 17-24 us): the 64-pixel
-            //     tile streams the wider weight matrix twice as often - those keep the list's 128 x 128 tile.
-            const bool wide_n = a.Cout >= 512 && t128 >= 320;
-            if (!wide_n && t64x128 >= 256 && v1 >= 0 && conv_variant_admissible(v1, a)) return v1;
-            if (t64x128 < 192 && t64 >= 192) {
-                // (conv_small.hip's two-K-steps-per-stage tile is 8 % faster here on ONE stream - batch 1 at 1024^2 777 -> 839 img/s -
-                // and, at 128 KB of LDS, 3-4 % slower on two to four: DIRTORCH_AMD_SMALL_K2 for callers that do not overlap forwards)
-                if (env().small_k2 && ok3) return v3;
-                if (ok2) return v2;
-            }
-            // Below 192 tiles of 64 x 64 the list further down fell to split-K on 64 x 128 tiles - a cliff native-size images sit right
-            // under (683 x 1024: 43 x 64 pixels in layer3 = 172 tiles; the tuner, scripts/exp_batch1_tune.py: 16 -> 10 us per conv1).
-            // conv_small.hip with two K-steps per stage instead, down to 32 tiles (layer4's 2048 -> 512 conv1 at 1024^2: 19 -> 14 us);
-            // gpurun_out/r6b1rules, img/s on 1 / 2 / 4 streams: 683 x 1024 760 / 1128 / 1097 -> 960 / 1330 / 1287, 500 x 375 1010 /
-            // 1590 / 1550 -> 1137 / 2100 / 2094, nothing lost at 1024^2 or 768 x 1024.  (K >= 4096, layer4's 3x3, keeps split-K.)
-            if (t64x128 < 192 && t64 >= 32 && t64 < 192 && T < 64) {
-                if (ok3) return v3;
-                if (ok2) return v2;
-            }
-        }
-    }
-    // Ragged maps (round 6, distilled from the tuner on configs[4]'s three scales, scripts/exp_multiscale_tune.py): the 16 x 32-pixel
-    // patch tile wastes what a map leaves of its last tiles (107^2: 20 %, 54^2: 29 %, 38^2: 53 %) where the implicit-GEMM tile walks
-    // the flattened pixels; both lose the idle part of their last round of workgroups.  With the 16-wave tile at 0.91 of the patch
-    // kernel's rate on full tiles (133 vs 121 us on layer3 at batch 32): 16 x 107^2 x 256 channels 0.70 vs 0.85 -> the flattened tile
-    // (tuner: 216 -> 201 us), 16 x 75^2 0.69 vs 0.63 and 16 x 54^2 0.71 vs 0.65 -> the patch kernel (tuner: the same), 16 x 38^2 x 512
-    // 0.35 vs 0.65 -> the flattened tile.  DIRTORCH_AMD_NO_SMALLMAP switches this off with the other distilled rules.
-    const int v_pw = find_variant("512x128_patch3x3w");
-    long pw_wgs = 0;   // (set when the map fills at least 60 % of its tiles: a 7 x 7 map's one tile per image is no workgroup to count)
-    if (v_pw >= 0 && a.R * a.S > 1 && a.Cin >= 128 && !env().no_patchw && conv_variant_admissible(v_pw, a)) {
-        pw_wgs = (long)a.B * ceil_div(a.OH, 16) * ceil_div(a.OW, 32) * (a.Cout / 128);
-        const double fill = (double)a.M / ((double)(pw_wgs / (a.Cout / 128)) * 512.0);
-        const int v_g = find_variant("256x256_w4x4");
-        if (!env().no_smallmap && a.Cout % 256 == 0 && v_g >= 0 && conv_variant_admissible(v_g, a)) {
-            auto round_eff = [](long wgs) { return (double)wgs / (double)(ceil_div((int)wgs, 256) * 256L); };
-            const long t256 = (long)ceil_div(a.M, 256) * (a.Cout / 256);
-            const double eff_p = fill * round_eff(pw_wgs);
-            const double eff_g = 0.91 * round_eff(t256);
-            if (t256 >= 176 && eff_g > 1.05 * eff_p) return v_g;
-        }
-        if (fill < 0.6) pw_wgs = 0;
-    }
-    int last = -1, prev = -1;
-    for (int i = 0; i < n; ++i) {
-        const int v = find_variant(c[i].name);
-        if (v < 0 || !conv_variant_admissible(v, a)) continue;
-        prev = last;
-        last = v;
-        // (the patch kernel's workgroups are per-image tiles: on a ragged map more than ceil(M / 512))
-        const long tiles = v == v_pw && pw_wgs && !env().no_smallmap ? pw_wgs : (long)ceil_div(a.M, kVariants[v].BM) * (a.Cout / kVariants[v].BN);
-        if (tiles >= 192L * c[i].wg_per_cu) return v;
-    }
-    // nothing fills the chip: the smallest tile, unless it is the split-K fallback of a list whose
-    // deep-ring sibling still gets ~100 workgroups
-    if (prev >= 0 && last >= 0 && kVariants[last].has_splitk &&
-        strcmp(kVariants[prev].name, "64x128_w2x2_s4") == 0 &&
-        (long)ceil_div(a.M, 64) * (a.Cout / 128) >= 96)
-        return prev;
-    return last;
-}
-
-// Two-source form (conv3 + downsample of the first block of layers 2-4): the one kernel that carries it.
-// History: conv_igemm.hip's own 256x256 tile (rounds 2-3: 0.359 / 0.261 / 0.206 ms on the first blocks of layers 2 / 3 / 4 where the
-// persistent ring takes 0.311 / 0.238 / 0.197, bit-identical), a 3-slot 128x256 tile (0.39 / 0.29 / 0.22) and a split loader /
-// consumer ring (0.357 / 0.267 / 0.224) were measured and retired.
-int conv_pick_dual_variant(const ConvArgs& a, bool any_size) {
-    const bool ok = a.x2 && a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0 && a.H == a.OH && a.W == a.OW &&
-                    a.Cin % 64 == 0 && a.Cin2 % 64 == 0 && a.res == nullptr && a.ksplit <= 1;
-    if (!ok) return -1;
-    // (any_size: the op-level entry point runs the form on small shapes too - the tests')
-    // layer2's first block (K = 128 + 256): weights stationary in registers, from ~4 pixel tiles per persistent workgroup
-    // (round 6, A/B at batch 32 in profiles/r06_wregd.txt; DIRTORCH_AMD_NO_WREGD: the DUAL ring again)
-    {
-        const int v = find_variant("64x256_wregd1x1");
-        if (v >= 0 && !env().no_wregd && conv1x1_wregd_admissible(a) &&
-            (any_size || (long)ceil_div(a.M, 64) * (a.Cout / 256) >= 1024))
-            return v;
-    }
-    if (a.Cout % 256 != 0 || (!any_size && (long)ceil_div(a.M, 256) * (a.Cout / 256) < 192)) return -1;
-    // (conv_persistlc.hip - the same ring with loader / consumer wave roles - measured on layers 3-4, gpurun_out/r6lc1x1*: 4-8 % off the
-    // launch by per-layer events, nothing on the whole step in two same-box A/Bs, and 5-15 % SLOWER on the plain 1x1 convs inside the
-    // network; an opt-in (DIRTORCH_AMD_LC1X1) and a tuner candidate, not a default)
-    if (env().lc1x1) {
-        const int vl = find_variant("256x256_lc1x1");
-        if (vl >= 0 && conv1x1_lc_admissible(a)) return vl;
-    }
-    const int v = find_variant("256x256_persist1x1_x3");
-    if (v < 0 || kVariants[v].launch_dual == nullptr) return -1;
-    return v;
-}
+// (conv_pick_variant, conv_pick_dual_variant and conv_splitk_factor - which row a shape takes - are conv_pick.hip's)
 
 // ---- split-K ---------------------------------------------------------------------------------------
 // y = act(sum_z partial[z] + bias (+ res)): the z order is fixed, so the result does not depend on
@@ -756,24 +545,6 @@ __global__ void conv_splitk_finalize_kernel(const float* __restrict__ partial, c
     Ovf<DT> ovf;
     ovf.see(ov);
     ovf.flush(ovf_flag);
-}
-
-size_t conv_splitk_bytes(const ConvArgs& a, int ksplit) {
-    return ksplit > 1 ? (size_t)ksplit * a.M * a.Cout * sizeof(float) : 0;
-}
-
-// When a layer has too few output tiles to give every CU work (batch 1 at the deep stages), the K loop
-// is cut into slices that run as separate workgroups.  Only the implicit-GEMM variants split, only
-// when each slice keeps >= 4 K-steps, and only within the scratch the engine reserves.
-int conv_splitk_factor(int v, const ConvArgs& a) {
-    if (v < 0 || v >= kNumVariants || !kVariants[v].has_splitk || a.Cin == 16) return 1;
-    const ConvVariant& cv = kVariants[v];
-    const long tiles = (long)ceil_div(a.M, cv.BM) * (a.Cout / cv.BN);
-    const int T = a.Ktot / cv.BK;
-    if (tiles > 160 || T < 8) return 1;
-    int s = (int)std::min<long>(std::min<long>(8, 512 / tiles), T / 4);
-    while (s > 1 && conv_splitk_bytes(a, s) > kSplitKMaxBytes) --s;
-    return s < 2 ? 1 : s;
 }
 
 int conv_launch(const ConvArgs& a, int dtype, int variant, hipStream_t stream) {

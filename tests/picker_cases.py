@@ -1,6 +1,6 @@
 """The (tile variant, split-K factor) pairs the conv picker launches, one real layer shape each (a helper module like synth.py).
 
-conv_pick_variant (csrc/conv_igemm.hip) chooses a tile kernel per layer shape and conv_splitk_factor how many K slices it runs
+conv_pick_variant (csrc/conv_pick.hip) chooses a tile kernel per layer shape and conv_splitk_factor how many K slices it runs
 in; the engine launches exactly that pair for every plain convolution it has not tuned.  PICKER_CASES holds one row per pair
 the picker emits on the workloads this project claims (workload_layers), plus the launch forms those shapes do not reach:
 persistent kernels walking several rounds of tiles with a ragged last one, split-K with K-steps that do not divide evenly, and

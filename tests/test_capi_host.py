@@ -400,6 +400,63 @@ def test_host_dispatch_digest_is_unchanged():
     assert h.hexdigest() == DISPATCH_DIGEST
 
 
+# (switches set, without the DIRTORCH_AMD_ prefix) -> SHA-256 over '%s/%d\n' % dir_conv_heuristic of the digest test's shapes
+SWITCH_DIGESTS = {
+    ('NO_PATCHLC',): 'b4db553450a944e7a671fb23b7151c96671a874db72bdc17b0821eec33e34910',
+    ('NO_PATCHS2',): '7d666469c9036cce912937f173e96c3c54e68ded60ce17a9464d554548d879bd',
+    ('NO_WREG',): '82133b9d07b9d8fc6d785085a561e7fbe14330f3ca526b8e4ec6822ace466cf7',
+    ('NO_PATCHW',): '631c5a61f2edb441002378a617a80f5d587e507e02fad602813e4cdc8f855ab6',
+    ('NO_X3',): '9e468971992a90d45b167e1074961e0e1bc80ef2c8ef730e07326e4dfb466e79',
+    ('X3_K2048',): '9b124792cc9ebb50256c0a5e556cba9c5cf119b8b416d2d94ab597bd3c7c8d69',
+    ('NO_PATCHS',): 'a4837a85063c3c2c6eeac8dc7148f4c5ce400baa4f464690e3aab51fc1a5ff72',   # (= no switch at all, on these shapes)
+    ('LC1X1',): '1ccca271cfa43eb25ebcbd23475103ccb5b046ea46db1c3d3f379e8c1f196fc1',
+    ('SMALL_K2',): '99193f34ffcfce8c9f03403f886876818c2118b74ce375a3ea28a0d687a9978e',
+    ('NO_SMALLMAP',): '5f5d4969f80081ebbc8ef3668da1dbbf3617edac1c712173593ed41349c0abee',
+    ('NO_PATCHW', 'NO_PATCHS'): '06939f6bd86bc96bb3a6ef7047902aedc60b55a889055465e0a610cc68d97f04',
+    ('NO_PATCHW', 'NO_SMALLMAP'): '7e0c296616e3c957656ff29316c61340af3b3b2d895dc7b8464c9fe6d7e38b69',
+}
+
+
+def test_host_dispatch_digest_under_each_switch():
+    """The picker under its A/B switches (the digest above covers the default switches only): for each configuration, with
+    only its variables set, SHA-256 over (picked variant, ksplit) of dir_conv_heuristic on the digest test's shapes - the
+    picker and its split factor alone.  The constants were taken from a library built from the commit before the picker moved
+    into conv_pick.hip (a separate worktree of that commit, never the code under test); a picker refactor must leave them
+    alone.  (With no switch set the same digest is a4837a85...: DIRTORCH_AMD_NO_PATCHS alone moves no pick on these shapes.)"""
+    import ctypes
+    import hashlib
+    import picker_cases as P
+    from dirtorch_amd import _lib
+    saved = {k: os.environ.pop(k) for k in list(os.environ) if k.startswith('DIRTORCH_AMD_') and k != 'DIRTORCH_AMD_LIB'}
+    got = {}
+    try:
+        lib = _lib.load()
+        geos = []
+        for B, H, W, Cin, Cout, k, stride, pad, res in list(P.synthetic_grid()) + [l[2:11] for l in P.workload_layers()]:
+            OH, OW = P.out_hw(H, W, k, stride, pad)
+            geos.append((B, H, W, Cin, Cout, k, k, stride, pad, OH, OW, int(res)))
+        out, buf = ctypes.c_int(), ctypes.create_string_buffer(64)
+        pout = ctypes.byref(out)
+        for cfg in SWITCH_DIGESTS:
+            for name in cfg:
+                os.environ['DIRTORCH_AMD_' + name] = '1'
+            try:
+                _lib.reload_env()
+                h = hashlib.sha256()
+                for geo in geos:
+                    assert lib.dir_conv_heuristic(*geo, buf, 64, pout) == 0
+                    h.update(('%s/%d\n' % (buf.value.decode(), out.value)).encode())
+                got[cfg] = h.hexdigest()
+            finally:
+                for name in cfg:
+                    del os.environ['DIRTORCH_AMD_' + name]
+    finally:
+        os.environ.update(saved)
+        _lib.reload_env()
+    assert len(geos) == DISPATCH_SHAPES
+    assert got == SWITCH_DIGESTS, 'the picker moved under: ' + ', '.join('+'.join(c) for c in SWITCH_DIGESTS if got.get(c) != SWITCH_DIGESTS[c])
+
+
 def test_engine_cases_cover_every_launch_form_in_every_regime():
     """tests/engine_cases.py (the engine's seams, two-source GEMMs, paired convs and stems; tests/test_engine_launch_parity_gpu.py
     runs it) against its mirror of the engine's choices and against launch_geometry:
@@ -418,13 +475,13 @@ def test_engine_cases_cover_every_launch_form_in_every_regime():
 
 def test_engine_cases_mirror_the_engine_thresholds():
     """The mirror's thresholds are the engine's: kSeamMinTiles (engine.hip) and conv_pick_dual_variant's unit counts
-    (conv_igemm.hip).  (The GPU gate checks the whole mirror against the engine's launch record.)"""
+    (conv_pick.hip).  (The GPU gate checks the whole mirror against the engine's launch record.)"""
     import engine_cases as E
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'deep-image-retrieval_amd', 'csrc')
     engine = open(os.path.join(csrc, 'engine.hip')).read()
-    igemm = open(os.path.join(csrc, 'conv_igemm.hip')).read()
+    picker = open(os.path.join(csrc, 'conv_pick.hip')).read()
     assert re.search(r'kSeamMinTiles = (\d+);', engine).group(1) == str(E.SEAM_MIN_TILES)
-    dual = igemm[igemm.index('int conv_pick_dual_variant('):]
+    dual = picker[picker.index('int conv_pick_dual_variant('):]
     dual = dual[:dual.index('\n}\n')]
     assert re.search(r'\(a\.Cout / 256\) >= (\d+)\)', dual).group(1) == str(E.WREGD_MIN_UNITS)
     assert re.search(r'\(a\.Cout / 256\) < (\d+)\)', dual).group(1) == str(E.X3_MIN_UNITS)
