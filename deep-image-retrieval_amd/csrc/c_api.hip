@@ -14,6 +14,11 @@ using namespace dir;
 // databases at least this long take the split-bf16 similarity kernel (sim_split.hip)
 static constexpr int kSimSplitMinRows = 32768;
 
+// dir_op_overflow_word: the device word the per-op 16-bit entry points hand their kernels (null = none, as before the hook
+// existed).  Process-wide, not thread-scoped; it never takes part in picking a kernel.
+static std::atomic<int*> g_op_ovf{nullptr};
+static inline int* op_ovf() { return g_op_ovf.load(std::memory_order_relaxed); }
+
 #define DIR_TRY try {
 #define DIR_CATCH                                                   \
     }                                                               \
@@ -34,6 +39,11 @@ const char* dir_version(void) { return "dir_engine 0.1 gfx950"; }
 
 int dir_reload_env(void) {
     dir::reload_env();
+    return DIR_OK;
+}
+
+int dir_op_overflow_word(int* device_word) {
+    g_op_ovf.store(device_word, std::memory_order_relaxed);
     return DIR_OK;
 }
 
@@ -165,6 +175,7 @@ int dir_conv_bn_act_pair(const void* x_hi, const void* x_lo, const void* w_hi, c
     a.w_lo = (const uint16_t*)w_lo;
     a.res_lo = (const uint16_t*)res_lo;
     a.y_lo = (uint16_t*)y_lo;
+    a.ovf = op_ovf();
     return conv_pair_launch(a, (hipStream_t)stream);
     DIR_CATCH
 }
@@ -183,6 +194,7 @@ int dir_conv_pair_dual(const void* t2_hi, const void* t2_lo, const void* x_hi, c
     a.w_lo = (const uint16_t*)wcat_lo;
     a.y_lo = (uint16_t*)y_lo;
     conv_args_second_source(a, (const uint16_t*)x_hi, (const uint16_t*)x_lo, Cin);
+    a.ovf = op_ovf();
     return conv_pair_launch(a, (hipStream_t)stream);
     DIR_CATCH
 }
@@ -204,7 +216,8 @@ int dir_stem_pool_pair(const void* s2d_hi, const void* s2d_lo, const void* w_hi,
     // grid, for even and odd H alike; any other OH / OW would size the grid and the stores beyond the caller's buffers
     if (OH != H2 || OW != W2)
         return fail(DIR_ERR_INVALID, "stem_pool_pair: OH x OW must equal the space-to-depth grid H2 x W2 (conv 7x7 s2 p3)");
-    return stem_pool_pair_launch(s2d_hi, s2d_lo, w_hi, w_lo, bias, y_hi, y_lo, B, H2, W2, OH, OW, (hipStream_t)stream);
+    return stem_pool_pair_launch(s2d_hi, s2d_lo, w_hi, w_lo, bias, y_hi, y_lo, B, H2, W2, OH, OW, (hipStream_t)stream,
+                                 op_ovf());
     DIR_CATCH
 }
 
@@ -233,7 +246,7 @@ int dir_stem_pool_u8(const void* img_u8, const float* w_oihw, const float* bn_sc
     int rc = raw ? DIR_OK : prep_input_u8(img_u8, s2d_ws, B, H, W, (hipStream_t)stream);
     if (rc == DIR_OK)
         rc = stem_pool_u8_launch(raw ? img_u8 : nullptr, s2d_ws, d, d + nw, (const float*)(d + 2 * nw), (const float*)(d + 2 * nw + nb), y_hi, y_lo, B, H, W,
-                                 (hipStream_t)stream, nullptr, seg_tiles);
+                                 (hipStream_t)stream, op_ovf(), seg_tiles);
     e = hipStreamSynchronize((hipStream_t)stream);
     (void)hipFree(d);
     if (rc != DIR_OK) return rc;
@@ -371,7 +384,8 @@ int dir_conv_variant_name(int variant, char* buf, int cap) {
     return DIR_OK;
 }
 
-// Validates the arguments every 16-bit per-op conv shares and builds its ConvArgs (ovf and partial stay null here).
+// Validates the arguments every 16-bit per-op conv shares and builds its ConvArgs (partial stays null here; ovf is the
+// word of dir_op_overflow_word, null unless a host set one).
 static int fill_conv_args(ConvArgs& a, const void* x, const void* w, const float* bias,
                           const void* res, void* y, int B, int H, int W, int Cin, int Cout, int R,
                           int S, int stride, int pad, int OH, int OW, int relu) {
@@ -381,6 +395,7 @@ static int fill_conv_args(ConvArgs& a, const void* x, const void* w, const float
         return fail(DIR_ERR_INVALID, "conv: bad dimension");
     conv_args_init(a, {B, H, W, Cin, Cout, R, S, stride, pad, OH, OW, relu ? 1 : 0}, (const uint16_t*)x, (const uint16_t*)w, bias,
                    (const uint16_t*)res, (uint16_t*)y);
+    a.ovf = op_ovf();
     return DIR_OK;
 }
 
@@ -617,7 +632,7 @@ int dir_stem_pool(const void* s2d, const void* w, const float* bias, void* y, in
         return fail(DIR_ERR_INVALID, "stem_pool: bad argument");
     if (OH != H2 || OW != W2)   // (conv 7x7 s2 p3: (H - 1) / 2 + 1 == (H + 1) / 2 for every H; see dir_stem_pool_pair)
         return fail(DIR_ERR_INVALID, "stem_pool: OH x OW must equal the space-to-depth grid H2 x W2 (conv 7x7 s2 p3)");
-    return stem_pool_launch(s2d, w, bias, y, B, H2, W2, OH, OW, dtype, (hipStream_t)stream);
+    return stem_pool_launch(s2d, w, bias, y, B, H2, W2, OH, OW, dtype, (hipStream_t)stream, op_ovf());
     DIR_CATCH
 }
 
@@ -660,7 +675,7 @@ int dir_upsample_add(const void* x, const void* low, void* y, int B, int H, int 
     DIR_TRY
     if (!x || !low || !y || B <= 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0 || C <= 0)
         return fail(DIR_ERR_INVALID, "upsample_add: bad argument");
-    return upsample_add(x, low, y, B, H, W, h, w, C, dtype, (hipStream_t)stream);
+    return upsample_add(x, low, y, B, H, W, h, w, C, dtype, (hipStream_t)stream, op_ovf());
     DIR_CATCH
 }
 

@@ -75,6 +75,7 @@ SIGNATURES = {
     'dir_stem_pool_pair': (c_int, [c_void_p] * 7 + [c_int] * 5 + [c_void_p]),
     'dir_stem_pool_u8': (c_int, [c_void_p] * 9 + [c_int] * 4 + [c_void_p]),
     'dir_engine_overflow': (c_int, [c_void_p, c_void_p, POINTER(c_int)]),
+    'dir_op_overflow_word': (c_int, [c_void_p]),
     'dir_conv_heuristic': (c_int, [c_int] * 12 + [c_char_p, c_int, POINTER(c_int)]),
     'dir_conv_variant_admissible': (c_int, [c_int] * 13 + [POINTER(c_int)]),
     'dir_conv_variant_splitk': (c_int, [c_int] * 13 + [POINTER(c_int)]),
@@ -188,6 +189,12 @@ def reload_env():
     process (tests, A/B scripts) call this, then build a new engine.  No-op when the library has not been loaded yet."""
     if _lib is not None:
         _lib.dir_reload_env()
+
+
+def set_op_overflow_word(address):
+    """dir_op_overflow_word: the device int32 at `address` (0 / None: none) becomes the overflow word of every 16-bit per-op
+    launch of this PROCESS - a diagnostic hook, not thread-scoped (ops.overflow_watch is the scoped form)."""
+    check(load().dir_op_overflow_word(c_void_p(address or 0)))
 
 
 def check(code):

@@ -39,6 +39,37 @@ def conv_variant_names():
     return out
 
 
+class overflow_watch:
+    """with ops.overflow_watch() as watch: ... - every 16-bit per-op launch inside the block reports into one zeroed device
+    word, as an engine's launches report into the engine's (include/dir_engine.h, dir_engine_overflow): bit 0 = an fp16 store
+    overflowed, bit 1 = a bounded LDS-counter wait ran out.  watch.read() synchronises the device, returns the word as an int
+    and zeroes it (sticky until then).  The hook behind it is process-wide, not thread-scoped, and blocks do not nest: a
+    diagnostic tool for tests.  Leaving the block clears the hook."""
+
+    def __init__(self, device=None):
+        self._device = device
+        self._word = None
+
+    def __enter__(self):
+        self._word = torch.zeros(1, dtype=torch.int32, device=self._device or 'cuda')
+        torch.cuda.synchronize()      # the word is zero before any launch on any stream can report
+        _lib.set_op_overflow_word(self._word.data_ptr())
+        return self
+
+    def read(self):
+        torch.cuda.synchronize()
+        value = int(self._word.item())
+        self._word.zero_()
+        torch.cuda.synchronize()
+        return value
+
+    def __exit__(self, *exc):
+        _lib.set_op_overflow_word(None)
+        torch.cuda.synchronize()      # no kernel that still holds the word outlives it
+        self._word = None
+        return False
+
+
 def pack_conv_weight(w_oihw, dtype=torch.bfloat16):
     """OIHW fp32 -> [Cout][R][S][Cin] 16-bit (what dir_conv_bn_act expects)."""
     return w_oihw.permute(0, 2, 3, 1).contiguous().to(dtype)

@@ -192,6 +192,14 @@ int dir_stem_pool_u8(const void* img_u8, const float* w_oihw, const float* bn_sc
  * Always 0 for DIR_BF16 (fp32's exponent range).  The host mirror raises FloatingPointError naming the
  * DIRTORCH_AMD_DTYPE switch (dirtorch_amd/test_dir.py _check_finite). */
 int dir_engine_overflow(dir_engine* e, void* stream, int* overflowed);
+/* Diagnostic hook: the same word for the PER-OP entry points.  device_word: a zeroed device int the caller owns, or NULL to
+ * clear the hook (the state at load).  While it is set, every 16-bit per-op launch (the conv, split-K, seam, two-source, paired,
+ * stem and upsample-add entry points above and below) hands it to its kernel as an engine hands its own word: bit 0 = an fp16 store
+ * overflowed, bit 1 = a bounded LDS-counter wait ran out.  The caller reads and zeroes the word itself (after synchronising the
+ * streams it launched on) and must clear the hook before it frees the word.  Engines keep their own word and ignore this one.  The
+ * pointer is PROCESS-WIDE, not thread-scoped - a tool for tests, not for concurrent hosts - and never takes part in picking a
+ * kernel: with it unset every launch is what it was without the hook. */
+int dir_op_overflow_word(int* device_word);
 
 /* Tile-variant selection for the implicit-GEMM convolutions: run every admissible variant on each
  * layer shape of a B x H x W forward and keep the fastest (synchronises).  Optional. */
