@@ -159,6 +159,40 @@ int dir_conv_bn_act_f32(const float* x, const float* w, const float* bias, const
     DIR_CATCH
 }
 
+// The fp32 twins of dir_prep_input / dir_maxpool_3x3s2 / dir_global_pool / dir_upsample_add (conv_f32.hip): the same
+// checks and argument order, no dtype.
+int dir_prep_input_f32(const void* img, int fmt, const float* mean3, const float* std3, float* out, int B, int H, int W,
+                       void* stream) {
+    DIR_TRY
+    if (!img || !out || B <= 0 || H <= 0 || W <= 0) return fail(DIR_ERR_INVALID, "prep_input: bad argument");
+    return prep_input_f32(img, fmt, mean3, std3, out, B, H, W, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_maxpool_3x3s2_f32(const float* x, float* y, int B, int H, int W, int C, void* stream) {
+    DIR_TRY
+    if (!x || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0) return fail(DIR_ERR_INVALID, "maxpool: bad argument");
+    return maxpool_3x3s2_f32(x, y, B, H, W, C, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_global_pool_f32(const float* x, float* out, int B, int H, int W, int C, int pooling, float p, float eps,
+                        float center_bias, void* stream) {
+    DIR_TRY
+    if (!x || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0) return fail(DIR_ERR_INVALID, "global_pool: bad argument");
+    return global_pool_f32(x, out, C, B, H, W, C, pooling, p, eps, center_bias, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_upsample_add_f32(const float* x, const float* low, float* y, int B, int H, int W, int h, int w, int C,
+                         void* stream) {
+    DIR_TRY
+    if (!x || !low || !y || B <= 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0 || C <= 0)
+        return fail(DIR_ERR_INVALID, "upsample_add: bad argument");
+    return upsample_add_f32(x, low, y, B, H, W, h, w, C, (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_conv_bn_act_pair(const void* x_hi, const void* x_lo, const void* w_hi, const void* w_lo, const float* bias,
                          const void* res_hi, const void* res_lo, void* y_hi, void* y_lo, int B, int H, int W, int Cin,
                          int Cout, int R, int S, int stride, int pad, int OH, int OW, int relu, void* stream) {

@@ -322,6 +322,64 @@ def upsample_add(x, low):
     return y
 
 
+def _need_f32(*ts):
+    _need_cuda(*ts)
+    for t in ts:
+        if t.dtype != torch.float32:
+            raise TypeError('fp32 tensors expected')
+
+
+def prep_input_f32(img, mean=None, std=None):
+    """prep_input of the strict path (dir_prep_input_f32, conv_f32.hip): the same feeds -> fp32 [B,ceil(H/2),ceil(W/2),16]."""
+    _need_cuda(img)
+    if img.dtype == torch.float32:
+        B, C, H, W = img.shape
+        fmt = _lib.DIR_IMG_F32_NCHW
+    elif img.dtype == torch.uint8:
+        B, H, W, C = img.shape
+        fmt = _lib.DIR_IMG_U8_NHWC
+    else:
+        raise TypeError('image must be float32 NCHW or uint8 NHWC')
+    if C != 3:
+        raise ValueError('3-channel image expected')
+    out = torch.empty(B, (H + 1) // 2, (W + 1) // 2, 16, dtype=torch.float32, device=img.device)
+    m = (ctypes.c_float * 3)(*(mean or (0, 0, 0)))
+    s = (ctypes.c_float * 3)(*(std or (1, 1, 1)))
+    call('dir_prep_input_f32', ptr(img), fmt, m, s, ptr(out), B, H, W, stream_ptr())
+    return out
+
+
+def maxpool_3x3s2_f32(x):
+    """maxpool_3x3s2 on fp32 NHWC, C % 4 == 0 (dir_maxpool_3x3s2_f32)."""
+    _need_f32(x)
+    B, H, W, C = x.shape
+    y = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C, dtype=torch.float32, device=x.device)
+    call('dir_maxpool_3x3s2_f32', ptr(x), ptr(y), B, H, W, C, stream_ptr())
+    return y
+
+
+def global_pool_f32(x, pooling='gem', p=3.0, eps=1e-6, center_bias=0.0):
+    """global_pool on fp32 NHWC, C % 64 == 0 (dir_global_pool_f32)."""
+    _need_f32(x)
+    B, H, W, C = x.shape
+    out = torch.empty(B, C, dtype=torch.float32, device=x.device)
+    call('dir_global_pool_f32', ptr(x), ptr(out), B, H, W, C, POOLING[pooling], float(p), float(eps),
+         float(center_bias), stream_ptr())
+    return out
+
+
+def upsample_add_f32(x, low):
+    """upsample_add on fp32 NHWC, C % 4 == 0 (dir_upsample_add_f32)."""
+    if x.shape[0] != low.shape[0] or x.shape[3] != low.shape[3]:
+        raise ValueError('upsample_add: x and low must share batch and channels')
+    x, low = x.contiguous(), low.contiguous()
+    _need_f32(x, low)
+    B, H, W, C = x.shape
+    y = torch.empty_like(x)
+    call('dir_upsample_add_f32', ptr(x), ptr(low), ptr(y), B, H, W, low.shape[1], low.shape[2], C, stream_ptr())
+    return y
+
+
 def l2norm_rows_(x, eps=1e-12):
     """In place: x[i] /= max(||x[i]||, eps)."""
     _need_cuda(x)

@@ -148,6 +148,17 @@ int dir_forward_features(dir_engine* e, const void* img, int B, int H, int W, in
 int dir_conv_bn_act_f32(const float* x, const float* w, const float* bias, const float* res, float* y, int B, int H,
                         int W, int Cin, int Cout, int R, int S, int stride, int pad, int OH, int OW, int relu,
                         void* stream);
+/* Strict-path pointwise kernels (DIR_F32, csrc/conv_f32.hip): dir_prep_input, dir_maxpool_3x3s2, dir_global_pool and
+ * dir_upsample_add with fp32 NHWC activations - the same contracts, argument order and checks without the dtype; channel
+ * counts are multiples of 4 (maxpool, upsample_add) or 64 (global_pool).  Op-level entry points of what dir_forward runs
+ * after dir_engine_finalize(e, DIR_F32). */
+int dir_prep_input_f32(const void* img, int img_format, const float* mean3, const float* std3, float* out, int B, int H,
+                       int W, void* stream);
+int dir_maxpool_3x3s2_f32(const float* x, float* y, int B, int H, int W, int C, void* stream);
+int dir_global_pool_f32(const float* x, float* out, int B, int H, int W, int C, int pooling, float p, float eps,
+                        float center_bias, void* stream);
+int dir_upsample_add_f32(const float* x, const float* low, float* y, int B, int H, int W, int h, int w, int C,
+                         void* stream);
 /* The paired-fp16 head of DIR_FP16P (csrc/conv_pair.hip).  Every operand is a PAIR of fp16 planes of the ordinary
  * layout, value = hi + lo with hi = fp16(v), lo = fp16(v - hi) (~22 significant bits); every product runs as three fp16
  * MFMAs into one fp32 accumulator (w_hi.x_hi + w_hi.x_lo + w_lo.x_hi).  Replaces, at ~fp32 accuracy,
