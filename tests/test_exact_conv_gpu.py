@@ -19,8 +19,9 @@ The first test anchors the device itself: the naive kernel (plain FMAs) and one 
 MFMA alone to disagree there, v_mfma_f32_32x32x16_{bf16,f16} would not add these terms without loss and the lattice would have to
 shrink.  On the MI355X both reproduce the CPU's bits in bf16 and in fp16, and so does every other kernel below.
 
-Not here: the paired-fp16 entry points (conv_bn_act_pair, conv_pair_dual, conv_c3c1_wpair, conv_c3c1_ds_wpair) - their lattice
-needs lo planes and a budget of its own; a follow-up.
+The paired-fp16 entry points (conv_bn_act_pair, conv_pair_dual, conv_c3c1_wpair, conv_c3c1_ds_wpair, the paired stems) have a
+lattice with lo planes and a budget of its own: tests/exact_pair.py, compared bit for bit in both planes by
+tests/test_exact_pair_gpu.py.
 """
 import functools
 
