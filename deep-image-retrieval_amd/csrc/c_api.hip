@@ -1097,6 +1097,68 @@ int dir_expand_lists(const float* descs, int ldd, int n, const float* db, int ld
     DIR_CATCH
 }
 
+int dir_diffusion_slab_rows(void) { return diffusion_slab_rows(); }
+
+// gamma of the graph and of the seeds: non-negative, not a NaN
+static int diffusion_check_gamma(const char* who, float gamma) {
+    if (!(gamma >= 0.f)) return fail(DIR_ERR_INVALID, std::string(who) + ": gamma must be non-negative");
+    return DIR_OK;
+}
+
+int dir_knn_graph(const int* idx, const float* vals, int ldl, int N, int k, float gamma, float* S, int lds, void* stream) {
+    DIR_TRY
+    if (N < 0 || k < 0) return fail(DIR_ERR_INVALID, "knn_graph: negative size");
+    if (k > topk_max_k()) return fail(DIR_ERR_INVALID, "knn_graph: k exceeds dir_topk_max_k()");
+    if (ldl < k || lds < k) return fail(DIR_ERR_INVALID, "knn_graph: ldl, lds < k");
+    DIR_CHECK(diffusion_check_gamma("knn_graph", gamma));
+    if (N == 0 || k == 0) return DIR_OK;
+    if (!idx || !vals || !S) return fail(DIR_ERR_INVALID, "knn_graph: null pointer");
+    return knn_graph(idx, vals, ldl, N, k, gamma, S, lds, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_diffusion_seed(const int* qidx, const float* qvals, int ldq, int Q, int kq, int N, float gamma, float* Y, int ldy,
+                       void* stream) {
+    DIR_TRY
+    if (Q < 0 || kq < 0 || N < 0) return fail(DIR_ERR_INVALID, "diffusion_seed: negative size");
+    if (kq > topk_max_k()) return fail(DIR_ERR_INVALID, "diffusion_seed: kq exceeds dir_topk_max_k()");
+    if (ldq < kq) return fail(DIR_ERR_INVALID, "diffusion_seed: ldq < kq");
+    if (ldy < Q) return fail(DIR_ERR_INVALID, "diffusion_seed: ldy < Q");
+    DIR_CHECK(diffusion_check_gamma("diffusion_seed", gamma));
+    if (Q == 0 || N == 0) return DIR_OK;
+    if (!Y || (kq > 0 && (!qidx || !qvals))) return fail(DIR_ERR_INVALID, "diffusion_seed: null pointer");
+    return diffusion_seed(qidx, qvals, ldq, Q, kq, N, gamma, Y, ldy, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_diffusion_workspace_bytes(int N, int Q, size_t* bytes) {
+    DIR_TRY
+    if (!bytes) return fail(DIR_ERR_INVALID, "diffusion_workspace_bytes: null pointer");
+    if (N < 0 || Q < 0) return fail(DIR_ERR_INVALID, "diffusion_workspace_bytes: negative size");
+    *bytes = diffusion_workspace_bytes(N, Q);
+    return DIR_OK;
+    DIR_CATCH
+}
+
+int dir_diffusion_solve(const int* idx, int ldl, const float* S, int lds, int N, int k, const float* Y, int ldy, int Q,
+                        float alpha, int iters, float* F, int ldf, void* workspace, size_t workspace_bytes, void* stream) {
+    DIR_TRY
+    if (N < 0 || k < 0 || Q < 0 || iters < 0) return fail(DIR_ERR_INVALID, "diffusion_solve: negative size");
+    if (k > topk_max_k()) return fail(DIR_ERR_INVALID, "diffusion_solve: k exceeds dir_topk_max_k()");
+    if (ldl < k || lds < k) return fail(DIR_ERR_INVALID, "diffusion_solve: ldl, lds < k");
+    if (ldy < Q || ldf < Q) return fail(DIR_ERR_INVALID, "diffusion_solve: ldy, ldf < Q");
+    if (!(alpha >= 0.f && alpha < 1.f)) return fail(DIR_ERR_INVALID, "diffusion_solve: alpha outside [0, 1)");
+    if (N == 0 || Q == 0) return DIR_OK;
+    if (!Y || !F || (k > 0 && (!idx || !S))) return fail(DIR_ERR_INVALID, "diffusion_solve: null pointer");
+    if (iters > 0) {
+        if (!workspace || workspace_bytes < diffusion_workspace_bytes(N, Q))
+            return fail(DIR_ERR_INVALID, "diffusion_solve: workspace smaller than dir_diffusion_workspace_bytes");
+        if ((((uintptr_t)workspace) & 15) != 0) return fail(DIR_ERR_INVALID, "diffusion_solve: a 16-byte aligned workspace expected");
+    }
+    return diffusion_solve(idx, ldl, S, lds, N, k, Y, ldy, Q, alpha, iters, F, ldf, workspace, (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_multiscale_pool(const float* x, float* out, int S, int N, int D, int mode, float gemp,
                         void* stream) {
     DIR_TRY

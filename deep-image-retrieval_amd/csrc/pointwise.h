@@ -88,6 +88,15 @@ int expand_descriptors(const float* descs, int n, const float* db, int m, int D,
 // the same expansion from neighbour lists (expand_lists.hip): a gather of k + 1 rows per output row, no score matrix
 int expand_lists(const float* descs, int ldd, int n, const float* db, int ldb, int D, const int* idx, const float* vals,
                  int ldl, int k, float alpha, float* out, int ldo, hipStream_t stream);
+// diffusion on the kNN graph of the database (diffusion.hip): the mutual, normalised graph in the list layout, the seed
+// columns of a query set, conjugate gradients on (I - alpha S) F = Y for all columns at once
+int knn_graph(const int* idx, const float* vals, int ldl, int N, int k, float gamma, float* S, int lds, hipStream_t stream);
+int diffusion_seed(const int* qidx, const float* qvals, int ldq, int Q, int kq, int N, float gamma, float* Y, int ldy,
+                   hipStream_t stream);
+int diffusion_slab_rows();
+size_t diffusion_workspace_bytes(int N, int Q);
+int diffusion_solve(const int* idx, int ldl, const float* S, int lds, int N, int k, const float* Y, int ldy, int Q, float alpha,
+                    int iters, float* F, int ldf, void* workspace, hipStream_t stream);
 // scratch (optional): fp32 workspace for the split-K partial sums of shapes with few output tiles; without one
 // the partials live in stream-ordered memory (hipMallocAsync)
 constexpr size_t kGemmSplitKMaxBytes = 64u << 20;

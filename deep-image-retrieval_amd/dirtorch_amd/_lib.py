@@ -156,6 +156,12 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_size_t, c_void_p]),
     'dir_expand_lists': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                  c_float, c_void_p, c_int, c_void_p]),
+    'dir_diffusion_slab_rows': (c_int, []),
+    'dir_knn_graph': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
+    'dir_diffusion_seed': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
+    'dir_diffusion_workspace_bytes': (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    'dir_diffusion_solve': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_int,
+                                    c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'dir_comm_init_all': (c_int, [c_int, POINTER(c_int), POINTER(c_void_p)]),
     'dir_comm_size': (c_int, [c_void_p, POINTER(c_int)]),
     'dir_comm_destroy': (c_int, [c_void_p]),

@@ -10,6 +10,11 @@ applies to the revisited Oxford / Paris datasets - is scored and ranked on the G
 sorting every row (test_dir.py:153-178).  Every other case IS test_dir.eval_model.
 --expand lists (that device route only; default --expand matrix): --aqe / --adba take their neighbours from exact top-k lists
 and a gather (ranking.expand_device) instead of the n x m score matrix of test_dir.expand_descriptors.
+--diffusion K KQ (default off; a dataset with a query set of its own): the scores are ranking.diffuse_device's - diffusion
+on the mutual K-NN graph of the database from the KQ best rows of every query, "+DFS" of the revisited Oxford / Paris
+tables - with --diffusion-alpha 0.99, --diffusion-gamma 3, --diffusion-iters 20.  It composes after --adba / --aqe: it
+scores the descriptors those produce.  The APs come from ranking.eval_aps_device for the revisitop / classic datasets and
+from db.eval_query_AP on downloaded rows otherwise.
 """
 import json
 import os
@@ -35,6 +40,23 @@ def labelled_on_device(db):
 EXPAND_ROUTES = ('matrix', 'lists')
 EXPAND_FLAG = (('--expand',), dict(type=str, default='matrix', choices=list(EXPAND_ROUTES),
                                    help='--aqe / --adba from the score matrix (default) or from neighbour lists'))
+
+
+DIFFUSION_FLAGS = [
+    (('--diffusion',), dict(type=int, nargs=2, default=None, metavar=('K', 'KQ'),
+                            help='diffusion re-ranking: neighbours per database row, seeds per query')),
+    (('--diffusion-alpha',), dict(type=float, default=0.99, help='with --diffusion: the damping of the walk, in [0, 1)')),
+    (('--diffusion-gamma',), dict(type=float, default=3, help='with --diffusion: the power applied to a similarity')),
+    (('--diffusion-iters',), dict(type=int, default=20, help='with --diffusion: conjugate-gradient iterations')),
+]
+
+
+def diffusion_options(args):
+    """the diffuse_device keywords of parsed DIFFUSION_FLAGS, None without --diffusion"""
+    if args.diffusion is None:
+        return None
+    return dict(k=args.diffusion[0], kq=args.diffusion[1], alpha=args.diffusion_alpha, gamma=args.diffusion_gamma,
+                iters=args.diffusion_iters)
 
 
 def descriptors(db, net, trfs, pooling='mean', gemp=3, whiten=None, aqe=None, adba=None, threads=8, batch_size=16,
@@ -89,13 +111,19 @@ def descriptors(db, net, trfs, pooling='mean', gemp=3, whiten=None, aqe=None, ad
 
 
 def eval_model(db, net, trfs, pooling='mean', gemp=3, detailed=False, whiten=None, aqe=None, adba=None, threads=8,
-               batch_size=16, save_feats=None, load_feats=None, dbg=(), expand='matrix'):
+               batch_size=16, save_feats=None, load_feats=None, dbg=(), expand='matrix', diffusion=None):
     """test_dir.eval_model, except that a class-labelled dataset under the device-rank switch (labelled_on_device) is
     ranked on the GPU; `mAP`, `APs`, `top<k>` and `tops` are filled as the host branch fills them.  expand='lists'
     (descriptors above) exists on that device route only: test_dir.eval_model has one expansion, the matrix, and asking
-    it for lists raises instead of quietly running the matrix."""
+    it for lists raises instead of quietly running the matrix.
+    diffusion: None, or the keywords of ranking.diffuse_device (k, kq, gamma, alpha, iters) - the queries are then scored
+    by diffusion on the database's kNN graph (a dataset with a query set of its own; the same dict comes back)."""
     if expand not in EXPAND_ROUTES:
         raise ValueError('expand: one of %s expected, got %r' % (', '.join(EXPAND_ROUTES), expand))
+    if diffusion is not None:
+        return _eval_diffusion(db, net, trfs, diffusion, detailed, expand,
+                               dict(pooling=pooling, gemp=gemp, whiten=whiten, aqe=aqe, adba=adba, threads=threads,
+                                    batch_size=batch_size, save_feats=save_feats, load_feats=load_feats))
     if not labelled_on_device(db):
         if expand != 'matrix' and (aqe is not None or adba is not None):
             raise ValueError("expand='lists' needs the device route of a class-labelled dataset "
@@ -117,6 +145,35 @@ def eval_model(db, net, trfs, pooling='mean', gemp=3, detailed=False, whiten=Non
     return res
 
 
+def _eval_diffusion(db, net, trfs, diffusion, detailed, expand, desc_kw):
+    """eval_model with diffusion scores: descriptors(), ranking.diffuse_device, then the APs on the device where the
+    dataset has the revisitop / classic fields and through db.eval_query_AP / eval_query_top on downloaded rows otherwise"""
+    if db.get_query_db() is db:
+        raise ValueError('diffusion needs a dataset with a query set of its own: queries that are database rows are '
+                         'not supported')
+    print("\n>> Evaluation...")
+    qdescs, bdescs = descriptors(db, net, trfs, expand=expand, **desc_kw)
+    scores = ranking.diffuse_device(qdescs, bdescs, **diffusion)
+    res = {}
+    if hasattr(db, 'junk'):
+        test_dir._mean_ap(ranking.eval_aps_device(db, scores), detailed, res)
+        return res
+    scores = scores.cpu().numpy()
+    try:
+        test_dir._mean_ap([db.eval_query_AP(q, s) for q, s in enumerate(scores)], detailed, res)
+    except NotImplementedError:
+        print(" AP not implemented!")
+    try:
+        tops = [db.eval_query_top(q, s) for q, s in enumerate(scores)]
+        if detailed:
+            res['tops'] = tops
+        for k in tops[0]:
+            res['top%d' % k] = float(np.mean([t[k] for t in tops]))
+    except NotImplementedError:
+        pass
+    return res
+
+
 def main(argv=None):
     """test_dir.main (test_dir.py:194-) around this module's eval_model: same flags, same printout, same json."""
     args = test_dir.build_parser(extra=[
@@ -128,7 +185,7 @@ def main(argv=None):
         (('--adba',), dict(type=int, nargs='+', help='alpha-database augmentation paramenters')),
         (('--whitenp',), dict(type=float, default=0.25, help='whitening power, default is 0.5 (i.e., the sqrt)')),
         EXPAND_FLAG,
-    ]).parse_args(argv)
+    ] + DIFFUSION_FLAGS).parse_args(argv)
     iscuda = test_dir.setup_devices(args.gpu)
     qe = {name: (None if val is None else {'k': val[0], 'alpha': val[1]})
           for name, val in (('aqe', args.aqe), ('adba', args.adba))}
@@ -138,7 +195,8 @@ def main(argv=None):
     whiten = test_dir.select_whitening(net, args)
     res = eval_model(dataset, net, args.trfs, pooling=args.pooling, gemp=args.gemp, detailed=args.detailed,
                      threads=args.threads, dbg=args.dbg, whiten=whiten, aqe=qe['aqe'], adba=qe['adba'],
-                     save_feats=args.save_feats, load_feats=args.load_feats, expand=args.expand)
+                     save_feats=args.save_feats, load_feats=args.load_feats, expand=args.expand,
+                     diffusion=diffusion_options(args))
     if ddist.rank() == 0:
         print(' * ' + '\n * '.join('%s = %g' % kv for kv in res.items() if np.isscalar(kv[1])))
         if args.out_json:

@@ -1020,6 +1020,85 @@ def expand_lists(descs, db, idx, vals, alpha):
     return out
 
 
+# ---- diffusion on the kNN graph (csrc/diffusion.hip) ---------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def diffusion_slab_rows():
+    """The rows of a slab of the solve's dot products (dir_diffusion_slab_rows; host-only)."""
+    return int(_lib.load().dir_diffusion_slab_rows())
+
+
+def _list_pair(idx, vals, what):
+    """(idx, vals, pitch) of a pair of [n,k] int32 / fp32 list tables at one row pitch"""
+    _on_device(idx, vals)
+    if idx.dtype != torch.int32 or vals.dtype != torch.float32:
+        raise TypeError('int32 %s ids and float32 values expected' % what)
+    if idx.dim() != 2 or tuple(vals.shape) != tuple(idx.shape):
+        raise ValueError('%s ids and values [n,k] expected' % what)
+    k = idx.shape[1]
+    if k == 0:
+        return idx, vals, 0
+    idx, ldi = _rows_pitch(idx, k)
+    vals, ldv = _rows_pitch(vals, k)
+    if ldi != ldv:      # (one pitch for both tables in the C ABI)
+        idx, vals, ldi = idx.contiguous(), vals.contiguous(), k
+    return idx, vals, ldi
+
+
+def knn_graph(idx, vals, gamma=3):
+    """The mutual kNN graph of a database from its self-set neighbour lists (dir_knn_graph, csrc/diffusion.hip;
+    include/dir_engine.h gives the definition, tests/diffusion_ref.py restates it) -> S [N,k] fp32 CUDA in the layout of
+    the lists: S[i][t] = min(vals[i][t]^gamma, vals[j][t']^gamma) / sqrt(deg[i] deg[j]) for the mutual neighbours
+    j = idx[i][t], +0 for every other slot (a hole, an id out of range, the row itself, a later duplicate, a score <= 0 or
+    NaN, a neighbour that does not list the row back).  idx / vals [N,k] int32 / fp32 CUDA as ops.topk or an index's
+    search(same_set=True) gives them."""
+    idx, vals, ldl = _list_pair(idx, vals, 'list')
+    N, k = idx.shape
+    S = torch.empty(N, k, dtype=torch.float32, device=idx.device)
+    if N and k:
+        call('dir_knn_graph', ptr(idx), ptr(vals), ldl, N, k, float(gamma), ptr(S), k, stream_ptr())
+    return S
+
+
+def diffusion_seed(qidx, qvals, N, gamma=3):
+    """The seed columns of a query set (dir_diffusion_seed) -> Y [N,Q] fp32 CUDA: zero except Y[qidx[q][t]][q] =
+    qvals[q][t]^gamma for the slots with an id in [0, N) and a score > 0; a later slot of a list that names the same row
+    overwrites an earlier one.  qidx / qvals [Q,kq]: the kq best database rows of every query."""
+    qidx, qvals, ldq = _list_pair(qidx, qvals, 'query list')
+    Q, kq = qidx.shape
+    N = int(N)
+    Y = torch.empty(N, Q, dtype=torch.float32, device=qidx.device)
+    if N and Q:
+        call('dir_diffusion_seed', ptr(qidx), ptr(qvals), ldq, Q, kq, N, float(gamma), ptr(Y), Q, stream_ptr())
+    return Y
+
+
+def diffusion_solve(idx, S, Y, alpha=0.99, iters=20):
+    """(I - alpha S) F = Y by `iters` conjugate-gradient iterations, all Q columns at once (dir_diffusion_solve) ->
+    F [N,Q] fp32 CUDA.  idx / S [N,k]: the graph as knn_graph gives it (a slot with S == 0 or an id outside [0, N) is
+    skipped); Y [N,Q] fp32 CUDA.  0 <= alpha < 1.  No host synchronisation; the workspace is allocated here.  The result
+    of a column does not depend on the other columns of the call."""
+    idx, S, ldl = _list_pair(idx, S, 'graph')
+    _on_device(Y)
+    if Y.dtype != torch.float32 or Y.dim() != 2 or Y.shape[0] != idx.shape[0]:
+        raise ValueError('float32 Y [N,Q] expected for a graph of N rows')
+    if not 0 <= alpha < 1:
+        raise ValueError('0 <= alpha < 1 expected, got %g' % alpha)
+    if iters < 0:
+        raise ValueError('iters must be non-negative')
+    N, k = idx.shape
+    Q = Y.shape[1]
+    F = torch.empty(N, Q, dtype=torch.float32, device=Y.device)
+    if N == 0 or Q == 0:
+        return F
+    Y, ldy = _rows_pitch(Y, Q)
+    need = ctypes.c_size_t(0)
+    call('dir_diffusion_workspace_bytes', N, Q, ctypes.byref(need))
+    ws = torch.empty(max(int(need.value), 16), dtype=torch.uint8, device=Y.device)
+    call('dir_diffusion_solve', ptr(idx), ldl, ptr(S), ldl, N, k, ptr(Y), ldy, Q, float(alpha), int(iters), ptr(F), Q,
+         ptr(ws), int(need.value), stream_ptr())
+    return F
+
+
 def stem_pool(s2d, w_packed, bias, out_hw):
     """Fused stem: s2d image [B,H2,W2,16] + packed 4x4x16 filter -> pooled [B,PH,PW,64];
     out_hw = (OH, OW) of the 7x7 s2 convolution."""

@@ -289,3 +289,63 @@ def expand_device(descs, db=None, alpha=0, k=0, index=None, scratch_bytes=256 <<
             search_kw = dict(search_kw, source=pool_)
         idx, vals = index.search(x, k, same_set=same_set, scratch_bytes=scratch_bytes, **search_kw)
     return ops.expand_lists(x, pool_, idx, vals, float(alpha))
+
+
+# ---- diffusion re-ranking on the database's kNN graph -------------------------------------------------------------------
+def _lists(x, pool_, k, same_set, index, scratch_bytes, search_kw):
+    """neighbour lists of x among pool_: exact (retrieve_device) or from an index over pool_, with expand_device's checks"""
+    if index is None:
+        if search_kw:
+            raise TypeError('%s only apply to an index' % ', '.join(sorted(search_kw)))
+        return retrieve_device(x, pool_, k, same_set=same_set, scratch_bytes=scratch_bytes)
+    if len(index) != pool_.shape[0] or index.D != pool_.shape[1]:
+        raise ValueError('an index over the %d x %d rows of the database expected, got %d x %d' % (
+            pool_.shape[0], pool_.shape[1], len(index), index.D))
+    if search_kw.get('rerank') and search_kw.get('source') is None:
+        search_kw = dict(search_kw, source=pool_)
+    return index.search(x, k, same_set=same_set, scratch_bytes=scratch_bytes, **search_kw)
+
+
+def knn_graph_device(bdescs, k, gamma=3, index=None, scratch_bytes=256 << 20, **search_kw):
+    """(idx [N,k] int32, S [N,k] fp32), both CUDA: the mutual kNN graph of the database, normalised (ops.knn_graph;
+    include/dir_engine.h gives the arithmetic) - the offline stage of diffuse_device, reusable across query sets.
+    The k neighbours of every row are retrieve_device(bdescs, bdescs, k, same_set=True), or with `index` (one of the four
+    classes of dirtorch_amd.index, already holding exactly the rows of bdescs) index.search(bdescs, k, same_set=True,
+    **search_kw); search_kw carries nprobe, rerank and source (source defaults to the rows themselves when rerank is
+    given).  Lists that end in empty slots, as a narrowly probed inverted file gives, only make the graph sparser."""
+    from .utils.common import _dev
+    b = _dev(bdescs)
+    if b.dim() != 2:
+        raise ValueError('bdescs [N, D] expected')
+    idx, vals = _lists(b, b, int(k), True, index, scratch_bytes, search_kw)
+    return idx, ops.knn_graph(idx, vals, gamma)
+
+
+def diffuse_device(qdescs, bdescs, k=50, kq=10, gamma=3, alpha=0.99, iters=20, graph=None, index=None,
+                   scratch_bytes=256 << 20, **search_kw):
+    """Diffusion scores [Q, N] fp32 CUDA, contiguous - the "+DFS" row of the revisited Oxford / Paris tables (Iscen et al.,
+    "Efficient Diffusion on Region Manifolds", global descriptors): the kq best database rows of every query seed a
+    column (score^gamma), and (I - alpha S) f = y is solved on the mutual k-NN graph S of the database by `iters`
+    conjugate-gradient iterations on the device (ops.diffusion_seed, ops.diffusion_solve).  The result fits ops.topk,
+    ops.rank_counts and eval_aps_device unchanged.  graph: (idx, S) of knn_graph_device(bdescs, k, gamma, ...), made once
+    per database; None: it is made here.  index / search_kw: as in knn_graph_device, for the graph (when made here) and
+    for the queries' lists.
+    The queries are a set of their own: a query that is a database row would need a one-hot seed at its own row and that
+    row kept out of its list, which this does not do - passing the database as the query set raises ValueError."""
+    from .utils.common import _dev
+    q, b = _dev(qdescs), _dev(bdescs)
+    if q.dim() != 2 or b.dim() != 2 or q.shape[1] != b.shape[1]:
+        raise ValueError('qdescs [Q, D] and bdescs [N, D] expected')
+    if qdescs is bdescs or (q.data_ptr() == b.data_ptr() and q.shape == b.shape):
+        raise ValueError('diffuse_device: the query set is the database itself - queries that are database rows are not '
+                         'supported (the queries must be a set of their own)')
+    N = b.shape[0]
+    if graph is None:
+        graph = knn_graph_device(b, k, gamma, index=index, scratch_bytes=scratch_bytes, **search_kw)
+    idx, S = graph
+    if idx.shape[0] != N or tuple(S.shape) != tuple(idx.shape):
+        raise ValueError('a graph (idx, S) over the %d rows of the database expected' % N)
+    qidx, qvals = _lists(q, b, int(kq), False, index, scratch_bytes, search_kw)
+    Y = ops.diffusion_seed(qidx, qvals, N, gamma)
+    F = ops.diffusion_solve(idx, S, Y, alpha=alpha, iters=iters)
+    return F.t().contiguous()

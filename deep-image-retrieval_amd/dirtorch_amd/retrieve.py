@@ -24,6 +24,10 @@ the default, --expand matrix, is test_dir.expand_descriptors.  Without --index t
 --index KIND they come from indexes of that kind with the same --nlist / --pq-m / --nprobe / --rerank: --adba from one
 trained and filled on the un-augmented database descriptors (self-set), --aqe from the index over the (augmented)
 database that the final search then reuses - it is built once.
+--diffusion K KQ (default off; a dataset with a query set of its own): the lists and their scores are ops.topk over
+ranking.diffuse_device's scores - diffusion on the mutual K-NN graph of the database from the KQ best rows of every query
+(--diffusion-alpha 0.99, --diffusion-gamma 3, --diffusion-iters 20), after --adba / --aqe.  With --index KIND the graph's
+lists and the queries' come from that index, built once over the database as it is scored.
 """
 import sys
 
@@ -80,7 +84,7 @@ def main(argv=None):
         (('--pq-m',), dict(type=int, default=0, help='with --index pq / ivfpq: bytes (sub-spaces) per database image')),
         (('--rerank',), dict(type=int, default=0, help='with --index: shortlist size re-scored in fp32 (0 = none)')),
         eval_dir.EXPAND_FLAG,
-    ]).parse_args(argv)
+    ] + eval_dir.DIFFUSION_FLAGS).parse_args(argv)
     if args.rerank and not args.index:
         raise SystemExit('--rerank needs --index')
     class_name, flags, trained = INDEX_KINDS.get(args.index, ('', (), False))
@@ -116,7 +120,15 @@ def main(argv=None):
                                           save_feats=args.save_feats, load_feats=args.load_feats, expand=args.expand,
                                           expand_index=(lambda rows: (build_index(rows), search_kw)) if by_index else None)
     same_set = dataset.get_query_db() is dataset
-    if args.index:
+    diffusion = eval_dir.diffusion_options(args)
+    if diffusion is not None:
+        if same_set:
+            raise ValueError('--diffusion needs a dataset with a query set of its own: queries that are database rows '
+                             'are not supported')
+        from . import ops
+        by = dict(search_kw, index=build_index(bdescs)) if args.index else {}
+        idx, vals = ops.topk(ranking.diffuse_device(qdescs, bdescs, **diffusion, **by), args.topk)
+    elif args.index:
         idx, vals = build_index(bdescs).search(qdescs, args.topk, source=bdescs if args.rerank else None,
                                                same_set=same_set, **search_kw)
     else:

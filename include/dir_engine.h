@@ -703,6 +703,66 @@ int dir_expand_descriptors(const float* descs, int n, const float* db, int m, in
  * DIR_ERR_INVALID before anything is launched; n == 0 is DIR_OK and launches nothing. */
 int dir_expand_lists(const float* descs, int ldd, int n, const float* db, int ldb, int m, int D, const int* idx,
                      const float* vals, int ldl, int k, float alpha, float* out, int ldo, void* stream);
+/* Diffusion re-ranking on the kNN graph of the database (diffusion.hip; dirtorch_amd/ranking.py knn_graph_device /
+ * diffuse_device; numpy restatement: tests/diffusion_ref.py): Iscen et al., "Efficient Diffusion on Region Manifolds", in
+ * its global-descriptor form.  The house rule holds: every number is a chain of single IEEE fp32 operations rounded to
+ * nearest, in the stated order (no fused multiply-add), and a numpy float32 restatement reproduces it bit for bit - except
+ * powf, below.
+ * GRAPH (dir_knn_graph).  idx / vals [N][ldl] int32 / fp32 are the self-set lists of the database, k slots a row, as
+ *   dir_topk or an index's search(same_set) writes them; S [N][lds] fp32 is the graph in the same layout (ldl, lds >= k).
+ *   Slot (i, t) is LIVE when j = idx[i][t] has 0 <= j < N and j != i, no earlier slot of row i holds j, and vals[i][t] > 0
+ *     (a NaN fails).  Every other slot - a -1 hole, an id out of range, the row itself, a later duplicate, a score that is
+ *     zero, negative or NaN - has S = +0 and its id is never dereferenced.
+ *   w(i,t) = vals[i][t]^gamma: gamma an integer in 0 .. 64: w = 1, then gamma times w = w * v; otherwise powf(v, gamma), the
+ *     one step that is not bit-defined (dir_expand_lists' rule).
+ *   a(i,t) = min(w(i,t), w(j,t')), t' the first live slot of row j that holds i; +0 when there is none.  Mutual edges only:
+ *     the graph is a subset of every row's own list and symmetric bit for bit.
+ *   deg[i] = the chain deg = deg + a(i,t) over t ascending from +0;  dinv[i] = 1 / sqrtf(deg[i]) when deg[i] > 0 (two
+ *     correctly rounded operations), else 0;  S[i][t] = a(i,t) * (dinv[i] * dinv[j]), the product of the two dinv first, so
+ *     S is symmetric bit for bit as well; a slot with a(i,t) == 0 keeps +0.  A row of degree 0 is isolated: all zero.
+ *   Three kernels (one thread per slot, per row, per slot); dinv lives in stream-ordered scratch.
+ * SEEDS (dir_diffusion_seed).  qidx / qvals [Q][ldq], the kq best database rows of every query; Y [N][ldy] fp32, ldy >= Q.
+ *   Columns 0 .. Q of every row of Y are set to +0 by this call, then for every query q and t = 0 .. kq - 1 ascending with
+ *   0 <= j = qidx[q][t] < N and qvals[q][t] > 0:  Y[j][q] = qvals[q][t]^gamma (the power above).  A later slot of a list that
+ *   names the same row overwrites an earlier one; any other slot writes nothing.  The queries are a set of their own: there
+ *   is no self test.  Columns at or past Q are not touched.
+ * SOLVE (dir_diffusion_solve).  (I - alpha S) f = y for each of the Q columns of Y by conjugate gradients, `iters`
+ *   iterations, no early exit and no host synchronisation; the columns are independent.  Per column, x r p ap over the N rows:
+ *       x = 0; r = y; p = y; rr = dot(r, r)
+ *       repeat iters times:
+ *           g[i]  = the chain g = g + S[i][t] * p[idx[i][t]] over t ascending from +0 (product, then sum) - over the slots
+ *                   with 0 <= idx[i][t] < N and S[i][t] != 0; any other slot is skipped and its id is not dereferenced
+ *           ap[i] = p[i] - alpha * g[i]                                   (product, then difference)
+ *           pap = dot(p, ap);    a = pap > 0 ? rr / pap : 0
+ *           x[i] = x[i] + a * p[i];    r[i] = r[i] - a * ap[i];    rn = dot(r, r)
+ *           b = rr > 0 ? rn / rr : 0;    p[i] = r[i] + b * p[i];    rr = rn
+ *       f = x
+ *   dot(u, v): the rows are cut into slabs of dir_diffusion_slab_rows() = 256 consecutive rows (host-only query).  Row r
+ *     of a slab belongs to chain r mod 64; chain c = the sum c = c + u[i] * v[i] over its rows in ascending order from +0
+ *     (a row at or past N ends the chain); then for s = 32, 16, 8, 4, 2, 1: chain[c] = chain[c] + chain[c + s] for c < s; the
+ *     slab's partial is chain[0].  dot = the chain d = d + partial over the slabs in ascending order from +0.  Nothing in
+ *     this order depends on the CU count, on Q, on a pitch or alignment, or on how the columns are blocked: solving the same
+ *     columns in one call or in several gives the same bits.
+ *   Consequences: alpha = 0 gives F = Y bit for bit after one iteration; a zero column stays zero; iters = 0 gives F = 0.
+ *   idx [N][ldl], S [N][lds], Y [N][ldy], F [N][ldf] (ldy, ldf >= Q; F must not overlap the other operands).  workspace: at
+ *   least dir_diffusion_workspace_bytes(N, Q) bytes (host-only), 16-byte aligned; it holds x r p ap as [N][Qp] fp32, Qp = Q
+ *   rounded up to 4 with zero padding columns, the slab partials and rr, a, b.  Per iteration: the apply kernel (ap and the
+ *   slab partials of pap; a lane owns four columns - one 16-byte load per gathered row - of one chain of a slab and takes
+ *   two of its rows at a time, the rows of four slots of each are requested before the first is added and the next four
+ *   ids and weights before those adds; a skipped slot reads the lane's own row instead and its add is dropped by a
+ *   select), one thread per column that finishes pap and writes a, the x / r update with the slab partials
+ *   of rn, one thread per column that writes b and rr, and the p update.  No atomics.
+ * All three: a negative count, a pitch below its width, k or kq above dir_topk_max_k(), gamma < 0 (or NaN), alpha outside
+ * [0, 1), N * k (graph) or N * Q (seeds, solve) at or above 2^32 - 256 (the pointwise kernels take one thread per slot or
+ * element), a null pointer, a short or misaligned workspace fail with DIR_ERR_INVALID before anything is launched; N == 0 or
+ * Q == 0 (k == 0 for the graph) is DIR_OK and launches nothing. */
+int dir_diffusion_slab_rows(void);
+int dir_knn_graph(const int* idx, const float* vals, int ldl, int N, int k, float gamma, float* S, int lds, void* stream);
+int dir_diffusion_seed(const int* qidx, const float* qvals, int ldq, int Q, int kq, int N, float gamma, float* Y, int ldy,
+                       void* stream);
+int dir_diffusion_workspace_bytes(int N, int Q, size_t* bytes);
+int dir_diffusion_solve(const int* idx, int ldl, const float* S, int lds, int N, int k, const float* Y, int ldy, int Q,
+                        float alpha, int iters, float* F, int ldf, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- the exchange step ------------------------------------------------------------
  * All-gather of per-GPU descriptor blocks over RCCL / xGMI for ONE process driving several GPUs - the

@@ -203,6 +203,14 @@ def bench_kernel_name(k):
             'ivfpq_base_kernel': 'expand_rows_kernel', 'ivfpq_scan_kernel': 'rank_hist_kernel',
             # alpha-QE / DBA from neighbour lists: the row gather (csrc/expand_lists.hip; no timed bench.py step launches it)
             'expand_lists_kernel': 'expand_rows_kernel',
+            # diffusion on the kNN graph: the graph's three kernels, the seeds, the CG step (csrc/diffusion.hip; no timed bench.py
+            # step launches them) - the apply is a row gather, the rest is pointwise with a slab reduction
+            'knn_affinity_kernel': 'expand_rows_kernel', 'knn_degree_kernel': 'l2norm_rows_kernel',
+            'knn_normalise_kernel': 'expand_rows_kernel', 'diffusion_zero_kernel': 'fill_noise_kernel',
+            'diffusion_seed_kernel': 'fill_noise_kernel', 'diffusion_init_kernel': 'l2norm_rows_kernel',
+            'diffusion_apply_kernel': 'expand_rows_kernel', 'diffusion_update_kernel': 'l2norm_rows_kernel',
+            'diffusion_direction_kernel': 'l2norm_rows_kernel', 'diffusion_finish_kernel': 'gemm_splitk_finalize_kernel',
+            'diffusion_result_kernel': 'fill_noise_kernel',
             'maxpool_kernel': 'maxpool_3x3s2', 'upsample_add_kernel': 'upsample_add',
             'prep_input_f32_kernel': 'prep_input_f32', 'maxpool_f32_kernel': 'maxpool_f32',
             'global_pool_f32_kernel': 'global_pool_f32', 'upsample_add_f32_kernel': 'upsample_add_f32',
