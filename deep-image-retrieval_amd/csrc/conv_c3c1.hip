@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(512) conv_c3c1_kernel(const ConvArgs a) {
     constexpr int KSW = KW / 16;                // ... that have weights of their own
     constexpr int XBUF = BM * KA * 2;           // one t2 (+ x) tile: KA/64 blocks of [64 px][128 B]
     constexpr int NX = XBUF / 16 / NT;          // staging loads per lane per tile (1 / 2)
-    constexpr int EROW = 32 * 4 + 16;           // staging row: 32 fp32 + pad
+    constexpr int EROW = Staged<1>::EROW;       // staging row: 32 fp32 + pad
     constexpr int EPI_OFF = 2 * XBUF;
     constexpr int OUT_OFF = EPI_OFF + 8 * 32 * EROW;
     constexpr int OUTB = BM * C4 * 2;           // the out-tile: C4/64 blocks of [64 px][128 B]
@@ -237,42 +237,27 @@ __global__ void __launch_bounds__(512) conv_c3c1_kernel(const ConvArgs a) {
                 }
             }
 #pragma unroll
-            for (int i = 0; i < TA; ++i) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4_t v = {acc[i][4 * g + 0], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]};
-                    *(f32x4_t*)(ebase + lrow * EROW + (8 * g + 4 * lhi) * 4) = v;
-                }
-                wave_lds_sync();
+            for (int i = 0; i < TA; ++i) {   // one channel block at a time: 32-channel staging rows
                 const float* const bz = sbias3 + n_wave + i * 32 + ecol;
                 const f32x4_t b0 = *(const f32x4_t*)bz, b1 = *(const f32x4_t*)(bz + 4);
+                epilogue_strip<1>(ebase, lrow, lhi, ecol, erow, [&](int) -> const f32x16_t& { return acc[i]; },
+                                  [&](int pass, int mrow, float (&v)[8]) {
 #pragma unroll
-                for (int pass = 0; pass < 2; ++pass) {
-                    const int mrow = pass * 16 + erow;
-                    const f32x4_t f0 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4);
-                    const f32x4_t f1 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4 + 16);
-                    float v[8] = {f0[0] + b0[0], f0[1] + b0[1], f0[2] + b0[2], f0[3] + b0[3],
-                                  f1[0] + b1[0], f1[1] + b1[1], f1[2] + b1[2], f1[3] + b1[3]};
-                    if (!DS) {
-                        const u32x4_t rv = j == 0 ? rres0[i * 2 + pass] : rres1[i * 2 + pass];
-                        add_res8<DT>(v, rv);
-                    }
+                    for (int e = 0; e < 4; ++e) v[e] += b0[e], v[4 + e] += b1[e];
+                    if (!DS) add_res8<DT>(v, j == 0 ? rres0[i * 2 + pass] : rres1[i * 2 + pass]);
                     if (a.relu) relu8(v);
-                    u32x4_t ov;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) ov[e] = DT::pack(v[2 * e], v[2 * e + 1]);
+                    const u32x4_t ov = pack8<DT>(v);
                     const int p = j * 32 + mrow;
                     // (a dropped pixel's store goes where a row beyond M goes: the descriptor discards it)
                     const uint32_t keep16 = (uint32_t)(ykeep >> (j * 32 + pass * 16));   // (scalar: this pass's 16 rows)
                     // (a wave-uniform branch around the store of a pass without a kept row was measured: the branches cost both
                     // forms of the kernel 5 % - profiles/seam_stores.txt - so every pass issues its store)
-                    __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y, DS || ((keep16 >> erow) & 1) ? row_off(m0 + p) : kOOB, i * 64, 0);
+                    bstore16(rsrc_y, DS || ((keep16 >> erow) & 1) ? row_off(m0 + p) : kOOB, i * 64, ov);
                     ovf.see(ov);
                     // the same 16 bytes into the out-tile (B operand of phase B), whether stored to HBM or not
                     const int n = n_wave + i * 32 + ecol;
                     *(u32x4_t*)(otile + (n >> 6) * (BM * 128) + p * 128 + ((((n & 63) >> 3) ^ ((p >> 1) & 7)) << 4)) = ov;
-                }
-                wave_lds_sync();
+                });
             }
             if (!DS && j == 0) load_res(next, 0, rres0);   // next tile's strip 0, one tile ahead
         }
@@ -327,28 +312,20 @@ __global__ void __launch_bounds__(512) conv_c3c1_kernel(const ConvArgs a) {
             __syncthreads();   // (3) partner done reading before the areas are reused
             if (finishes) {
                 const int j = WIDE ? kh : jb;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4_t v = {sum[4 * g + 0], sum[4 * g + 1], sum[4 * g + 2], sum[4 * g + 3]};
-                    *(f32x4_t*)(ebase + lrow * EROW + (8 * g + 4 * lhi) * 4) = v;
-                }
-                wave_lds_sync();
                 const float* const bz = sbias1 + nt * 32 + ecol;
                 const f32x4_t b0 = *(const f32x4_t*)bz, b1 = *(const f32x4_t*)(bz + 4);
+                // (the strip's closing wave_lds_sync is followed by hand-off (4) or the end of the kernel)
+                epilogue_strip<1>(ebase, lrow, lhi, ecol, erow, [&](int) -> const f32x16_t& { return sum; },
+                                  [&](int, int mrow, float (&v)[8]) {
 #pragma unroll
-                for (int pass = 0; pass < 2; ++pass) {
-                    const int mrow = pass * 16 + erow;
-                    const f32x4_t f0 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4);
-                    const f32x4_t f1 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4 + 16);
-                    float v[8] = {f0[0] + b0[0], f0[1] + b0[1], f0[2] + b0[2], f0[3] + b0[3],
-                                  f1[0] + b1[0], f1[1] + b1[1], f1[2] + b1[2], f1[3] + b1[3]};
+                    for (int e = 0; e < 4; ++e) v[e] += b0[e], v[4 + e] += b1[e];
                     if (a.relu2) relu8(v);
                     const u32x4_t ov = pack8<DT>(v);
                     const int m = m0 + j * 32 + mrow;
                     const uint32_t off = m < a.M ? (uint32_t)m * (uint32_t)(P2 * 2) + (uint32_t)((nt * 32 + ecol) * 2) : kOOB;
-                    __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y2, off, 0, 0);
+                    bstore16(rsrc_y2, off, 0, ov);
                     ovf.see(ov);
-                }
+                });
             }
         }
         if (!more) break;

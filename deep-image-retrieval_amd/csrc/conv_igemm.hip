@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_kernel(const ConvAr
     static_assert((NT / CPR) % 16 == 0, "swizzle term must be constant per lane");
     constexpr int XS = BM * RB;  // bytes of the X tile of one stage
     constexpr int STAGE_BYTES = (BM + BN) * RB;
-    constexpr int EROW = TN * 128 + 16;  // epilogue: one pixel row of TN*32 fp32 + pad
+    constexpr int EROW = Staged<TN>::EROW;  // epilogue: one pixel row of TN*32 fp32 + pad
     typedef typename DT::frag_t frag_t;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -91,37 +91,11 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_kernel(const ConvAr
     for (int i = 0; i < NA; ++i) {
         const int row = i * (NT / CPR) + tid / CPR;
         const int m = tile_m * BM + row;
-        const bool mvalid = m < a.M;
         if (a.flat) {  // 1x1, stride 1: output pixel m reads input pixel m
             xbase[i] = (m * a.Cin + srcchunk * 8) * 2;
-            xmask[i] = mvalid ? 1u : 0u;
+            xmask[i] = m < a.M ? 1u : 0u;
         } else {
-            const uint32_t mm = mvalid ? (uint32_t)m : 0u;
-            const uint32_t b = fast_div(mm, a.div_ohw_mul, a.div_ohw_shr);
-            const uint32_t rem = mm - b * (uint32_t)(a.OH * a.OW);
-            const uint32_t oh = fast_div(rem, a.div_ow_mul, a.div_ow_shr);
-            const uint32_t ow = rem - oh * (uint32_t)a.OW;
-            const int ih0 = (int)oh * a.stride - a.pad;
-            const int iw0 = (int)ow * a.stride - a.pad;
-            xbase[i] = (((int)b * a.H + ih0) * a.W + iw0) * a.Cin * 2 + srcchunk * 16;
-            // validity bits in closed form (R, S <= 4): rows r in [max(0,-ih0), min(R, H-ih0)),
-            // columns s in [max(0,-iw0), min(S, W-iw0))
-            auto range_bits = [](int lo, int hi) -> uint32_t {
-                return hi > lo ? (((1u << hi) - 1u) & ~((1u << lo) - 1u)) : 0u;
-            };
-            const int R_ = CIN16 ? 4 : a.R;
-            const uint32_t rbits = range_bits(max(0, -ih0), min(R_, a.H - ih0));
-            if (CIN16) {
-                // one K-step per filter row; this lane's chunk is pixel (srcchunk >> 1) of the row
-                const bool wok = (unsigned)(iw0 + (srcchunk >> 1)) < (unsigned)a.W;
-                xmask[i] = (mvalid && wok) ? rbits : 0u;
-            } else {
-                const uint32_t cbits = range_bits(max(0, -iw0), min(a.S, a.W - iw0));
-                uint32_t mask = 0;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) mask |= ((rbits >> r) & 1u) ? (cbits << (r * a.S)) : 0u;
-                xmask[i] = mvalid ? mask : 0u;
-            }
+            im2col_lane<CIN16>(a, m, srcchunk, xbase[i], xmask[i]);
         }
     }
     uint32_t xvoff[NA];  // 1x1 path: final voffset with the row mask folded in
@@ -160,19 +134,10 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_kernel(const ConvAr
 
     // ---- accumulators start at the bias of their 4 consecutive channels -----------------------
     f32x16_t acc[TN][TM];
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4_t b4 = {0.f, 0.f, 0.f, 0.f};   // split-K partial sums carry no bias
-            if (!SPLITK)
-                b4 = *(const DIR_GLOBAL f32x4_t*)(a.bias + tile_n * BN + wn * TN * 32 + i * 32 + 8 * g +
-                                                  4 * lhi);
-#pragma unroll
-            for (int j = 0; j < TM; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[i][j][4 * g + e] = b4[e];
-        }
+    if (SPLITK)
+        acc_init_zero(acc);   // split-K partial sums carry no bias
+    else
+        acc_init_bias(acc, a.bias + tile_n * BN + wn * TN * 32, lhi);
 
     auto compute = [&](const char* stage) {
 #pragma unroll
@@ -192,9 +157,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_kernel(const ConvAr
     };
 
     // ---- residual tile fetched up front: its HBM latency hides under the whole K loop ----------
-    constexpr int LPR = TN * 4;                  // lanes covering one pixel row (8 channels each)
-    constexpr int RPP = 64 / LPR;                // pixel rows per pass
-    constexpr int NPASS = 32 / RPP;              // passes per 32-pixel strip
+    constexpr int LPR = Staged<TN>::LPR, RPP = Staged<TN>::RPP, NPASS = Staged<TN>::NPASS;
     constexpr bool PRE_RES = (TM * NPASS <= 16); // 16 B per lane each: at most 64 VGPRs
     const int ecol = (lane % LPR) * 8;
     const int erow = lane / LPR;
@@ -226,46 +189,14 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_kernel(const ConvAr
     // 32 CUs x that footprint overflowed the 4 MB L2 and the 3x3 layers fetched their input ~3x
     // from the fabric - profiles/r01_bench_b32_hbm_pmc.json history).  The stem (CIN16) has one
     // K-step per filter row and keeps row order.
-    int tap = 0, cc = 0, r = 0, s = 0;         // state of the step being ISSUED
-    if (SPLITK && t_begin > 0) {               // split-K: start in the middle of the K sequence
-        if (CIN16) {
-            r = tap = t_begin;
-        } else {
-            const int taps = a.R * a.S;
-            cc = t_begin / taps;
-            tap = t_begin - cc * taps;
-            r = tap / a.S;
-            s = tap - r * a.S;
-        }
-    }
-    auto koff_now = [&]() {                    // bytes into the input, relative to tap (0,0)
-        return CIN16 ? (r * a.W * 32) : (((r * a.W + s) * a.Cin + cc * BK) * 2);
-    };
-    auto wstep_now = [&]() {                   // index of this K-step's slice in a weight row
-        return CIN16 ? r : (tap * cpb + cc);
-    };
-    auto advance = [&]() {
-        if (CIN16) {
-            ++r;
-            ++tap;
-        } else {
-            ++tap;
-            if (++s == a.S) {
-                s = 0;
-                if (++r == a.R) {
-                    r = 0;
-                    tap = 0;
-                    ++cc;
-                }
-            }
-        }
-    };
+    KWalker<BK, CIN16> kw;                     // the step being ISSUED
+    if (SPLITK && t_begin > 0) kw.seek(a, t_begin);
     int issued = 0;
 #pragma unroll
     for (int p = 0; p < NST - 1; ++p) {
         if (p < T) {
-            issue(wstep_now(), tap, koff_now(), smem + p * STAGE_BYTES);
-            advance();
+            issue(kw.wstep(cpb), kw.tap, kw.koff(a), smem + p * STAGE_BYTES);
+            kw.advance(a);
             ++issued;
         }
     }
@@ -294,9 +225,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_kernel(const ConvAr
         ring_barrier();
         if (issued < T) {
 #ifndef DIR_EXP_NO_FILL     // experiment builds (scripts/exp_abl.sh conv_igemm DIR_EXP_NO_FILL 1): MFMA + fragment reads alone
-            issue(wstep_now(), tap, koff_now(), smem + slot_i * STAGE_BYTES);
+            issue(kw.wstep(cpb), kw.tap, kw.koff(a), smem + slot_i * STAGE_BYTES);
 #endif
-            advance();
+            kw.advance(a);
             ++issued;
             if (++slot_i == NST) slot_i = 0;
         }
@@ -309,6 +240,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_kernel(const ConvAr
     Ovf<DT> ovf;
 
     // ---- epilogue: acc -> LDS (fp32, pixel-major) -> residual / ReLU / convert -> 16-byte stores --
+    // (conv_device.h's epilogue_strip, written out: through the helper the 256x128 _k32 forms took 130 VGPRs instead of 128 - one
+    // wave per SIMD less - and 256x256_w4x4 spilled 8 registers)
     char* ebase = smem + wave * (32 * EROW);
 #pragma unroll
     for (int j = 0; j < TM; ++j) {
@@ -335,24 +268,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_kernel(const ConvAr
             } else if (!SPLITK && m < a.M) {
                 float v[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
                 const size_t o = (size_t)m * a.Cout + n_glob;
-                if (a.res) {
-                    const u32x4_t rv = PRE_RES ? rres[PRE_RES ? j : 0][PRE_RES ? pass : 0]
-                                               : gload16(a.res + o);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float lo, hi;
-                        DT::unpack(rv[e], lo, hi);
-                        v[2 * e] += lo;
-                        v[2 * e + 1] += hi;
-                    }
-                }
-                if (a.relu) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-                }
-                u32x4_t ov;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) ov[e] = DT::pack(v[2 * e], v[2 * e + 1]);
+                if (a.res) add_res8<DT>(v, PRE_RES ? rres[PRE_RES ? j : 0][PRE_RES ? pass : 0] : gload16(a.res + o));
+                if (a.relu) relu8(v);
+                const u32x4_t ov = pack8<DT>(v);
                 gstore16(a.y + o, ov);
                 ovf.see(ov);
             }
@@ -367,7 +285,7 @@ template <class DT, int BM, int BN, int WGM, int WGN, int NST, int BK, bool CIN1
 static hipError_t launch_variant(const ConvArgs& a, hipStream_t stream) {
     constexpr int NT = 64 * WGM * WGN;
     constexpr int TN = BN / WGN / 32;
-    constexpr int EROW = TN * 128 + 16;
+    constexpr int EROW = Staged<TN>::EROW;
     constexpr int STAGE_BYTES = (BM + BN) * BK * 2;
     constexpr int EPI_BYTES = (NT / 64) * 32 * EROW;
     constexpr int LDS = (NST * STAGE_BYTES > EPI_BYTES) ? NST * STAGE_BYTES : EPI_BYTES;
@@ -529,16 +447,7 @@ __global__ void conv_splitk_finalize_kernel(const float* __restrict__ partial, c
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] += p0[e], v[4 + e] += p1[e];
     }
-    if (res) {
-        const u32x4_t rv = gload16(res + o);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float lo, hi;
-            DT::unpack(rv[e], lo, hi);
-            v[2 * e] += lo;
-            v[2 * e + 1] += hi;
-        }
-    }
+    if (res) add_res8<DT>(v, gload16(res + o));
     if (relu) relu8(v);
     const u32x4_t ov = pack8<DT>(v);
     gstore16(y + o, ov);

@@ -37,6 +37,16 @@ __device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t&
     FP16::unpack(hi, ha, hb);
     lo = FP16::pack(a - ha, b - hb);
 }
+// ... eight values -> four hi words, four lo words
+__device__ __forceinline__ void split8(const float (&v)[8], u32x4_t& hi, u32x4_t& lo) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        uint32_t h, l;
+        split2(v[2 * e], v[2 * e + 1], h, l);
+        hi[e] = h;
+        lo[e] = l;
+    }
+}
 
 // ---- convolution ----------------------------------------------------------------------------------------------------
 // K-step = 32 input channels of one filter tap; a stage = Xh [BM][32] (+ Xl) + Wh [BN][32] + Wl [BN][32], rows of 64 B
@@ -58,7 +68,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_pair_kernel(const ConvArg
     constexpr int XS = BM * RB, WS = BN * RB;
     constexpr int WOFF = XPL * XS;
     constexpr int STAGE_BYTES = XPL * XS + 2 * WS;
-    constexpr int EROW = TN * 128 + 16;
+    constexpr int EROW = Staged<TN>::EROW;
     static_assert(TM >= 1 && TN >= 1 && NA >= 1 && NB >= 1, "tile split");
     static_assert((BM * CPR) % NT == 0 && (BN * CPR) % NT == 0 && (NT / CPR) % 16 == 0, "chunk split");
 
@@ -90,28 +100,11 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_pair_kernel(const ConvArg
     for (int i = 0; i < NA; ++i) {
         const int row = i * (NT / CPR) + tid / CPR;
         const int m = tile_m * BM + row;
-        const bool mvalid = m < a.M;
         if (a.flat) {
             xbase[i] = (m * a.Cin + srcchunk * 8) * 2;
-            xmask[i] = mvalid ? 1u : 0u;
+            xmask[i] = m < a.M ? 1u : 0u;
         } else {
-            const uint32_t mm = mvalid ? (uint32_t)m : 0u;
-            const uint32_t b = fast_div(mm, a.div_ohw_mul, a.div_ohw_shr);
-            const uint32_t rem = mm - b * (uint32_t)(a.OH * a.OW);
-            const uint32_t oh = fast_div(rem, a.div_ow_mul, a.div_ow_shr);
-            const uint32_t ow = rem - oh * (uint32_t)a.OW;
-            const int ih0 = (int)oh * a.stride - a.pad;
-            const int iw0 = (int)ow * a.stride - a.pad;
-            xbase[i] = (((int)b * a.H + ih0) * a.W + iw0) * a.Cin * 2 + srcchunk * 16;
-            auto range_bits = [](int lo, int hi) -> uint32_t {
-                return hi > lo ? (((1u << hi) - 1u) & ~((1u << lo) - 1u)) : 0u;
-            };
-            const uint32_t rbits = range_bits(max(0, -ih0), min(a.R, a.H - ih0));
-            const uint32_t cbits = range_bits(max(0, -iw0), min(a.S, a.W - iw0));
-            uint32_t mask = 0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) mask |= ((rbits >> r) & 1u) ? (cbits << (r * a.S)) : 0u;
-            xmask[i] = mvalid ? mask : 0u;
+            im2col_lane(a, m, srcchunk, xbase[i], xmask[i]);
         }
     }
     uint32_t wvoff[NB];
@@ -151,16 +144,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_pair_kernel(const ConvArg
     const int wfrag = WOFF + (wn * TN * 32) * RB;
 
     f32x16_t acc[TN][TM];
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4_t b4 = *(const DIR_GLOBAL f32x4_t*)(a.bias + tile_n * BN + wn * TN * 32 + i * 32 + 8 * g + 4 * lhi);
-#pragma unroll
-            for (int j = 0; j < TM; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[i][j][4 * g + e] = b4[e];
-        }
+    acc_init_bias(acc, a.bias + tile_n * BN + wn * TN * 32, lhi);
 
     auto compute = [&](const char* stage) {
 #pragma unroll
@@ -190,7 +174,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_pair_kernel(const ConvArg
     // ---- residual tile (both planes) fetched up front: its HBM latency hides under the K loop (conv_igemm.hip's
     //      PRE_RES).  Read in the epilogue it cost eight exposed round trips per wave and tile: conv3 of the paired
     //      layer1 ran at 0.81 ms for 2.7 GB, 3.3 TB/s. -----------------------------------------------------------------
-    constexpr int LPR = TN * 4, RPP = 64 / LPR, NPASS = 32 / RPP;
+    constexpr int LPR = Staged<TN>::LPR, RPP = Staged<TN>::RPP, NPASS = Staged<TN>::NPASS;
     const int ecol = (lane % LPR) * 8;
     const int erow = lane / LPR;
     const int n_glob = tile_n * BN + wn * TN * 32 + ecol;
@@ -211,30 +195,18 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_pair_kernel(const ConvArg
     // ---- K loop: channel slice outermost, filter taps innermost (conv_igemm.hip's order); two slots -----------------
     const int cpb = a.Cin / BK;
     const int T = a.T;
-    int tap = 0, cc = 0, r = 0, s = 0;
+    KWalker<BK> kw;
     // (DUAL: flat 1x1 only - tap == 0, cc counts K-steps over both sources, the second one starts at cc == cpb)
-    auto second_now = [&]() { return DUAL && cc >= cpb; };
-    auto koff_now = [&]() { return ((r * a.W + s) * a.Cin + (second_now() ? cc - cpb : cc) * BK) * 2; };
-    auto wstep_now = [&]() { return tap * cpb + cc; };
-    auto advance = [&]() {
-        ++tap;
-        if (++s == a.S) {
-            s = 0;
-            if (++r == a.R) {
-                r = 0;
-                tap = 0;
-                ++cc;
-            }
-        }
-    };
-    issue(wstep_now(), tap, koff_now(), second_now(), smem);
-    advance();
+    auto second_now = [&]() { return DUAL && kw.cc >= cpb; };
+    auto koff_now = [&]() { return kw.koff(a, second_now() ? kw.cc - cpb : kw.cc); };
+    issue(kw.wstep(cpb), kw.tap, koff_now(), second_now(), smem);
+    kw.advance(a);
     for (int t = 0; t < T; ++t) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ring_barrier();   // stage t landed everywhere; everyone is done reading the other slot
         if (t + 1 < T) {
-            issue(wstep_now(), tap, koff_now(), second_now(), smem + ((t + 1) & 1) * STAGE_BYTES);
-            advance();
+            issue(kw.wstep(cpb), kw.tap, koff_now(), second_now(), smem + ((t + 1) & 1) * STAGE_BYTES);
+            kw.advance(a);
         }
         compute(smem + (t & 1) * STAGE_BYTES);
     }
@@ -243,6 +215,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_pair_kernel(const ConvArg
 
     // ---- epilogue: acc -> LDS (fp32, pixel-major) -> + residual pair -> ReLU -> split into (hi, lo) -> 16-byte stores
     char* ebase = smem + wave * (32 * EROW);
+    // (epilogue_strip's round trip written out: through the helper the 128x64 form with pixel pairs ran 2 % longer per launch,
+    // 0.153 against 0.150 ms in layer1 - profiles/epilogue_refactor.txt)
 #pragma unroll
     for (int j = 0; j < TM; ++j) {
 #pragma unroll
@@ -272,13 +246,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_pair_kernel(const ConvArg
                 }
                 if (a.relu) relu8(v);
                 u32x4_t oh, ol;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    uint32_t h, l;
-                    split2(v[2 * e], v[2 * e + 1], h, l);
-                    oh[e] = h;
-                    ol[e] = l;
-                }
+                split8(v, oh, ol);
                 gstore16(a.y + o, oh);
                 if (a.y_lo) gstore16(a.y_lo + o, ol);
                 ovf.see(oh);
@@ -306,7 +274,7 @@ __global__ void __launch_bounds__(256, 2) conv_pair_patch64_kernel(const ConvArg
     constexpr int WSTAGE = C * 128, NBW = C * 8 / NTH, NSTW = 3;
     constexpr int WOFF = 2 * PLANE_BYTES;
     constexpr int TN = 2;
-    constexpr int EROW = TN * 128 + 16;
+    constexpr int EROW = Staged<TN>::EROW;
     constexpr int NS = 18;                              // (tap, plane) steps
     static_assert(WOFF + NSTW * WSTAGE <= 80 * 1024 && 4 * 32 * EROW <= WOFF, "two workgroups per CU; staging aliases the patch");
 
@@ -362,14 +330,7 @@ __global__ void __launch_bounds__(256, 2) conv_pair_patch64_kernel(const ConvArg
     };
 
     f32x16_t acc[TN];
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4_t b4 = *(const DIR_GLOBAL f32x4_t*)(a.bias + i * 32 + 8 * g + 4 * lhi);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[i][4 * g + e] = b4[e];
-        }
+    acc_init_bias_n(acc, a.bias, lhi);
     const int wswz = (lane >> 1) & 7;
     int woffk[4];
 #pragma unroll
@@ -449,40 +410,23 @@ __global__ void __launch_bounds__(256, 2) conv_pair_patch64_kernel(const ConvArg
     Ovf<DT> ovf;
 
     char* ebase = smem + wave * (32 * EROW);
-    constexpr int LPR = TN * 4, RPP = 64 / LPR, NPASS = 32 / RPP;
+    constexpr int LPR = Staged<TN>::LPR;
     const int ecol = (lane % LPR) * 8, erow = lane / LPR;
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4_t v = {acc[i][4 * g + 0], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]};
-            *(f32x4_t*)(ebase + lrow * EROW + (i * 32 + 8 * g + 4 * lhi) * 4) = v;
-        }
-    wave_lds_sync();
     const int oy = oy0 + wave;
-#pragma unroll
-    for (int pass = 0; pass < NPASS; ++pass) {
-        const int mrow = pass * RPP + erow;
-        const f32x4_t f0 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4);
-        const f32x4_t f1 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4 + 16);
+    // (no second use of the staging rows: the strip's closing wave_lds_sync is the only thing the helper adds here)
+    epilogue_strip<TN>(ebase, lrow, lhi, ecol, erow, [&](int i) -> const f32x16_t& { return acc[i]; },
+                       [&](int, int mrow, float (&v)[8]) {
         const int ox = ox0 + mrow;
         if (oy < a.OH && ox < a.OW) {
-            float v[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
             if (a.relu) relu8(v);
             u32x4_t oh, ol;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                uint32_t h, l;
-                split2(v[2 * e], v[2 * e + 1], h, l);
-                oh[e] = h;
-                ol[e] = l;
-            }
+            split8(v, oh, ol);
             const size_t o = ((size_t)(b * a.OH + oy) * a.OW + ox) * C + ecol;
             gstore16(a.y + o, oh);
             if (a.y_lo) gstore16(a.y_lo + o, ol);
             ovf.see(oh);
         }
-    }
+    });
     ovf.flush(a.ovf);
 }
 
@@ -506,7 +450,7 @@ template <int BM, int BN, int WGM, int WGN, bool XP, bool DUAL = false>
 static hipError_t launch_pair(const ConvArgs& a, hipStream_t stream) {
     constexpr int NT = 64 * WGM * WGN;
     constexpr int TN = BN / WGN / 32;
-    constexpr int EROW = TN * 128 + 16;
+    constexpr int EROW = Staged<TN>::EROW;
     constexpr int STAGE_BYTES = ((XP ? 2 : 1) * BM + 2 * BN) * 64;
     constexpr int EPI_BYTES = (NT / 64) * 32 * EROW;
     constexpr int LDS = (2 * STAGE_BYTES > EPI_BYTES) ? 2 * STAGE_BYTES : EPI_BYTES;
@@ -645,16 +589,7 @@ __global__ void __launch_bounds__(256) stem_pool_pair_kernel(const StemPairArgs 
         }
 
     f32x16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4_t b4 = *(const DIR_GLOBAL f32x4_t*)(a.bias + i * 32 + 8 * g + 4 * lhi);
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[i][j][4 * g + e] = b4[e];
-        }
+    acc_init_bias(acc, a.bias, lhi);
     const int wswz = (lane >> 1) & 7;
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -736,13 +671,7 @@ __global__ void __launch_bounds__(256) stem_pool_pair_kernel(const StemPairArgs 
             }
         u32x4_t oh, ol;
         const float mv[8] = {m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            uint32_t h, l;
-            split2(mv[2 * e], mv[2 * e + 1], h, l);
-            oh[e] = h;
-            ol[e] = l;
-        }
+        split8(mv, oh, ol);
         const size_t o = ((size_t)(b * a.PH + ph) * a.PW + pw) * 64 + c8 * 8;
         gstore16(a.yh + o, oh);
         gstore16(a.yl + o, ol);
@@ -845,14 +774,7 @@ __global__ void __launch_bounds__(512) stem_pool_pair_persist_kernel(const StemP
         ring_barrier();   // patch landed everywhere; everyone is done pooling the previous tile
 
         f32x16_t acc[2];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4_t b4 = *(const f32x4_t*)(lbias + ci * 32 + 8 * g + 4 * lhi);
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[j][4 * g + e] = b4[e];
-        }
+        acc_init_bias_m<true>(acc, lbias + ci * 32, lhi);
 #pragma unroll
         for (int R = 0; R < 4; ++R)
 #pragma unroll
@@ -926,13 +848,7 @@ __global__ void __launch_bounds__(512) stem_pool_pair_persist_kernel(const StemP
                 }
             u32x4_t oh, ol;
             const float mv[8] = {m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                uint32_t hh, ll;
-                split2(mv[2 * e], mv[2 * e + 1], hh, ll);
-                oh[e] = hh;
-                ol[e] = ll;
-            }
+            split8(mv, oh, ol);
             const size_t o = ((size_t)(b * a.PH + ph) * a.PW + pw) * 64 + c8 * 8;
             gstore16(a.yh + o, oh);
             gstore16(a.yl + o, ol);

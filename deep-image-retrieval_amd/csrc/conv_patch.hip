@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(NTH) conv_patch3x3_kernel(const ConvArgs a) {
     constexpr int NBW = COUT * 8 / NTH;      // weight DMA instructions per lane per stage
     constexpr int T = 9 * KC;
     constexpr int WOFF = KC * PLANE_BYTES;   // ring starts after the patch
-    constexpr int EROW = TN * 128 + 16;
+    constexpr int EROW = Staged<TN>::EROW;
     typedef typename DT::frag_t frag_t;
     static_assert(CIN % 64 == 0 && COUT % (32 * WGN) == 0 && (NTH == 256 || NTH == 512), "shape");
 
@@ -95,16 +95,7 @@ __global__ void __launch_bounds__(NTH) conv_patch3x3_kernel(const ConvArgs a) {
 
     // ---- accumulators start at the bias ------------------------------------------------------------
     f32x16_t acc[TN][TMR];
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4_t b4 = *(const DIR_GLOBAL f32x4_t*)(a.bias + (wn * TN + i) * 32 + 8 * g + 4 * lhi);
-#pragma unroll
-            for (int j = 0; j < TMR; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[i][j][4 * g + e] = b4[e];
-        }
+    acc_init_bias(acc, a.bias + wn * TN * 32, lhi);
 
     const int wswz = (lane >> 1) & 7;
     int woffk[4];
@@ -168,48 +159,25 @@ __global__ void __launch_bounds__(NTH) conv_patch3x3_kernel(const ConvArgs a) {
 
     // ---- epilogue (as conv_igemm): acc -> LDS fp32 -> ReLU -> 16-byte stores ------------------------
     char* ebase = smem + wave * (32 * EROW);
-    constexpr int LPR = TN * 4, RPP = 64 / LPR, NPASS = 32 / RPP;
+    constexpr int LPR = Staged<TN>::LPR;
     const int ecol = (lane % LPR) * 8;
     const int erow = lane / LPR;
     const int ncol = wn * TN * 32 + ecol;   // first of this lane's 8 output channels
 #pragma unroll
     for (int j = 0; j < TMR; ++j) {
-#pragma unroll
-        for (int i = 0; i < TN; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4_t v = {acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2],
-                             acc[i][j][4 * g + 3]};
-                *(f32x4_t*)(ebase + lrow * EROW + (i * 32 + 8 * g + 4 * lhi) * 4) = v;
-            }
-        wave_lds_sync();
         const int oy = oy0 + wrow * TMR + j;
-#pragma unroll
-        for (int pass = 0; pass < NPASS; ++pass) {
-            const int mrow = pass * RPP + erow;
-            const f32x4_t f0 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4);
-            const f32x4_t f1 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4 + 16);
+        epilogue_strip<TN>(ebase, lrow, lhi, ecol, erow, [&](int i) -> const f32x16_t& { return acc[i][j]; },
+                           [&](int, int mrow, float (&v)[8]) {
             const int ox = ox0 + mrow;
             if (oy < a.OH && ox < a.OW) {
-                float v[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
                 const size_t o = ((size_t)(b * a.OH + oy) * a.OW + ox) * COUT + ncol;
-                if (a.res) {
-                    const u32x4_t rv = gload16(a.res + o);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float lo, hi;
-                        DT::unpack(rv[e], lo, hi);
-                        v[2 * e] += lo;
-                        v[2 * e + 1] += hi;
-                    }
-                }
+                if (a.res) add_res8<DT>(v, gload16(a.res + o));
                 if (a.relu) relu8(v);
                 const u32x4_t ov = pack8<DT>(v);
                 gstore16(a.y + o, ov);
                 ovf.see(ov);
             }
-        }
-        wave_lds_sync();
+        });
     }
     ovf.flush(a.ovf);
 }
@@ -225,7 +193,7 @@ static hipError_t launch_patch(const ConvArgs& a, hipStream_t stream) {
     constexpr int PLANE_BYTES = ((10 * 34 * 8 + NTH - 1) / NTH) * NTH * 16;
     constexpr int TN = C / 32 / (NTH / 256);
     constexpr int MAIN = KC * PLANE_BYTES + 3 * C * 128;
-    constexpr int EPI = (NTH / 64) * 32 * (TN * 128 + 16);
+    constexpr int EPI = (NTH / 64) * 32 * Staged<TN>::EROW;
     constexpr int LDS = MAIN > EPI ? MAIN : EPI;
     static_assert(LDS <= 160 * 1024, "LDS budget");
     auto kern = conv_patch3x3_kernel<DT, C, C, NTH>;
@@ -267,7 +235,7 @@ __global__ void __launch_bounds__(512) conv_patch3x3s_kernel(const ConvArgs a) {
     constexpr int NSTW = 3;
     constexpr int WOFF = PLANE_BYTES;
     constexpr int T = 9 * KC;
-    constexpr int EROW = TN * 128 + 16;
+    constexpr int EROW = Staged<TN>::EROW;
     typedef typename DT::frag_t frag_t;
     static_assert(CIN % 64 == 0 && WOFF + NSTW * WSTAGE <= 160 * 1024, "shape / LDS map");
 
@@ -323,16 +291,7 @@ __global__ void __launch_bounds__(512) conv_patch3x3s_kernel(const ConvArgs a) {
     };
 
     f32x16_t acc[TN][TMR];
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4_t b4 = *(const DIR_GLOBAL f32x4_t*)(a.bias + tile_n * BN + (wn * TN + i) * 32 + 8 * g + 4 * lhi);
-#pragma unroll
-            for (int j = 0; j < TMR; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[i][j][4 * g + e] = b4[e];
-        }
+    acc_init_bias(acc, a.bias + tile_n * BN + wn * TN * 32, lhi);
 
     const int wswz = (lane >> 1) & 7;
     int woffk[4];
@@ -404,47 +363,25 @@ __global__ void __launch_bounds__(512) conv_patch3x3s_kernel(const ConvArgs a) {
     Ovf<DT> ovf;
 
     char* ebase = smem + wave * (32 * EROW);
-    constexpr int LPR = TN * 4, RPP = 64 / LPR, NPASS = 32 / RPP;
+    constexpr int LPR = Staged<TN>::LPR;
     const int ecol = (lane % LPR) * 8;
     const int erow = lane / LPR;
     const int ncol = tile_n * BN + wn * TN * 32 + ecol;
 #pragma unroll
     for (int j = 0; j < TMR; ++j) {
-#pragma unroll
-        for (int i = 0; i < TN; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4_t v = {acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
-                *(f32x4_t*)(ebase + lrow * EROW + (i * 32 + 8 * g + 4 * lhi) * 4) = v;
-            }
-        wave_lds_sync();
         const int oy = oy0 + wrow * TMR + j;
-#pragma unroll
-        for (int pass = 0; pass < NPASS; ++pass) {
-            const int mrow = pass * RPP + erow;
-            const f32x4_t f0 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4);
-            const f32x4_t f1 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4 + 16);
+        epilogue_strip<TN>(ebase, lrow, lhi, ecol, erow, [&](int i) -> const f32x16_t& { return acc[i][j]; },
+                           [&](int, int mrow, float (&v)[8]) {
             const int ox = ox0 + mrow;
             if (oy < a.OH && ox < a.OW) {
-                float v[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
                 const size_t o = ((size_t)(b * a.OH + oy) * a.OW + ox) * a.Cout + ncol;
-                if (a.res) {
-                    const u32x4_t rv = gload16(a.res + o);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float lo, hi;
-                        DT::unpack(rv[e], lo, hi);
-                        v[2 * e] += lo;
-                        v[2 * e + 1] += hi;
-                    }
-                }
+                if (a.res) add_res8<DT>(v, gload16(a.res + o));
                 if (a.relu) relu8(v);
                 const u32x4_t ov = pack8<DT>(v);
                 gstore16(a.y + o, ov);
                 ovf.see(ov);
             }
-        }
-        wave_lds_sync();
+        });
     }
     ovf.flush(a.ovf);
 }

@@ -152,8 +152,7 @@ __global__ void __launch_bounds__(512) conv_patch64_lc_kernel(const ConvArgs a) 
                         for (int j = 0; j < 2; ++j) acc[i][j] = DT::mfma32(wf[i], xf[j][ks], acc[i][j]);
                 }
             }
-        // ---- ReLU, pack; v_permlane32_swap on the pair (g, g + 1) leaves lanes 0-31 with channels 8 g .. 8 g + 7 and lanes
-        //      32-63 with the next eight: one 16-byte store each ------------------------------------------------
+        // ---- straight from the accumulators (swap_pack16): one 16-byte store per lane and half block ----------------------
         int t = tile;
         const int tx = t % tiles_x;
         t /= tiles_x;
@@ -169,21 +168,7 @@ __global__ void __launch_bounds__(512) conv_patch64_lc_kernel(const ConvArgs a) 
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    uint32_t q2[2][2];
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        float v[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float x = acc[i][j][4 * (2 * h + q) + e];
-                            v[e] = a.relu ? fmaxf(x, 0.f) : x;
-                        }
-                        q2[q][0] = DT::pack(v[0], v[1]);
-                        q2[q][1] = DT::pack(v[2], v[3]);
-                    }
-                    const auto r0 = __builtin_amdgcn_permlane32_swap(q2[0][0], q2[1][0], false, false);
-                    const auto r1 = __builtin_amdgcn_permlane32_swap(q2[0][1], q2[1][1], false, false);
-                    const u32x4_t ov = {r0[0], r1[0], r0[1], r1[1]};
+                    const u32x4_t ov = swap_pack16<DT>(acc[i][j], h, a.relu);
                     if (ok) {
                         gstore16(yrow + i * 32 + h * 16, ov);
                         ovf.see(ov);

@@ -141,14 +141,7 @@ __global__ void __launch_bounds__(768) conv_patch3x3s2_kernel(const ConvArgs a) 
         const int tile_n = tile % tiles_n;
         const int tn_next = it + 1 < my_tiles ? (tile + G) % tiles_n : tile_n;
         f32x16_t acc[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4_t b4 = *(const DIR_GLOBAL f32x4_t*)(a.bias + tile_n * BN + ct * 32 + 8 * g + 4 * lhi);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[j][4 * g + e] = b4[e];
-        }
+        acc_init_bias_m(acc, a.bias + tile_n * BN + ct * 32, lhi);
         auto plane_step = [&](int q, auto par) __attribute__((always_inline)) {
             constexpr int PAR = decltype(par)::value;
             ring_barrier();   // hand-off (see the loaders); NQ is even, so plane q of any tile sits in buffer q & 1 = PAR
@@ -182,8 +175,7 @@ __global__ void __launch_bounds__(768) conv_patch3x3s2_kernel(const ConvArgs a) 
             plane_step(q, std::integral_constant<int, 0>{});
             plane_step(q + 1, std::integral_constant<int, 1>{});
         }
-        // ---- ReLU, pack; v_permlane32_swap on the pair (g, g + 1) leaves lanes 0-31 with channels 8 g .. 8 g + 7 and lanes
-        //      32-63 with the next eight: one 16-byte store each ------------------------------------------------------------------
+        // ---- straight from the accumulators (swap_pack16): one 16-byte store per lane and half block --------------------------------
         int t = tile / tiles_n;
         const int tx = t % tiles_x;
         t /= tiles_x;
@@ -197,21 +189,7 @@ __global__ void __launch_bounds__(768) conv_patch3x3s2_kernel(const ConvArgs a) 
             uint16_t* yrow = a.y + ((size_t)((b * a.OH + (ok ? oy : 0)) * a.OW + (ok ? ox : 0)) * a.Cout + tile_n * BN + ct * 32 + lhi * 8);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                uint32_t q2[2][2];
-#pragma unroll
-                for (int qq = 0; qq < 2; ++qq) {
-                    float v[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float x = acc[j][4 * (2 * h + qq) + e];
-                        v[e] = a.relu ? fmaxf(x, 0.f) : x;
-                    }
-                    q2[qq][0] = DT::pack(v[0], v[1]);
-                    q2[qq][1] = DT::pack(v[2], v[3]);
-                }
-                const auto r0 = __builtin_amdgcn_permlane32_swap(q2[0][0], q2[1][0], false, false);
-                const auto r1 = __builtin_amdgcn_permlane32_swap(q2[0][1], q2[1][1], false, false);
-                const u32x4_t ov = {r0[0], r1[0], r0[1], r1[1]};
+                const u32x4_t ov = swap_pack16<DT>(acc[j], h, a.relu);
                 if (ok) {
                     gstore16(yrow + h * 16, ov);
                     ovf.see(ov);

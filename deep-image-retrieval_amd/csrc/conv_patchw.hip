@@ -50,7 +50,7 @@ __global__ void __launch_bounds__(512) conv_patch3x3w_kernel(const ConvArgs a) {
     constexpr int NPL_X = (DIR_PATCHW_ABL & 32) ? 7 : 0;             // (experiment) extra fetches of every plane
     constexpr int NSTW = 3;
     constexpr int WOFF = 2 * PLANE_BYTES;
-    constexpr int EROW = TN * 128 + 16;
+    constexpr int EROW = Staged<TN>::EROW;
     typedef typename DT::frag_t frag_t;
     static_assert(WOFF + NSTW * WSTAGE <= 160 * 1024 && NBW * NTH * 16 == WSTAGE, "LDS map");
 
@@ -119,16 +119,7 @@ __global__ void __launch_bounds__(512) conv_patch3x3w_kernel(const ConvArgs a) {
     };
 
     f32x16_t acc[TN][TMR];
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4_t b4 = *(const DIR_GLOBAL f32x4_t*)(a.bias + tile_n * BN + i * 32 + 8 * g + 4 * lhi);
-#pragma unroll
-            for (int j = 0; j < TMR; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[i][j][4 * g + e] = b4[e];
-        }
+    acc_init_bias(acc, a.bias + tile_n * BN, lhi);
 
     // A fragment of channel tile i, K-sub-step kk: row n = i * 32 + lrow of a tap's [128][64 B] block
     int woffk[2];
@@ -215,47 +206,25 @@ __global__ void __launch_bounds__(512) conv_patch3x3w_kernel(const ConvArgs a) {
     }
 
     char* ebase = smem + wave * (32 * EROW);
-    constexpr int LPR = TN * 4, RPP = 64 / LPR, NPASS = 32 / RPP;
+    constexpr int LPR = Staged<TN>::LPR;
     const int ecol = (lane % LPR) * 8;
     const int erow = lane / LPR;
     const int ncol = tile_n * BN + ecol;
 #pragma unroll
     for (int j = 0; j < TMR; ++j) {
-#pragma unroll
-        for (int i = 0; i < TN; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4_t v = {acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
-                *(f32x4_t*)(ebase + lrow * EROW + (i * 32 + 8 * g + 4 * lhi) * 4) = v;
-            }
-        wave_lds_sync();
         const int oy = oy0 + wave * TMR + j;
-#pragma unroll
-        for (int pass = 0; pass < NPASS; ++pass) {
-            const int mrow = pass * RPP + erow;
-            const f32x4_t f0 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4);
-            const f32x4_t f1 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4 + 16);
+        epilogue_strip<TN>(ebase, lrow, lhi, ecol, erow, [&](int i) -> const f32x16_t& { return acc[i][j]; },
+                           [&](int, int mrow, float (&v)[8]) {
             const int ox = ox0 + mrow;
             if (oy < a.OH && ox < a.OW) {
-                float v[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
                 const size_t o = ((size_t)(b * a.OH + oy) * a.OW + ox) * a.Cout + ncol;
-                if (a.res) {
-                    const u32x4_t rv = gload16(a.res + o);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float lo, hi;
-                        DT::unpack(rv[e], lo, hi);
-                        v[2 * e] += lo;
-                        v[2 * e + 1] += hi;
-                    }
-                }
+                if (a.res) add_res8<DT>(v, gload16(a.res + o));
                 if (a.relu) relu8(v);
                 const u32x4_t ov = pack8<DT>(v);
                 if (!(DIR_PATCHW_ABL & 1) || ov[0] == 0x12345678u) gstore16(a.y + o, ov);
                 ovf.see(ov);
             }
-        }
-        wave_lds_sync();
+        });
     }
     ovf.flush(a.ovf);
 }
@@ -282,7 +251,7 @@ __global__ void __launch_bounds__(768) conv_patch3x3w_lc_kernel(const ConvArgs a
     constexpr int WSTAGE = 3 * BN * 64, NBW = WSTAGE / (NLD * 16);   // 24 KB, 6 instructions per loader lane
     constexpr int NSTW = 3;
     constexpr int WOFF = 2 * PLANE_BYTES;
-    constexpr int EROW = TN * 128 + 16;
+    constexpr int EROW = Staged<TN>::EROW;
     typedef typename DT::frag_t frag_t;
     static_assert(WOFF + NSTW * WSTAGE <= 160 * 1024 && NBW * NLD * 16 == WSTAGE, "LDS map");
 
@@ -384,16 +353,7 @@ __global__ void __launch_bounds__(768) conv_patch3x3w_lc_kernel(const ConvArgs a
 
     // ==================================== consumers ================================================================================
     f32x16_t acc[TN][TMR];
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4_t b4 = *(const DIR_GLOBAL f32x4_t*)(a.bias + tile_n * BN + i * 32 + 8 * g + 4 * lhi);
-#pragma unroll
-            for (int j = 0; j < TMR; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[i][j][4 * g + e] = b4[e];
-        }
+    acc_init_bias(acc, a.bias + tile_n * BN, lhi);
     int woffk[2];
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) woffk[kk] = lrow * 64 + (((2 * kk + lhi) ^ ((lrow >> 2) & 3)) << 4);
@@ -438,47 +398,25 @@ __global__ void __launch_bounds__(768) conv_patch3x3w_lc_kernel(const ConvArgs a
     ring_barrier();  // planes and weight slots become epilogue staging (the loaders leave here)
     Ovf<DT> ovf;
     char* ebase = smem + wave * (32 * EROW);
-    constexpr int LPR = TN * 4, RPP = 64 / LPR, NPASS = 32 / RPP;
+    constexpr int LPR = Staged<TN>::LPR;
     const int ecol = (lane % LPR) * 8;
     const int erow = lane / LPR;
     const int ncol = tile_n * BN + ecol;
 #pragma unroll
     for (int j = 0; j < TMR; ++j) {
-#pragma unroll
-        for (int i = 0; i < TN; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4_t v = {acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
-                *(f32x4_t*)(ebase + lrow * EROW + (i * 32 + 8 * g + 4 * lhi) * 4) = v;
-            }
-        wave_lds_sync();
         const int oy = oy0 + wave * TMR + j;
-#pragma unroll
-        for (int pass = 0; pass < NPASS; ++pass) {
-            const int mrow = pass * RPP + erow;
-            const f32x4_t f0 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4);
-            const f32x4_t f1 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4 + 16);
+        epilogue_strip<TN>(ebase, lrow, lhi, ecol, erow, [&](int i) -> const f32x16_t& { return acc[i][j]; },
+                           [&](int, int mrow, float (&v)[8]) {
             const int ox = ox0 + mrow;
             if (oy < a.OH && ox < a.OW) {
-                float v[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
                 const size_t o = ((size_t)(b * a.OH + oy) * a.OW + ox) * a.Cout + ncol;
-                if (a.res) {
-                    const u32x4_t rv = gload16(a.res + o);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float lo, hi;
-                        DT::unpack(rv[e], lo, hi);
-                        v[2 * e] += lo;
-                        v[2 * e + 1] += hi;
-                    }
-                }
+                if (a.res) add_res8<DT>(v, gload16(a.res + o));
                 if (a.relu) relu8(v);
                 const u32x4_t ov = pack8<DT>(v);
                 gstore16(a.y + o, ov);
                 ovf.see(ov);
             }
-        }
-        wave_lds_sync();
+        });
     }
     ovf.flush(a.ovf);
 }

@@ -41,7 +41,7 @@ __global__ void __launch_bounds__(512) conv1x1_persist_kernel(const ConvArgs a) 
     constexpr int TM = 2, TN = 4;              // wave tile 64 pixels x 128 channels (4 x 2 waves)
     constexpr int NA = 4, NB = 4;              // DMA instructions per lane per stage (X, W)
     constexpr int XS = BM * 128, STAGE = (BM + BN) * 128;   // 32 KiB + 32 KiB
-    constexpr int EROW = 2 * 128 + 16;         // staging row: 64 fp32 + pad
+    constexpr int EROW = Staged<2>::EROW;       // staging row: 64 fp32 + pad
     constexpr int EPI_OFF = XDEEP ? XS : STAGE;   // staging: above slot 0 / above X slot 0
     constexpr int WOFF = 3 * XS;               // XDEEP: first weight slot
     typedef typename DT::frag_t frag_t;
@@ -156,7 +156,7 @@ __global__ void __launch_bounds__(512) conv1x1_persist_kernel(const ConvArgs a) 
         for (int i = 0; i < TN; ++i)
 #pragma unroll
             for (int g = 0; g < 4; ++g)
-                bz[XDEEP ? i : 0][XDEEP ? g : 0] = *(const DIR_GLOBAL f32x4_t*)(a.bias + nw + i * 32 + 8 * g + 4 * lhi);
+                bz[XDEEP ? i : 0][XDEEP ? g : 0] = bias4(a.bias + nw + i * 32, g, lhi);
     };
     load_bias(tile);
     tile_offsets(tile);
@@ -174,17 +174,9 @@ __global__ void __launch_bounds__(512) conv1x1_persist_kernel(const ConvArgs a) 
         const int n_wave = tile_n * BN + wn * TN * 32;
 
         f32x16_t acc[TN][TM];
-#pragma unroll
-        for (int i = 0; i < TN; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4_t b4 = XDEEP ? bz[XDEEP ? i : 0][XDEEP ? g : 0]
-                                         : *(const DIR_GLOBAL f32x4_t*)(a.bias + n_wave + i * 32 + 8 * g + 4 * lhi);
-#pragma unroll
-                for (int j = 0; j < TM; ++j)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[i][j][4 * g + e] = b4[e];
-            }
+        acc_init(acc, [&](int i, int g) {   // XDEEP: the bias is cached in registers
+            return XDEEP ? bz[XDEEP ? i : 0][XDEEP ? g : 0] : bias4(a.bias + n_wave + i * 32, g, lhi);
+        });
 
         // residual tile of this wave: 2 strips x 2 channel halves x 4 passes of 16 B per lane
         const int ecol = (lane & 7) * 8, erow = lane >> 3;
@@ -275,43 +267,18 @@ __global__ void __launch_bounds__(512) conv1x1_persist_kernel(const ConvArgs a) 
 #pragma unroll
         for (int j = 0; j < TM; ++j)
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-#pragma unroll
-                for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int i = 2 * h + ii;
-                        f32x4_t v = {acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2],
-                                     acc[i][j][4 * g + 3]};
-                        *(f32x4_t*)(ebase + lrow * EROW + (ii * 32 + 8 * g + 4 * lhi) * 4) = v;
-                    }
-                wave_lds_sync();
-#pragma unroll
-                for (int pass = 0; pass < 4; ++pass) {
-                    const int mrow = pass * 8 + erow;
-                    const f32x4_t f0 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4);
-                    const f32x4_t f1 = *(const f32x4_t*)(ebase + mrow * EROW + ecol * 4 + 16);
+            for (int h = 0; h < 2; ++h)   // the four channel blocks in two halves of two
+                epilogue_strip<2>(ebase, lrow, lhi, ecol, erow, [&](int ii) -> const f32x16_t& { return acc[2 * h + ii][j]; },
+                                  [&](int pass, int mrow, float (&v)[8]) {
                     const int m = m_epi + j * 32 + mrow;
                     if (m < a.M) {
-                        float v[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
-                        if (RES && a.res) {
-                            const u32x4_t rv = rres[RES ? j : 0][h][RES ? pass : 0];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                float lo, hi;
-                                DT::unpack(rv[e], lo, hi);
-                                v[2 * e] += lo;
-                                v[2 * e + 1] += hi;
-                            }
-                        }
+                        if (RES && a.res) add_res8<DT>(v, rres[RES ? j : 0][h][RES ? pass : 0]);
                         if (a.relu) relu8(v);
                         const u32x4_t ov = pack8<DT>(v);
                         gstore16(a.y + ((size_t)m * a.Cout + n_wave + h * 64 + ecol), ov);
                         ovf.see(ov);
                     }
-                }
-                wave_lds_sync();
-            }
+                });
         if (next >= ntiles) break;
         if (XDEEP && T > 1) {
             // every wave is done with the staging area (it covers X slot 1).  Raw barrier: __syncthreads()

@@ -153,14 +153,7 @@ __global__ void __launch_bounds__(768) conv1x1_lc_kernel(const ConvArgs a) {
     int tile = first, t = 0, xslot = 0, wslot = 0;
     for (int g = 0; g < total; ++g) {
         ring_barrier();   // hand-off g (see the loaders)
-        if (t == 0) {
-#pragma unroll
-            for (int i = 0; i < TN; ++i)
-#pragma unroll
-                for (int j = 0; j < TM; ++j)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-        }
+        if (t == 0) acc_init_zero(acc);   // the bias is added in the epilogue
         const char* xs = smem + xslot * XS;
         const char* ws = smem + wslot * XS;
 #pragma unroll
@@ -179,9 +172,7 @@ __global__ void __launch_bounds__(768) conv1x1_lc_kernel(const ConvArgs a) {
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this step's LDS reads retired before the next hand-off
         if (t == T - 1) {
-            // ---- tile complete: + bias, ReLU, pack; v_permlane32_swap on the pair (gg, gg + 1) leaves lanes 0-31 with
-            //      channels 8 gg .. 8 gg + 7 and lanes 32-63 with the next eight: 16-byte stores (conv_ring.hip).
-            //      acc[i][j][4 gg + e] = channel i*32 + 8 gg + 4 lhi + e of pixel j*32 + lrow.
+            // ---- tile complete: + bias, then straight from the accumulators (swap_pack16): 16-byte stores
             const int tile_n = tile % a.tiles_n, tile_m = tile / a.tiles_n;
             const int n_wave = tile_n * BN + wn * TN * 32;
             const int m_wave = tile_m * BM + wm * TM * 32;
@@ -189,26 +180,12 @@ __global__ void __launch_bounds__(768) conv1x1_lc_kernel(const ConvArgs a) {
             for (int i = 0; i < TN; ++i) {
                 f32x4_t b4[4];
 #pragma unroll
-                for (int gg = 0; gg < 4; ++gg) b4[gg] = *(const DIR_GLOBAL f32x4_t*)(a.bias + n_wave + i * 32 + 8 * gg + 4 * lhi);
+                for (int gg = 0; gg < 4; ++gg) b4[gg] = bias4(a.bias + n_wave + i * 32, gg, lhi);
 #pragma unroll
                 for (int j = 0; j < TM; ++j)
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        uint32_t q2[2][2];
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            float v[4];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const float x = acc[i][j][4 * (2 * h + q) + e] + b4[2 * h + q][e];
-                                v[e] = a.relu ? fmaxf(x, 0.f) : x;
-                            }
-                            q2[q][0] = DT::pack(v[0], v[1]);
-                            q2[q][1] = DT::pack(v[2], v[3]);
-                        }
-                        const auto r0 = __builtin_amdgcn_permlane32_swap(q2[0][0], q2[1][0], false, false);
-                        const auto r1 = __builtin_amdgcn_permlane32_swap(q2[0][1], q2[1][1], false, false);
-                        const u32x4_t ov = {r0[0], r1[0], r0[1], r1[1]};
+                        const u32x4_t ov = swap_pack16<DT>(acc[i][j], h, a.relu, b4);
                         const int m = m_wave + j * 32 + lrow;
                         if (m < a.M) {
                             gstore16(a.y + ((size_t)m * a.Cout + n_wave + i * 32 + h * 16 + lhi * 8), ov);

@@ -185,16 +185,7 @@ __global__ void __launch_bounds__(512) conv1x1_ring_kernel(const ConvArgs a) {
         ring_barrier();   // hand-off g (see the loaders)
         if (t == 0) {
             const int n_wave = (tile % a.tiles_n) * BN + wn * TN * 32;
-#pragma unroll
-            for (int i = 0; i < TN; ++i)
-#pragma unroll
-                for (int gg = 0; gg < 4; ++gg) {
-                    const f32x4_t b4 = *(const f32x4_t*)(lbias + n_wave + i * 32 + 8 * gg + 4 * lhi);
-#pragma unroll
-                    for (int j = 0; j < TM; ++j)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[i][j][4 * gg + e] = b4[e];
-                }
+            acc_init_bias<true>(acc, lbias + n_wave, lhi);
         }
         const char* stage = smem + slot * STAGE;
         if (!(DIR_RING_ABL & 4)) {
@@ -223,30 +214,14 @@ __global__ void __launch_bounds__(512) conv1x1_ring_kernel(const ConvArgs a) {
         }
         if (t == T - 1) {
             if (!(DIR_RING_ABL & 8)) {
-                // ---- tile complete: ReLU, pack; v_permlane32_swap on the pair (gg, gg + 1) leaves lanes 0-31 with
-                //      channels 8 gg .. 8 gg + 7 and lanes 32-63 with the next eight (CDNA guide T21): 16-byte stores.
-                //      acc[i][j][4 gg + e] = channel i*32 + 8 gg + 4 lhi + e of pixel j*32 + lrow.
+                // ---- tile complete: straight from the accumulators (swap_pack16): 16-byte stores
 #pragma unroll
                 for (int j = 0; j < TM; ++j)
 #pragma unroll
                     for (int i = 0; i < TN; ++i)
 #pragma unroll
                         for (int h = 0; h < 2; ++h) {
-                            uint32_t q2[2][2];
-#pragma unroll
-                            for (int q = 0; q < 2; ++q) {
-                                float v[4];
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) {
-                                    const float x = acc[i][j][4 * (2 * h + q) + e];
-                                    v[e] = a.relu ? fmaxf(x, 0.f) : x;
-                                }
-                                q2[q][0] = DT::pack(v[0], v[1]);
-                                q2[q][1] = DT::pack(v[2], v[3]);
-                            }
-                            const auto r0 = __builtin_amdgcn_permlane32_swap(q2[0][0], q2[1][0], false, false);
-                            const auto r1 = __builtin_amdgcn_permlane32_swap(q2[0][1], q2[1][1], false, false);
-                            const u32x4_t ov = {r0[0], r1[0], r0[1], r1[1]};
+                            const u32x4_t ov = swap_pack16<DT>(acc[i][j], h, a.relu);
                             const long o = piece_off(tile, wave, j * 8 + i * 2 + h);
                             if (o >= 0) {
                                 gstore16(a.y + o, ov);

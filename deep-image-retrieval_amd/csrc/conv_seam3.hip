@@ -198,16 +198,7 @@ __global__ void __launch_bounds__(512) conv_seam3_kernel(const ConvArgs a) {
             for (int kh = 0; kh < 2; ++kh) {
                 ring_barrier();
                 const char* st = smem + slot * SLOT + a_row;
-                if (kh == 0) {
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-#pragma unroll
-                        for (int gg = 0; gg < 4; ++gg) {
-                            const f32x4_t b4 = *(const f32x4_t*)(lbias3 + 128 * c + half * 64 + i * 32 + 8 * gg + 4 * lhi);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[i][4 * gg + e] = b4[e];
-                        }
-                }
+                if (kh == 0) acc_init_bias_n<true>(acc, lbias3 + 128 * c + half * 64, lhi);
                 if (!(DIR_SEAM3_ABL & 4)) {
                 frag_t wf[4][2];     // fragments four K-slices ahead: one wave per SIMD has nobody else to hide LDS latency
 #pragma unroll
@@ -231,36 +222,25 @@ __global__ void __launch_bounds__(512) conv_seam3_kernel(const ConvArgs a) {
                     // The residual chunk landed with slot A0(c) (two barriers ago); the Y tile was last read in step
                     // B1(c - 1), two barriers ago.  Both are free to be overwritten two barriers from now.
 #pragma unroll
-                    for (int i = 0; i < 2; ++i)
+                    for (int i = 0; i < 2; ++i) {
+                        f32x4_t res[4];   // residual of channels 8 gg + 4 lhi .. + 3 of channel tile i: 8 bytes of 16-byte chunk
+                                          // half * 8 + 4 i + gg of this pixel's row
+#pragma unroll
+                        for (int gg = 0; gg < 4; ++gg) {
+                            const u32x2_t r2 = *(const u32x2_t*)(rtile + p * 256 + (((half * 8 + 4 * i + gg) ^ psw) << 4) + lhi * 8);
+                            float r0, r1, r2f, r3;
+                            DT::unpack(r2[0], r0, r1);
+                            DT::unpack(r2[1], r2f, r3);
+                            res[gg] = f32x4_t{r0, r1, r2f, r3};
+                        }
 #pragma unroll
                         for (int h = 0; h < 2; ++h) {
-                            uint32_t q2[2][2];
-#pragma unroll
-                            for (int q = 0; q < 2; ++q) {
-                                const int gg = 2 * h + q;
-                                // residual of channels 8 gg + 4 lhi .. + 3 of channel tile i: 8 bytes of 16-byte chunk
-                                // half * 8 + 4 i + gg of this pixel's row
-                                const u32x2_t r2 = *(const u32x2_t*)(rtile + p * 256 + (((half * 8 + 4 * i + gg) ^ psw) << 4) + lhi * 8);
-                                float r0, r1, r2f, r3;
-                                DT::unpack(r2[0], r0, r1);
-                                DT::unpack(r2[1], r2f, r3);
-                                float v[4] = {acc[i][4 * gg + 0] + r0, acc[i][4 * gg + 1] + r1, acc[i][4 * gg + 2] + r2f,
-                                              acc[i][4 * gg + 3] + r3};
-                                if (a.relu) {
-#pragma unroll
-                                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                                }
-                                q2[q][0] = DT::pack(v[0], v[1]);
-                                q2[q][1] = DT::pack(v[2], v[3]);
-                            }
-                            // lanes 0-31 end up with channels 16 h .. 16 h + 7 of pixel lrow, lanes 32-63 with the next eight
-                            const auto s0 = __builtin_amdgcn_permlane32_swap(q2[0][0], q2[1][0], false, false);
-                            const auto s1 = __builtin_amdgcn_permlane32_swap(q2[0][1], q2[1][1], false, false);
-                            const u32x4_t ov = {s0[0], s1[0], s0[1], s1[1]};
+                            const u32x4_t ov = swap_pack16<DT>(acc[i], h, a.relu, res);
                             const int chn = half * 64 + i * 32 + h * 16 + lhi * 8;      // channel within the chunk
                             ovf.see(ov);
                             *(u32x4_t*)(ytile + p * 256 + ((((chn >> 3)) ^ psw) << 4)) = ov;
                         }
+                    }
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 next_slot();
@@ -282,16 +262,7 @@ __global__ void __launch_bounds__(512) conv_seam3_kernel(const ConvArgs a) {
                         __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y, (uint32_t)(((m0 + r) * C4 + 128 * c + ((sl ^ (r & 15)) << 3)) * 2), 0, 0);
                     }
                 }
-                if (c == 0 && kb == 0) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int gg = 0; gg < 4; ++gg) {
-                            const f32x4_t b4 = *(const f32x4_t*)(lbias1 + half * 128 + i * 32 + 8 * gg + 4 * lhi);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc1[i][4 * gg + e] = b4[e];
-                        }
-                }
+                if (c == 0 && kb == 0) acc_init_bias_n<true>(acc1, lbias1 + half * 128, lhi);
                 if (!(DIR_SEAM3_ABL & 4)) {
                 frag_t wb[2][4], yb[2];
 #pragma unroll
@@ -318,22 +289,7 @@ __global__ void __launch_bounds__(512) conv_seam3_kernel(const ConvArgs a) {
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
                         for (int h = 0; h < 2; ++h) {
-                            uint32_t q2[2][2];
-#pragma unroll
-                            for (int q = 0; q < 2; ++q) {
-                                const int gg = 2 * h + q;
-                                float v[4];
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) {
-                                    const float x = acc1[i][4 * gg + e];
-                                    v[e] = a.relu2 ? fmaxf(x, 0.f) : x;
-                                }
-                                q2[q][0] = DT::pack(v[0], v[1]);
-                                q2[q][1] = DT::pack(v[2], v[3]);
-                            }
-                            const auto s0 = __builtin_amdgcn_permlane32_swap(q2[0][0], q2[1][0], false, false);
-                            const auto s1 = __builtin_amdgcn_permlane32_swap(q2[0][1], q2[1][1], false, false);
-                            const u32x4_t ov = {s0[0], s1[0], s0[1], s1[1]};
+                            const u32x4_t ov = swap_pack16<DT>(acc1[i], h, a.relu2);
                             const int chn = half * 128 + i * 32 + h * 16 + lhi * 8;
                             if (!(DIR_SEAM3_ABL & 16))
                                 __builtin_amdgcn_raw_buffer_store_b128(ov, rsrc_y2, (uint32_t)(((m0 + p) * P + chn) * 2), 0, 0);

@@ -90,27 +90,12 @@ __global__ void __launch_bounds__(512) conv_small_kernel(const ConvArgs a) {
             for (int i = 0; i < 2; ++i) {
                 const int row = (2 * l + i) * 8 + (lane >> 3);
                 const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-                const int m = tile_m * BM + row;
-                const bool mvalid = m < a.M;
-                const uint32_t mm = mvalid ? (uint32_t)m : 0u;
-                const uint32_t b = a.div_ohw_mul ? (__umulhi(mm, a.div_ohw_mul) >> a.div_ohw_shr) : mm;
-                const uint32_t rem = mm - b * (uint32_t)(a.OH * a.OW);
-                const uint32_t oh = a.div_ow_mul ? (__umulhi(rem, a.div_ow_mul) >> a.div_ow_shr) : rem;
-                const uint32_t ow = rem - oh * (uint32_t)a.OW;
-                const int ih0 = (int)oh * a.stride - a.pad, iw0 = (int)ow * a.stride - a.pad;
-                xbase[i] = (((int)b * a.H + ih0) * a.W + iw0) * a.Cin * 2 + chunk * 16;
-                // validity bit per tap (conv_igemm.hip): rows r in [max(0, -ih0), min(R, H - ih0)), columns likewise
-                auto range_bits = [](int lo, int hi) -> uint32_t { return hi > lo ? (((1u << hi) - 1u) & ~((1u << lo) - 1u)) : 0u; };
-                const uint32_t rbits = range_bits(max(0, -ih0), min(a.R, a.H - ih0));
-                const uint32_t cbits = range_bits(max(0, -iw0), min(a.S, a.W - iw0));
-                uint32_t mask = 0;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) mask |= ((rbits >> r) & 1u) ? (cbits << (r * a.S)) : 0u;
-                xmask[i] = mvalid ? mask : 0u;
+                im2col_lane(a, tile_m * BM + row, chunk, xbase[i], xmask[i]);
                 wvoff[i] = (uint32_t)(((tile_n * BN + row) * a.Ktot + chunk * 8) * 2);
             }
         };
-        int tile = first, t = 0, tap = 0, cc = 0, r = 0, s = 0, slot = 0;
+        int tile = first, t = 0, slot = 0;
+        KWalker<64> kw;
         tile_offsets(first);
         const uint32_t cnt_lds = (uint32_t)(uintptr_t)(DIR_LDS int*)cnt;
         for (int g = 0; g < total; ++g) {
@@ -128,29 +113,20 @@ __global__ void __launch_bounds__(512) conv_small_kernel(const ConvArgs a) {
 #pragma unroll
             for (int kk = 0; kk < KPS; ++kk) {
                 char* dst = smem + slot * STAGE + kk * KSTEP + (2 * l) * 1024;
-                const int koff = ((r * a.W + s) * a.Cin + cc * 64) * 2;
-                const int wstep = tap * (a.Cin / 64) + cc;
+                const int koff = kw.koff(a);
+                const int wstep = kw.wstep(a.Cin / 64);
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    const uint32_t v = ((xmask[i] >> tap) & 1u) ? (uint32_t)(xbase[i] + koff) : kOOB;
+                    const uint32_t v = ((xmask[i] >> kw.tap) & 1u) ? (uint32_t)(xbase[i] + koff) : kOOB;
                     dma16(rsrc_x, dst + i * 1024, v, 0);
                 }
 #pragma unroll
                 for (int i = 0; i < 2; ++i) dma16(rsrc_w, dst + XS + i * 1024, wvoff[i], wstep * 128);
-                // K order: channel slice outermost, taps innermost (conv_igemm.hip)
-                ++tap;
-                if (++s == a.S) {
-                    s = 0;
-                    if (++r == a.R) {
-                        r = 0;
-                        tap = 0;
-                        ++cc;
-                    }
-                }
+                kw.advance(a);
             }
             slot = slot + 1 == NST ? 0 : slot + 1;
             if (++t == T) {
-                t = 0, tap = 0, cc = 0, r = 0, s = 0;
+                t = 0, kw = KWalker<64>();
                 tile += (int)gridDim.x;
                 if (tile < ntiles) tile_offsets(tile);
             }

@@ -30,7 +30,7 @@ __global__ void __launch_bounds__(512) conv1x1_wreg_kernel(const ConvArgs a) {
     constexpr int KS = KB * 4;                 // 16-wide k-slices
     constexpr int XBUF = KB * BM * 128;        // one input tile: KB blocks of [64 px][128 B]
     constexpr int NX = XBUF / 16 / NT;         // DMA instructions per lane per tile (KB = 4: 4)
-    constexpr int EROW = 2 * 128 + 16;         // staging row: 64 fp32 + pad
+    constexpr int EROW = Staged<2>::EROW;       // staging row: 64 fp32 + pad
     constexpr int EPI_OFF = 2 * XBUF;          // staging above the two input buffers
     constexpr int BIAS_OFF = EPI_OFF + 8 * 32 * EROW;   // 512 fp32 bias values after the staging rows
     typedef typename DT::frag_t frag_t;
@@ -151,10 +151,7 @@ __global__ void __launch_bounds__(512) conv1x1_wreg_kernel(const ConvArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             f32x16_t acc[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
+            acc_init_zero(acc);   // the bias is added after staging
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const frag_t xf = *(const frag_t*)(xb + (ks >> 2) * (BM * 128) + j * (32 * 128) + lbase +
@@ -165,6 +162,7 @@ __global__ void __launch_bounds__(512) conv1x1_wreg_kernel(const ConvArgs a) {
                 if ((ks & 3) == 3) __builtin_amdgcn_sched_barrier(0);
             }
             // ---- epilogue of the strip: acc -> LDS fp32 -> bias / residual / ReLU -> 16-byte stores ----
+            // (epilogue_strip's round trip written out: through the helper the 256-channel form took 181 VGPRs instead of 168)
             // one wait for the strip's residual (requested long ago) instead of a counted wait per pass
             // that would also wait for this tile's own stores
 #pragma unroll

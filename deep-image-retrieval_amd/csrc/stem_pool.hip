@@ -87,16 +87,7 @@ __global__ void __launch_bounds__(256) stem_pool_kernel(const StemPoolArgs a) {
 
     // ---- accumulators start at the bias: 2 channel tiles x 2 conv rows per wave --------------------
     f32x16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4_t b4 = *(const DIR_GLOBAL f32x4_t*)(a.bias + i * 32 + 8 * g + 4 * lhi);
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[i][j][4 * g + e] = b4[e];
-        }
+    acc_init_bias(acc, a.bias, lhi);
     const int wswz = (lane >> 1) & 7;
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -259,6 +250,7 @@ __global__ void __launch_bounds__(256, 2) stem_pool_persist_kernel(const StemPoo
         ring_barrier();   // patch landed everywhere; everyone is done pooling the previous tile
 
         f32x16_t acc[2][2];   // start at the bias, like every conv kernel of this library (same fp32 order)
+        // (written out, not acc_init_bias<true>: at 256 VGPRs the helper's form spilled 9 registers where this one spills 1)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll

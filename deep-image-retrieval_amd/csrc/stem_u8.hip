@@ -386,14 +386,7 @@ __global__ void __launch_bounds__(128 * NRP, NRP == 2 ? 2 : 1) stem_pool_u8_kern
         const bool edge = cur.c <= 1 || 2 * (cur.c + TH - 1) + 4 > a.H || cur.pw0 == 0 || 2 * (2 * cur.pw0 + TW - 2) + 4 > a.W;
         f32x16_t acc[2];
         if (XPAIR) {   // the generic pair form sums FROM the bias, like the kernels it replaces (same fp32 roundings)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4_t b4 = *(const f32x4_t*)(lbias + ci * 32 + 8 * g + 4 * lhi);
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[j][4 * g + e] = b4[e];
-            }
+            acc_init_bias_m<true>(acc, lbias + ci * 32, lhi);
         } else {
 #pragma unroll
             for (int j = 0; j < 2; ++j)
