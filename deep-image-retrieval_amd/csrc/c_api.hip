@@ -37,6 +37,8 @@ extern "C" {
 const char* dir_last_error(void) { return last_error(); }
 const char* dir_version(void) { return "dir_engine 0.1 gfx950"; }
 
+int64_t dir_launch_max_threads(void) { return (int64_t)kMaxLaunchThreads; }
+
 int dir_reload_env(void) {
     dir::reload_env();
     return DIR_OK;

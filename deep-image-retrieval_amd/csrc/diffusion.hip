@@ -34,7 +34,6 @@ constexpr int kDiffUnroll = 4;     // gathered rows requested ahead of the adds,
 constexpr int kDiffAhead = 64;     // slab partials the finishing thread of a column requests at a time
 constexpr int kDiffPair = 2;       // rows of a chain a lane works on at a time
 constexpr int kDiffThreads = 1024;  // the largest workgroup: 64 chains x 16 column groups
-constexpr size_t kDiffMaxThreads = 0xffffff00u;   // a launch stays below 2^32 threads
 constexpr int kDiffFew = 256;       // threads of a workgroup that takes several slabs of a narrow solve
 
 // w = v^gamma: gamma multiplications from 1 for an integer gamma in 0..64, powf otherwise (expand_lists.hip's rule)
@@ -105,7 +104,7 @@ __global__ void __launch_bounds__(256) knn_normalise_kernel(const int* __restric
 
 int knn_graph(const int* idx, const float* vals, int ldl, int N, int k, float gamma, float* S, int lds, hipStream_t stream) {
     if (N <= 0 || k <= 0) return DIR_OK;
-    if ((size_t)N * k > kDiffMaxThreads) return fail(DIR_ERR_INVALID, "knn_graph: N * k must stay below 2^32 (one thread per slot)");
+    if (!launch_fits(((long)N * k + 255) / 256, 256)) return fail(DIR_ERR_INVALID, "knn_graph: N * k must stay below 2^32 (one thread per slot)");
     float* dinv = nullptr;
     DIR_HIP_CHECK(hipMallocAsync((void**)&dinv, (size_t)N * sizeof(float), stream));   // stream-ordered: freed after the kernels
     const size_t slots = (size_t)N * k;
@@ -143,7 +142,7 @@ __global__ void __launch_bounds__(64) diffusion_seed_kernel(const int* __restric
 int diffusion_seed(const int* qidx, const float* qvals, int ldq, int Q, int kq, int N, float gamma, float* Y, int ldy,
                    hipStream_t stream) {
     if (N <= 0 || Q <= 0) return DIR_OK;
-    if ((size_t)N * Q > kDiffMaxThreads) return fail(DIR_ERR_INVALID, "diffusion_seed: N * Q must stay below 2^32");
+    if (!launch_fits(((long)N * Q + 255) / 256, 256)) return fail(DIR_ERR_INVALID, "diffusion_seed: N * Q must stay below 2^32");
     const size_t elems = (size_t)N * Q;
     hipLaunchKernelGGL(diffusion_zero_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, stream, Y, ldy, N, Q);
     if (kq > 0)
@@ -435,7 +434,9 @@ __global__ void __launch_bounds__(256) diffusion_result_kernel(const float* __re
 int diffusion_solve(const int* idx, int ldl, const float* S, int lds, int N, int k, const float* Y, int ldy, int Q, float alpha,
                     int iters, float* F, int ldf, void* workspace, hipStream_t stream) {
     if (N <= 0 || Q <= 0) return DIR_OK;
-    if ((size_t)N * Q > kDiffMaxThreads) return fail(DIR_ERR_INVALID, "diffusion_solve: N * Q must stay below 2^32");
+    if (!launch_fits(((long)N * Q + 255) / 256, 256)) return fail(DIR_ERR_INVALID, "diffusion_solve: N * Q must stay below 2^32");
+    if (iters > 0 && Q > kMaxGridYZ * 4 * kDiffMaxCg)   // (diff_cut's grid.y: workgroups of 64 columns)
+        return fail(DIR_ERR_INVALID, "diffusion_solve: more than 65535 * 64 columns in one call");
     const unsigned gres = (unsigned)(((size_t)N * Q + 255) / 256);
     if (iters <= 0) {
         hipLaunchKernelGGL(diffusion_result_kernel, dim3(gres), dim3(256), 0, stream, (const float*)nullptr, 0, N, Q, F, ldf);

@@ -237,6 +237,17 @@ __device__ inline int xcd_remap(int bid, int nwg) {
 }
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// ---- launch extents ------------------------------------------------------------------------------------------------------
+// An AQL dispatch packet holds every grid extent as a uint32_t count of WORK-ITEMS (hsa_kernel_dispatch_packet_t::
+// grid_size_x), so gridDim.x * blockDim.x must stay below 2^32: kMaxLaunchThreads, the largest multiple of 256 that does
+// (dir_launch_max_threads() is the host's view of it).  gridDim.y and .z stay within 65535, as the launchers always held
+// them.  A launcher whose extent follows a caller's size either refuses the size (DIR_ERR_INVALID before anything is
+// launched) or cuts the work into several launches (gather_scores); tests/launch_limits.py lists which does what.
+constexpr uint32_t kMaxLaunchThreads = 0xffffff00u;
+constexpr int kMaxGridYZ = 65535;
+// whether a 1-D launch of `blocks` workgroups of `threads` threads can be expressed (threads: 1 .. 1024)
+inline bool launch_fits(long blocks, int threads) { return blocks >= 0 && blocks <= (long)(kMaxLaunchThreads / (uint32_t)threads); }
 // the row length of an int8 code matrix: D rounded up to a multiple of 64
 __host__ __device__ inline int pad64(int D) { return (D + 63) & ~63; }
 

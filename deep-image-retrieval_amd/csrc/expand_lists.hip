@@ -174,6 +174,7 @@ __global__ void __launch_bounds__(256) expand_lists_kernel(const float* __restri
 int expand_lists(const float* descs, int ldd, int n, const float* db, int ldb, int D, const int* idx, const float* vals,
                  int ldl, int k, float alpha, float* out, int ldo, hipStream_t stream) {
     if (n <= 0) return DIR_OK;
+    if (!launch_fits(n, 256)) return fail(DIR_ERR_INVALID, "expand_lists: n * 256 must stay below 2^32 (one workgroup per row): cut the rows");
     const int ia = (int)alpha;
     const int ialpha = ((float)ia == alpha && ia >= 0 && ia <= 64) ? ia : -1;
     const float inv = 1.f / (float)(k + 1);

@@ -275,6 +275,8 @@ int gemm_nt_f32(const float* P, int ldp, const float* Q, int ldq, float* out, in
     const bool few_q = gemm_splitk_factor(NP, NQ, K) == 1;
     if (few_q && NQ <= 32 && K <= 2048 && K > 0 && !(K & 3) && !(ldp & 3) && !(ldq & 3) &&
         !((uintptr_t)P & 15) && !((uintptr_t)Q & 15) && !(qsub && ((uintptr_t)qsub & 15))) {
+        if (!launch_fits(((long)NP + 7) / 8, 256))
+            return fail(DIR_ERR_INVALID, "gemm_nt_f32: NP * 32 must stay below 2^32 (one wave per two rows): cut the rows");
         const unsigned blocks = (unsigned)ceil_div(NP, 8);   // 4 waves x 2 rows
         if (K <= 1024)
             hipLaunchKernelGGL(gemm_nt_small_kernel<4>, dim3(blocks), dim3(256), 0, stream, P, ldp,
@@ -297,7 +299,8 @@ int gemm_nt_f32(const float* P, int ldp, const float* Q, int ldq, float* out, in
     int tj = NQ >= 97 ? 4 : (NQ >= 65 ? 3 : (NQ >= 33 ? 2 : 1));
     const int tiles_j = ceil_div(NQ, 32 * tj);
     const long nblk = (long)tiles_i * tiles_j;
-    if (nblk >= (1L << 31)) return fail(DIR_ERR_INVALID, "gemm_nt_f32: grid too large");
+    if (!launch_fits(nblk, 256))
+        return fail(DIR_ERR_INVALID, "gemm_nt_f32: tiles * 256 must stay below 2^32 (one workgroup per 128 x 32..128 tile): cut the rows");
     int ksplit = gemm_splitk_factor(NP, NQ, K);
     float* partial = nullptr;
     bool own = false;

@@ -90,8 +90,10 @@ __global__ void __launch_bounds__(256) quantize_rows_i8_kernel(const float* __re
 
 int quantize_rows_i8(const float* X, int ldx, int N, int D, int8_t* codes, int ldc, float* scales, hipStream_t stream) {
     if (N <= 0) return DIR_OK;
-    hipLaunchKernelGGL(quantize_rows_i8_kernel, dim3((unsigned)ceil_div(N, 4)), dim3(256), 0, stream, X, ldx, N, D, codes, ldc,
-                       scales);
+    const long blocks = ((long)N + 3) / 4;
+    if (!launch_fits(blocks, 256))
+        return fail(DIR_ERR_INVALID, "quantize_rows_i8: N * 64 must stay below 2^32 (one wave per row): cut the rows");
+    hipLaunchKernelGGL(quantize_rows_i8_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, X, ldx, N, D, codes, ldc, scales);
     DIR_HIP_CHECK(hipGetLastError());
     return DIR_OK;
 }
@@ -171,7 +173,9 @@ int similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, co
                   const float* bscales, int N, int D, float* scores, int lds, hipStream_t stream) {
     if (Q <= 0 || N <= 0) return DIR_OK;
     const int Kp = pad64(D), T = ceil_div(Kp, kStripRow), qblocks = ceil_div(Q, kI8QB);
-    if (qblocks > 65535) return fail(DIR_ERR_INVALID, "similarity_i8: more than 65535 * 96 queries in one call");
+    if (qblocks > kMaxGridYZ) return fail(DIR_ERR_INVALID, "similarity_i8: more than 65535 * 96 queries in one call");
+    if (!launch_fits(ceil_div(N, kStripRows), 768))
+        return fail(DIR_ERR_INVALID, "similarity_i8: N * 3 must stay below 2^32 (768 threads per 256 rows): cut the database");
     static std::atomic<uint64_t> attr_done{0};
     DIR_HIP_CHECK(ensure_dynamic_lds((const void*)sim_i8_kernel, kI8Lds, attr_done));
     int8_t* img = nullptr;
@@ -204,9 +208,9 @@ bool similarity_i8_admissible(const int8_t* bcodes, int ldb, int D) {
 // butterfly), D / 64 + 6 roundings on the longest path.
 __global__ void __launch_bounds__(256) gather_scores_kernel(const float* __restrict__ Qm, int ldq, const float* __restrict__ B,
                                                           int ldb, int D, const int* __restrict__ cand, int ldcand, int R,
-                                                          float* __restrict__ scores, int ldsc, long total) {
+                                                          float* __restrict__ scores, int ldsc, long item0, long total) {
     const int lane = threadIdx.x & 63;
-    const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long item = item0 + (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (item >= total) return;
     const int q = (int)(item / R), r = (int)(item % R);
     const int c = cand[(size_t)q * ldcand + r];
@@ -237,11 +241,16 @@ __global__ void __launch_bounds__(256) gather_scores_kernel(const float* __restr
 int gather_scores(const float* queries, int ldq, int Q, const float* database, int ldb, int D, const int* cand, int ldcand,
                   int R, float* scores, int ldsc, hipStream_t stream) {
     if (Q <= 0 || R <= 0) return DIR_OK;
+    // the pairs are independent: as many launches of at most kMaxLaunchThreads threads as Q * R asks for, launch i from
+    // pair i * kGatherMaxBlocks * 4 (a pair's wave and its order of operations do not depend on the cut)
+    constexpr long kGatherMaxBlocks = kMaxLaunchThreads / 256;
     const long total = (long)Q * R, blocks = (total + 3) / 4;
-    if (blocks > 0x7fffffffL) return fail(DIR_ERR_INVALID, "gather_scores: more than 2^33 (query, candidate) pairs");
-    hipLaunchKernelGGL(gather_scores_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, queries, ldq, database, ldb, D, cand,
-                       ldcand, R, scores, ldsc, total);
-    DIR_HIP_CHECK(hipGetLastError());
+    for (long b0 = 0; b0 < blocks; b0 += kGatherMaxBlocks) {
+        const long nb = blocks - b0 < kGatherMaxBlocks ? blocks - b0 : kGatherMaxBlocks;
+        hipLaunchKernelGGL(gather_scores_kernel, dim3((unsigned)nb), dim3(256), 0, stream, queries, ldq, database, ldb, D, cand,
+                           ldcand, R, scores, ldsc, b0 * 4, total);
+        DIR_HIP_CHECK(hipGetLastError());
+    }
     return DIR_OK;
 }
 

@@ -73,7 +73,7 @@ __global__ void __launch_bounds__(256) segment_sums_kernel(const float* __restri
 int segment_sums(const float* X, int ldx, int N, int D, const int* order, const int* seg_off, int S, float* sums, int lds,
                  hipStream_t stream) {
     if (S <= 0) return DIR_OK;
-    if (S > 65535) return fail(DIR_ERR_INVALID, "segment_sums: more than 65535 segments");
+    if (S > kMaxGridYZ) return fail(DIR_ERR_INVALID, "segment_sums: more than 65535 segments");
     hipLaunchKernelGGL(segment_sums_kernel, dim3((unsigned)ceil_div(D, kSegCols), (unsigned)S), dim3(256), 0, stream, X, ldx, N,
                        D, order, seg_off, sums, lds);
     DIR_HIP_CHECK(hipGetLastError());
@@ -193,6 +193,11 @@ int ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, cons
                 int lds, int width, hipStream_t stream) {
     if (Q <= 0 || width <= 0) return DIR_OK;
     const long total = (long)Q * width;
+    // (refused, not cut: a caller reaches Q * width >= 2^32 only with score and id rows of 32 GiB for one chunk)
+    if (!launch_fits((total + 255) / 256, 256))
+        return fail(DIR_ERR_INVALID, "ivf_scan_i8: Q * width must stay below 2^32 (one thread per id slot): cut the queries");
+    if (!launch_fits(items, 768))
+        return fail(DIR_ERR_INVALID, "ivf_scan_i8: items * 768 must stay below 2^32 (768 threads per item): cut the queries");
     hipLaunchKernelGGL(fill_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, out_ids, lds, width, total);
     DIR_HIP_CHECK(hipGetLastError());
     if (items <= 0 || N <= 0) return DIR_OK;

@@ -88,7 +88,8 @@ int ivfpq_base(const float* queries, int ldq, int Q, const float* centroids, int
     const long slots = (long)Q * nprobe;
     if (slots <= 0) return DIR_OK;
     if (M > kBaseThreads) return fail(DIR_ERR_INVALID, "ivfpq_base: M above the sub-spaces of a workgroup");
-    if (slots > 0x7fffffffL) return fail(DIR_ERR_INVALID, "ivfpq_base: more than 2^31 - 1 slots: cut the queries");
+    if (!launch_fits(slots, kBaseThreads))
+        return fail(DIR_ERR_INVALID, "ivfpq_base: Q * nprobe * 128 must stay below 2^32 (one workgroup per slot): cut the queries");
     hipLaunchKernelGGL(ivfpq_base_kernel, dim3((unsigned)slots), dim3(kBaseThreads), 0, stream, queries, ldq, centroids, ldc,
                        nlist, D, M, probe, nprobe, base);
     DIR_HIP_CHECK(hipGetLastError());
@@ -208,7 +209,8 @@ static int ivfpq_scan_launch(const float* lut, const float* base, int Q, int M, 
                              float* scores, int* out_ids, int lds, int width, hipStream_t stream) {
     const int spans = ceil_div(width, kScanCols);
     const long blocks = (long)Q * spans;
-    if (blocks > 0x7fffffffL) return fail(DIR_ERR_INVALID, "ivfpq_scan: more than 2^31 - 1 workgroups: cut the queries");
+    if (!launch_fits(blocks, kScanCols))
+        return fail(DIR_ERR_INVALID, "ivfpq_scan: Q * width (rounded up to 1024 columns) must stay below 2^32: cut the queries");
     const int words = (M + 3) >> 2;
     const int bytes = std::min(kWords, (words + 1) & ~1) * 4096 + kScanSlotBytes;
     static std::atomic<uint64_t> attr_done{0};

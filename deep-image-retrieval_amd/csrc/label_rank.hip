@@ -237,6 +237,8 @@ int label_rank(const float* scores, int lds, int Q, int N, const int* labels, co
                hipStream_t stream) {
     if (Q <= 0) return DIR_OK;
     if (lds < N) return fail(DIR_ERR_INVALID, "label_rank: lds < N");
+    if (!launch_fits(Q, kLabelThreads))
+        return fail(DIR_ERR_INVALID, "label_rank: Q * 512 must stay below 2^32 (one workgroup per query): cut the queries");
     int* result = nullptr;
     const size_t result_bytes = ((size_t)N + 2) * sizeof(int);
     if (hipMallocAsync((void**)&result, result_bytes, stream) != hipSuccess) {

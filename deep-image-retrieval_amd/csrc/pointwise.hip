@@ -67,6 +67,8 @@ int prep_input(const void* img, int fmt, const float* mean3, const float* std3, 
     const int H2 = (H + 1) / 2, W2 = (W + 1) / 2;
     const long total = (long)B * H2 * W2;
     const int threads = 256;
+    if (!launch_fits((total + threads - 1) / threads, threads))
+        return fail(DIR_ERR_INVALID, "prep_input: B * ceil(H / 2) * ceil(W / 2) must stay below 2^32 (one thread per 2 x 2 cell): lower the batch");
     const unsigned blocks = (unsigned)((total + threads - 1) / threads);
     float m[3] = {0, 0, 0}, s[3] = {1, 1, 1};
     if (fmt == DIR_IMG_U8_NHWC) {
@@ -140,6 +142,8 @@ int maxpool_3x3s2(const void* x, void* y, int B, int H, int W, int C, int dtype,
     const int PH = (H - 1) / 2 + 1, PW = (W - 1) / 2 + 1;  // floor((H + 2 - 3) / 2) + 1
     const long total = (long)B * PH * PW * (C / 8);
     const int threads = 256;
+    if (!launch_fits((total + threads - 1) / threads, threads))
+        return fail(DIR_ERR_INVALID, "maxpool: B * PH * PW * C / 8 must stay below 2^32 (one thread per 8 channels): lower the batch");
     const unsigned blocks = (unsigned)((total + threads - 1) / threads);
     if (dtype == DIR_BF16)
         hipLaunchKernelGGL(maxpool_kernel<BF16>, dim3(blocks), dim3(threads), 0, stream,
@@ -241,6 +245,8 @@ int global_pool(const void* x, float* out, int ldo, int B, int H, int W, int C, 
     if (C % 64 != 0) return fail(DIR_ERR_INVALID, "global_pool: C must be a multiple of 64");
     if (pooling == DIR_POOL_GEM && !(p > 0.f)) return fail(DIR_ERR_INVALID, "global_pool: p <= 0");
     if (dtype != DIR_BF16 && dtype != DIR_FP16) return fail(DIR_ERR_INVALID, "global_pool: bad dtype");
+    if (!launch_fits(C / 64, 256)) return fail(DIR_ERR_INVALID, "global_pool: C * 4 must stay below 2^32 (256 threads per 64 channels)");
+    if (B > kMaxGridYZ) return fail(DIR_ERR_INVALID, "global_pool: more than 65535 images in one call");
     const dim3 grid(C / 64, B);
 #define DIR_GP(DT, POOL)                                                                      \
     hipLaunchKernelGGL((global_pool_kernel<DT, POOL>), grid, dim3(256), 0, stream,            \
@@ -297,6 +303,8 @@ int upsample_add(const void* x, const void* low, void* y, int B, int H, int W, i
     if (C % 8 != 0) return fail(DIR_ERR_INVALID, "upsample_add: C must be a multiple of 8");
     if (dtype != DIR_BF16 && dtype != DIR_FP16) return fail(DIR_ERR_INVALID, "upsample_add: bad dtype");
     const long total = (long)B * H * W * (C / 8);
+    if (!launch_fits((total + 255) / 256, 256))
+        return fail(DIR_ERR_INVALID, "upsample_add: B * H * W * C / 8 must stay below 2^32 (one thread per 8 channels): lower the batch");
     const dim3 grid((unsigned)((total + 255) / 256));
     const float sy = (float)h / (float)H, sx = (float)w / (float)W;
     if (dtype == DIR_BF16)
@@ -330,6 +338,7 @@ __global__ void __launch_bounds__(256) l2norm_rows_kernel(float* __restrict__ x,
 
 int l2norm_rows(float* x, int rows, int cols, float eps, hipStream_t stream) {
     if (rows <= 0) return DIR_OK;
+    if (!launch_fits(rows, 256)) return fail(DIR_ERR_INVALID, "l2norm_rows: rows * 256 must stay below 2^32 (one workgroup per row): cut the rows");
     hipLaunchKernelGGL(l2norm_rows_kernel, dim3(rows), dim3(256), 0, stream, x, cols, eps);
     DIR_HIP_CHECK(hipGetLastError());
     return DIR_OK;
@@ -365,6 +374,8 @@ int multiscale_pool(const float* x, float* out, int S, int N, int D, int mode, f
     if (mode != 0 && mode != 1) return fail(DIR_ERR_INVALID, "multiscale_pool: bad mode");
     const long ND = (long)N * D;
     if (ND == 0) return DIR_OK;
+    if (!launch_fits((ND + 255) / 256, 256))
+        return fail(DIR_ERR_INVALID, "multiscale_pool: N * D must stay below 2^32 (one thread per element): cut the rows");
     const unsigned blocks = (unsigned)((ND + 255) / 256);
     hipLaunchKernelGGL(multiscale_pool_kernel, dim3(blocks), dim3(256), 0, stream, x, out, S, ND,
                        mode, gemp);

@@ -146,7 +146,8 @@ __global__ void __launch_bounds__(256) pq_encode_kernel(const float* __restrict_
 int pq_encode(const float* X, int ldx, int N, int D, int M, const float* codebooks, uint8_t* codes, int ldc, hipStream_t stream) {
     if (N <= 0) return DIR_OK;
     const long blocks = (long)ceil_div(N, kEncPasses * kSubRows) * M;
-    if (blocks > 0x7fffffffL) return fail(DIR_ERR_INVALID, "pq_encode: more than 2^31 - 1 workgroups: cut the rows");
+    if (!launch_fits(blocks, 256))
+        return fail(DIR_ERR_INVALID, "pq_encode: N * M (N rounded up to 256 rows) must stay below 2^32: cut the rows");
     hipLaunchKernelGGL(pq_encode_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, X, ldx, N, D, M, codebooks, codes, ldc);
     DIR_HIP_CHECK(hipGetLastError());
     return DIR_OK;
@@ -178,7 +179,8 @@ __global__ void __launch_bounds__(256) pq_lut_kernel(const float* __restrict__ Q
 int pq_lut(const float* queries, int ldq, int Q, int D, int M, const float* codebooks, float* lut, hipStream_t stream) {
     if (Q <= 0) return DIR_OK;
     const long blocks = (long)ceil_div(Q, kLutPasses * kSubRows) * M;
-    if (blocks > 0x7fffffffL) return fail(DIR_ERR_INVALID, "pq_lut: more than 2^31 - 1 workgroups: cut the queries");
+    if (!launch_fits(blocks, 256))
+        return fail(DIR_ERR_INVALID, "pq_lut: Q * M * 8 (Q rounded up to 32 queries) must stay below 2^32: cut the queries");
     hipLaunchKernelGGL(pq_lut_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, queries, ldq, Q, D, M, codebooks, lut);
     DIR_HIP_CHECK(hipGetLastError());
     return DIR_OK;

@@ -174,6 +174,8 @@ int rank_counts(const float* scores, int lds, int Q, int N, const int* probe_idx
                 float* probe_scores, hipStream_t stream) {
     if (Q <= 0 || P <= 0 || N <= 0) return DIR_OK;
     if (lds < N) return fail(DIR_ERR_INVALID, "rank_counts: lds < N");
+    // (the histogram's grid.y; the sort and the finish then launch Q * 256 < 2^24 threads)
+    if (Q > kMaxGridYZ) return fail(DIR_ERR_INVALID, "rank_counts: more than 65535 queries in one call");
     DIR_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)Q * P * sizeof(int), stream));
     static std::atomic<uint64_t> attr_sort{0}, attr_hist{0}, attr_fin{0};
     DIR_HIP_CHECK(ensure_dynamic_lds((const void*)rank_sort_kernel, kMaxProbes * 12, attr_sort));
@@ -304,6 +306,8 @@ int expand_descriptors(const float* descs, int n, const float* db, int m, int D,
     if (self_set && m != n) return fail(DIR_ERR_INVALID, "expand_descriptors: self expansion needs db == descs");
     const size_t rows_fit = sim_bytes / ((size_t)m * sizeof(float));
     if (rows_fit == 0) return fail(DIR_ERR_WORKSPACE, "expand_descriptors: scratch smaller than one score row");
+    if (!launch_fits((long)std::min<size_t>(rows_fit, (size_t)n), 256))
+        return fail(DIR_ERR_INVALID, "expand_descriptors: rows of a pass * 256 must stay below 2^32 (one workgroup per row): pass a smaller scratch");
     for (int r0 = 0; r0 < n; r0 += (int)std::min<size_t>(rows_fit, 1 << 30)) {
         const int rows = (int)std::min<size_t>(rows_fit, (size_t)(n - r0));
         // sim[r][j] = <descs[r0 + r], db[j]>  (P = db: the long operand; exact fp32 MFMA)
@@ -381,6 +385,8 @@ int revisitop_ap(const int* probe_idx, int Q, int P, const int* counts, const fl
                  const int* pos_list, const int* junk_off, const int* junk_list, int modes, double* terms,
                  double* ap_out, hipStream_t stream) {
     if (Q <= 0 || modes <= 0) return DIR_OK;
+    if (!launch_fits(Q, 256)) return fail(DIR_ERR_INVALID, "revisitop_ap: Q * 256 must stay below 2^32 (one workgroup per query and mode)");
+    if (modes > kMaxGridYZ) return fail(DIR_ERR_INVALID, "revisitop_ap: more than 65535 modes");
     hipLaunchKernelGGL(revisitop_ap_kernel, dim3(Q, modes), dim3(256), 0, stream, probe_idx, P, counts, pscores,
                        pos_off, pos_list, junk_off, junk_list, modes, terms, ap_out);
     DIR_HIP_CHECK(hipGetLastError());

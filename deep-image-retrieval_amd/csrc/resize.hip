@@ -97,6 +97,11 @@ int resize_bilinear_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, in
         return fail(DIR_ERR_WORKSPACE, "resize: workspace too small");
     if (((uintptr_t)ws & 3) != 0) return fail(DIR_ERR_INVALID, "resize: workspace must be 4-byte aligned");
     const bool horiz = OW != W, vert = OH != H;
+    // one thread per output byte of a pass (the coefficient tables: OW or OH threads, fewer than either pass)
+    if (horiz && !launch_fits(((long)B * H * OW * 3 + 255) / 256, 256))
+        return fail(DIR_ERR_INVALID, "resize: B * H * OW * 3 must stay below 2^32 (one thread per byte of the horizontal pass): lower the batch");
+    if (vert && !launch_fits(((long)B * OH * OW * 3 + 255) / 256, 256))
+        return fail(DIR_ERR_INVALID, "resize: B * OH * OW * 3 must stay below 2^32 (one thread per output byte): lower the batch");
     if (!horiz && !vert) {
         DIR_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)B * H * W * 3, hipMemcpyDeviceToDevice, stream));
         return DIR_OK;

@@ -294,7 +294,8 @@ size_t whiten_split_workspace_bytes(int v, int K) { return (size_t)ceil_div(v, k
 bool whiten_split_admissible(const float* X, int ldx, int N, int K, int v) {
     return N > 0 && v > 0 && K > 0 && (K % 32) == 0 && (ldx % 4) == 0 && ((uintptr_t)X & 15) == 0 && ldx >= K &&
            (size_t)ldx * 4 * kStripRows < (1ull << 31) && (size_t)ceil_div(K, 32) * kSlabQ2 < (1ull << 31) &&
-           kLds2 + (size_t)K * 4 <= 160 * 1024 && (size_t)ceil_div(N, kStripRows) * ceil_div(v, kQB) < (1ull << 30);
+           kLds2 + (size_t)K * 4 <= 160 * 1024 && ceil_div(v, kQB) <= kMaxGridYZ &&
+           launch_fits(8L * ceil_div(ceil_div(N, kStripRows), 8) * ceil_div(v, kQB), 768);   // (the grid of whiten_split below)
 }
 
 // X [N, K] (row stride ldx), components [v, K] (row stride ldc), mean [K] or null, alpha [v] or null -> out [N, v] (row stride ldo).
@@ -332,7 +333,7 @@ bool similarity_split_admissible(const float* P, int ldp, const float* Q, int ld
     (void)Q, (void)ldq;
     return NP > 0 && NQ > 0 && K > 0 && (K % 32) == 0 && (ldp % 4) == 0 && ((uintptr_t)P & 15) == 0 &&
            (size_t)ldp * 4 * kStripRows < (1ull << 31) && (size_t)ceil_div(K, 32) * kSlabQ < (1ull << 31) &&
-           ceil_div(NQ, kQB) < 65536;
+           ceil_div(NQ, kQB) <= kMaxGridYZ && launch_fits(ceil_div(NP, kStripRows), 768);   // (grid.y, grid.x * 768 threads)
 }
 
 int similarity_split(const float* P, int ldp, const float* Q, int ldq, float* out, int ldo, int NP, int NQ, int K,

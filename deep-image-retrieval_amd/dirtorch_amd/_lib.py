@@ -45,6 +45,7 @@ class ProfRecord(Structure):
 SIGNATURES = {
     'dir_last_error': (c_char_p, []),
     'dir_version': (c_char_p, []),
+    'dir_launch_max_threads': (c_int64, []),
     'dir_engine_create': (c_int, [POINTER(ModelDesc), c_int, POINTER(c_void_p)]),
     'dir_engine_destroy': (c_int, [c_void_p]),
     'dir_engine_set_tensor': (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),

@@ -104,6 +104,43 @@ typedef struct dir_engine dir_engine;
 const char* dir_last_error(void);
 /* "dir_engine <version> gfx950" — lets the host check it loaded the library it expects. */
 const char* dir_version(void);
+/* Launch extents (host-only query).  A dispatch holds gridDim.x * blockDim.x as a 32-bit count of threads, so no launch of
+ * this library exceeds dir_launch_max_threads() = 2^32 - 256 threads, nor 65535 on gridDim.y.  An entry whose launch follows
+ * a caller's size states the size it refuses below ("launch limit:"): such a call fails with DIR_ERR_INVALID and a message
+ * that names the entry and the product, before anything is launched.  dir_gather_scores cuts its work into several launches
+ * instead and takes any Q * R.  Entries that state none are held below the limit by their other rules (int sizes, k and M
+ * maxima, the 2^31-byte rule of an engine call).
+ * launch limit, per entry (L = dir_launch_max_threads(); "<=" is what a call may have):
+ *   dir_prep_input           B * ceil(H / 2) * ceil(W / 2) <= L
+ *   dir_maxpool_3x3s2        B * PH * PW * C / 8 <= L
+ *   dir_global_pool          C * 4 <= L, B <= 65535
+ *   dir_upsample_add         B * H * W * C / 8 <= L
+ *   dir_resize_bilinear_u8   B * H * OW * 3 <= L where OW != W, B * OH * OW * 3 <= L where OH != H
+ *   dir_l2norm_rows          rows * 256 <= L
+ *   dir_multiscale_pool      N * D <= L
+ *   dir_gemm_nt_f32          NP * 32 <= L on the few-row form (NQ <= 32, K <= 2048, aligned), else
+ *                            ceil(NP / 128) * ceil(NQ / (32 .. 128)) * 256 <= L; dir_fc_l2, dir_pca_whiten_l2*, dir_similarity*
+ *                            and dir_expand_descriptors inherit it (their split forms turn away what does not fit and leave
+ *                            the shape to this one)
+ *   dir_rank_counts          Q <= 65535
+ *   dir_revisitop_ap         Q * 256 <= L, modes <= 65535
+ *   dir_label_rank           Q * 512 <= L
+ *   dir_expand_descriptors   min(n, rows the scratch holds) * 256 <= L
+ *   dir_expand_lists         n * 256 <= L
+ *   dir_quantize_rows_i8     N * 64 <= L (N rounded up to 4)
+ *   dir_similarity_i8        N * 3 <= L (N rounded up to 256), Q <= 65535 * 96
+ *   dir_gather_scores        none: several launches
+ *   dir_segment_sums         S <= 65535
+ *   dir_ivf_scan_i8          Q * width <= L, items * 768 <= L (refused, not cut: Q * width of 2^32 means 32 GiB of score and id
+ *                            rows for one chunk; index.py's chunks are scratch_bytes / 8 slots, 2^25 by default)
+ *   dir_pq_encode            N * M <= L (N rounded up to 256)
+ *   dir_pq_lut               Q * M * 8 <= L (Q rounded up to 32)
+ *   dir_ivfpq_base           Q * nprobe * 128 <= L
+ *   dir_ivfpq_scan           Q * width <= L (width rounded up to 1024)
+ *   dir_knn_graph            N * k <= L
+ *   dir_diffusion_seed       N * Q <= L
+ *   dir_diffusion_solve      N * Q <= L, Q <= 65535 * 64 */
+int64_t dir_launch_max_threads(void);
 /* The DIRTORCH_AMD_* A/B switches (kernel-selection toggles for bisecting; no reference counterpart - the reference reads no
  * environment on this path) are read from the environment ONCE, at the library's first use, and copied into an engine at
  * dir_engine_create.  A host that changes one of them afterwards (tests, A/B scripts) calls this to re-read them.  Two lifetimes:
