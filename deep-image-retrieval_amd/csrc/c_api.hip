@@ -1161,6 +1161,52 @@ int dir_diffusion_solve(const int* idx, int ldl, const float* S, int lds, int N,
     DIR_CATCH
 }
 
+int dir_diffusion_local_max_rows(void) { return topk_max_k(); }
+
+int dir_diffusion_subgraph(const int* idx, int ldl, const float* S, int lds, int N, int k, const int* cidx, const float* cvals,
+                           int ldc, int Q, int T, int kq, float gamma, int one_hot, int* cid, int* lidx, float* lw, float* y,
+                           int ldt, void* stream) {
+    DIR_TRY
+    if (N < 0 || k < 0 || Q < 0 || T < 0 || kq < 0) return fail(DIR_ERR_INVALID, "diffusion_subgraph: negative size");
+    if (k > topk_max_k()) return fail(DIR_ERR_INVALID, "diffusion_subgraph: k exceeds dir_topk_max_k()");
+    if (T < 1 || T > topk_max_k()) return fail(DIR_ERR_INVALID, "diffusion_subgraph: 1 <= T <= dir_diffusion_local_max_rows() expected");
+    if (ldl < k || lds < k) return fail(DIR_ERR_INVALID, "diffusion_subgraph: ldl, lds < k");
+    if (ldc < T || ldt < T) return fail(DIR_ERR_INVALID, "diffusion_subgraph: ldc, ldt < T");
+    DIR_CHECK(diffusion_check_gamma("diffusion_subgraph", gamma));
+    if (Q == 0) return DIR_OK;
+    if (!cidx || !cid || !y || (k > 0 && (!lidx || !lw)) || (k > 0 && N > 0 && (!idx || !S)) || (!one_hot && kq > 0 && !cvals))
+        return fail(DIR_ERR_INVALID, "diffusion_subgraph: null pointer");
+    return diffusion_subgraph(idx, ldl, S, lds, N, k, cidx, cvals, ldc, Q, T, kq, gamma, one_hot, cid, lidx, lw, y, ldt,
+                              (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_diffusion_solve_local(const int* lidx, const float* lw, int k, const float* y, const int* cid, int ldt, int Q, int T,
+                              float alpha, int iters, float* f, int ldf, void* stream) {
+    DIR_TRY
+    if (k < 0 || Q < 0 || T < 0 || iters < 0) return fail(DIR_ERR_INVALID, "diffusion_solve_local: negative size");
+    if (k > topk_max_k()) return fail(DIR_ERR_INVALID, "diffusion_solve_local: k exceeds dir_topk_max_k()");
+    if (T < 1 || T > topk_max_k()) return fail(DIR_ERR_INVALID, "diffusion_solve_local: 1 <= T <= dir_diffusion_local_max_rows() expected");
+    if (ldt < T || ldf < T) return fail(DIR_ERR_INVALID, "diffusion_solve_local: ldt, ldf < T");
+    if (!(alpha >= 0.f && alpha < 1.f)) return fail(DIR_ERR_INVALID, "diffusion_solve_local: alpha outside [0, 1)");
+    if (Q == 0) return DIR_OK;
+    if (!y || !f || (k > 0 && (!lidx || !lw))) return fail(DIR_ERR_INVALID, "diffusion_solve_local: null pointer");
+    return diffusion_solve_local(lidx, lw, k, y, cid, ldt, Q, T, alpha, iters, f, ldf, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_diffusion_spread(float* scores, int lds, int Q, int N, const int* cid, const float* f, int ldt, int T, void* stream) {
+    DIR_TRY
+    if (Q < 0 || N < 0 || T < 0) return fail(DIR_ERR_INVALID, "diffusion_spread: negative size");
+    if (T > topk_max_k()) return fail(DIR_ERR_INVALID, "diffusion_spread: T exceeds dir_diffusion_local_max_rows()");
+    if (lds < N) return fail(DIR_ERR_INVALID, "diffusion_spread: lds < N");
+    if (ldt < T) return fail(DIR_ERR_INVALID, "diffusion_spread: ldt < T");
+    if (Q == 0 || N == 0) return DIR_OK;
+    if (!scores || (T > 0 && (!cid || !f))) return fail(DIR_ERR_INVALID, "diffusion_spread: null pointer");
+    return diffusion_spread(scores, lds, Q, N, cid, f, ldt, T, (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_multiscale_pool(const float* x, float* out, int S, int N, int D, int mode, float gemp,
                         void* stream) {
     DIR_TRY

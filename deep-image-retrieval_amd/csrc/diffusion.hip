@@ -18,6 +18,7 @@
 // tree (s = 32, 16, 8, 4, 2, 1: chain[c] += chain[c + s]), and one thread per column adds the slab partials in ascending slab
 // order from +0.  (A slab of 256 rows keeps that last, serial pass short at 10^6 rows: 3931 partials a column.)
 #include "dir_common.h"
+#include "diffusion_device.h"
 #include "pointwise.h"
 
 // products THEN sums, never a fused multiply-add (see expand_lists.hip)
@@ -25,9 +26,7 @@
 
 namespace dir {
 
-constexpr int kDiffSlab = 256;     // rows per slab of a dot product
-constexpr int kDiffChains = 64;    // chains of a slab: row r belongs to chain r mod 64
-constexpr int kDiffPer = kDiffSlab / kDiffChains;   // rows of a chain
+// (kDiffSlab = 256 rows per slab, kDiffChains = 64 chains, kDiffPer rows of a chain: diffusion_device.h)
 static_assert(kDiffPer % 2 == 0, "a lane takes the rows of its chain two at a time");
 constexpr int kDiffMaxCg = 16;     // column groups (of 4 columns) a workgroup covers: 64 columns
 constexpr int kDiffUnroll = 4;     // gathered rows requested ahead of the adds, per row
@@ -36,18 +35,7 @@ constexpr int kDiffPair = 2;       // rows of a chain a lane works on at a time
 constexpr int kDiffThreads = 1024;  // the largest workgroup: 64 chains x 16 column groups
 constexpr int kDiffFew = 256;       // threads of a workgroup that takes several slabs of a narrow solve
 
-// w = v^gamma: gamma multiplications from 1 for an integer gamma in 0..64, powf otherwise (expand_lists.hip's rule)
-__device__ __forceinline__ float diff_weight(float v, float gamma, int igamma) {
-    if (igamma < 0) return powf(v, gamma);
-    float w = 1.f;
-    for (int e = 0; e < igamma; ++e) w = w * v;
-    return w;
-}
-
-static int diff_igamma(float gamma) {
-    const int ig = (int)gamma;
-    return ((float)ig == gamma && ig >= 0 && ig <= 64) ? ig : -1;
-}
+// (diff_weight, the power rule, and diff_igamma: diffusion_device.h)
 
 // ---- the graph -------------------------------------------------------------------------------------------------------
 // one thread per slot (i, t): its liveness, its weight, the first slot of row j that holds i, the minimum of the two weights

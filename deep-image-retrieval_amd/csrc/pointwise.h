@@ -97,6 +97,14 @@ int diffusion_slab_rows();
 size_t diffusion_workspace_bytes(int N, int Q);
 int diffusion_solve(const int* idx, int ldl, const float* S, int lds, int N, int k, const float* Y, int ldy, int Q, float alpha,
                     int iters, float* F, int ldf, void* workspace, hipStream_t stream);
+// truncated diffusion (diffusion_local.hip): the subgraph of every query's T best rows, its solve in one workgroup, and
+// the spread of the list scores over a [Q][N] score row
+int diffusion_subgraph(const int* idx, int ldl, const float* S, int lds, int N, int k, const int* cidx, const float* cvals, int ldc,
+                       int Q, int T, int kq, float gamma, int one_hot, int* cid, int* lidx, float* lw, float* y, int ldt,
+                       hipStream_t stream);
+int diffusion_solve_local(const int* lidx, const float* lw, int k, const float* y, const int* cid, int ldt, int Q, int T, float alpha,
+                          int iters, float* f, int ldf, hipStream_t stream);
+int diffusion_spread(float* scores, int lds, int Q, int N, const int* cid, const float* f, int ldt, int T, hipStream_t stream);
 // scratch (optional): fp32 workspace for the split-K partial sums of shapes with few output tiles; without one
 // the partials live in stream-ordered memory (hipMallocAsync)
 constexpr size_t kGemmSplitKMaxBytes = 64u << 20;

@@ -163,6 +163,12 @@ SIGNATURES = {
     'dir_diffusion_workspace_bytes': (c_int, [c_int, c_int, POINTER(c_size_t)]),
     'dir_diffusion_solve': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_int,
                                     c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    'dir_diffusion_local_max_rows': (c_int, []),
+    'dir_diffusion_subgraph': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                       c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    'dir_diffusion_solve_local': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int,
+                                          c_void_p, c_int, c_void_p]),
+    'dir_diffusion_spread': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'dir_comm_init_all': (c_int, [c_int, POINTER(c_int), POINTER(c_void_p)]),
     'dir_comm_size': (c_int, [c_void_p, POINTER(c_int)]),
     'dir_comm_destroy': (c_int, [c_void_p]),

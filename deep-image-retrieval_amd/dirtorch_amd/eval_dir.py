@@ -15,6 +15,10 @@ on the mutual K-NN graph of the database from the KQ best rows of every query, "
 tables - with --diffusion-alpha 0.99, --diffusion-gamma 3, --diffusion-iters 20.  It composes after --adba / --aqe: it
 scores the descriptors those produce.  The APs come from ranking.eval_aps_device for the revisitop / classic datasets and
 from db.eval_query_AP on downloaded rows otherwise.
+--diffusion-trunc T (with --diffusion; default off): the scores are the dense form of ranking.diffuse_truncated_device -
+every query solved on the subgraph of its T best database rows, those rows ranked by their diffusion score above all
+others, the others in cosine order.  With it a dataset whose queries are its database rows is accepted (the row itself
+is the one-hot seed).
 """
 import json
 import os
@@ -48,15 +52,25 @@ DIFFUSION_FLAGS = [
     (('--diffusion-alpha',), dict(type=float, default=0.99, help='with --diffusion: the damping of the walk, in [0, 1)')),
     (('--diffusion-gamma',), dict(type=float, default=3, help='with --diffusion: the power applied to a similarity')),
     (('--diffusion-iters',), dict(type=int, default=20, help='with --diffusion: conjugate-gradient iterations')),
+    (('--diffusion-trunc',), dict(type=int, default=0, metavar='T',
+                                  help='with --diffusion: solve every query on the subgraph of its T best rows (0 = all rows)')),
 ]
 
 
 def diffusion_options(args):
-    """the diffuse_device keywords of parsed DIFFUSION_FLAGS, None without --diffusion"""
+    """the diffuse_device keywords of parsed DIFFUSION_FLAGS, None without --diffusion; with --diffusion-trunc T also
+    trunc=T, which selects ranking.diffuse_truncated_device"""
     if args.diffusion is None:
+        if getattr(args, 'diffusion_trunc', 0):
+            raise SystemExit('--diffusion-trunc needs --diffusion K KQ')
         return None
-    return dict(k=args.diffusion[0], kq=args.diffusion[1], alpha=args.diffusion_alpha, gamma=args.diffusion_gamma,
-                iters=args.diffusion_iters)
+    out = dict(k=args.diffusion[0], kq=args.diffusion[1], alpha=args.diffusion_alpha, gamma=args.diffusion_gamma,
+               iters=args.diffusion_iters)
+    if getattr(args, 'diffusion_trunc', 0):
+        if args.diffusion_trunc < 0:
+            raise SystemExit('--diffusion-trunc must be positive')
+        out['trunc'] = args.diffusion_trunc
+    return out
 
 
 def descriptors(db, net, trfs, pooling='mean', gemp=3, whiten=None, aqe=None, adba=None, threads=8, batch_size=16,
@@ -117,7 +131,8 @@ def eval_model(db, net, trfs, pooling='mean', gemp=3, detailed=False, whiten=Non
     (descriptors above) exists on that device route only: test_dir.eval_model has one expansion, the matrix, and asking
     it for lists raises instead of quietly running the matrix.
     diffusion: None, or the keywords of ranking.diffuse_device (k, kq, gamma, alpha, iters) - the queries are then scored
-    by diffusion on the database's kNN graph (a dataset with a query set of its own; the same dict comes back)."""
+    by diffusion on the database's kNN graph (a dataset with a query set of its own; the same dict comes back).  With a
+    `trunc` among them the scores are ranking.diffuse_truncated_device's dense form, and a self-set dataset is accepted."""
     if expand not in EXPAND_ROUTES:
         raise ValueError('expand: one of %s expected, got %r' % (', '.join(EXPAND_ROUTES), expand))
     if diffusion is not None:
@@ -148,12 +163,16 @@ def eval_model(db, net, trfs, pooling='mean', gemp=3, detailed=False, whiten=Non
 def _eval_diffusion(db, net, trfs, diffusion, detailed, expand, desc_kw):
     """eval_model with diffusion scores: descriptors(), ranking.diffuse_device, then the APs on the device where the
     dataset has the revisitop / classic fields and through db.eval_query_AP / eval_query_top on downloaded rows otherwise"""
-    if db.get_query_db() is db:
+    same_set = db.get_query_db() is db
+    if same_set and not diffusion.get('trunc'):
         raise ValueError('diffusion needs a dataset with a query set of its own: queries that are database rows are '
                          'not supported')
     print("\n>> Evaluation...")
     qdescs, bdescs = descriptors(db, net, trfs, expand=expand, **desc_kw)
-    scores = ranking.diffuse_device(qdescs, bdescs, **diffusion)
+    if diffusion.get('trunc'):
+        scores = ranking.diffuse_truncated_device(qdescs, bdescs, same_set=same_set, dense=True, **diffusion)
+    else:
+        scores = ranking.diffuse_device(qdescs, bdescs, **diffusion)
     res = {}
     if hasattr(db, 'junk'):
         test_dir._mean_ap(ranking.eval_aps_device(db, scores), detailed, res)

@@ -1099,6 +1099,121 @@ def diffusion_solve(idx, S, Y, alpha=0.99, iters=20):
     return F
 
 
+# ---- truncated diffusion: a query's top-T subgraph solved in one workgroup (csrc/diffusion_local.hip) -------------------
+@functools.lru_cache(maxsize=None)
+def diffusion_local_max_rows():
+    """The largest T of the truncated diffusion (dir_diffusion_local_max_rows; host-only): topk_max_k()."""
+    return int(_lib.load().dir_diffusion_local_max_rows())
+
+
+def _local_pitch(t, T, what):
+    """a [Q, .., T] table of the local graph with unit stride along T and its rows packed at one pitch -> (t, pitch)"""
+    if t.shape[-1] != T:
+        raise ValueError('%s: %d local rows expected, got %d' % (what, T, t.shape[-1]))
+    if t.numel() == 0:
+        return t, T
+    rows = t.shape[-2]                                    # (k for lidx / lw, Q for y / cid / f)
+    outer = t.shape[0] if t.dim() == 3 else 1
+    if rows > 1:
+        ld = int(t.stride(-2))
+    elif outer > 1:
+        ld = int(t.stride(0))                             # one slot a query: the queries are a pitch apart
+    else:
+        ld = T
+    packed = (T == 1 or t.stride(-1) == 1) and ld >= T and (outer <= 1 or t.stride(0) == ld * rows)
+    if not packed:
+        t, ld = t.contiguous(), T
+    return t, ld
+
+
+def diffusion_subgraph(idx, S, cidx, cvals, kq=10, gamma=3, one_hot=False, ldt=None):
+    """The subgraph of every query's candidate list (dir_diffusion_subgraph; include/dir_engine.h gives the definition,
+    tests/diffusion_trunc_ref.py restates it) -> (cid [Q,T] int32, lidx [Q,k,T] int32, lw [Q,k,T] fp32, y [Q,T] fp32), all
+    CUDA.  idx / S [N,k]: the graph as knn_graph gives it; cidx / cvals [Q,T] int32 / fp32: T candidates a query, best
+    first, as ops.topk or an index's search gives them, 1 <= T <= diffusion_local_max_rows().  cid is the id of a live
+    candidate (in [0, N), first of its id in the list), -1 of a dead one; lidx / lw are the edges among the live candidates
+    in local numbering, slot-major, -1 / +0 elsewhere; y the seeds: cvals^gamma of the live ones among the first kq with a
+    score > 0, or with one_hot 1 at candidate 0.  ldt: the pitch of the T axis of the results (>= T; None = T) - they come
+    back as views [.., :T] of it, which diffusion_solve_local and diffusion_spread take as they are."""
+    idx, S, ldl = _list_pair(idx, S, 'graph')
+    cidx, cvals, ldc = _list_pair(cidx, cvals, 'candidate list')
+    N, k = idx.shape
+    Q, T = cidx.shape
+    if not 1 <= T <= diffusion_local_max_rows():
+        raise ValueError('1 <= T <= %d candidates expected, got %d' % (diffusion_local_max_rows(), T))
+    ldt = T if ldt is None else int(ldt)
+    if ldt < T or kq < 0:
+        raise ValueError('ldt >= T and kq >= 0 expected')
+    dev = cidx.device
+    cid = torch.empty(Q, ldt, dtype=torch.int32, device=dev)
+    lidx = torch.empty(Q, k, ldt, dtype=torch.int32, device=dev)
+    lw = torch.empty(Q, k, ldt, dtype=torch.float32, device=dev)
+    y = torch.empty(Q, ldt, dtype=torch.float32, device=dev)
+    if Q:
+        call('dir_diffusion_subgraph', ptr(idx), ldl, ptr(S), ldl, N, k, ptr(cidx), ptr(cvals), ldc, Q, T, int(kq), float(gamma),
+             int(bool(one_hot)), ptr(cid), ptr(lidx), ptr(lw), ptr(y), ldt, stream_ptr())
+    return cid[:, :T], lidx[:, :, :T], lw[:, :, :T], y[:, :T]
+
+
+def diffusion_solve_local(lidx, lw, y, cid=None, alpha=0.99, iters=20):
+    """(I - alpha S_q) f = y_q on every query's own subgraph by `iters` conjugate-gradient iterations, one workgroup per
+    query and one launch in all (dir_diffusion_solve_local) -> f [Q,T] fp32 CUDA, at the pitch of y.  lidx / lw [Q,k,T],
+    y [Q,T] and cid [Q,T] (optional) as diffusion_subgraph gives them; a slot with lidx outside [0, T) or lw == 0 is
+    skipped.  f is NaN where cid < 0.  The result of a query is diffusion_solve's on that query's graph with the one
+    column y, bit for bit, and does not depend on the other queries of the call."""
+    _on_device(lidx, lw, y, cid)
+    if lidx.dtype != torch.int32 or lw.dtype != torch.float32 or y.dtype != torch.float32 or (
+            cid is not None and cid.dtype != torch.int32):
+        raise TypeError('int32 lidx / cid and float32 lw / y expected')
+    if lidx.dim() != 3 or tuple(lw.shape) != tuple(lidx.shape) or y.dim() != 2 or y.shape[0] != lidx.shape[0] or (
+            cid is not None and tuple(cid.shape) != tuple(y.shape)):
+        raise ValueError('lidx / lw [Q,k,T], y [Q,T] and cid [Q,T] expected')
+    if not 0 <= alpha < 1:
+        raise ValueError('0 <= alpha < 1 expected, got %g' % alpha)
+    if iters < 0:
+        raise ValueError('iters must be non-negative')
+    Q, k, T = lidx.shape
+    if not 1 <= T <= diffusion_local_max_rows():
+        raise ValueError('1 <= T <= %d local rows expected, got %d' % (diffusion_local_max_rows(), T))
+    tabs = [_local_pitch(t, T, 'local table') for t in (lidx, lw, y) + ((cid,) if cid is not None else ())]
+    if len({ld for _, ld in tabs}) != 1:      # (one pitch for all tables in the C ABI)
+        tabs = [(t.contiguous(), T) for t, _ in tabs]
+    ldt = tabs[0][1]
+    lidx, lw, y = tabs[0][0], tabs[1][0], tabs[2][0]
+    cid = tabs[3][0] if cid is not None else None
+    f = torch.empty(Q, ldt, dtype=torch.float32, device=y.device)
+    if Q:
+        call('dir_diffusion_solve_local', ptr(lidx), ptr(lw), k, ptr(y), ptr(cid) if cid is not None else None, ldt, Q, T,
+             float(alpha), int(iters), ptr(f), ldt, stream_ptr())
+    return f[:, :T]
+
+
+def diffusion_spread(scores, cid, f):
+    """List scores back into score rows, IN PLACE (dir_diffusion_spread) -> scores.  scores [Q,N] fp32 CUDA (the plain
+    similarities; unit column stride); cid [Q,T] int32 and f [Q,T] fp32 as diffusion_subgraph / diffusion_solve_local give
+    them.  Every score drops by 4, then a live candidate's column takes max(f, -2) (a NaN f: -2): every candidate outranks
+    every non-candidate, and the non-candidates keep their cosine order."""
+    _on_device(scores, cid, f)
+    if scores.dtype != torch.float32 or f.dtype != torch.float32 or cid.dtype != torch.int32:
+        raise TypeError('float32 scores / f and int32 cid expected')
+    if scores.dim() != 2 or cid.dim() != 2 or tuple(f.shape) != tuple(cid.shape) or cid.shape[0] != scores.shape[0]:
+        raise ValueError('scores [Q,N], cid [Q,T] and f [Q,T] expected')
+    Q, N = scores.shape
+    T = cid.shape[1]
+    if T > diffusion_local_max_rows():
+        raise ValueError('T <= %d expected, got %d' % (diffusion_local_max_rows(), T))
+    if Q == 0 or N == 0:
+        return scores
+    if scores.stride(1) != 1 or (Q > 1 and scores.stride(0) < N):
+        raise ValueError('scores with unit column stride and a row pitch >= N expected (they are changed in place)')
+    lds = int(scores.stride(0)) if Q > 1 else N
+    (cid, ldc), (f, ldf) = _local_pitch(cid, T, 'cid'), _local_pitch(f, T, 'f')
+    if ldc != ldf:
+        cid, f, ldc = cid.contiguous(), f.contiguous(), T
+    call('dir_diffusion_spread', ptr(scores), lds, Q, N, ptr(cid), ptr(f), ldc, T, stream_ptr())
+    return scores
+
+
 def stem_pool(s2d, w_packed, bias, out_hw):
     """Fused stem: s2d image [B,H2,W2,16] + packed 4x4x16 filter -> pooled [B,PH,PW,64];
     out_hw = (OH, OW) of the 7x7 s2 convolution."""

@@ -349,3 +349,50 @@ def diffuse_device(qdescs, bdescs, k=50, kq=10, gamma=3, alpha=0.99, iters=20, g
     Y = ops.diffusion_seed(qidx, qvals, N, gamma)
     F = ops.diffusion_solve(idx, S, Y, alpha=alpha, iters=iters)
     return F.t().contiguous()
+
+
+def diffuse_truncated_device(qdescs, bdescs, trunc=1000, k=50, kq=10, gamma=3, alpha=0.99, iters=20, graph=None, index=None,
+                             same_set=False, dense=False, scratch_bytes=256 << 20, **search_kw):
+    """Truncated diffusion: every query solved on the subgraph of its `trunc` best database rows, as Iscen et al. do at
+    query time - (idx [Q, trunc] int32, vals [Q, trunc] fp32), both CUDA: the candidates re-ranked by their diffusion
+    score, best first (ops.topk over the list scores with the candidates' ids; dead candidates end as (-1, NaN)).
+    The candidates are the `trunc` best rows of every query - exact (retrieve_device) or index.search(..., **search_kw) -
+    with trunc clipped to N and at most ops.diffusion_local_max_rows(); the first kq of them seed the solve (score^gamma).
+    The subgraph of the candidates is cut out of the graph (ops.diffusion_subgraph) and (I - alpha S_q) f = y_q is solved
+    by `iters` conjugate-gradient iterations in one workgroup per query and one launch (ops.diffusion_solve_local):
+    nothing of size N is touched after the lists.  graph / index / search_kw: as in diffuse_device.
+    same_set=True: the queries ARE the database rows (qdescs and bdescs hold the same rows): the query's own row is
+    candidate 0 with a one-hot seed, followed by its trunc - 1 best other rows - the case diffuse_device refuses.
+    dense=True: scores [Q, N] fp32 CUDA instead, for eval_aps_device, ops.topk and ops.rank_counts: the similarities
+    (similarity_device) minus 4, a candidate's column overwritten by max(f, -2) (ops.diffusion_spread), so every candidate
+    outranks every other row and the other rows keep their cosine order."""
+    from .utils.common import _dev
+    q, b = _dev(qdescs), _dev(bdescs)
+    if q.dim() != 2 or b.dim() != 2 or q.shape[1] != b.shape[1]:
+        raise ValueError('qdescs [Q, D] and bdescs [N, D] expected')
+    Q, N = q.shape[0], b.shape[0]
+    if same_set and Q != N:
+        raise ValueError('same_set: the queries are the database, got %d and %d rows' % (Q, N))
+    trunc = min(int(trunc), N)
+    if trunc < (2 if same_set else 1) or trunc > ops.diffusion_local_max_rows():
+        raise ValueError('%d <= trunc <= %d expected, got %d (N = %d)' % (2 if same_set else 1, ops.diffusion_local_max_rows(),
+                                                                          trunc, N))
+    if graph is None:
+        graph = knn_graph_device(b, k, gamma, index=index, scratch_bytes=scratch_bytes, **search_kw)
+    idx, S = graph
+    if idx.shape[0] != N or tuple(S.shape) != tuple(idx.shape):
+        raise ValueError('a graph (idx, S) over the %d rows of the database expected' % N)
+    if same_set:
+        oidx, ovals = _lists(q, b, trunc - 1, True, index, scratch_bytes, search_kw)
+        own = torch.arange(Q, dtype=torch.int32, device=b.device)[:, None]
+        cidx = torch.cat([own, oidx], dim=1)
+        cvals = torch.cat([torch.ones(Q, 1, dtype=torch.float32, device=b.device), ovals], dim=1)
+    else:
+        cidx, cvals = _lists(q, b, trunc, False, index, scratch_bytes, search_kw)
+    cid, lidx, lw, y = ops.diffusion_subgraph(idx, S, cidx, cvals, kq=int(kq), gamma=gamma, one_hot=same_set)
+    f = ops.diffusion_solve_local(lidx, lw, y, cid=cid, alpha=alpha, iters=iters)
+    if not dense:
+        if Q == 0:
+            return cid, f
+        return ops.topk(f, trunc, ids=cid)
+    return ops.diffusion_spread(similarity_device(q, b), cid, f)      # (a fresh matrix: changed in place)

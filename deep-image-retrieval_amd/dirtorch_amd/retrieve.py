@@ -28,6 +28,10 @@ database that the final search then reuses - it is built once.
 ranking.diffuse_device's scores - diffusion on the mutual K-NN graph of the database from the KQ best rows of every query
 (--diffusion-alpha 0.99, --diffusion-gamma 3, --diffusion-iters 20), after --adba / --aqe.  With --index KIND the graph's
 lists and the queries' come from that index, built once over the database as it is scored.
+--diffusion-trunc T (with --diffusion; default off): ranking.diffuse_truncated_device instead - every query solved on the
+subgraph of its T best database rows (exact, or --index's), and the first --topk (<= T) of those rows as re-ranked by
+their diffusion scores are written.  With it a dataset whose queries are its database rows is accepted: the row itself
+seeds the solve and is left out of its list (--topk <= T - 1).
 """
 import sys
 
@@ -121,7 +125,19 @@ def main(argv=None):
                                           expand_index=(lambda rows: (build_index(rows), search_kw)) if by_index else None)
     same_set = dataset.get_query_db() is dataset
     diffusion = eval_dir.diffusion_options(args)
-    if diffusion is not None:
+    if diffusion is not None and diffusion.get('trunc'):
+        by = dict(search_kw, index=build_index(bdescs)) if args.index else {}
+        trunc = min(diffusion['trunc'], len(bdescs))
+        if args.topk > trunc - int(same_set):
+            raise SystemExit('--topk %d exceeds the %d re-ranked rows of --diffusion-trunc' % (args.topk, trunc - int(same_set)))
+        idx, vals = ranking.diffuse_truncated_device(qdescs, bdescs, same_set=same_set, **diffusion, **by)
+        if same_set:      # a query is not its own neighbour: its row leaves the list, the order of the others stays
+            import torch
+            own = torch.arange(idx.shape[0], dtype=idx.dtype, device=idx.device)[:, None]
+            order = torch.argsort((idx == own).to(torch.int8), dim=1, stable=True)
+            idx, vals = torch.gather(idx, 1, order), torch.gather(vals, 1, order)
+        idx, vals = idx[:, :args.topk].contiguous(), vals[:, :args.topk].contiguous()
+    elif diffusion is not None:
         if same_set:
             raise ValueError('--diffusion needs a dataset with a query set of its own: queries that are database rows '
                              'are not supported')

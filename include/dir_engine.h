@@ -139,7 +139,9 @@ const char* dir_version(void);
  *   dir_ivfpq_scan           Q * width <= L (width rounded up to 1024)
  *   dir_knn_graph            N * k <= L
  *   dir_diffusion_seed       N * Q <= L
- *   dir_diffusion_solve      N * Q <= L, Q <= 65535 * 64 */
+ *   dir_diffusion_solve      N * Q <= L, Q <= 65535 * 64
+ *   dir_diffusion_subgraph   Q * 1024 <= L (a workgroup per query); dir_diffusion_solve_local the same
+ *   dir_diffusion_spread     Q * N <= L, Q * T <= L */
 int64_t dir_launch_max_threads(void);
 /* The DIRTORCH_AMD_* A/B switches (kernel-selection toggles for bisecting; no reference counterpart - the reference reads no
  * environment on this path) are read from the environment ONCE, at the library's first use, and copied into an engine at
@@ -800,6 +802,48 @@ int dir_diffusion_seed(const int* qidx, const float* qvals, int ldq, int Q, int 
 int dir_diffusion_workspace_bytes(int N, int Q, size_t* bytes);
 int dir_diffusion_solve(const int* idx, int ldl, const float* S, int lds, int N, int k, const float* Y, int ldy, int Q,
                         float alpha, int iters, float* F, int ldf, void* workspace, size_t workspace_bytes, void* stream);
+/* Truncated diffusion (diffusion_local.hip; dirtorch_amd/ranking.py diffuse_truncated_device; numpy restatement:
+ * tests/diffusion_trunc_ref.py): the system of a query restricted to its T best database rows, as Iscen et al. do at query
+ * time.  The same house rule: every number a chain of single fp32 operations in the stated order, no fused multiply-add,
+ * powf of a non-integer gamma the one exception.  1 <= T <= dir_diffusion_local_max_rows() (host-only; = dir_topk_max_k(),
+ * 2048), k <= dir_topk_max_k().
+ * INPUTS.  The graph idx / S [N][ldl / lds] as dir_knn_graph writes it; per query a candidate list cidx / cvals [Q][ldc]
+ *   with T slots, best first, as dir_topk or an index's search writes it.
+ * LIVENESS.  Candidate slot a of query q is live when 0 <= cidx[q][a] < N and no earlier slot of the list holds the same
+ *   id; cid[q][a] is the id when live, else -1.  A dead candidate is a row without edges or seed; its id is never
+ *   dereferenced.
+ * SUBGRAPH (dir_diffusion_subgraph).  lidx / lw [Q][k][ldt] int32 / fp32, slot-major (ldt >= T), and the seeds y [Q][ldt];
+ *   cid [Q][ldt].  For a live a with i = cid[q][a] and slot t, j = idx[i][t]: when S[i][t] != 0, 0 <= j < N and j is the id
+ *   of live candidate b of the same query, lidx[q][t][a] = b and lw[q][t][a] = S[i][t]; otherwise -1 and +0.  Every slot of
+ *   a dead row is -1 / +0.  The local matrix is a principal sub-matrix of the symmetric S: symmetric bit for bit.
+ *   one_hot == 0: y[q][a] = cvals[q][a]^gamma (dir_knn_graph's power rule) for a < kq, live, cvals[q][a] > 0; else +0.
+ *   one_hot != 0: y[q][0] = 1 when slot 0 is live; everything else +0 (the query is candidate 0, a database row; cvals is
+ *   not read).  Columns at or past T of cid, lidx, lw and y are not touched.
+ *   One workgroup per query: the T ids go into an LDS hash table whose entry keeps the MINIMUM slot that holds an id (an
+ *   LDS atomic min, so the result does not depend on the order of the insertions), then T x k look-ups.  No global atomics.
+ * SOLVE (dir_diffusion_solve_local).  Per query, the recurrence of dir_diffusion_solve verbatim on the T local rows, one
+ *   column, dot() being that entry's with N := T (slabs of 256 rows, 64 chains, the tree, the partials in slab order): the
+ *   result is what dir_diffusion_solve gives on (lidx[q]^T, lw[q]^T, y[q]) as a one-column problem, bit for bit.  A slot with
+ *   lidx outside [0, T) or lw == 0 is skipped.  f[q][a] = x[a], NaN where cid[q][a] < 0 (cid may be null: all live);
+ *   f [Q][ldf], ldf >= T.  alpha = 0 returns y after one iteration, iters = 0 returns 0, a zero seed stays zero.
+ *   One workgroup per query and ONE launch for all iterations: p and the products of a dot live in LDS (16 KiB), x r ap of
+ *   a row in the registers of the lane that owns it; a lane walks the k slots of its rows in slot order from the slot-major
+ *   arrays, the next four ids and weights requested before the current four adds; a skipped slot is a select.  a, b and rr
+ *   are computed by one thread and broadcast through LDS.  No workspace, no scratch, no atomics.
+ * SPREAD (dir_diffusion_spread).  scores [Q][lds] fp32 (the plain similarities, lds >= N) in place, two kernels in stream
+ *   order: scores[q][j] = scores[q][j] - 4 for every j < N; then for every live candidate scores[q][cid[q][a]] =
+ *   f[q][a] > -2 ? f[q][a] : -2 (a NaN becomes -2); cid and f [Q][ldt].  Cosines lie in [-1, 1], hence in [-5, -3] after
+ *   the shift: every candidate outranks every non-candidate and the non-candidates keep their cosine order.
+ * All three: a negative count, a pitch below its width, T or k above the limits (T < 1 for the first two), gamma < 0 or
+ * alpha outside [0, 1) (or NaN), Q * 1024 (subgraph, solve) or Q * N, Q * T (spread) at or above 2^32 - 256, a null pointer
+ * fail with DIR_ERR_INVALID before anything is launched; Q == 0 (N == 0 for the spread) is DIR_OK and launches nothing. */
+int dir_diffusion_local_max_rows(void);
+int dir_diffusion_subgraph(const int* idx, int ldl, const float* S, int lds, int N, int k, const int* cidx, const float* cvals,
+                           int ldc, int Q, int T, int kq, float gamma, int one_hot, int* cid, int* lidx, float* lw, float* y,
+                           int ldt, void* stream);
+int dir_diffusion_solve_local(const int* lidx, const float* lw, int k, const float* y, const int* cid, int ldt, int Q, int T,
+                              float alpha, int iters, float* f, int ldf, void* stream);
+int dir_diffusion_spread(float* scores, int lds, int Q, int N, const int* cid, const float* f, int ldt, int T, void* stream);
 
 /* ---- the exchange step ------------------------------------------------------------
  * All-gather of per-GPU descriptor blocks over RCCL / xGMI for ONE process driving several GPUs - the

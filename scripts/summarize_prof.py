@@ -211,6 +211,10 @@ def bench_kernel_name(k):
             'diffusion_apply_kernel': 'expand_rows_kernel', 'diffusion_update_kernel': 'l2norm_rows_kernel',
             'diffusion_direction_kernel': 'l2norm_rows_kernel', 'diffusion_finish_kernel': 'gemm_splitk_finalize_kernel',
             'diffusion_result_kernel': 'fill_noise_kernel',
+            # truncated diffusion (csrc/diffusion_local.hip; no timed bench.py step launches it): the look-ups and the solve
+            # are gathers, the spread is pointwise
+            'diffusion_subgraph_kernel': 'expand_rows_kernel', 'diffusion_solve_local_kernel': 'expand_rows_kernel',
+            'diffusion_shift_kernel': 'fill_noise_kernel', 'diffusion_place_kernel': 'fill_noise_kernel',
             'maxpool_kernel': 'maxpool_3x3s2', 'upsample_add_kernel': 'upsample_add',
             'prep_input_f32_kernel': 'prep_input_f32', 'maxpool_f32_kernel': 'maxpool_f32',
             'global_pool_f32_kernel': 'global_pool_f32', 'upsample_add_f32_kernel': 'upsample_add_f32',
