@@ -35,6 +35,11 @@
 #ifndef DIR_PATCHW_ABL
 #define DIR_PATCHW_ABL 0
 #endif
+// 0 = the loader / consumer form without the rolling fragment prefetch of its consumers: every (tap, K half) group reads its six
+// fragments at its top (scripts/exp_abl.sh conv_patchw DIR_PATCHW_ROLL 0).  The same bits; profiles/patchw_consumer_schedule.txt.
+#ifndef DIR_PATCHW_ROLL
+#define DIR_PATCHW_ROLL 1
+#endif
 
 namespace dir {
 
@@ -241,6 +246,10 @@ __global__ void __launch_bounds__(512) conv_patch3x3w_kernel(const ConvArgs a) {
 // without; not kept.)
 // Twelve waves = three per SIMD = 168 VGPRs per wave: the consumers' 128 accumulator registers leave 40, so fragments are
 // fetched one K half (kk) at a time.
+// The consumers' schedule (profiles/patchw_consumer_schedule.txt; step 12.86-12.90 -> 12.71-12.74 ms, layer3 121 -> 114 us): the
+// patch image of THIS form is swizzled by the pixel's column, which takes the address arithmetic out of the stage loop, and a
+// group's fragments are read while the group before it multiplies.  A third lever, pixel fragments read across the stage barrier,
+// measured nothing and is not here.
 template <class DT>
 __global__ void __launch_bounds__(768) conv_patch3x3w_lc_kernel(const ConvArgs a) {
     constexpr int TH = 16, TW = 32, PH = TH + 2, PW = TW + 2, PP = PH * PW;   // 612 patch pixels
@@ -254,6 +263,7 @@ __global__ void __launch_bounds__(768) conv_patch3x3w_lc_kernel(const ConvArgs a
     constexpr int EROW = Staged<TN>::EROW;
     typedef typename DT::frag_t frag_t;
     static_assert(WOFF + NSTW * WSTAGE <= 160 * 1024 && NBW * NLD * 16 == WSTAGE, "LDS map");
+    constexpr int ROWB = PW * 64;                         // one patch row
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -289,7 +299,8 @@ __global__ void __launch_bounds__(768) conv_patch3x3w_lc_kernel(const ConvArgs a
             const int py = p / PW, px = p - py * PW;
             const int iy = oy0 - 1 + py, ix = ox0 - 1 + px;
             const bool ok = p < PP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-            pvoff[i] = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * a.Cin + ((pos ^ ((p >> 2) & 3)) << 3)) * 2) : kOOB;
+            // (swizzled by the pixel's patch COLUMN, not by p as in the one-role kernel: the consumers' fragment addresses below)
+            pvoff[i] = ok ? (uint32_t)((((b * a.H + iy) * a.W + ix) * a.Cin + ((pos ^ ((px >> 2) & 3)) << 3)) * 2) : kOOB;
         }
         // a.w_pw (conv_patch3x3w_pack): the filter as the sequence of 24 KB LDS stage images - a DMA instruction copies one
         // contiguous KB instead of gathering sixteen 64-byte runs of the [Cout][3][3][Cin] layout
@@ -359,41 +370,107 @@ __global__ void __launch_bounds__(768) conv_patch3x3w_lc_kernel(const ConvArgs a
     for (int kk = 0; kk < 2; ++kk) woffk[kk] = lrow * 64 + (((2 * kk + lhi) ^ ((lrow >> 2) & 3)) << 4);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the bias: the only VMEM loads of a consumer before the epilogue
 
-    int q = 0, r = 0, slot_c = 0;
-    for (int sigma = 0; sigma < NS; ++sigma) {
-        ring_barrier();
-        const char* plane = smem + (q & 1) * PLANE_BYTES;
-        const char* wst = smem + WOFF + slot_c * WSTAGE;
+    // Fragment addresses, all computed here: ten adds per plane are what is left of them inside the plane loop.
+    //   * Three stages per plane and three weight slots: stage (q, r) reads slot r, so in the plane body (r unrolled) a weight
+    //     address is a lane offset + a constant; two bases because the DS offset field holds 16 bits.
+    //   * The patch image is swizzled by the pixel's COLUMN, (px >> 2) & 3, so the lane part of a pixel-fragment address depends
+    //     on (s, kk) alone: six registers, stepped to the other plane buffer once per plane; rows (j, r) are immediate offsets.
+    //     A ds_read_b128 lane group is four quads of lanes at l, l + 12, l + 20, l + 24 (or l, l + 4, l + 12, l + 24): px >> 2
+    //     differs by 0, 3, 5, 6 (0, 1, 3, 6) between lanes of equal px % 4 - distinct mod 4, so the sixteen lanes still read
+    //     sixteen distinct 16-byte slots of the 256-byte bank row (SQ_LDS_BANK_CONFLICT = 0, measured).
+    const DIR_LDS char* const lds = (const DIR_LDS char*)smem;
+    const DIR_LDS char *wbase[2][2], *xrow[3][2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        wbase[kk][0] = lds + WOFF + woffk[kk];
+        wbase[kk][1] = lds + WOFF + 2 * WSTAGE + woffk[kk];
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
-            // same (kk, i, j) MFMA order per accumulator as conv_patch3x3w_kernel: bit-identical sums
+            const int px = s + lrow;
+            xrow[s][kk] = lds + (wave * TMR * PW + px) * 64 + (((2 * kk + lhi) ^ ((px >> 2) & 3)) << 4);
+        }
+    }
+    auto xptr = [&](int r, int s, int kk, int j) { return (const DIR_LDS frag_t*)(xrow[s][kk] + (j + r) * ROWB); };
+    auto wptr = [&](int r, int s, int kk, int i) {
+        return (const DIR_LDS frag_t*)(wbase[kk][r >> 1] + (r & 1) * WSTAGE + s * (BN * 64) + i * 2048);
+    };
+
+    for (int q = 0; q < NQ; ++q) {
 #pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                frag_t xf[TMR], wf[TN];
+        for (int r = 0; r < 3; ++r) {
+            ring_barrier();   // weight stage (q, r) and, at r == 0, plane q have landed; everyone has left the stage before
+            // Six (tap s, K half kk) groups of 8 MFMAs.  Same (s, kk) order per accumulator as conv_patch3x3w_kernel:
+            // bit-identical sums.  Issue order: the PIXEL fragment is held over four consecutive MFMAs while the weight
+            // fragment changes (j outer, i inner).  The kernel is power-bound (MfmaUtil x clock is constant across its forms);
+            // which operand toggles between consecutive MFMAs is worth 2-3 % of the launch: 126.5 -> 123.5 us in layer3,
+            // 117.5 -> 113.5 us in layer4, step 14.14 -> 14.07 ms (A/B, three orders, profiles/r05_patchw_phases.txt).
+            frag_t xf[TMR], wf[TN];
+#if DIR_PATCHW_ROLL
+            // In that order xf[0] is dead after MFMA 4 of a group, wf[i] after MFMA 5 + i, xf[1] after MFMA 8: the next
+            // group's fragment is read into the same register right there, so every read has 3-4 MFMAs of cover and is
+            // waited for by count at its first use.  The sched_group_barriers pin that interleave (left to itself hipcc
+            // issues half of a group's reads after the last MFMA of the group before and waits for them at once).
+            // Group 0's reads stand uncovered behind the barrier that publishes the weight slot; the first MFMA's two
+            // operands go first, so that it waits for two reads and not for six.
+            xf[0] = *xptr(r, 0, 0, 0);
+            wf[0] = *wptr(r, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int j = 0; j < TMR; ++j) {
-                    const int p = (wave * TMR + j + r) * PW + s + lrow;
-                    xf[j] = *(const frag_t*)(plane + p * 64 + (((2 * kk + lhi) ^ ((p >> 2) & 3)) << 4));
+            for (int i = 1; i < TN; ++i) wf[i] = *wptr(r, 0, 0, i);
+            xf[1] = *xptr(r, 0, 0, 1);
+            __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);   // 0x100: DS reads, 0x008: MFMAs
+#pragma unroll
+            for (int g = 0; g < 6; ++g) {
+                const bool last = g == 5;
+                const int sn = (g + 1) >> 1, kn = (g + 1) & 1;   // the next group
+#pragma unroll
+                for (int i = 0; i < TN; ++i) acc[i][0] = DT::mfma32(wf[i], xf[0], acc[i][0]);
+                if (!last) xf[0] = *xptr(r, sn, kn, 0);
+#pragma unroll
+                for (int i = 0; i < TN; ++i) {
+                    acc[i][1] = DT::mfma32(wf[i], xf[1], acc[i][1]);
+                    if (!last) wf[i] = *wptr(r, sn, kn, i);
                 }
+                if (!last) xf[1] = *xptr(r, sn, kn, 1);
+                __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+                if (!last) {
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
 #pragma unroll
-                for (int i = 0; i < TN; ++i) wf[i] = *(const frag_t*)(wst + s * (BN * 64) + i * 2048 + woffk[kk]);
-                // Issue order: the PIXEL fragment is held over four consecutive MFMAs while the weight fragment changes (j outer, i
-                // inner - and written so, because hipcc's own schedule of the i-outer loop interleaved them irregularly).  The kernel
-                // is power-bound (MfmaUtil x clock is constant across its forms); which operand toggles between consecutive
-                // MFMAs is worth 2-3 % of the launch: 126.5 -> 123.5 us in layer3, 117.5 -> 113.5 us in layer4, step 14.14 -> 14.07 ms
-                // (A/B, three orders, profiles/r05_patchw_phases.txt).  Per accumulator the k order is unchanged: bit-identical.
-#pragma unroll
-                for (int j = 0; j < TMR; ++j)
-#pragma unroll
-                    for (int i = 0; i < TN; ++i) acc[i][j] = DT::mfma32(wf[i], xf[j], acc[i][j]);
+                    for (int i = 0; i < TN; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                    }
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                } else {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+                }
             }
+            // This stage's LDS reads retired before the next barrier frees its weight slot.  Every one of them has been consumed
+            // by an MFMA by now; the wait takes the last accumulator as an operand so that it stays behind the last MFMA.
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(acc[TN - 1][TMR - 1])::"memory");
+#else
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) {
+#pragma unroll
+                    for (int j = 0; j < TMR; ++j) xf[j] = *xptr(r, s, kk, j);
+#pragma unroll
+                    for (int i = 0; i < TN; ++i) wf[i] = *wptr(r, s, kk, i);
+#pragma unroll
+                    for (int j = 0; j < TMR; ++j)
+#pragma unroll
+                        for (int i = 0; i < TN; ++i) acc[i][j] = DT::mfma32(wf[i], xf[j], acc[i][j]);
+                }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this stage's LDS reads retired before the next barrier
+#endif
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this stage's LDS reads retired before the next barrier
-        if (++slot_c == NSTW) slot_c = 0;
-        if (++r == 3) {
-            r = 0;
-            ++q;
-        }
+        const int d = (q & 1) ? -PLANE_BYTES : PLANE_BYTES;   // the other plane buffer
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) xrow[s][kk] += d;
     }
     ring_barrier();  // planes and weight slots become epilogue staging (the loaders leave here)
     Ovf<DT> ovf;

@@ -7,6 +7,8 @@
 #                      conv_ring   DIR_RING_ABL   (1 no pixel DMA, 2 no weight DMA, 4 no MFMAs, 8 no epilogue)
 #                      sim_split   DIR_SIM_ABL    (1 no database DMA, 2 no query DMA, 4 consumers only take the barriers)
 #                      conv_igemm  DIR_EXP_FILL_ONLY / DIR_EXP_NO_FILL (value 1): the LDS-DMA ring alone / the MFMAs alone
+#                      conv_patchw DIR_PATCHW_ABL (phase / Winograd pricing builds, see the source), DIR_PATCHW_ROLL (0: the consumers of
+#                                  the loader / consumer form without their rolling fragment prefetch - a VALID kernel, same bits)
 #                      all         DIR_EXP_NO_RING_FENCE (value 1): ring_barrier() as a raw s_barrier - what the fences cost
 # (Replaces the one-off exp_ring.sh / exp_sim.sh / exp_fill.sh / exp_fence.sh of rounds 2-3: same recipe, parameterised.)
 set -e
