@@ -914,6 +914,54 @@ int dir_similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q
     DIR_CATCH
 }
 
+int dir_index_fp4_max_dim(void) { return index_fp4_max_dim(); }
+
+static int fp4_check_dim(const char* who, int D) {
+    if (D < 1) return fail(DIR_ERR_INVALID, std::string(who) + ": D < 1");
+    if (D > index_fp4_max_dim()) return fail(DIR_ERR_INVALID, std::string(who) + ": D exceeds dir_index_fp4_max_dim()");
+    return DIR_OK;
+}
+
+static int fp4_exps_width(int D) { return 8 * ceil_div(pad64(D), 256); }   // block bytes of whole slabs of 256 k
+
+int dir_quantize_rows_fp4(const float* X, int ldx, int N, int D, uint8_t* codes, int ldc, uint8_t* exps, int lde,
+                          float* scales, void* stream) {
+    DIR_TRY
+    if (N < 0) return fail(DIR_ERR_INVALID, "quantize_rows_fp4: negative size");
+    DIR_CHECK(fp4_check_dim("quantize_rows_fp4", D));
+    if (ldx < D) return fail(DIR_ERR_INVALID, "quantize_rows_fp4: ldx < D");
+    if (ldc < pad64(D) / 2) return fail(DIR_ERR_INVALID, "quantize_rows_fp4: ldc < half of D rounded up to a multiple of 64");
+    if (lde < fp4_exps_width(D)) return fail(DIR_ERR_INVALID, "quantize_rows_fp4: lde < 8 * ceil(D / 256)");
+    if (N == 0) return DIR_OK;
+    if (!X || !codes || !exps || !scales) return fail(DIR_ERR_INVALID, "quantize_rows_fp4: null pointer");
+    if ((ldc & 1) != 0 || ((uintptr_t)codes & 1) != 0)
+        return fail(DIR_ERR_INVALID, "quantize_rows_fp4: ldc % 2 == 0 and 2-byte aligned codes");
+    return quantize_rows_fp4(X, ldx, N, D, codes, ldc, exps, lde, scales, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_similarity_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe, const float* qscales, int Q,
+                       const uint8_t* bcodes, int ldb, const uint8_t* bexps, int ldbe, const float* bscales, int N, int D,
+                       float* scores, int lds, void* stream) {
+    DIR_TRY
+    if (Q < 0 || N < 0) return fail(DIR_ERR_INVALID, "similarity_fp4: negative size");
+    DIR_CHECK(fp4_check_dim("similarity_fp4", D));
+    if (ldq < (D + 1) / 2) return fail(DIR_ERR_INVALID, "similarity_fp4: ldq < ceil(D / 2)");
+    if (ldqe < ceil_div(D, 32)) return fail(DIR_ERR_INVALID, "similarity_fp4: ldqe < ceil(D / 32)");
+    if (ldb < pad64(D) / 2) return fail(DIR_ERR_INVALID, "similarity_fp4: ldb < half of D rounded up to a multiple of 64");
+    if (ldbe < fp4_exps_width(D)) return fail(DIR_ERR_INVALID, "similarity_fp4: ldbe < 8 * ceil(D / 256)");
+    if (lds < N) return fail(DIR_ERR_INVALID, "similarity_fp4: lds < N");
+    if (Q == 0 || N == 0) return DIR_OK;
+    if (!qcodes || !qexps || !qscales || !bcodes || !bexps || !bscales || !scores)
+        return fail(DIR_ERR_INVALID, "similarity_fp4: null pointer");
+    if (!similarity_fp4_admissible(bcodes, ldb, bexps, ldbe, D))
+        return fail(DIR_ERR_INVALID, "similarity_fp4: ldb % 16 == 0, ldb < 2^23 and 16-byte aligned bcodes, ldbe % 8 == 0 and "
+                                     "8-byte aligned bexps");
+    return similarity_fp4(qcodes, ldq, qexps, ldqe, qscales, Q, bcodes, ldb, bexps, ldbe, bscales, N, D, scores, lds,
+                          (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_gather_scores(const float* queries, int ldq, int Q, const float* database, int ldb, int N, int D, const int* cand,
                       int ldcand, int R, float* scores, int ldsc, void* stream) {
     DIR_TRY

@@ -63,6 +63,14 @@ int similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, co
                   const float* bscales, int N, int D, float* scores, int lds, hipStream_t stream);
 int gather_scores(const float* queries, int ldq, int Q, const float* database, int ldb, int D, const int* cand, int ldcand,
                   int R, float* scores, int ldsc, hipStream_t stream);
+// the fp4 descriptor index (index_fp4.hip): e2m1 codes + e8m0 block bytes + row scales, the scan on the scaled matrix cores
+int index_fp4_max_dim();
+int quantize_rows_fp4(const float* X, int ldx, int N, int D, uint8_t* codes, int ldc, uint8_t* exps, int lde, float* scales,
+                      hipStream_t stream);
+bool similarity_fp4_admissible(const uint8_t* bcodes, int ldb, const uint8_t* bexps, int ldbe, int D);
+int similarity_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe, const float* qscales, int Q,
+                   const uint8_t* bcodes, int ldb, const uint8_t* bexps, int ldbe, const float* bscales, int N, int D,
+                   float* scores, int lds, hipStream_t stream);
 // the inverted-file int8 index (ivf.hip): the sums of a k-means step, the scan of the probed lists
 int segment_sums(const float* X, int ldx, int N, int D, const int* order, const int* seg_off, int S, float* sums, int lds,
                  hipStream_t stream);

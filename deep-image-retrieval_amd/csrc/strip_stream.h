@@ -241,4 +241,38 @@ __device__ __forceinline__ void code_slab_mma(const StripLane& L, const char* st
     }
 }
 
+// ---- fp4 codes ---------------------------------------------------------------------------------------------------------
+// One 256-wide K slab of a stage of e2m1 codes (two k per byte): the query part is NB blocks of 32 rows x 128 bytes,
+// swizzled like the database rows, then [2 lane halves][NB * 32 rows] dwords of e8m0 block bytes.  A lane's operand of
+// step s is chunk 2 s + lhi of its row = one block of 32 k on both sides, so the k order inside the lane does not matter;
+// its scales are byte s of `bexp` (the database row's, from the caller) and of the query row's dword for this lane half.
+typedef __attribute__((ext_vector_type(8))) int i32x8_t;
+
+template <int S, int NB>
+__device__ __forceinline__ void fp4_step(const StripLane& L, const char* stage, const uint32_t (&aexp)[NB], uint32_t bexp,
+                                         f32x16_t (&acc)[NB]) {
+    const int aoff = kStripSlab + L.lrow * kStripRow;
+    const int ch = L.chunk(S * 2 + L.lhi);
+    const i32x4_t b = *(const i32x4_t*)(stage + L.boff + ch);
+    const i32x8_t b8 = {b[0], b[1], b[2], b[3], 0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+        const i32x4_t a = *(const i32x4_t*)(stage + aoff + j * 4096 + ch);
+        const i32x8_t a8 = {a[0], a[1], a[2], a[3], 0, 0, 0, 0};
+        acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc[j], 4, 4, S, (int)aexp[j], S, (int)bexp);
+    }
+}
+
+template <int NB>
+__device__ __forceinline__ void fp4_slab_mma(const StripLane& L, const char* stage, uint32_t bexp, f32x16_t (&acc)[NB]) {
+    const int eoff = kStripSlab + NB * 4096 + (L.lhi * NB * 32 + L.lrow) * 4;
+    uint32_t aexp[NB];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) aexp[j] = *(const uint32_t*)(stage + eoff + j * 128);
+    fp4_step<0, NB>(L, stage, aexp, bexp, acc);   // k = 256 u + 64 s + 32 lhi + 0..31
+    fp4_step<1, NB>(L, stage, aexp, bexp, acc);
+    fp4_step<2, NB>(L, stage, aexp, bexp, acc);
+    fp4_step<3, NB>(L, stage, aexp, bexp, acc);
+}
+
 }  // namespace dir

@@ -138,6 +138,10 @@ SIGNATURES = {
     'dir_quantize_rows_i8': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'dir_similarity_i8': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
                                   c_int, c_void_p]),
+    'dir_index_fp4_max_dim': (c_int, []),
+    'dir_quantize_rows_fp4': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    'dir_similarity_fp4': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                   c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     'dir_gather_scores': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int,
                                   c_void_p, c_int, c_void_p]),
     'dir_segment_sums': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),

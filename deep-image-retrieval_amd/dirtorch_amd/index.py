@@ -10,6 +10,15 @@ include/dir_engine.h defines the quantisation and the quantised score; an int8 d
 so a quantised score is one defined fp32 number and the lists of a scan do not depend on scratch_bytes, db_rows or on how
 many add() calls built the database.
 
+The fp4 index halves the row again - 4-bit block-scaled codes (D <= ops.index_fp4_max_dim()) on the scaled matrix cores:
+
+    index = Fp4Index(D)
+    index.add(bdescs)
+    idx, vals = index.search(qdescs, 10, rerank=40, source=bdescs)   # its raw scores are coarse: made for use with rerank
+
+Every partial sum of one of its scores is exact in fp32 (include/dir_engine.h), so its lists are those of tests/fp4_ref.py bit
+for bit and as independent of the cut of the work as Int8Index's.
+
 The inverted file reads only the lists a query falls into instead of the whole database:
 
     index = IVFInt8Index(D, nlist=1024)
@@ -289,6 +298,71 @@ class Int8Index(_CodedIndex):
         f = _read_npz(path)
         index = cls(int(f['D']))
         index._load_i8(path, f)
+        return index
+
+
+class Fp4Index(_CodedIndex):
+    """The fp4 index (include/dir_engine.h gives the definition; numpy restatement: tests/fp4_ref.py): half of Int8Index's
+    bytes.  codes [N, ldc] uint8 (two e2m1 values per byte), exps [N, lde] uint8 (one e8m0 byte per block of 32 values) and
+    scales [N] fp32, all CUDA; (ldc, lde) = ops.fp4_widths(D).  A score is the exact inner product of the two dequantised
+    rows, so the lists do not depend on how the scan or the adds were cut."""
+
+    def __init__(self, D):
+        D = int(D)
+        if D < 1 or D > ops.index_fp4_max_dim():
+            raise ValueError('1 <= D <= %d expected, got %d' % (ops.index_fp4_max_dim(), D))
+        self.D = D
+        ldc, lde = ops.fp4_widths(D)
+        self.codes = torch.empty(0, ldc, dtype=torch.uint8, device='cuda')
+        self.exps = torch.empty(0, lde, dtype=torch.uint8, device='cuda')
+        self.scales = torch.empty(0, dtype=torch.float32, device='cuda')
+
+    def nbytes(self):
+        """the bytes the database rows take on the device: codes, block bytes and scales"""
+        return sum(int(t.numel()) * t.element_size() for t in (self.codes, self.exps, self.scales))
+
+    def add(self, descs):
+        """Int8Index.add's contract: the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap), quantised
+        in chunks of ADD_CHUNK_BYTES."""
+        self._check_rows(descs)
+        if int(descs.shape[0]):
+            self.codes, self.exps, self.scales = _appended([self.codes, self.exps, self.scales], descs, self.D,
+                                                           ops.quantize_rows_fp4)
+        return self
+
+    def search(self, qdescs, k, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20, db_rows=None):
+        """Int8Index.search's contract with the fp4 scores in place of the int8 ones: (idx [Q,k] int32, vals [Q,k] float32);
+        rerank = 0: ranked by the quantised scores; rerank = R: the R best are re-scored against `source` in fp32."""
+        def scan(q, keep):
+            qc, qe, qs = ops.quantize_rows_fp4(q)
+
+            def scorer(r0, r1):
+                return lambda b0, b1: ops.similarity_fp4(qc[r0:r1], qe[r0:r1], qs[r0:r1], self.codes[b0:b1], self.exps[b0:b1],
+                                                         self.scales[b0:b1], self.D)
+            return self._scan_blocks(q.shape[0], keep, same_set, scratch_bytes, db_rows, scorer)
+        return self._search(qdescs, k, rerank, source, same_set, scratch_bytes, scan)
+
+    def save(self, path):
+        """One .npz: `codes` [N, ceil(D / 2)] uint8, `exps` [N, ceil(D / 32)] uint8 (both without the padding), `scales` [N]
+        float32, `D`."""
+        nc, ne = (self.D + 1) // 2, (self.D + 31) // 32
+        np.savez(path, D=np.int64(self.D), codes=self.codes[:, :nc].cpu().numpy(), exps=self.exps[:, :ne].cpu().numpy(),
+                 scales=self.scales.cpu().numpy())
+
+    @classmethod
+    def load(cls, path):
+        f = _read_npz(path)
+        index = cls(int(f['D']))
+        D = index.D
+        ldc, lde = ops.fp4_widths(D)
+        index.codes = _padded_codes(path, f['codes'], (D + 1) // 2, np.uint8, ldc)
+        if f['exps'].dtype != np.uint8 or f['exps'].shape != (len(index), (D + 31) // 32):
+            raise ValueError('%s: exps [N, %d] uint8 expected for codes of N rows' % (path, (D + 31) // 32))
+        index.exps = torch.full((len(index), lde), 127, dtype=torch.uint8, device='cuda')
+        index.exps[:, :(D + 31) // 32] = torch.from_numpy(f['exps']).cuda()
+        if f['scales'].shape != (len(index),):
+            raise ValueError('%s: scales [N] expected for codes [N, ...]' % path)
+        index.scales = torch.from_numpy(f['scales'].astype(np.float32)).cuda()
         return index
 
 

@@ -596,10 +596,10 @@ def _on_device(*ts):
             raise ValueError('device tensor expected')
 
 
-def _i8_codes(codes, ldc):
-    """int8 codes [n, >= ldc] -> (codes, row pitch) at a 16-byte pitch and address; copies what is not"""
+def _i8_codes(codes, ldc, align=16):
+    """one-byte codes [n, >= ldc] -> (codes, row pitch) at a pitch and address that are multiples of `align`; copies what is not"""
     codes, ld = _rows_pitch(codes, ldc)
-    if ld % 16 or codes.data_ptr() % 16:
+    if ld % align or codes.data_ptr() % align:
         codes, ld = codes[:, :ldc].contiguous(), ldc
     return codes, ld
 
@@ -707,6 +707,72 @@ def similarity_i8(qcodes, qscales, bcodes, bscales, D, out=None):
     if Q and N:
         call('dir_similarity_i8', ptr(qcodes), ldq, ptr(qscales), Q, ptr(bcodes), ldb, ptr(bscales), N, D, ptr(out), lds,
              stream_ptr())
+    return out[:, :N]
+
+
+# ---- the fp4 descriptor index (csrc/index_fp4.hip) ----------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def index_fp4_max_dim():
+    """The widest row the fp4 index takes (dir_index_fp4_max_dim; host-only)."""
+    return int(_lib.load().dir_index_fp4_max_dim())
+
+
+def fp4_widths(D):
+    """(bytes of codes, block bytes) of a row as quantize_rows_fp4 stores it: D rounded up to 64, halved; 8 * ceil(D / 256)"""
+    return (D + 63) // 64 * 32, (D + 255) // 256 * 8
+
+
+def quantize_rows_fp4(X):
+    """fp32 rows -> (codes uint8 [N, ldc], exps uint8 [N, lde], scales fp32 [N]), all CUDA (dir_quantize_rows_fp4;
+    include/dir_engine.h gives the definition): e2m1 codes two to a byte, one e8m0 byte per block of 32, one power of two
+    per row; (ldc, lde) = fp4_widths(D), the padding written.  X [N,D] fp32 CUDA with unit column stride and any row pitch."""
+    _on_device(X)
+    if X.dtype != torch.float32 or X.dim() != 2:
+        raise TypeError('float32 rows [N,D] expected')
+    N, D = X.shape
+    if D < 1 or D > index_fp4_max_dim():
+        raise ValueError('1 <= D <= %d expected, got %d' % (index_fp4_max_dim(), D))
+    X, ldx = _rows_pitch(X, D)
+    ldc, lde = fp4_widths(D)
+    codes = torch.empty(N, ldc, dtype=torch.uint8, device=X.device)
+    exps = torch.empty(N, lde, dtype=torch.uint8, device=X.device)
+    scales = torch.empty(N, dtype=torch.float32, device=X.device)
+    if N:
+        call('dir_quantize_rows_fp4', ptr(X), ldx, N, D, ptr(codes), ldc, ptr(exps), lde, ptr(scales), stream_ptr())
+    return codes, exps, scales
+
+
+def similarity_fp4(qcodes, qexps, qscales, bcodes, bexps, bscales, D, out=None):
+    """scores [Q,N] fp32 CUDA of two fp4-coded sets (dir_similarity_fp4): (acc * qscales[q]) * bscales[n] with acc the exact
+    sum of the products of the dequantised values - one defined fp32 number per pair.  codes / exps uint8 and scales fp32
+    as quantize_rows_fp4 gives them (row slices included), D the width they were made from.  out: a [Q, >= N] fp32 CUDA
+    tensor with unit column stride to write into (its first N columns are returned)."""
+    _on_device(qcodes, qexps, qscales, bcodes, bexps, bscales, out)
+    for t in (qcodes, qexps, bcodes, bexps):
+        if t.dtype != torch.uint8 or t.dim() != 2:
+            raise TypeError('uint8 codes [rows, ldc] and block bytes [rows, lde] expected')
+    if qscales.dtype != torch.float32 or bscales.dtype != torch.float32:
+        raise TypeError('float32 scales expected')
+    D = int(D)
+    Q, N = qcodes.shape[0], bcodes.shape[0]
+    if D < 1 or D > index_fp4_max_dim():
+        raise ValueError('1 <= D <= %d expected, got %d' % (index_fp4_max_dim(), D))
+    ldc, lde = fp4_widths(D)
+    if qcodes.shape[1] < ldc or bcodes.shape[1] < ldc or qexps.shape[1] < lde or bexps.shape[1] < lde:
+        raise ValueError('codes of %d and block bytes of %d columns at least expected for D = %d' % (ldc, lde, D))
+    if qexps.shape[0] != Q or bexps.shape[0] != N:
+        raise ValueError('block bytes of Q and N rows expected for codes of Q and N rows')
+    if qscales.dim() != 1 or bscales.dim() != 1 or qscales.numel() != Q or bscales.numel() != N:
+        raise ValueError('scales [Q] and [N] expected for codes of Q and N rows')
+    qcodes, ldq = _rows_pitch(qcodes, ldc)
+    qexps, ldqe = _rows_pitch(qexps, lde)
+    bcodes, ldb = _i8_codes(bcodes, ldc)
+    bexps, ldbe = _i8_codes(bexps, lde, align=8)
+    qscales, bscales = qscales.contiguous(), bscales.contiguous()
+    out, lds = _score_out(out, Q, N, bcodes.device)
+    if Q and N:
+        call('dir_similarity_fp4', ptr(qcodes), ldq, ptr(qexps), ldqe, ptr(qscales), Q, ptr(bcodes), ldb, ptr(bexps), ldbe,
+             ptr(bscales), N, D, ptr(out), lds, stream_ptr())
     return out[:, :N]
 
 

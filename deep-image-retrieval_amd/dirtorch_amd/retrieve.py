@@ -12,6 +12,8 @@ When the query set is the database itself a query is not its own neighbour.  Wri
 --index int8: the database descriptors go through an index.Int8Index (int8 codes, a quarter of the bytes) and the lists are
 ranked by the quantised scores; --rerank R also re-scores the R best of every query against the fp32 descriptors and keeps
 the --topk best of those, with their fp32 scores.
+--index fp4: an index.Fp4Index instead (4-bit block-scaled codes, half of int8's bytes; descriptors of at most 7281 values);
+the quantised scores are coarser than int8's, so pair it with --rerank (4 x --topk gave the fp32 lists in our measurements).
 --index ivf --nlist L --nprobe P: an index.IVFInt8Index trained on the database descriptors themselves (L k-means lists);
 every query scans its P best lists only, --rerank as above.  With P = L the lists are those of --index int8.
 --index pq --pq-m M: an index.PQIndex trained on the database descriptors themselves (M bytes per image, M dividing the
@@ -42,7 +44,7 @@ from . import distributed as ddist
 from .utils.convenient import mkdir
 
 # --index kind -> (its class in dirtorch_amd.index, the flags its constructor takes after the width, whether it is trained)
-INDEX_KINDS = {'int8': ('Int8Index', (), False), 'ivf': ('IVFInt8Index', ('nlist',), True),
+INDEX_KINDS = {'int8': ('Int8Index', (), False), 'fp4': ('Fp4Index', (), False), 'ivf': ('IVFInt8Index', ('nlist',), True),
                'pq': ('PQIndex', ('pq_m',), True), 'ivfpq': ('IVFPQIndex', ('nlist', 'pq_m'), True)}
 
 

@@ -130,6 +130,8 @@ const char* dir_version(void);
  *   dir_quantize_rows_i8     N * 64 <= L (N rounded up to 4)
  *   dir_similarity_i8        N * 3 <= L (N rounded up to 256), Q <= 65535 * 96
  *   dir_gather_scores        none: several launches
+ *   dir_quantize_rows_fp4    N * 64 <= L (N rounded up to 4)
+ *   dir_similarity_fp4       N * 3 <= L (N rounded up to 256), Q <= 65535 * 96
  *   dir_segment_sums         S <= 65535
  *   dir_ivf_scan_i8          Q * width <= L, items * 768 <= L (refused, not cut: Q * width of 2^32 means 32 GiB of score and id
  *                            rows for one chunk; index.py's chunks are scratch_bytes / 8 slots, 2^25 by default)
@@ -570,6 +572,49 @@ int dir_similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q
                       const float* bscales, int N, int D, float* scores, int lds, void* stream);
 int dir_gather_scores(const float* queries, int ldq, int Q, const float* database, int ldb, int N, int D, const int* cand,
                       int ldcand, int R, float* scores, int ldsc, void* stream);
+/* The fp4 descriptor index (index_fp4.hip; dirtorch_amd/index.py Fp4Index; numpy restatement: tests/fp4_ref.py): half of the
+ * int8 index's bytes, scanned on the scaled matrix cores (v_mfma_scale_f32_32x32x64_f8f6f4).  It stands beside
+ * dir_quantize_rows_i8 / dir_similarity_i8 and replaces nothing in the reference, which keeps fp32 descriptors.
+ * A row x of D fp32 values, 1 <= D <= dir_index_fp4_max_dim() = 7281, is cut into blocks of 32 consecutive k (the last one
+ * padded with zeros) and stored as
+ *     codes  [ldc] bytes: two e2m1 values per byte, even k in the low nibble of byte k / 2; ldc >= D rounded up to 64,
+ *            divided by 2 - that many bytes are written, the padding as 0x0;
+ *     exps   [lde] bytes: one e8m0 byte per block, lde >= 8 * ceil(D / 256) (whole K slabs of the scan) - that many bytes
+ *            are written, 127 for every block past D;
+ *     scale  one fp32 power of two.
+ * The quantisation, in integer operations on the exponent field and exact fp32 multiplications by powers of two:
+ *     amax_b = max |x_k| over block b;  f_b = its biased exponent field (0 for zero and subnormal blocks)
+ *     F = max_b f_b;  E = F - 129  (= floor(log2 amax) - 2, the OCP MX rule);  m_b = max(f_b, F - 2)
+ *     e_b = m_b - 129: the block exponent, floor(log2 amax_b) - 2 clamped to [E - 2, E] - a clamped block is coded on the
+ *       grid of the row's top blocks, its absolute error never above theirs;  exps[b] = 127 + (e_b - E), one of 125, 126, 127
+ *     y_k = |x_k| * 2^-e_b  (exact, < 8);  code_k = the nearest of {0, 0.5, 1, 1.5, 2, 3, 4, 6} to y_k, a midpoint going to
+ *       the even code (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4), saturating: y in (5, 8) -> 6
+ *     nibble = sign bit : 3-bit e2m1 code; a value that rounds to zero is stored as +0 (nibble 0x0, like the padding)
+ *     scale = 2^E
+ *   a row that holds a NaN or an infinity has zero codes, block bytes 127 and scale NaN (all its scores are NaN);
+ *   a row with amax < 2^-60 (zero included) has zero codes, block bytes 127 and scale +0.
+ * dir_quantize_rows_fp4: X [N][ldx] fp32 (ldx >= D, any pitch) -> codes [N][ldc] (2-byte aligned, ldc % 2 == 0), exps
+ *   [N][lde] row-major at their own pitch, scales [N].  One wave per row; a row of up to 2048 values is read once.
+ * dir_similarity_fp4: scores[q][n] = (acc * qscales[q]) * bscales[n], two fp32 multiplies in that order, acc = the fp32
+ *   accumulator of the scaled MFMAs fed the stored block bytes = sum_k a_k b_k of the values code * 2^(exps - 127).  Every
+ *   product is a multiple of 1/64 of at most 36, so every partial sum in any order is a multiple of 1/64 below
+ *   36 * 7281 < 2^24 / 64: acc is exact whatever the K order, the tiling or the chunking, the scales are powers of two,
+ *   and the score is the exact inner product of the two dequantised rows (rounded once if it leaves fp32's range) - ONE
+ *   defined fp32 number.  That fixes the widest row.
+ *   qcodes [Q][ldq] (ldq >= ceil(D / 2)), qexps [Q][ldqe] (ldqe >= ceil(D / 32)): read up to D only.  bcodes [N][ldb]
+ *   (16-byte aligned, ldb % 16 == 0, ldb >= D rounded up to 64, divided by 2: that many bytes of every row are read; what
+ *   they hold past D does not matter), bexps [N][ldbe] (8-byte aligned, ldbe % 8 == 0, ldbe >= 8 * ceil(D / 256): that many
+ *   bytes of every row are read, one 8-byte load per slab; the bytes of blocks past D rounded up to 64 do not matter, the
+ *   others are e8m0 bytes other than 255).  The codes pitch need not cover a whole slab: the loader cuts the last slab by
+ *   16-byte chunk.  scores [Q][lds] fp32, lds >= N.  The query image lives in stream-ordered scratch.
+ * Both: a negative count, D < 1 or above the max dim, a pitch below its minimum, lds < N or a null pointer fail with
+ * DIR_ERR_INVALID before anything is launched; Q == 0 or N == 0 is DIR_OK and launches nothing. */
+int dir_index_fp4_max_dim(void);
+int dir_quantize_rows_fp4(const float* X, int ldx, int N, int D, uint8_t* codes, int ldc, uint8_t* exps, int lde,
+                          float* scales, void* stream);
+int dir_similarity_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe, const float* qscales, int Q,
+                       const uint8_t* bcodes, int ldb, const uint8_t* bexps, int ldbe, const float* bscales, int N, int D,
+                       float* scores, int lds, void* stream);
 /* The inverted-file int8 index (ivf.hip; dirtorch_amd/index.py IVFInt8Index; numpy restatement: tests/ivf_ref.py).
  * An index of width D with nlist lists holds
  *     centroids [nlist][D] fp32 with their codes and scales (dir_quantize_rows_i8),
