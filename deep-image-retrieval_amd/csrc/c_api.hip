@@ -1011,6 +1011,34 @@ int dir_ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, 
     DIR_CATCH
 }
 
+int dir_ivf_scan_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe, const float* qscales, int Q,
+                     const uint8_t* bcodes, int ldb, const uint8_t* bexps, int ldbe, const float* bscales, const int* ids, int N,
+                     int D, const int* list_off, int nlist, const int* pair_off, const int* pair_q, const int* pair_col,
+                     const int* item_off, int items, float* scores, int* out_ids, int lds, int width, void* stream) {
+    DIR_TRY
+    if (Q < 0 || N < 0 || nlist < 0 || items < 0 || width < 0) return fail(DIR_ERR_INVALID, "ivf_scan_fp4: negative size");
+    DIR_CHECK(fp4_check_dim("ivf_scan_fp4", D));
+    if (ldq < pad64(D) / 2 || ldb < pad64(D) / 2)
+        return fail(DIR_ERR_INVALID, "ivf_scan_fp4: ldq, ldb < half of D rounded up to a multiple of 64");
+    if (ldqe < fp4_exps_width(D) || ldbe < fp4_exps_width(D))
+        return fail(DIR_ERR_INVALID, "ivf_scan_fp4: ldqe, ldbe < 8 * ceil(D / 256)");
+    if (lds < width) return fail(DIR_ERR_INVALID, "ivf_scan_fp4: lds < width");
+    if (Q == 0 || width == 0) return DIR_OK;
+    if (!scores || !out_ids) return fail(DIR_ERR_INVALID, "ivf_scan_fp4: null pointer");
+    if (items > 0 && N > 0) {
+        if (nlist < 1) return fail(DIR_ERR_INVALID, "ivf_scan_fp4: items without a list");
+        if (!qcodes || !qexps || !qscales || !bcodes || !bexps || !bscales || !ids || !list_off || !pair_off || !pair_q ||
+            !pair_col || !item_off)
+            return fail(DIR_ERR_INVALID, "ivf_scan_fp4: null pointer");
+        if (!ivf_scan_fp4_admissible(qcodes, ldq, qexps, ldqe, Q, bcodes, ldb, bexps, ldbe, D))
+            return fail(DIR_ERR_INVALID, "ivf_scan_fp4: ldq, ldb % 16 == 0, ldb < 2^23, Q * ldq < 2^31 and 16-byte aligned codes, "
+                                         "ldqe, ldbe % 8 == 0 and 8-byte aligned block bytes");
+    }
+    return ivf_scan_fp4(qcodes, ldq, qexps, ldqe, qscales, Q, bcodes, ldb, bexps, ldbe, bscales, ids, N, D, list_off, nlist,
+                        pair_off, pair_q, pair_col, item_off, items, scores, out_ids, lds, width, (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_topk_max_k(void) { return topk_max_k(); }
 
 static int topk_check_sizes(int Q, int N, int k) {

@@ -30,7 +30,6 @@ namespace dir {
 
 static constexpr int kFp4MaxDim = 7281;            // 36 * 64 * 7281 = 16 775 424 < 2^24: every partial sum is exact in fp32
 static constexpr int kFp4QB = 96;                  // query rows per block
-static constexpr int kFp4SlabK = 2 * kStripRow;    // 256 k in a stage row
 static constexpr int kFp4SlabCodes = kFp4QB * kStripRow;          // 12288
 static constexpr int kFp4SlabQ = kFp4SlabCodes + kStripPiece;     // + the block bytes (768 of a 1 KiB piece)
 static constexpr int kFp4Stage = kStripSlab + kFp4SlabQ;
@@ -38,8 +37,6 @@ static constexpr int kFp4Stages = 3;
 static constexpr int kFp4Lds = kFp4Stages * kFp4Stage;            // 138240 of 163840
 
 int index_fp4_max_dim() { return kFp4MaxDim; }
-
-__host__ __device__ inline int fp4_slabs(int D) { return (pad64(D) + kFp4SlabK - 1) / kFp4SlabK; }
 
 // ---- quantisation ------------------------------------------------------------------------------------------------------
 // One wave per row, quantize_rows_i8_kernel's walk: a lane owns quads of consecutive k, quad (c * 8 + i) * 64 + lane, so
@@ -159,30 +156,6 @@ __global__ void __launch_bounds__(256) fp4_image_kernel(const uint8_t* __restric
         *(uint32_t*)(dst + kFp4SlabCodes + item * 4) = w;
     }
 }
-
-// The database side of a loader wave: StripLoader's pieces with a cut by chunk.  Kb (bytes of codes in a row, a multiple
-// of 32) leaves 2, 4, 6 or 8 chunks in the last slab; as the scalar offset takes no part in the range check, a lane whose
-// chunk lies past Kb asks for an address that is out of range by itself.
-struct Fp4Loader {
-    uint32_t pvoff[8];
-    uint32_t chunks = 0;     // 3 bits per piece: this lane's chunk of piece i
-    int lw, last, keep;      // the last slab and how many chunks of it exist
-
-    __device__ __forceinline__ Fp4Loader(int lw_, int lane, uint32_t pitch, int Kb, int T)
-        : lw(lw_), last(T - 1), keep((Kb - (T - 1) * kStripRow) >> 4) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            pvoff[i] = strip_piece_voff(lw * 8 + i, lane, pitch);
-            chunks |= (uint32_t)strip_piece_chunk(lw * 8 + i, lane) << (3 * i);
-        }
-    }
-    __device__ __forceinline__ void issue(__amdgpu_buffer_rsrc_t rsrc, char* stage, int u) const {
-        const uint32_t lim = u == last ? (uint32_t)keep : 8u;
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            dma16(rsrc, stage + (lw * 8 + i) * kStripPiece, ((chunks >> (3 * i)) & 7u) >= lim ? kOOB : pvoff[i], u * kStripRow);
-    }
-};
 
 __global__ void __launch_bounds__(768) sim_fp4_kernel(const uint8_t* __restrict__ P, int ldp, const uint8_t* __restrict__ PE,
                                                      int ldpe, int NP, int Kb, const uint8_t* __restrict__ img,

@@ -79,6 +79,13 @@ int ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, cons
                 const float* bscales, const int* ids, int N, int D, const int* list_off, int nlist, const int* pair_off,
                 const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
                 int lds, int width, hipStream_t stream);
+// the inverted file over fp4 codes (ivf_fp4.hip): the list-major scan of the probed lists on the scaled matrix cores
+bool ivf_scan_fp4_admissible(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe, int Q, const uint8_t* bcodes,
+                             int ldb, const uint8_t* bexps, int ldbe, int D);
+int ivf_scan_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe, const float* qscales, int Q,
+                 const uint8_t* bcodes, int ldb, const uint8_t* bexps, int ldbe, const float* bscales, const int* ids, int N,
+                 int D, const int* list_off, int nlist, const int* pair_off, const int* pair_q, const int* pair_col,
+                 const int* item_off, int items, float* scores, int* out_ids, int lds, int width, hipStream_t stream);
 // the product-quantised index (pq.hip): 8-bit codes per sub-space, the tables of a query, the scan that adds their entries
 int pq_max_m();
 int pq_encode(const float* X, int ldx, int N, int D, int M, const float* codebooks, uint8_t* codes, int ldc, hipStream_t stream);

@@ -1,4 +1,5 @@
-// strip_stream.h — the row-strip LDS-DMA pipeline of the scan kernels (sim_split.hip, index_i8.hip, ivf.hip), once.
+// strip_stream.h — the row-strip LDS-DMA pipeline of the scan kernels (sim_split.hip, index_i8.hip, index_fp4.hip, ivf.hip,
+// ivf_fp4.hip), once.
 //
 // One workgroup per 256 database rows.  Eight consumer waves own a 32-row strip each and multiply it against the query
 // rows of the stage; four loader waves (8 .. 11) only issue LDS-DMA and wait for it.  A stage is 32 KB of database (256
@@ -248,6 +249,41 @@ __device__ __forceinline__ void code_slab_mma(const StripLane& L, const char* st
 // its scales are byte s of `bexp` (the database row's, from the caller) and of the query row's dword for this lane half.
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 
+static constexpr int kFp4SlabK = 2 * kStripRow;    // 256 k in a stage row
+__host__ __device__ inline int fp4_slabs(int D) { return (pad64(D) + kFp4SlabK - 1) / kFp4SlabK; }
+
+// The database side of a loader wave: StripLoader's pieces with a cut by chunk.  Kb (bytes of codes in a row, a multiple
+// of 32) leaves 2, 4, 6 or 8 chunks in the last slab; as the scalar offset takes no part in the range check, a lane whose
+// chunk lies past Kb asks for an address that is out of range by itself.
+struct Fp4Loader {
+    uint32_t pvoff[8];
+    uint32_t chunks = 0;     // 3 bits per piece: this lane's chunk of piece i
+    int lw, last, keep;      // the last slab and how many chunks of it exist
+
+    __device__ __forceinline__ Fp4Loader(int lw_, int lane, uint32_t pitch, int Kb, int T)
+        : lw(lw_), last(T - 1), keep((Kb - (T - 1) * kStripRow) >> 4) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            pvoff[i] = strip_piece_voff(lw * 8 + i, lane, pitch);
+            chunks |= (uint32_t)strip_piece_chunk(lw * 8 + i, lane) << (3 * i);
+        }
+    }
+    __device__ __forceinline__ void issue(__amdgpu_buffer_rsrc_t rsrc, char* stage, int u) const {
+        const uint32_t lim = u == last ? (uint32_t)keep : 8u;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            dma16(rsrc, stage + (lw * 8 + i) * kStripPiece, ((chunks >> (3 * i)) & 7u) >= lim ? kOOB : pvoff[i], u * kStripRow);
+    }
+};
+
+// The block bytes of a slab for the lane half lhi, from the row's 8 bytes of that slab (one 8-byte load): byte s of the
+// result is block 2 s + lhi, the scale a step s selects with op_sel.
+__device__ __forceinline__ uint32_t fp4_pick_bytes(u32x2_t w, int lhi) {
+    const int sh = 8 * lhi;
+    return ((w[0] >> sh) & 0xffu) | (((w[0] >> (16 + sh)) & 0xffu) << 8) | (((w[1] >> sh) & 0xffu) << 16) |
+           (((w[1] >> (16 + sh)) & 0xffu) << 24);
+}
+
 template <int S, int NB>
 __device__ __forceinline__ void fp4_step(const StripLane& L, const char* stage, const uint32_t (&aexp)[NB], uint32_t bexp,
                                          f32x16_t (&acc)[NB]) {
@@ -270,6 +306,18 @@ __device__ __forceinline__ void fp4_slab_mma(const StripLane& L, const char* sta
 #pragma unroll
     for (int j = 0; j < NB; ++j) aexp[j] = *(const uint32_t*)(stage + eoff + j * 128);
     fp4_step<0, NB>(L, stage, aexp, bexp, acc);   // k = 256 u + 64 s + 32 lhi + 0..31
+    fp4_step<1, NB>(L, stage, aexp, bexp, acc);
+    fp4_step<2, NB>(L, stage, aexp, bexp, acc);
+    fp4_step<3, NB>(L, stage, aexp, bexp, acc);
+}
+
+// The same slab for a stage without block bytes in its query part (the list-major scan, whose query rows are gathered and
+// have no image): the query rows' scale dwords come in registers, aexp[j] = the dword of query row 32 j + lrow for this
+// lane half, picked like bexp.
+template <int NB>
+__device__ __forceinline__ void fp4_slab_mma(const StripLane& L, const char* stage, const uint32_t (&aexp)[NB], uint32_t bexp,
+                                             f32x16_t (&acc)[NB]) {
+    fp4_step<0, NB>(L, stage, aexp, bexp, acc);
     fp4_step<1, NB>(L, stage, aexp, bexp, acc);
     fp4_step<2, NB>(L, stage, aexp, bexp, acc);
     fp4_step<3, NB>(L, stage, aexp, bexp, acc);

@@ -30,6 +30,17 @@ The inverted file reads only the lists a query falls into instead of the whole d
 Its assignment, probing and scores are defined through the quantised score as well (include/dir_engine.h), so with
 nprobe = nlist it returns Int8Index's lists bit for bit, and with fewer lists those of tests/ivf_ref.py.
 
+The inverted file over fp4 codes keeps Fp4Index's rows in IVFInt8Index's lists - the same coarse quantiser (a row lands in
+the same list), 1096 bytes a row of 2048 instead of 2056:
+
+    index = IVFFp4Index(D, nlist=1024)                       # D <= ops.index_fp4_max_dim()
+    index.train(bdescs)                                      # IVFInt8Index.train
+    index.add(bdescs)
+    idx, vals = index.search(qdescs, 10, nprobe=8, rerank=40, source=bdescs)   # coarse raw scores: made for use with rerank
+
+Its scores are Fp4Index's numbers, so with nprobe = nlist it returns Fp4Index's lists bit for bit, and with fewer lists those
+of tests/ivffp4_ref.py.
+
 The product-quantised index keeps M bytes per row instead of D - a row is the numbers of its nearest of 256 centroids in
 each of M sub-spaces - and scores a query through M tables of 256 inner products:
 
@@ -142,6 +153,7 @@ def _padded_codes(path, codes, width, dtype, pitch):
 class _CodedIndex:
     """What every index shares: `codes` [N, ldc], one row per database row, CUDA - int8 with ldc = D rounded up to 64 (padding
     zero) and `scales` [N] fp32 for the int8 indexes, which is what the constructor makes, with their half of save and load;
+    the fp4 store (_init_fp4: codes, `exps` and scales) with its half of save and load for the two fp4 indexes;
     uint8 with ldc = M rounded up to 4 and scales None for the product-quantised ones, which replace both - what a search
     does around its scan (the argument checks, the fp32 re-rank of a shortlist) and the blocked scan loop."""
 
@@ -262,6 +274,36 @@ class _CodedIndex:
             raise ValueError('%s: scales [N] expected for codes [N, D]' % path)
         self.scales = torch.from_numpy(f['scales'].astype(np.float32)).cuda()
 
+    def _init_fp4(self, D):
+        """the empty fp4 store in place of the int8 one: codes [0, ldc] uint8, exps [0, lde] uint8, scales [0] fp32"""
+        D = int(D)
+        if D < 1 or D > ops.index_fp4_max_dim():
+            raise ValueError('1 <= D <= %d expected, got %d' % (ops.index_fp4_max_dim(), D))
+        self.D = D
+        ldc, lde = ops.fp4_widths(D)
+        self.codes = torch.empty(0, ldc, dtype=torch.uint8, device='cuda')
+        self.exps = torch.empty(0, lde, dtype=torch.uint8, device='cuda')
+        self.scales = torch.empty(0, dtype=torch.float32, device='cuda')
+
+    def _save_fp4(self):
+        """the fp4 store's arrays of a .npz: `codes` [N, ceil(D / 2)] uint8, `exps` [N, ceil(D / 32)] uint8 (both without the
+        padding), `scales` [N] float32"""
+        nc, ne = (self.D + 1) // 2, (self.D + 31) // 32
+        return dict(codes=self.codes[:, :nc].cpu().numpy(), exps=self.exps[:, :ne].cpu().numpy(),
+                    scales=self.scales.cpu().numpy())
+
+    def _load_fp4(self, path, f):
+        D = self.D
+        ldc, lde = ops.fp4_widths(D)
+        self.codes = _padded_codes(path, f['codes'], (D + 1) // 2, np.uint8, ldc)
+        if f['exps'].dtype != np.uint8 or f['exps'].shape != (len(self), (D + 31) // 32):
+            raise ValueError('%s: exps [N, %d] uint8 expected for codes of N rows' % (path, (D + 31) // 32))
+        self.exps = torch.full((len(self), lde), 127, dtype=torch.uint8, device='cuda')
+        self.exps[:, :(D + 31) // 32] = torch.from_numpy(f['exps']).cuda()
+        if f['scales'].shape != (len(self),):
+            raise ValueError('%s: scales [N] expected for codes [N, ...]' % path)
+        self.scales = torch.from_numpy(f['scales'].astype(np.float32)).cuda()
+
 
 class Int8Index(_CodedIndex):
     """codes [N, ldc] int8 (ldc = D rounded up to 64, padding zero) and scales [N] fp32, both CUDA."""
@@ -308,14 +350,7 @@ class Fp4Index(_CodedIndex):
     rows, so the lists do not depend on how the scan or the adds were cut."""
 
     def __init__(self, D):
-        D = int(D)
-        if D < 1 or D > ops.index_fp4_max_dim():
-            raise ValueError('1 <= D <= %d expected, got %d' % (ops.index_fp4_max_dim(), D))
-        self.D = D
-        ldc, lde = ops.fp4_widths(D)
-        self.codes = torch.empty(0, ldc, dtype=torch.uint8, device='cuda')
-        self.exps = torch.empty(0, lde, dtype=torch.uint8, device='cuda')
-        self.scales = torch.empty(0, dtype=torch.float32, device='cuda')
+        self._init_fp4(D)
 
     def nbytes(self):
         """the bytes the database rows take on the device: codes, block bytes and scales"""
@@ -345,29 +380,18 @@ class Fp4Index(_CodedIndex):
     def save(self, path):
         """One .npz: `codes` [N, ceil(D / 2)] uint8, `exps` [N, ceil(D / 32)] uint8 (both without the padding), `scales` [N]
         float32, `D`."""
-        nc, ne = (self.D + 1) // 2, (self.D + 31) // 32
-        np.savez(path, D=np.int64(self.D), codes=self.codes[:, :nc].cpu().numpy(), exps=self.exps[:, :ne].cpu().numpy(),
-                 scales=self.scales.cpu().numpy())
+        np.savez(path, D=np.int64(self.D), **self._save_fp4())
 
     @classmethod
     def load(cls, path):
         f = _read_npz(path)
         index = cls(int(f['D']))
-        D = index.D
-        ldc, lde = ops.fp4_widths(D)
-        index.codes = _padded_codes(path, f['codes'], (D + 1) // 2, np.uint8, ldc)
-        if f['exps'].dtype != np.uint8 or f['exps'].shape != (len(index), (D + 31) // 32):
-            raise ValueError('%s: exps [N, %d] uint8 expected for codes of N rows' % (path, (D + 31) // 32))
-        index.exps = torch.full((len(index), lde), 127, dtype=torch.uint8, device='cuda')
-        index.exps[:, :(D + 31) // 32] = torch.from_numpy(f['exps']).cuda()
-        if f['scales'].shape != (len(index),):
-            raise ValueError('%s: scales [N] expected for codes [N, ...]' % path)
-        index.scales = torch.from_numpy(f['scales'].astype(np.float32)).cuda()
+        index._load_fp4(path, f)
         return index
 
 
 class _InvertedLists:
-    """What the two inverted files share - the coarse quantiser and the list-major bookkeeping: centroids [nlist, D] fp32
+    """What the inverted files share - the coarse quantiser and the list-major bookkeeping: centroids [nlist, D] fp32
     with their codes `ccodes` and scales `cscales`, ids [N] int32, list_off [nlist+1] int32 and `_lens`, the host copy of
     the list lengths; assignment, probing, the spherical Lloyd iterations, the regrouping of a store after an add, the
     probed search loop and their half of save and load."""
@@ -590,6 +614,74 @@ class IVFInt8Index(_InvertedLists, _CodedIndex):
         f = _read_npz(path)
         index = cls(int(f['D']), int(f['nlist']))
         index._load_i8(path, f)
+        index._load_lists(path, f)
+        return index
+
+
+class IVFFp4Index(_InvertedLists, _CodedIndex):
+    """The inverted file over fp4 codes (include/dir_engine.h gives the definitions; numpy restatement: tests/ivffp4_ref.py).
+    All CUDA: IVFInt8Index's coarse quantiser (centroids [nlist, D] fp32, `ccodes`, `cscales`: assignment and probing by the
+    int8 score, so a row lands in the list IVFInt8Index puts it in) and the database LIST-MAJOR as Fp4Index stores a row -
+    codes [N, ldc] uint8, exps [N, lde] uint8, scales [N] fp32, (ldc, lde) = ops.fp4_widths(D) - with ids [N] int32 and
+    list_off [nlist+1] int32; inside a list the rows are in ascending id."""
+
+    def __init__(self, D, nlist):
+        self._init_fp4(D)
+        self._init_lists(nlist)
+
+    def nbytes(self):
+        """the bytes the database rows take on the device: codes, block bytes, scales and ids (centroids not counted)"""
+        return sum(int(t.numel()) * t.element_size() for t in (self.codes, self.exps, self.scales, self.ids))
+
+    def train(self, x, iters=10, seed=0, max_rows=None):
+        """IVFInt8Index.train: the same sample, the same iterations, the same centroids bit for bit."""
+        self._check_train(x)
+        max_rows = 256 * self.nlist if max_rows is None else int(max_rows)
+        self._lloyd_centroids(_training_rows(x, seed, max_rows, self.nlist, 'nlist = %d' % self.nlist), iters, seed)
+        return self
+
+    def add(self, descs):
+        """IVFInt8Index.add's contract: a chunk of ADD_CHUNK_BYTES is quantised to int8 for its assignment and to fp4 for
+        the store, and the three stores are regrouped by that class's stable integer sort, so what the index holds does
+        not depend on how the rows were cut into calls."""
+        self._check_rows(descs)
+        self._need_trained('add')
+        if int(descs.shape[0]) == 0:
+            return self
+        lists, codes, exps, scales = [], [self.codes], [self.exps], [self.scales]
+        for x in _row_chunks(descs, self.D):
+            lists.append(self._assign(*ops.quantize_rows(x)))
+            c, e, s = ops.quantize_rows_fp4(x)
+            codes.append(c)
+            exps.append(e)
+            scales.append(s)
+        self.codes, self.exps, self.scales = self._regroup(lists, [torch.cat(codes), torch.cat(exps), torch.cat(scales)])
+        return self
+
+    def _scan_lists(self, q, qc, qs, probe, col_off, rows, width):
+        fc, fe, fs = ops.quantize_rows_fp4(q[rows])
+        return ops.ivf_scan_fp4(fc, fe, fs, self.codes, self.exps, self.scales, self.ids, self.list_off, probe[rows],
+                                col_off[rows], self.D)
+
+    def search(self, qdescs, k, nprobe=1, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20):
+        """IVFInt8Index.search's contract with the fp4 scores in place of the int8 ones: the lists of a query are probed by
+        its int8 codes, their rows scored by its fp4 codes; a query whose lists hold fewer than k rows ends in (-1, NaN).
+        The queries go in chunks whose score and id rows (8 bytes per column) and fp4 codes fit scratch_bytes; every
+        chunk synchronises with the host once, inside ops.ivf_scan_fp4."""
+        ldc, lde = ops.fp4_widths(self.D)
+        return self._search_lists(qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, ldc + lde + 4)
+
+    def save(self, path):
+        """One .npz: Fp4Index's arrays (`codes` [N, ceil(D / 2)] uint8, `exps` [N, ceil(D / 32)] uint8, `scales` [N] float32,
+        `D`) and the lists' (`centroids` [nlist, D] float32, `ids` [N] int32, `list_off` [nlist+1] int32, `nlist`)."""
+        self._need_trained('save')
+        np.savez(path, D=np.int64(self.D), **self._save_fp4(), **self._save_lists())
+
+    @classmethod
+    def load(cls, path):
+        f = _read_npz(path)
+        index = cls(int(f['D']), int(f['nlist']))
+        index._load_fp4(path, f)
         index._load_lists(path, f)
         return index
 

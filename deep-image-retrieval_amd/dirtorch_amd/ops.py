@@ -890,6 +890,50 @@ def ivf_scan(qcodes, qscales, codes, scales, ids, list_off, probe, col_off, D, w
     return scores[:, :width], out_ids[:, :width]
 
 
+# ---- the inverted file over fp4 codes (csrc/ivf_fp4.hip) ----------------------------------------------------------------
+def ivf_scan_fp4(qcodes, qexps, qscales, codes, exps, scales, ids, list_off, probe, col_off, D, width=None, out=None,
+                 tables=None):
+    """ivf_scan over fp4 rows (dir_ivf_scan_fp4) -> (scores [Q,width] fp32, out_ids [Q,width] int32), both CUDA.  qcodes
+    [Q,ldc] / qexps [Q,lde] / qscales [Q] as quantize_rows_fp4 gives them (zero padding included; row slices too); codes
+    [N,ldc] uint8, exps [N,lde] uint8, scales [N] fp32, ids [N] int32, list_off [nlist+1] int32: a list-major database
+    (index.IVFFp4Index); (ldc, lde) = fp4_widths(D).  probe, col_off, width, out and tables under ivf_scan's contract: for
+    r < len(list probe[q][p]), column col_off[q][p] + r carries similarity_fp4's score (acc * qscales[q]) * scales[n] and
+    the id of row n = list_off[probe[q][p]] + r; a column no slot covers carries id -1; columns at or past width keep
+    what they hold.  tables: ivf_probe_tables' result for these list_off, probe and col_off (the call then does not
+    synchronise with the host)."""
+    _on_device(qcodes, qexps, qscales, codes, exps, scales, ids, list_off, probe, col_off, *(out or ()))
+    for t in (qcodes, qexps, codes, exps):
+        if t.dtype != torch.uint8 or t.dim() != 2:
+            raise TypeError('uint8 codes [rows, ldc] and block bytes [rows, lde] expected')
+    if qscales.dtype != torch.float32 or scales.dtype != torch.float32:
+        raise TypeError('float32 scales expected')
+    Q, N = qcodes.shape[0], codes.shape[0]
+    nlist = _list_tables(Q, N, ids, list_off, probe, col_off)
+    D = int(D)
+    if D < 1 or D > index_fp4_max_dim():
+        raise ValueError('1 <= D <= %d expected, got %d' % (index_fp4_max_dim(), D))
+    ldc, lde = fp4_widths(D)
+    if qcodes.shape[1] < ldc or codes.shape[1] < ldc or qexps.shape[1] < lde or exps.shape[1] < lde:
+        raise ValueError('codes of %d and block bytes of %d columns at least expected for D = %d' % (ldc, lde, D))
+    if qexps.shape[0] != Q or exps.shape[0] != N:
+        raise ValueError('block bytes of Q and N rows expected for codes of Q and N rows')
+    if qscales.dim() != 1 or scales.dim() != 1 or qscales.numel() != Q or scales.numel() != N:
+        raise ValueError('qscales [Q] and scales [N] expected for codes of Q and N rows')
+    qcodes, ldq = _i8_codes(qcodes, ldc)
+    qexps, ldqe = _i8_codes(qexps, lde, align=8)
+    codes, ldb = _i8_codes(codes, ldc)
+    exps, ldbe = _i8_codes(exps, lde, align=8)
+    qscales, scales, ids, list_off = qscales.contiguous(), scales.contiguous(), ids.contiguous(), list_off.contiguous()
+    pair_off, pair_q, pair_col, item_off, items, reach = tables if tables is not None else ivf_probe_tables(list_off, probe, col_off)
+    width = reach if width is None else int(width)
+    scores, out_ids, lds = _scan_out(out, Q, width, codes.device)
+    if Q and width:
+        call('dir_ivf_scan_fp4', ptr(qcodes), ldq, ptr(qexps), ldqe, ptr(qscales), Q, ptr(codes), ldb, ptr(exps), ldbe,
+             ptr(scales), ptr(ids), N, D, ptr(list_off), nlist, ptr(pair_off), ptr(pair_q), ptr(pair_col), ptr(item_off),
+             items, ptr(scores), ptr(out_ids), lds, width, stream_ptr())
+    return scores[:, :width], out_ids[:, :width]
+
+
 # ---- the product-quantised index (csrc/pq.hip) -------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)     # a constant of the library: asked once, not in every call of a search
 def pq_max_m():

@@ -16,6 +16,9 @@ the --topk best of those, with their fp32 scores.
 the quantised scores are coarser than int8's, so pair it with --rerank (4 x --topk gave the fp32 lists in our measurements).
 --index ivf --nlist L --nprobe P: an index.IVFInt8Index trained on the database descriptors themselves (L k-means lists);
 every query scans its P best lists only, --rerank as above.  With P = L the lists are those of --index int8.
+--index ivffp4 --nlist L --nprobe P: an index.IVFFp4Index - IVFInt8Index's lists (the same training, a row in the same
+list) holding Fp4Index's rows (descriptors of at most 7281 values); every query scans its P best lists only.  Its raw
+scores are fp4's, so pair it with --rerank like --index fp4.  With P = L the lists are those of --index fp4.
 --index pq --pq-m M: an index.PQIndex trained on the database descriptors themselves (M bytes per image, M dividing the
 descriptor width; at least 256 database images); the lists are ranked by the table scores, --rerank as above.
 --index ivfpq --nlist L --nprobe P --pq-m M: an index.IVFPQIndex trained on the database descriptors themselves (L k-means
@@ -45,7 +48,7 @@ from .utils.convenient import mkdir
 
 # --index kind -> (its class in dirtorch_amd.index, the flags its constructor takes after the width, whether it is trained)
 INDEX_KINDS = {'int8': ('Int8Index', (), False), 'fp4': ('Fp4Index', (), False), 'ivf': ('IVFInt8Index', ('nlist',), True),
-               'pq': ('PQIndex', ('pq_m',), True), 'ivfpq': ('IVFPQIndex', ('nlist', 'pq_m'), True)}
+               'ivffp4': ('IVFFp4Index', ('nlist',), True), 'pq': ('PQIndex', ('pq_m',), True), 'ivfpq': ('IVFPQIndex', ('nlist', 'pq_m'), True)}
 
 
 def query_keys(db):
@@ -85,8 +88,8 @@ def main(argv=None):
         (('--topk',), dict(type=int, default=20, help='neighbours per query')),
         (('--output',), dict(type=str, required=True, help='path of the list: .npz, or text')),
         (('--index',), dict(type=str, default='', choices=[''] + list(INDEX_KINDS), help='scan a quantised copy of the database')),
-        (('--nlist',), dict(type=int, default=0, help='with --index ivf / ivfpq: the number of k-means lists')),
-        (('--nprobe',), dict(type=int, default=1, help='with --index ivf / ivfpq: lists scanned per query')),
+        (('--nlist',), dict(type=int, default=0, help='with --index ivf / ivffp4 / ivfpq: the number of k-means lists')),
+        (('--nprobe',), dict(type=int, default=1, help='with --index ivf / ivffp4 / ivfpq: lists scanned per query')),
         (('--pq-m',), dict(type=int, default=0, help='with --index pq / ivfpq: bytes (sub-spaces) per database image')),
         (('--rerank',), dict(type=int, default=0, help='with --index: shortlist size re-scored in fp32 (0 = none)')),
         eval_dir.EXPAND_FLAG,

@@ -135,6 +135,7 @@ const char* dir_version(void);
  *   dir_segment_sums         S <= 65535
  *   dir_ivf_scan_i8          Q * width <= L, items * 768 <= L (refused, not cut: Q * width of 2^32 means 32 GiB of score and id
  *                            rows for one chunk; index.py's chunks are scratch_bytes / 8 slots, 2^25 by default)
+ *   dir_ivf_scan_fp4         Q * width <= L, items * 768 <= L (refused, not cut, as dir_ivf_scan_i8)
  *   dir_pq_encode            N * M <= L (N rounded up to 256)
  *   dir_pq_lut               Q * M * 8 <= L (Q rounded up to 32)
  *   dir_ivfpq_base           Q * nprobe * 128 <= L
@@ -667,6 +668,35 @@ int dir_ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, 
                     const float* bscales, const int* ids, int N, int D, const int* list_off, int nlist, const int* pair_off,
                     const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
                     int lds, int width, void* stream);
+/* The inverted file over fp4 codes (ivf_fp4.hip; dirtorch_amd/index.py IVFFp4Index; numpy restatement: tests/ivffp4_ref.py):
+ * the inverted file's lists with the fp4 index's rows in them, 1 <= D <= dir_index_fp4_max_dim() = 7281.
+ * Coarse side: the inverted-file int8 index's, unchanged - centroids [nlist][D] fp32 with their int8 codes and scales;
+ *   assignment and probing by the quantised int8 score under dir_topk's order, exactly as above.  A row therefore lands in
+ *   the same list in all three inverted files, and training is the int8 inverted file's.
+ * Lists: a row is stored as dir_quantize_rows_fp4 gives it - codes [N][ldc] uint8, block bytes [N][lde] uint8, scales [N]
+ *   fp32 - LIST-MAJOR with ids [N] int32 and list_off [nlist + 1] int32 as above, ids ascending inside a list.
+ * Score: that of query q against row n of a probed list is dir_similarity_fp4's number, (acc * qscales[q]) * bscales[n], two
+ *   fp32 multiplies in that order, with acc the exact sum: it does not depend on the tiling, the K order, the rotation,
+ *   the grouping of the queries or the chunking.  CONSEQUENCE: with nprobe = nlist a search returns the fp4 index's lists
+ *   bit for bit (dir_topk ranks the same set of (score, id) pairs); with fewer lists those of the numpy restatement.
+ * dir_ivf_scan_fp4: dir_ivf_scan_i8's contract - the same inverted probe table (pair_off, pair_q, pair_col, item_off, items:
+ *   256 rows a tile, 32 pairs a group), the same outputs: for every pair and r < len_l, scores[q][col + r] = the score
+ *   above against row list_off[l] + r and out_ids[q][col + r] = ids[list_off[l] + r]; out_ids[q][0 .. width) pre-filled with
+ *   -1 BY THIS CALL; columns at or past `width` untouched; a pair that would pass `width` or whose query is outside [0, Q)
+ *   stores nothing.  qcodes [Q][ldq] and bcodes [N][ldb]: 16-byte aligned, pitches % 16 == 0 and >= D rounded up to 64,
+ *   divided by 2 (need not cover a whole slab of 256 k: both sides are cut by 16-byte chunk in the last slab), Q * ldq <
+ *   2^31; the query codes must be ZERO in the nibbles D .. D rounded up to 64 (dir_quantize_rows_fp4 writes them so; what
+ *   the database holds there does not matter).  qexps [Q][ldqe] and bexps [N][ldbe]: 8-byte aligned, pitches % 8 == 0 and
+ *   >= 8 * ceil(D / 256) - one 8-byte load per slab and row on BOTH sides; the bytes of blocks past D rounded up to 64 do
+ *   not matter (they are replaced by 127), the others are e8m0 bytes other than 255.  The slots of one query must not
+ *   overlap.  LDS-DMA loaders (the query rows of a group gathered by a per-lane offset),
+ *   v_mfma_scale_f32_32x32x64_f8f6f4, K slabs of 256, four stages.
+ *   A negative count, D < 1 or above the max dim, a pitch below its minimum or a null pointer fail with DIR_ERR_INVALID
+ *   before anything is launched; Q == 0 or width == 0 is DIR_OK and launches nothing. */
+int dir_ivf_scan_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe, const float* qscales, int Q,
+                     const uint8_t* bcodes, int ldb, const uint8_t* bexps, int ldbe, const float* bscales, const int* ids, int N,
+                     int D, const int* list_off, int nlist, const int* pair_off, const int* pair_q, const int* pair_col,
+                     const int* item_off, int items, float* scores, int* out_ids, int lds, int width, void* stream);
 /* The product-quantised index (pq.hip; dirtorch_amd/index.py PQIndex; numpy restatement: tests/pq_ref.py).
  * A row of D fp32 values is cut into M sub-vectors of dsub = D / M values (M divides D, 1 <= M <= dir_pq_max_m(), D <=
  * dir_index_i8_max_dim()); sub-vector m is replaced by the number of one of the 256 centroids of sub-space m, so a row is
