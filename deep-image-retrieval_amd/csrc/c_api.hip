@@ -1039,6 +1039,24 @@ int dir_ivf_scan_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int l
     DIR_CATCH
 }
 
+int dir_ivf_plan_max_pairs(void) { return ivf_plan_max_pairs(); }
+
+int dir_ivf_plan(const int* probe, int Q, int nprobe, const int* list_off, int nlist, int* col_off, int* pair_off, int* pair_q,
+                 int* pair_col, int* item_off, int* counts, void* stream) {
+    DIR_TRY
+    if (Q < 0 || nprobe < 0 || nlist < 0) return fail(DIR_ERR_INVALID, "ivf_plan: negative size");
+    if (nlist > 65535) return fail(DIR_ERR_INVALID, "ivf_plan: more than 65535 lists");
+    if ((long)Q * nprobe > ivf_plan_max_pairs())
+        return fail(DIR_ERR_INVALID, "ivf_plan: Q * nprobe exceeds dir_ivf_plan_max_pairs(): cut the queries");
+    if (Q == 0) return DIR_OK;
+    if (nlist < 1) return fail(DIR_ERR_INVALID, "ivf_plan: queries without a list");
+    if (!list_off || !pair_off || !item_off || !counts || (nprobe > 0 && (!probe || !col_off || !pair_q || !pair_col)))
+        return fail(DIR_ERR_INVALID, "ivf_plan: null pointer");
+    return ivf_plan(probe, Q, nprobe, list_off, nlist, col_off, pair_off, pair_q, pair_col, item_off, counts,
+                    (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_topk_max_k(void) { return topk_max_k(); }
 
 static int topk_check_sizes(int Q, int N, int k) {

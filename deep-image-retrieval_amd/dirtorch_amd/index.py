@@ -72,6 +72,8 @@ from . import ops
 from .utils.common import _dev
 
 ADD_CHUNK_BYTES = 256 << 20     # fp32 bytes of a database that are on the device at a time while it is quantised
+DEFAULT_PLAN = 'auto'           # search(plan=) of the inverted files: the device plan was the faster one at every measured
+                                # point (profiles/ivf_plan.txt: 0.44 - 0.72 of the host plan's time)
 
 
 def _round_up(n, to):
@@ -396,6 +398,8 @@ class _InvertedLists:
     the list lengths; assignment, probing, the spherical Lloyd iterations, the regrouping of a store after an add, the
     probed search loop and their half of save and load."""
 
+    _inverted_table = True       # whether the scan walks the probe table inverted (by list): what ops.ivf_plan makes
+
     def _init_lists(self, nlist):
         nlist = int(nlist)
         if nlist < 1 or nlist > 65535:
@@ -459,27 +463,62 @@ class _InvertedLists:
         lens = (self.list_off[1:] - self.list_off[:-1])[probe.long()]
         return torch.cumsum(lens, dim=1, dtype=torch.int32) - lens
 
-    def _search_lists(self, qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, query_bytes):
-        """The search of an inverted file around self._scan_lists(q, qc, qs, probe, col_off, rows, width) -> the (scores,
-        ids) [len(rows), <= width] of the queries of the slice `rows` against the lists they probe: the queries go in
-        chunks whose score and id rows (8 bytes per column; the nprobe longest lists bound the width, by the host's copy
-        of the list lengths) and query_bytes more per query fit scratch_bytes."""
+    def _plan_items(self, rows, nprobe):
+        """A host bound of the workgroups a scan by list of `rows` queries at nprobe distinct lists each takes.  List l
+        (tiles_l = ceil(len_l / 256)), probed by n_l >= 1 queries of the chunk, takes tiles_l * ceil(n_l / 32) <=
+        tiles_l * (n_l + 31) / 32 workgroups.  With T(m) = the tiles of the m longest lists added up: the sum of
+        tiles_l * n_l is the sum over the queries of the tiles of their lists, at most rows * T(nprobe); the probed lists
+        are at most m = min(nlist, rows * nprobe), their tiles at most T(m).  So (rows * T(nprobe) + 31 * T(m)) / 32 bounds
+        the grid - never above the plain rows * T(nprobe), and exact for one query."""
+        if getattr(self, '_tiles_of', None) is not self._lens:         # (a new _lens array after every add and load)
+            tiles = np.sort((self._lens + 255) // 256)[::-1]
+            self._tiles_top, self._tiles_of = np.concatenate([[0], np.cumsum(tiles)]), self._lens
+        rows, top = int(rows), self._tiles_top
+        return (rows * int(top[nprobe]) + 31 * int(top[min(len(top) - 1, rows * nprobe)])) // 32
+
+    def _search_lists(self, qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, query_bytes, plan='host'):
+        """The search of an inverted file around self._scan_lists(q, qc, qs, probe, col_off, rows, width, tables) -> the
+        (scores, ids) [len(rows), <= width] of the queries of the slice `rows` against the lists they probe (probe and
+        col_off: those of the chunk): the queries go in chunks whose score and id rows (8 bytes per column; the nprobe
+        longest lists bound the width, by the host's copy of the list lengths) and query_bytes more per query fit
+        scratch_bytes.
+        plan: where the tables of a chunk come from.  'host': col_off from integer torch operations and, for the two scans
+        by list, the inverted table from ops.ivf_probe_tables, which reads its grid and its width back - one
+        synchronisation per chunk.  'device': ops.ivf_plan makes them in one launch, the width is the host's bound above
+        and the grid the bound of _plan_items: nothing is read back; a chunk the planner or the launch limit does not take
+        (more than ops.ivf_plan_max_pairs() pairs, a bound above ops.ivf_scan_max_items()) is a ValueError.  'auto':
+        'device' where the chunks are admissible, else 'host'.  The lists returned are the same bits either way."""
         nprobe = int(nprobe)
         if nprobe < 1 or nprobe > self.nlist:
             raise ValueError('1 <= nprobe <= nlist = %d expected, got %d' % (self.nlist, nprobe))
+        if plan not in ('auto', 'device', 'host'):
+            raise ValueError("plan: 'auto', 'device' or 'host' expected, got %r" % (plan,))
 
         def scan(q, keep):
             Q = q.shape[0]
             qc, qs = ops.quantize_rows(q)
             probe = self.probe(qc, qs, nprobe)
-            col_off = self._slots(probe)
             width = max(int(np.partition(self._lens, -nprobe)[-nprobe:].sum()), keep)     # the nprobe longest lists
             step = int(max(1, min(Q, scratch_bytes // (8 * width + query_bytes))))
+            planned = plan != 'host' and self._inverted_table
+            if planned:         # every chunk has at most `step` queries: the first decides for all
+                items = self._plan_items(step, nprobe)
+                planned = step * nprobe <= ops.ivf_plan_max_pairs() and items <= ops.ivf_scan_max_items()
+                if not planned and plan == 'device':
+                    raise ValueError("plan='device': a chunk of %d queries at %d lists has %d pairs and a grid bound of %d; "
+                                     "at most %d and %d are planned on the device - lower scratch_bytes or nprobe, or "
+                                     "plan='auto'" % (step, nprobe, step * nprobe, items, ops.ivf_plan_max_pairs(),
+                                                      ops.ivf_scan_max_items()))
+            col_off = None if planned else self._slots(probe)
             cand = torch.empty(Q, keep, dtype=torch.int32, device='cuda')
             vals = torch.empty(Q, keep, dtype=torch.float32, device='cuda')
             for r0 in range(0, Q, step):
                 r1 = min(Q, r0 + step)
-                scores, ids = self._scan_lists(q, qc, qs, probe, col_off, slice(r0, r1), width)
+                if planned:
+                    slots, tables, _ = ops.ivf_plan(self.list_off, probe[r0:r1], self._plan_items(r1 - r0, nprobe))
+                else:
+                    slots, tables = col_off[r0:r1], None
+                scores, ids = self._scan_lists(q, qc, qs, probe[r0:r1], slots, slice(r0, r1), width, tables)
                 if scores.shape[1] < keep:   # every row of the chunk runs short: top-k wants keep columns, the rest are empty
                     wide = torch.full((r1 - r0, keep), -1, dtype=torch.int32, device='cuda')
                     wide[:, :ids.shape[1]] = ids
@@ -592,16 +631,19 @@ class IVFInt8Index(_InvertedLists, _CodedIndex):
         self.codes, self.scales = self._regroup(lists, [torch.cat(codes), torch.cat(scales)])
         return self
 
-    def _scan_lists(self, q, qc, qs, probe, col_off, rows, width):
-        return ops.ivf_scan(qc[rows], qs[rows], self.codes, self.scales, self.ids, self.list_off, probe[rows], col_off[rows],
-                            self.D)
+    def _scan_lists(self, q, qc, qs, probe, col_off, rows, width, tables):
+        return ops.ivf_scan(qc[rows], qs[rows], self.codes, self.scales, self.ids, self.list_off, probe, col_off, self.D,
+                            width=None if tables is None else width, tables=tables)
 
-    def search(self, qdescs, k, nprobe=1, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20):
+    def search(self, qdescs, k, nprobe=1, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20, plan=DEFAULT_PLAN):
         """Int8Index.search's contract over the rows of the nprobe best lists of every query (1 <= nprobe <= nlist): a
         query whose lists hold fewer than k rows ends in (-1, NaN).  The queries go in chunks whose score and id rows
-        (8 bytes per column; the nprobe longest lists bound the width) fit scratch_bytes; every chunk synchronises with
-        the host once, inside ops.ivf_scan, to learn its grid and its width."""
-        return self._search_lists(qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, 0)
+        (8 bytes per column; the nprobe longest lists bound the width) fit scratch_bytes.  plan (_search_lists gives the
+        rules): with 'host' every chunk synchronises with the host once, inside ops.ivf_scan, to learn its grid and its
+        width; with 'device' - and with 'auto' wherever the chunks are admissible - ops.ivf_plan makes the probe tables in
+        one launch, grid and width are host bounds, and with queries (and a rerank source) on the device the search
+        never waits for the host.  The lists are the same bits."""
+        return self._search_lists(qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, 0, plan)
 
     def save(self, path):
         """One .npz: `centroids` [nlist, D] float32, `codes` [N, D] int8 (without the padding), `scales` [N] float32, `ids`
@@ -658,18 +700,19 @@ class IVFFp4Index(_InvertedLists, _CodedIndex):
         self.codes, self.exps, self.scales = self._regroup(lists, [torch.cat(codes), torch.cat(exps), torch.cat(scales)])
         return self
 
-    def _scan_lists(self, q, qc, qs, probe, col_off, rows, width):
+    def _scan_lists(self, q, qc, qs, probe, col_off, rows, width, tables):
         fc, fe, fs = ops.quantize_rows_fp4(q[rows])
-        return ops.ivf_scan_fp4(fc, fe, fs, self.codes, self.exps, self.scales, self.ids, self.list_off, probe[rows],
-                                col_off[rows], self.D)
+        return ops.ivf_scan_fp4(fc, fe, fs, self.codes, self.exps, self.scales, self.ids, self.list_off, probe, col_off,
+                                self.D, width=None if tables is None else width, tables=tables)
 
-    def search(self, qdescs, k, nprobe=1, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20):
+    def search(self, qdescs, k, nprobe=1, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20, plan=DEFAULT_PLAN):
         """IVFInt8Index.search's contract with the fp4 scores in place of the int8 ones: the lists of a query are probed by
         its int8 codes, their rows scored by its fp4 codes; a query whose lists hold fewer than k rows ends in (-1, NaN).
-        The queries go in chunks whose score and id rows (8 bytes per column) and fp4 codes fit scratch_bytes; every
-        chunk synchronises with the host once, inside ops.ivf_scan_fp4."""
+        The queries go in chunks whose score and id rows (8 bytes per column) and fp4 codes fit scratch_bytes.  plan as
+        in IVFInt8Index.search: 'host' synchronises once per chunk, inside ops.ivf_scan_fp4; 'device' (and 'auto' where
+        admissible) plans the chunk with ops.ivf_plan and does not."""
         ldc, lde = ops.fp4_widths(self.D)
-        return self._search_lists(qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, ldc + lde + 4)
+        return self._search_lists(qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, ldc + lde + 4, plan)
 
     def save(self, path):
         """One .npz: Fp4Index's arrays (`codes` [N, ceil(D / 2)] uint8, `exps` [N, ceil(D / 32)] uint8, `scales` [N] float32,
@@ -794,18 +837,22 @@ class IVFPQIndex(_InvertedLists, _ProductQuantizer, _CodedIndex):
         self.codes, = self._regroup(lists, [torch.cat(codes)])
         return self
 
-    def _scan_lists(self, q, qc, qs, probe, col_off, rows, width):
-        lut = ops.pq_lut(q[rows], self.codebooks)
-        base = ops.ivfpq_base(q[rows], self.centroids, probe[rows], self.M)
-        return ops.ivfpq_scan(lut, base, self.codes, self.ids, self.list_off, probe[rows], col_off[rows], width=width)
+    _inverted_table = False      # the scan is cut query-major: it reads probe and col_off as they are
 
-    def search(self, qdescs, k, nprobe=1, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20):
+    def _scan_lists(self, q, qc, qs, probe, col_off, rows, width, tables):
+        lut = ops.pq_lut(q[rows], self.codebooks)
+        base = ops.ivfpq_base(q[rows], self.centroids, probe, self.M)
+        return ops.ivfpq_scan(lut, base, self.codes, self.ids, self.list_off, probe, col_off, width=width)
+
+    def search(self, qdescs, k, nprobe=1, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20, plan=DEFAULT_PLAN):
         """IVFInt8Index.search's contract over the rows of the nprobe best lists of every query (1 <= nprobe <= nlist), with
         the score  <q, centroid of the list> + the row's table entries  in place of the quantised one; a query whose lists
         hold fewer than k rows ends in (-1, NaN).  The queries go in chunks whose score and id rows (8 bytes per column;
         the nprobe longest lists give the width) and tables (1024 * M bytes per query) fit scratch_bytes.  The width comes
-        from the host's copy of the list lengths: a search does not synchronise with the host."""
-        return self._search_lists(qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, 1024 * self.M)
+        from the host's copy of the list lengths: a search does not synchronise with the host.  plan is taken (and
+        checked) for one interface over the three inverted files and changes nothing here: this scan walks no inverted
+        table, and its col_off stays the four integer torch launches of every plan."""
+        return self._search_lists(qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, 1024 * self.M, plan)
 
     def save(self, path):
         """One .npz: `centroids` [nlist, D] float32, `codebooks` [M, 256, D / M] float32, `codes` [N, M] uint8 (without the

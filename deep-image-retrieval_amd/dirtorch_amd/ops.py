@@ -850,6 +850,56 @@ def ivf_probe_tables(list_off, probe, col_off):
     return pair_off, pair_q, pair_col, item_off.to(torch.int32), int(items), int(reach)
 
 
+@functools.lru_cache(maxsize=None)     # a constant of the library: asked once, not in every chunk of a search
+def ivf_plan_max_pairs():
+    """The most (query, slot) pairs one ivf_plan call takes (dir_ivf_plan_max_pairs; host-only)."""
+    return int(_lib.load().dir_ivf_plan_max_pairs())
+
+
+@functools.lru_cache(maxsize=None)
+def ivf_scan_max_items():
+    """The largest grid a scan by list takes: items * 768 threads within dir_launch_max_threads() (host-only)."""
+    return int(_lib.load().dir_launch_max_threads()) // 768
+
+
+def ivf_plan(list_off, probe, items_bound):
+    """ivf_probe_tables' tables from ONE kernel launch and without a synchronisation (dir_ivf_plan, csrc/ivf_plan.hip;
+    include/dir_engine.h gives the definition) -> (col_off [Q,nprobe] int32, tables, counts [2] int32), all CUDA.
+    list_off [nlist+1] int32 CUDA, nlist <= 65535; probe [Q,nprobe] int32 CUDA, a list outside [0, nlist) = an empty slot,
+    Q * nprobe <= ivf_plan_max_pairs().  col_off: the lists of a query side by side in probe order.  tables = (pair_off,
+    pair_q, pair_col, item_off, items_bound, None): what ivf_scan and ivf_scan_fp4 take as tables= TOGETHER WITH an
+    explicit width= (the reach is not known on the host) - the four tensors equal ivf_probe_tables' bit for bit.
+    items_bound: the grid of the scan, any host integer that is at least item_off[nlist] (the scans' surplus workgroups
+    return at once) and at most ivf_scan_max_items() - the caller's duty, as the tables of ivf_scan are.  counts =
+    (item_off[nlist], reach) stays on the device: for tests and measurements."""
+    _on_device(list_off, probe)
+    if list_off.dtype != torch.int32 or probe.dtype != torch.int32:
+        raise TypeError('int32 list_off and probe expected')
+    if list_off.dim() != 1 or list_off.numel() < 2:
+        raise ValueError('list_off [nlist+1] expected')
+    if probe.dim() != 2:
+        raise ValueError('probe [Q,nprobe] expected')
+    nlist, (Q, nprobe) = int(list_off.numel()) - 1, probe.shape
+    P = Q * nprobe
+    items_bound = int(items_bound)
+    if nlist > 65535:
+        raise ValueError('nlist <= 65535 expected, got %d' % nlist)
+    if P > ivf_plan_max_pairs():
+        raise ValueError('Q * nprobe <= %d expected, got %d: cut the queries' % (ivf_plan_max_pairs(), P))
+    if items_bound < 0 or items_bound > ivf_scan_max_items():
+        raise ValueError('0 <= items_bound <= %d expected, got %d: cut the queries' % (ivf_scan_max_items(), items_bound))
+    list_off, probe = list_off.contiguous(), probe.contiguous()
+    # one allocation: col_off, pair_q, pair_col [P], pair_off, item_off [nlist + 1], counts [2]
+    col_off, pair_q, pair_col, pair_off, item_off, counts = torch.empty(
+        3 * P + 2 * (nlist + 1) + 2, dtype=torch.int32, device=probe.device).split([P, P, P, nlist + 1, nlist + 1, 2])
+    if Q:
+        call('dir_ivf_plan', ptr(probe), Q, nprobe, ptr(list_off), nlist, ptr(col_off), ptr(pair_off), ptr(pair_q),
+             ptr(pair_col), ptr(item_off), ptr(counts), stream_ptr())
+    else:
+        pair_off.zero_(), item_off.zero_(), counts.zero_()
+    return col_off.view(Q, nprobe), (pair_off, pair_q, pair_col, item_off, items_bound, None), counts
+
+
 def ivf_scan(qcodes, qscales, codes, scales, ids, list_off, probe, col_off, D, width=None, out=None, tables=None):
     """The quantised scores of every query against the rows of the lists it probes (dir_ivf_scan_i8) -> (scores [Q,width]
     fp32, out_ids [Q,width] int32), both CUDA.  qcodes [Q,ldc] / qscales [Q] as quantize_rows gives them (zero padding
@@ -863,7 +913,8 @@ def ivf_scan(qcodes, qscales, codes, scales, ids, list_off, probe, col_off, D, w
     width keep what they hold.
     The inverted probe table the kernel walks (pairs grouped by list, workgroups per list) comes from ivf_probe_tables,
     which synchronises with the host ONCE, to learn the grid and the width; tables: its result for these list_off, probe
-    and col_off, when the caller has it already (the call then does not synchronise)."""
+    and col_off, when the caller has it already (the call then does not synchronise), or ivf_plan's tables for this
+    list_off and probe with its col_off and an explicit width (no synchronisation anywhere)."""
     _on_device(qcodes, qscales, codes, scales, ids, list_off, probe, col_off, *(out or ()))
     if qcodes.dtype != torch.int8 or codes.dtype != torch.int8 or qcodes.dim() != 2 or codes.dim() != 2:
         raise TypeError('int8 codes [rows, ldc] expected')
@@ -881,6 +932,8 @@ def ivf_scan(qcodes, qscales, codes, scales, ids, list_off, probe, col_off, D, w
     codes, ldb = _i8_codes(codes, ldc)
     qscales, scales, ids, list_off = qscales.contiguous(), scales.contiguous(), ids.contiguous(), list_off.contiguous()
     pair_off, pair_q, pair_col, item_off, items, reach = tables if tables is not None else ivf_probe_tables(list_off, probe, col_off)
+    if width is None and reach is None:
+        raise ValueError('tables of ivf_plan need an explicit width: their reach stays on the device')
     width = reach if width is None else int(width)
     scores, out_ids, lds = _scan_out(out, Q, width, codes.device)
     if Q and width:
@@ -925,6 +978,8 @@ def ivf_scan_fp4(qcodes, qexps, qscales, codes, exps, scales, ids, list_off, pro
     exps, ldbe = _i8_codes(exps, lde, align=8)
     qscales, scales, ids, list_off = qscales.contiguous(), scales.contiguous(), ids.contiguous(), list_off.contiguous()
     pair_off, pair_q, pair_col, item_off, items, reach = tables if tables is not None else ivf_probe_tables(list_off, probe, col_off)
+    if width is None and reach is None:
+        raise ValueError('tables of ivf_plan need an explicit width: their reach stays on the device')
     width = reach if width is None else int(width)
     scores, out_ids, lds = _scan_out(out, Q, width, codes.device)
     if Q and width:

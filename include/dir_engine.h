@@ -660,14 +660,37 @@ int dir_similarity_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int
  *   so; both operands are read in 16-byte pieces and what the database holds there does not matter).  The slots of one
  *   query must not overlap.  Otherwise sim_i8_kernel's pipeline: LDS-DMA loaders (the query rows of a group gathered by
  *   a per-lane offset), v_mfma_i32_32x32x32_i8, K slabs of 128, four stages.
+ *   `items` may be ANY upper bound of item_off[nlist] (dir_ivf_scan_fp4 too): a workgroup at or past item_off[nlist] finds
+ *   no rows of the last list left for it and returns before it loads or stores anything, so a caller that knows a bound
+ *   on the host (dir_ivf_plan's callers) need not read the count back.
  * Both: a negative count, D < 1, a pitch below its minimum or a null pointer fail with DIR_ERR_INVALID before anything is
- *   launched; S == 0, Q == 0 or width == 0 is DIR_OK and launches nothing. */
+ *   launched; S == 0, Q == 0 or width == 0 is DIR_OK and launches nothing.
+ * dir_ivf_plan: the tables of both scans by list from probe [Q][nprobe] int32 and list_off [nlist + 1] int32, in ONE kernel
+ *   launch on `stream` (ivf_plan.hip; one workgroup, the sort in LDS) and without a word coming back to the host; numpy
+ *   restatement: tests/ivf_plan_ref.py.  len_l = list_off[l + 1] - list_off[l]; a slot whose list is outside [0, nlist) is
+ *   EMPTY: length 0.  With P = Q * nprobe and the flat index f = q * nprobe + p of slot (q, p):
+ *     col_off [Q][nprobe]   col_off[q][p] = the sum of the lengths of the slots (q, p') with p' < p: the lists of a query
+ *                           side by side in probe order;
+ *     pair_q, pair_col [P]  the slots in the order: by list ascending, inside a list by f ascending, the empty slots last
+ *                           (by f ascending) - the order of a stable sort by list, whatever the launch; place i holds
+ *                           q and col_off[q][p] of its slot;
+ *     pair_off [nlist + 1]  the CSR of that order by list; pair_off[nlist] = the slots that are not empty;
+ *     item_off [nlist + 1]  the CSR of ceil(len_l / 256) * ceil(pairs_l / 32), pairs_l = pair_off[l + 1] - pair_off[l];
+ *     counts [2]            (item_off[nlist], reach), reach = the largest col_off[q][p] + the length of slot (q, p), 0
+ *                           without a slot: for tests and measurements; a search does not read it.
+ *   All int32; list_off ascending and item_off[nlist] and reach within int32 are the caller's duty.  These are, entry for
+ *   entry, the tables dirtorch_amd/ops.py ivf_probe_tables makes.  nlist <= 65535 and P <= dir_ivf_plan_max_pairs()
+ *   (host-only; 16384), else DIR_ERR_INVALID before anything is launched, as for a negative count, Q > 0 without a list
+ *   or a null pointer; Q == 0 is DIR_OK and launches nothing. */
 int dir_segment_sums(const float* X, int ldx, int N, int D, const int* order, const int* seg_off, int S, float* sums,
                      int lds, void* stream);
 int dir_ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, const int8_t* bcodes, int ldb,
                     const float* bscales, const int* ids, int N, int D, const int* list_off, int nlist, const int* pair_off,
                     const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
                     int lds, int width, void* stream);
+int dir_ivf_plan_max_pairs(void);
+int dir_ivf_plan(const int* probe, int Q, int nprobe, const int* list_off, int nlist, int* col_off, int* pair_off, int* pair_q,
+                 int* pair_col, int* item_off, int* counts, void* stream);
 /* The inverted file over fp4 codes (ivf_fp4.hip; dirtorch_amd/index.py IVFFp4Index; numpy restatement: tests/ivffp4_ref.py):
  * the inverted file's lists with the fp4 index's rows in them, 1 <= D <= dir_index_fp4_max_dim() = 7281.
  * Coarse side: the inverted-file int8 index's, unchanged - centroids [nlist][D] fp32 with their int8 codes and scales;
