@@ -962,6 +962,46 @@ int dir_similarity_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int
     DIR_CATCH
 }
 
+int dir_index_bin_max_dim(void) { return index_bin_max_dim(); }
+
+static int bin_check_dim(const char* who, int D) {
+    if (D < 1) return fail(DIR_ERR_INVALID, std::string(who) + ": D < 1");
+    if (D > index_bin_max_dim()) return fail(DIR_ERR_INVALID, std::string(who) + ": D exceeds dir_index_bin_max_dim()");
+    return DIR_OK;
+}
+
+static int bin_width(int D) { return ceil_div(D, 128) * 16; }   // bytes of a row of bits: D rounded up to 128, divided by 8
+
+int dir_quantize_rows_bin(const float* X, int ldx, int N, int D, uint8_t* bits, int ldb, float* scales, void* stream) {
+    DIR_TRY
+    if (N < 0) return fail(DIR_ERR_INVALID, "quantize_rows_bin: negative size");
+    DIR_CHECK(bin_check_dim("quantize_rows_bin", D));
+    if (ldx < D) return fail(DIR_ERR_INVALID, "quantize_rows_bin: ldx < D");
+    if (ldb < bin_width(D)) return fail(DIR_ERR_INVALID, "quantize_rows_bin: ldb < D rounded up to a multiple of 128, divided by 8");
+    if (N == 0) return DIR_OK;
+    if (!X || !bits || !scales) return fail(DIR_ERR_INVALID, "quantize_rows_bin: null pointer");
+    if ((ldb & 3) != 0 || ((uintptr_t)bits & 3) != 0)
+        return fail(DIR_ERR_INVALID, "quantize_rows_bin: ldb % 4 == 0 and 4-byte aligned bits");
+    return quantize_rows_bin(X, ldx, N, D, bits, ldb, scales, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_similarity_bin(const int8_t* qcodes, int ldq, const float* qscales, int Q, const uint8_t* bits, int ldb,
+                       const float* bscales, int N, int D, float* scores, int lds, void* stream) {
+    DIR_TRY
+    if (Q < 0 || N < 0) return fail(DIR_ERR_INVALID, "similarity_bin: negative size");
+    DIR_CHECK(bin_check_dim("similarity_bin", D));
+    if (ldq < D) return fail(DIR_ERR_INVALID, "similarity_bin: ldq < D");
+    if (ldb < bin_width(D)) return fail(DIR_ERR_INVALID, "similarity_bin: ldb < D rounded up to a multiple of 128, divided by 8");
+    if (lds < N) return fail(DIR_ERR_INVALID, "similarity_bin: lds < N");
+    if (Q == 0 || N == 0) return DIR_OK;
+    if (!qcodes || !qscales || !bits || !bscales || !scores) return fail(DIR_ERR_INVALID, "similarity_bin: null pointer");
+    if (!similarity_bin_admissible(bits, ldb))
+        return fail(DIR_ERR_INVALID, "similarity_bin: ldb % 16 == 0, ldb < 2^23 and 16-byte aligned bits");
+    return similarity_bin(qcodes, ldq, qscales, Q, bits, ldb, bscales, N, D, scores, lds, (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_gather_scores(const float* queries, int ldq, int Q, const float* database, int ldb, int N, int D, const int* cand,
                       int ldcand, int R, float* scores, int ldsc, void* stream) {
     DIR_TRY

@@ -122,6 +122,12 @@ __global__ void __launch_bounds__(256) code_image_kernel(const int8_t* __restric
     }
 }
 
+// the image of Q rows as qblocks blocks of T slabs (index_bin.hip streams the same image)
+hipError_t code_image(const int8_t* qcodes, int ldq, int Q, int D, int8_t* img, int T, int qblocks, hipStream_t stream) {
+    hipLaunchKernelGGL(code_image_kernel, dim3(T, qblocks), dim3(256), 0, stream, qcodes, ldq, Q, D, img);
+    return hipGetLastError();
+}
+
 __global__ void __launch_bounds__(768) sim_i8_kernel(const int8_t* __restrict__ P, int ldp, int NP, int Kp,
                                                     const int8_t* __restrict__ img, const float* __restrict__ qscales,
                                                     const float* __restrict__ bscales, float* __restrict__ out, int ldo,
@@ -184,8 +190,7 @@ int similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, co
         (void)hipGetLastError();
         return fail(DIR_ERR_NOMEM, "similarity_i8: no stream-ordered scratch for the query image");
     }
-    hipLaunchKernelGGL(code_image_kernel, dim3(T, qblocks), dim3(256), 0, stream, qcodes, ldq, Q, D, img);
-    hipError_t e = hipGetLastError();
+    hipError_t e = code_image(qcodes, ldq, Q, D, img, T, qblocks, stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(sim_i8_kernel, dim3(ceil_div(N, kStripRows), qblocks), dim3(768), kI8Lds, stream, bcodes, ldb, N, Kp,
                            (const int8_t*)img, qscales, bscales, scores, lds, Q, T);

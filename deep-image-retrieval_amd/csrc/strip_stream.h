@@ -1,5 +1,5 @@
-// strip_stream.h — the row-strip LDS-DMA pipeline of the scan kernels (sim_split.hip, index_i8.hip, index_fp4.hip, ivf.hip,
-// ivf_fp4.hip), once.
+// strip_stream.h — the row-strip LDS-DMA pipeline of the scan kernels (sim_split.hip, index_i8.hip, index_fp4.hip,
+// index_bin.hip, ivf.hip, ivf_fp4.hip), once.
 //
 // One workgroup per 256 database rows.  Eight consumer waves own a 32-row strip each and multiply it against the query
 // rows of the stage; four loader waves (8 .. 11) only issue LDS-DMA and wait for it.  A stage is 32 KB of database (256
@@ -253,8 +253,8 @@ static constexpr int kFp4SlabK = 2 * kStripRow;    // 256 k in a stage row
 __host__ __device__ inline int fp4_slabs(int D) { return (pad64(D) + kFp4SlabK - 1) / kFp4SlabK; }
 
 // The database side of a loader wave: StripLoader's pieces with a cut by chunk.  Kb (bytes of codes in a row, a multiple
-// of 32) leaves 2, 4, 6 or 8 chunks in the last slab; as the scalar offset takes no part in the range check, a lane whose
-// chunk lies past Kb asks for an address that is out of range by itself.
+// of 32; of 16 for rows of bits) leaves 2, 4, 6 or 8 (bits: 1 .. 8) chunks in the last slab; as the scalar offset takes no
+// part in the range check, a lane whose chunk lies past Kb asks for an address that is out of range by itself.
 struct Fp4Loader {
     uint32_t pvoff[8];
     uint32_t chunks = 0;     // 3 bits per piece: this lane's chunk of piece i
@@ -268,11 +268,14 @@ struct Fp4Loader {
             chunks |= (uint32_t)strip_piece_chunk(lw * 8 + i, lane) << (3 * i);
         }
     }
+    // piece i (a constant once unrolled) of slab u, of which the chunks below lim exist
+    __device__ __forceinline__ void piece(__amdgpu_buffer_rsrc_t rsrc, char* stage, int u, int i, uint32_t lim) const {
+        dma16(rsrc, stage + (lw * 8 + i) * kStripPiece, ((chunks >> (3 * i)) & 7u) >= lim ? kOOB : pvoff[i], u * kStripRow);
+    }
     __device__ __forceinline__ void issue(__amdgpu_buffer_rsrc_t rsrc, char* stage, int u) const {
         const uint32_t lim = u == last ? (uint32_t)keep : 8u;
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
-            dma16(rsrc, stage + (lw * 8 + i) * kStripPiece, ((chunks >> (3 * i)) & 7u) >= lim ? kOOB : pvoff[i], u * kStripRow);
+        for (int i = 0; i < 8; ++i) piece(rsrc, stage, u, i, lim);
     }
 };
 
@@ -321,6 +324,42 @@ __device__ __forceinline__ void fp4_slab_mma(const StripLane& L, const char* sta
     fp4_step<1, NB>(L, stage, aexp, bexp, acc);
     fp4_step<2, NB>(L, stage, aexp, bexp, acc);
     fp4_step<3, NB>(L, stage, aexp, bexp, acc);
+}
+
+// ---- sign bits ---------------------------------------------------------------------------------------------------------
+// A 128-byte stage row of bits is 1024 k, eight times what a stage row of int8 query codes holds, so the two operands ride
+// in two rings: the database ring keeps the 32 KB slabs above (Fp4Loader's pieces and cut by chunk: a row of bits is a
+// multiple of 16 bytes, 1 .. 8 chunks in the last slab), the query ring holds index_i8.hip's 12 KB images of 128 k, eight
+// of them to a database slab.  Sub-slab s of the walk is chunk s & 7 of slab s >> 3 on the database side.
+static constexpr int kBinSub = kQB * kStripRow;        // 12288: the query image of 128 k
+static constexpr int kBinDbStages = 3, kBinQStages = 4;
+static constexpr int kBinQOff = kBinDbStages * kStripSlab;
+static constexpr int kBinLds = kBinQOff + kBinQStages * kBinSub;    // 147456 of 163840
+
+// 16 bits -> 16 code bytes of 0 / 1: bit 4 d + e becomes byte e of dword d, the k order of the query bytes.  The four
+// copies of a nibble at shifts 0, 7, 14, 21 do not overlap, and bits 0, 8, 16, 24 of their sum are its bits 0 .. 3.
+__device__ __forceinline__ i32x4_t bin_widen(uint32_t h) {
+    i32x4_t b;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) b[d] = (int)((((h >> (4 * d)) & 0xfu) * 0x00204081u) & 0x01010101u);
+    return b;
+}
+
+// One sub-slab: the lane's 16-byte chunk c of its row in the database slab `db` (128 bits, k = 128 s + 0 .. 127) against
+// the query image `q` of the same k.  Step m takes the 16 bits of k = 32 m + 16 lhi + 0 .. 15, where the query operand is
+// chunk 2 m + lhi of the query row, as in code_slab_mma.
+template <int NB>
+__device__ __forceinline__ void bin_sub_mma(const StripLane& L, const char* db, int c, const char* q, i32x16_t (&acc)[NB]) {
+    const u32x4_t w = *(const u32x4_t*)(db + L.b(c));
+    const int aoff = L.lrow * kStripRow, sh = 16 * L.lhi;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const i32x4_t b = bin_widen(w[m] >> sh);
+        const int ch = L.chunk(m * 2 + L.lhi);
+#pragma unroll
+        for (int j = 0; j < NB; ++j)
+            acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(*(const i32x4_t*)(q + aoff + j * 4096 + ch), b, acc[j], 0, 0, 0);
+    }
 }
 
 }  // namespace dir

@@ -142,6 +142,10 @@ SIGNATURES = {
     'dir_quantize_rows_fp4': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'dir_similarity_fp4': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                    c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'dir_index_bin_max_dim': (c_int, []),
+    'dir_quantize_rows_bin': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    'dir_similarity_bin': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                                   c_int, c_void_p]),
     'dir_gather_scores': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int,
                                   c_void_p, c_int, c_void_p]),
     'dir_segment_sums': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),

@@ -19,6 +19,15 @@ The fp4 index halves the row again - 4-bit block-scaled codes (D <= ops.index_fp
 Every partial sum of one of its scores is exact in fp32 (include/dir_engine.h), so its lists are those of tests/fp4_ref.py bit
 for bit and as independent of the cut of the work as Int8Index's.
 
+The binary index keeps one sign bit per value and one fp32 scale per row - 260 bytes a row of 2048, a quarter of the fp4 row -
+and scores int8-coded queries against them on the int8 matrix cores:
+
+    index = BinaryIndex(D)
+    index.add(bdescs)
+    idx, vals = index.search(qdescs, 10, rerank=1280, source=bdescs)   # its raw lists are coarser still: use a long shortlist
+
+Its sum is an exact int32, so its lists are those of tests/bin_ref.py bit for bit and as independent of the cut of the work.
+
 The inverted file reads only the lists a query falls into instead of the whole database:
 
     index = IVFInt8Index(D, nlist=1024)
@@ -389,6 +398,61 @@ class Fp4Index(_CodedIndex):
         f = _read_npz(path)
         index = cls(int(f['D']))
         index._load_fp4(path, f)
+        return index
+
+
+class BinaryIndex(_CodedIndex):
+    """The binary index (include/dir_engine.h gives the definition; numpy restatement: tests/bin_ref.py): one sign bit
+    per value and one fp32 scale per row, a quarter of Fp4Index's bytes.  codes [N, ldb] uint8 (ldb = ops.bin_width(D),
+    bit k & 7 of byte k >> 3, padding zero) and scales [N] fp32, both CUDA.  The queries are coded as Int8Index codes
+    them, and a score is ((float)t * qscale) * scale with t an exact int32, so the lists do not depend on how the scan
+    or the adds were cut.  Its raw lists are coarse: pair it with rerank."""
+
+    def __init__(self, D):
+        D = int(D)
+        if D < 1 or D > ops.index_bin_max_dim():
+            raise ValueError('1 <= D <= %d expected, got %d' % (ops.index_bin_max_dim(), D))
+        self.D = D
+        self.codes = torch.empty(0, ops.bin_width(D), dtype=torch.uint8, device='cuda')
+        self.scales = torch.empty(0, dtype=torch.float32, device='cuda')
+
+    def nbytes(self):
+        """the bytes the database rows take on the device: bits (rows padded to 128 bits) and scales"""
+        return sum(int(t.numel()) * t.element_size() for t in (self.codes, self.scales))
+
+    def add(self, descs):
+        """Int8Index.add's contract: the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap), coded
+        in chunks of ADD_CHUNK_BYTES."""
+        self._check_rows(descs)
+        if int(descs.shape[0]):
+            self.codes, self.scales = _appended([self.codes, self.scales], descs, self.D, ops.quantize_rows_bin)
+        return self
+
+    def search(self, qdescs, k, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20, db_rows=None):
+        """Int8Index.search's contract with the sign-bit scores in place of the int8 ones: (idx [Q,k] int32, vals [Q,k]
+        float32); rerank = 0: ranked by the quantised scores; rerank = R: the R best are re-scored against `source` in
+        fp32."""
+        def scan(q, keep):
+            qc, qs = ops.quantize_rows(q)
+
+            def scorer(r0, r1):
+                return lambda b0, b1: ops.similarity_bin(qc[r0:r1], qs[r0:r1], self.codes[b0:b1], self.scales[b0:b1], self.D)
+            return self._scan_blocks(q.shape[0], keep, same_set, scratch_bytes, db_rows, scorer)
+        return self._search(qdescs, k, rerank, source, same_set, scratch_bytes, scan)
+
+    def save(self, path):
+        """One .npz: `bits` [N, ceil(D / 8)] uint8 (without the padding), `scales` [N] float32, `D`."""
+        np.savez(path, D=np.int64(self.D), bits=self.codes[:, :(self.D + 7) // 8].cpu().numpy(),
+                 scales=self.scales.cpu().numpy())
+
+    @classmethod
+    def load(cls, path):
+        f = _read_npz(path)
+        index = cls(int(f['D']))
+        index.codes = _padded_codes(path, f['bits'], (index.D + 7) // 8, np.uint8, 16)
+        if f['scales'].shape != (len(index),):
+            raise ValueError('%s: scales [N] expected for bits [N, ...]' % path)
+        index.scales = torch.from_numpy(f['scales'].astype(np.float32)).cuda()
         return index
 
 

@@ -776,6 +776,69 @@ def similarity_fp4(qcodes, qexps, qscales, bcodes, bexps, bscales, D, out=None):
     return out[:, :N]
 
 
+# ---- the binary descriptor index (csrc/index_bin.hip) -------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def index_bin_max_dim():
+    """The widest row the binary index takes (dir_index_bin_max_dim; host-only)."""
+    return int(_lib.load().dir_index_bin_max_dim())
+
+
+def bin_width(D):
+    """bytes of a row of bits as quantize_rows_bin stores it: D rounded up to 128, divided by 8 (a multiple of 16)"""
+    return (D + 127) // 128 * 16
+
+
+def quantize_rows_bin(X):
+    """fp32 rows -> (bits uint8 [N, ldb], scales fp32 [N]), both CUDA (dir_quantize_rows_bin; include/dir_engine.h gives
+    the definition): bit k & 7 of byte k >> 3 is set where x_k has a clear sign bit, scale = sumsq / sumabs; ldb =
+    bin_width(D), the padding bits zero.  X [N,D] fp32 CUDA with unit column stride and any row pitch."""
+    _on_device(X)
+    if X.dtype != torch.float32 or X.dim() != 2:
+        raise TypeError('float32 rows [N,D] expected')
+    N, D = X.shape
+    if D < 1 or D > index_bin_max_dim():
+        raise ValueError('1 <= D <= %d expected, got %d' % (index_bin_max_dim(), D))
+    X, ldx = _rows_pitch(X, D)
+    ldb = bin_width(D)
+    bits = torch.empty(N, ldb, dtype=torch.uint8, device=X.device)
+    scales = torch.empty(N, dtype=torch.float32, device=X.device)
+    if N:
+        call('dir_quantize_rows_bin', ptr(X), ldx, N, D, ptr(bits), ldb, ptr(scales), stream_ptr())
+    return bits, scales
+
+
+def similarity_bin(qcodes, qscales, bits, bscales, D, out=None):
+    """scores [Q,N] fp32 CUDA of int8-coded queries against sign-bit rows (dir_similarity_bin): ((float)t * qscales[q]) *
+    bscales[n] with t the exact int32 sum of +-qcodes[q][k] - one defined fp32 number per pair.  qcodes [Q,ldc] int8 and
+    qscales [Q] fp32 as quantize_rows gives them, bits [N,ldb] uint8 and bscales [N] fp32 as quantize_rows_bin gives them
+    (row slices included), D the width they were made from.  out: a [Q, >= N] fp32 CUDA tensor with unit column stride to
+    write into (its first N columns are returned)."""
+    _on_device(qcodes, qscales, bits, bscales, out)
+    if qcodes.dtype != torch.int8 or qcodes.dim() != 2:
+        raise TypeError('int8 query codes [Q, ldc] expected')
+    if bits.dtype != torch.uint8 or bits.dim() != 2:
+        raise TypeError('uint8 bits [N, ldb] expected')
+    if qscales.dtype != torch.float32 or bscales.dtype != torch.float32:
+        raise TypeError('float32 scales expected')
+    D = int(D)
+    Q, N = qcodes.shape[0], bits.shape[0]
+    if D < 1 or D > index_bin_max_dim():
+        raise ValueError('1 <= D <= %d expected, got %d' % (index_bin_max_dim(), D))
+    ldb = bin_width(D)
+    if qcodes.shape[1] < D or bits.shape[1] < ldb:
+        raise ValueError('query codes of %d and bits of %d columns at least expected for D = %d' % (D, ldb, D))
+    if qscales.dim() != 1 or bscales.dim() != 1 or qscales.numel() != Q or bscales.numel() != N:
+        raise ValueError('scales [Q] and [N] expected for codes of Q and bits of N rows')
+    qcodes, ldq = _rows_pitch(qcodes, D)
+    bits, ldb = _i8_codes(bits, ldb)
+    qscales, bscales = qscales.contiguous(), bscales.contiguous()
+    out, lds = _score_out(out, Q, N, bits.device)
+    if Q and N:
+        call('dir_similarity_bin', ptr(qcodes), ldq, ptr(qscales), Q, ptr(bits), ldb, ptr(bscales), N, D, ptr(out), lds,
+             stream_ptr())
+    return out[:, :N]
+
+
 def gather_scores(queries, database, cand):
     """scores [Q,R] fp32 CUDA, scores[q][r] = <queries[q], database[cand[q][r]]> (dir_gather_scores): the re-score of a
     shortlist.  queries [Q,D], database [N,D] fp32 CUDA, cand [Q,R] int32 CUDA with entries in [-1, N) - the caller's

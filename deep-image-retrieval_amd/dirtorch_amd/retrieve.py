@@ -14,6 +14,9 @@ ranked by the quantised scores; --rerank R also re-scores the R best of every qu
 the --topk best of those, with their fp32 scores.
 --index fp4: an index.Fp4Index instead (4-bit block-scaled codes, half of int8's bytes; descriptors of at most 7281 values);
 the quantised scores are coarser than int8's, so pair it with --rerank (4 x --topk gave the fp32 lists in our measurements).
+--index bin: an index.BinaryIndex instead (one sign bit per value and a scale per image, a quarter of fp4's bytes); its raw
+lists are the coarsest of the three, so pair it with a long --rerank (on the 3000-image test set the fp32 top 10 needed a
+shortlist of 1108, the top 100 one of 1978).
 --index ivf --nlist L --nprobe P: an index.IVFInt8Index trained on the database descriptors themselves (L k-means lists);
 every query scans its P best lists only, --rerank as above.  With P = L the lists are those of --index int8.
 --index ivffp4 --nlist L --nprobe P: an index.IVFFp4Index - IVFInt8Index's lists (the same training, a row in the same
@@ -47,7 +50,8 @@ from . import distributed as ddist
 from .utils.convenient import mkdir
 
 # --index kind -> (its class in dirtorch_amd.index, the flags its constructor takes after the width, whether it is trained)
-INDEX_KINDS = {'int8': ('Int8Index', (), False), 'fp4': ('Fp4Index', (), False), 'ivf': ('IVFInt8Index', ('nlist',), True),
+INDEX_KINDS = {'int8': ('Int8Index', (), False), 'fp4': ('Fp4Index', (), False), 'bin': ('BinaryIndex', (), False),
+               'ivf': ('IVFInt8Index', ('nlist',), True),
                'ivffp4': ('IVFFp4Index', ('nlist',), True), 'pq': ('PQIndex', ('pq_m',), True), 'ivfpq': ('IVFPQIndex', ('nlist', 'pq_m'), True)}
 
 

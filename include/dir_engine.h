@@ -132,6 +132,8 @@ const char* dir_version(void);
  *   dir_gather_scores        none: several launches
  *   dir_quantize_rows_fp4    N * 64 <= L (N rounded up to 4)
  *   dir_similarity_fp4       N * 3 <= L (N rounded up to 256), Q <= 65535 * 96
+ *   dir_quantize_rows_bin    N * 64 <= L (N rounded up to 4)
+ *   dir_similarity_bin       N * 3 <= L (N rounded up to 256), Q <= 65535 * 96
  *   dir_segment_sums         S <= 65535
  *   dir_ivf_scan_i8          Q * width <= L, items * 768 <= L (refused, not cut: Q * width of 2^32 means 32 GiB of score and id
  *                            rows for one chunk; index.py's chunks are scratch_bytes / 8 slots, 2^25 by default)
@@ -616,6 +618,40 @@ int dir_quantize_rows_fp4(const float* X, int ldx, int N, int D, uint8_t* codes,
 int dir_similarity_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe, const float* qscales, int Q,
                        const uint8_t* bcodes, int ldb, const uint8_t* bexps, int ldbe, const float* bscales, int N, int D,
                        float* scores, int lds, void* stream);
+/* The binary descriptor index (index_bin.hip; dirtorch_amd/index.py BinaryIndex; numpy restatement: tests/bin_ref.py): one
+ * sign bit per value and one fp32 scale per row - at D = 2048 a row is 260 bytes, a quarter of the fp4 row - scanned on the
+ * int8 matrix cores (v_mfma_i32_32x32x32_i8) against int8 query codes.  It stands beside the int8 and fp4 indexes and
+ * replaces nothing in the reference, which keeps fp32 descriptors.
+ * A row x of D fp32 values, 1 <= D <= dir_index_bin_max_dim() = 131072 (= dir_index_i8_max_dim(): 127 * D < 2^24, so the
+ * int32 sum of a score converts to fp32 exactly), is stored as
+ *     bits   [ldb] bytes, ldb >= D rounded up to 128, divided by 8 (a multiple of 16) - that many bytes are written: bit
+ *            k & 7 of byte k >> 3 is 1 when the sign bit of x_k is clear, for k < D, and 0 for k >= D (numpy:
+ *            packbits(~signbit(x), bitorder='little')); -0.0 codes as 0;
+ *     scale  = sumsq / sumabs, one fp32 division, of sumabs = sum |x_k| and sumsq = sum (x_k * x_k) - each product rounded,
+ *            then added, no fma - both as chains of single fp32 additions in THIS order: 64 chains, chain l over
+ *            k = 256 j + 4 l + e for j = 0, 1, .. and e = 0 .. 3 ascending (k >= D adds +0), each from +0; then six
+ *            butterfly steps d = 32, 16, 8, 4, 2, 1, every chain l replaced by chain l + chain (l ^ d).  The order does not
+ *            depend on N, the pitch, the alignment or the launch.
+ *   a row that holds a NaN or an infinity has all-zero bits and scale NaN (all its scores are NaN: dir_topk ranks them last);
+ *   a row whose sumabs is zero, or whose sumabs or sumsq overflows to infinity, has all-zero bits and scale +0.
+ * The query side is dir_quantize_rows_i8's, unchanged (qcodes, qscales).
+ * dir_quantize_rows_bin: X [N][ldx] fp32 (ldx >= D, any pitch) -> bits [N][ldb] (4-byte aligned, ldb % 4 == 0) and scales
+ *   [N].  One wave per row; a row of up to 2048 values is read once, a wider one twice; whole dwords of bits are stored.
+ * dir_similarity_bin: scores[q][n] = ((float)t * qscales[q]) * bscales[n], t = sum_{k < D} qcodes[q][k] * s_k with s_k = +1
+ *   where bit k of row n is set and -1 where it is clear: an exact int32 of at most 127 * D < 2^24, the conversion exact,
+ *   the two fp32 multiplies in that order (dir_similarity_i8's form) - ONE defined fp32 number, independent of tiling, K
+ *   order, chunking and sharding.  The kernel computes t = 2 * sum_k qc_k b_k - sum_{k < D} qc_k with b_k the bit.
+ *   qcodes [Q][ldq] int8 (ldq >= D: read up to D only), bits [N][ldb] (16-byte aligned, ldb % 16 == 0, ldb >= D rounded up
+ *   to 128, divided by 8: that many bytes of every row are read; the bits past D meet zero query codes and do not
+ *   matter), scores [Q][lds] fp32, lds >= N.  256 database rows per workgroup, brought in once per query block by LDS-DMA
+ *   in 128-byte pieces of a row (1024 k); the query block (96 rows) streams beside them as dir_similarity_i8's image, in
+ *   sub-slabs of 128 k.  The query image and the query sums live in stream-ordered scratch.
+ * Both: a negative count, D < 1 or above the max dim, a pitch below its minimum, lds < N or a null pointer fail with
+ * DIR_ERR_INVALID before anything is launched; Q == 0 or N == 0 is DIR_OK and launches nothing. */
+int dir_index_bin_max_dim(void);
+int dir_quantize_rows_bin(const float* X, int ldx, int N, int D, uint8_t* bits, int ldb, float* scales, void* stream);
+int dir_similarity_bin(const int8_t* qcodes, int ldq, const float* qscales, int Q, const uint8_t* bits, int ldb,
+                       const float* bscales, int N, int D, float* scores, int lds, void* stream);
 /* The inverted-file int8 index (ivf.hip; dirtorch_amd/index.py IVFInt8Index; numpy restatement: tests/ivf_ref.py).
  * An index of width D with nlist lists holds
  *     centroids [nlist][D] fp32 with their codes and scales (dir_quantize_rows_i8),

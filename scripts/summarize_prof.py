@@ -197,6 +197,9 @@ def bench_kernel_name(k):
             # the fp4 index: quantiser, query image and scan (csrc/index_fp4.hip; no timed bench.py step launches them)
             'quantize_rows_fp4_kernel': 'l2norm_rows_kernel', 'fp4_image_kernel': 'split_queries_kernel',
             'sim_fp4_kernel': 'sim_split_lc_kernel',
+            # the binary index: quantiser, query sums and scan (csrc/index_bin.hip; no timed bench.py step launches them)
+            'quantize_rows_bin_kernel': 'l2norm_rows_kernel', 'code_sums_kernel': 'split_queries_kernel',
+            'sim_bin_kernel': 'sim_split_lc_kernel',
             # the inverted file: the sums of a k-means step, the id pre-fill and the scan of the probed lists (csrc/ivf.hip; no timed bench.py step launches them)
             'segment_sums_kernel': 'expand_rows_kernel', 'fill_ids_kernel': 'fill_noise_kernel',
             'ivf_scan_i8_kernel': 'sim_split_lc_kernel',
