@@ -1079,6 +1079,41 @@ int dir_ivf_scan_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int l
     DIR_CATCH
 }
 
+int dir_code_sums(const int8_t* qcodes, int ldq, int Q, int D, int* qsums, void* stream) {
+    DIR_TRY
+    if (Q < 0) return fail(DIR_ERR_INVALID, "code_sums: negative size");
+    DIR_CHECK(bin_check_dim("code_sums", D));
+    if (ldq < D) return fail(DIR_ERR_INVALID, "code_sums: ldq < D");
+    if (Q == 0) return DIR_OK;
+    if (!qcodes || !qsums) return fail(DIR_ERR_INVALID, "code_sums: null pointer");
+    return code_sums(qcodes, ldq, Q, D, qsums, (hipStream_t)stream);
+    DIR_CATCH
+}
+
+int dir_ivf_scan_bin(const int8_t* qcodes, int ldq, const float* qscales, const int* qsums, int Q, const uint8_t* bits, int ldb,
+                     const float* bscales, const int* ids, int N, int D, const int* list_off, int nlist, const int* pair_off,
+                     const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
+                     int lds, int width, void* stream) {
+    DIR_TRY
+    if (Q < 0 || N < 0 || nlist < 0 || items < 0 || width < 0) return fail(DIR_ERR_INVALID, "ivf_scan_bin: negative size");
+    DIR_CHECK(bin_check_dim("ivf_scan_bin", D));
+    if (ldq < pad64(D)) return fail(DIR_ERR_INVALID, "ivf_scan_bin: ldq < D rounded up to a multiple of 64");
+    if (ldb < bin_width(D)) return fail(DIR_ERR_INVALID, "ivf_scan_bin: ldb < D rounded up to a multiple of 128, divided by 8");
+    if (lds < width) return fail(DIR_ERR_INVALID, "ivf_scan_bin: lds < width");
+    if (Q == 0 || width == 0) return DIR_OK;
+    if (!scores || !out_ids) return fail(DIR_ERR_INVALID, "ivf_scan_bin: null pointer");
+    if (items > 0 && N > 0) {
+        if (nlist < 1) return fail(DIR_ERR_INVALID, "ivf_scan_bin: items without a list");
+        if (!qcodes || !qscales || !qsums || !bits || !bscales || !ids || !list_off || !pair_off || !pair_q || !pair_col || !item_off)
+            return fail(DIR_ERR_INVALID, "ivf_scan_bin: null pointer");
+        if (!ivf_scan_bin_admissible(qcodes, ldq, Q, bits, ldb))
+            return fail(DIR_ERR_INVALID, "ivf_scan_bin: ldq, ldb % 16 == 0, ldb < 2^23, Q * ldq < 2^31 and 16-byte aligned codes and bits");
+    }
+    return ivf_scan_bin(qcodes, ldq, qscales, qsums, Q, bits, ldb, bscales, ids, N, D, list_off, nlist, pair_off, pair_q, pair_col,
+                        item_off, items, scores, out_ids, lds, width, (hipStream_t)stream);
+    DIR_CATCH
+}
+
 int dir_ivf_plan_max_pairs(void) { return ivf_plan_max_pairs(); }
 
 int dir_ivf_plan(const int* probe, int Q, int nprobe, const int* list_off, int nlist, int* col_off, int* pair_off, int* pair_q,

@@ -127,6 +127,17 @@ __global__ void __launch_bounds__(256) code_sums_kernel(const int8_t* __restrict
     if (lane == 0) qsum[q] = s;
 }
 
+// the sums of Q rows for a caller that keeps them (the list scan of ivf_bin.hip takes them as an argument)
+int code_sums(const int8_t* qcodes, int ldq, int Q, int D, int* qsums, hipStream_t stream) {
+    if (Q <= 0) return DIR_OK;
+    const long blocks = ((long)Q + 3) / 4;
+    if (!launch_fits(blocks, 256))
+        return fail(DIR_ERR_INVALID, "code_sums: Q * 64 must stay below 2^32 (one wave per row): cut the rows");
+    hipLaunchKernelGGL(code_sums_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qcodes, ldq, Q, D, Q, qsums);
+    DIR_HIP_CHECK(hipGetLastError());
+    return DIR_OK;
+}
+
 // S sub-slabs of 128 k = the 16-byte chunks of a row of bits; T = ceil(S / 8) database slabs.
 // STREAM: rows wider than two slabs - the database ring turns, one piece per loader and hand-off.
 template <bool STREAM>

@@ -98,6 +98,14 @@ int ivf_scan_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe,
 int ivf_plan_max_pairs();
 int ivf_plan(const int* probe, int Q, int nprobe, const int* list_off, int nlist, int* col_off, int* pair_off, int* pair_q,
              int* pair_col, int* item_off, int* counts, hipStream_t stream);
+// the inverted file over sign-bit rows (ivf_bin.hip): the list-major scan of the probed lists on the int8 matrix cores;
+// code_sums (index_bin.hip): the query sums it takes, the launch of code_sums_kernel
+int code_sums(const int8_t* qcodes, int ldq, int Q, int D, int* qsums, hipStream_t stream);
+bool ivf_scan_bin_admissible(const int8_t* qcodes, int ldq, int Q, const uint8_t* bits, int ldb);
+int ivf_scan_bin(const int8_t* qcodes, int ldq, const float* qscales, const int* qsums, int Q, const uint8_t* bits, int ldb,
+                 const float* bscales, const int* ids, int N, int D, const int* list_off, int nlist, const int* pair_off,
+                 const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
+                 int lds, int width, hipStream_t stream);
 // the product-quantised index (pq.hip): 8-bit codes per sub-space, the tables of a query, the scan that adds their entries
 int pq_max_m();
 int pq_encode(const float* X, int ldx, int N, int D, int M, const float* codebooks, uint8_t* codes, int ldc, hipStream_t stream);

@@ -1,5 +1,5 @@
 // strip_stream.h — the row-strip LDS-DMA pipeline of the scan kernels (sim_split.hip, index_i8.hip, index_fp4.hip,
-// index_bin.hip, ivf.hip, ivf_fp4.hip), once.
+// index_bin.hip, ivf.hip, ivf_fp4.hip, ivf_bin.hip), once.
 //
 // One workgroup per 256 database rows.  Eight consumer waves own a 32-row strip each and multiply it against the query
 // rows of the stage; four loader waves (8 .. 11) only issue LDS-DMA and wait for it.  A stage is 32 KB of database (256

@@ -158,6 +158,10 @@ SIGNATURES = {
     'dir_ivf_plan_max_pairs': (c_int, []),
     'dir_ivf_plan': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p]),
+    'dir_code_sums': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'dir_ivf_scan_bin': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                 c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                 c_int, c_void_p]),
     'dir_pq_max_m': (c_int, []),
     'dir_pq_encode': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     'dir_pq_lut': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

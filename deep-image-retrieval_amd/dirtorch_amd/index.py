@@ -50,6 +50,16 @@ the same list), 1096 bytes a row of 2048 instead of 2056:
 Its scores are Fp4Index's numbers, so with nprobe = nlist it returns Fp4Index's lists bit for bit, and with fewer lists those
 of tests/ivffp4_ref.py.
 
+The inverted file over sign-bit rows keeps BinaryIndex's rows in the same lists, 264 bytes a row of 2048:
+
+    index = IVFBinaryIndex(D, nlist=1024)                    # D <= ops.index_bin_max_dim()
+    index.train(bdescs)                                      # IVFInt8Index.train
+    index.add(bdescs)
+    idx, vals = index.search(qdescs, 10, nprobe=8, rerank=2048, source=bdescs)   # coarse raw lists: use a long shortlist
+
+Its scores are BinaryIndex's numbers, so with nprobe = nlist it returns BinaryIndex's lists bit for bit, and with fewer
+lists those of tests/ivfbin_ref.py.
+
 The product-quantised index keeps M bytes per row instead of D - a row is the numbers of its nearest of 256 centroids in
 each of M sub-spaces - and scores a query through M tables of 256 inner products:
 
@@ -165,6 +175,7 @@ class _CodedIndex:
     """What every index shares: `codes` [N, ldc], one row per database row, CUDA - int8 with ldc = D rounded up to 64 (padding
     zero) and `scales` [N] fp32 for the int8 indexes, which is what the constructor makes, with their half of save and load;
     the fp4 store (_init_fp4: codes, `exps` and scales) with its half of save and load for the two fp4 indexes;
+    the sign-bit store (_init_bin: bits as `codes`, and scales) with its half of save and load for the two binary indexes;
     uint8 with ldc = M rounded up to 4 and scales None for the product-quantised ones, which replace both - what a search
     does around its scan (the argument checks, the fp32 re-rank of a shortlist) and the blocked scan loop."""
 
@@ -315,6 +326,25 @@ class _CodedIndex:
             raise ValueError('%s: scales [N] expected for codes [N, ...]' % path)
         self.scales = torch.from_numpy(f['scales'].astype(np.float32)).cuda()
 
+    def _init_bin(self, D):
+        """the empty sign-bit store in place of the int8 one: codes [0, ops.bin_width(D)] uint8, scales [0] fp32"""
+        D = int(D)
+        if D < 1 or D > ops.index_bin_max_dim():
+            raise ValueError('1 <= D <= %d expected, got %d' % (ops.index_bin_max_dim(), D))
+        self.D = D
+        self.codes = torch.empty(0, ops.bin_width(D), dtype=torch.uint8, device='cuda')
+        self.scales = torch.empty(0, dtype=torch.float32, device='cuda')
+
+    def _save_bin(self):
+        """the sign-bit store's arrays of a .npz: `bits` [N, ceil(D / 8)] uint8 (without the padding), `scales` [N] float32"""
+        return dict(bits=self.codes[:, :(self.D + 7) // 8].cpu().numpy(), scales=self.scales.cpu().numpy())
+
+    def _load_bin(self, path, f):
+        self.codes = _padded_codes(path, f['bits'], (self.D + 7) // 8, np.uint8, 16)
+        if f['scales'].shape != (len(self),):
+            raise ValueError('%s: scales [N] expected for bits [N, ...]' % path)
+        self.scales = torch.from_numpy(f['scales'].astype(np.float32)).cuda()
+
 
 class Int8Index(_CodedIndex):
     """codes [N, ldc] int8 (ldc = D rounded up to 64, padding zero) and scales [N] fp32, both CUDA."""
@@ -409,12 +439,7 @@ class BinaryIndex(_CodedIndex):
     or the adds were cut.  Its raw lists are coarse: pair it with rerank."""
 
     def __init__(self, D):
-        D = int(D)
-        if D < 1 or D > ops.index_bin_max_dim():
-            raise ValueError('1 <= D <= %d expected, got %d' % (ops.index_bin_max_dim(), D))
-        self.D = D
-        self.codes = torch.empty(0, ops.bin_width(D), dtype=torch.uint8, device='cuda')
-        self.scales = torch.empty(0, dtype=torch.float32, device='cuda')
+        self._init_bin(D)
 
     def nbytes(self):
         """the bytes the database rows take on the device: bits (rows padded to 128 bits) and scales"""
@@ -442,17 +467,13 @@ class BinaryIndex(_CodedIndex):
 
     def save(self, path):
         """One .npz: `bits` [N, ceil(D / 8)] uint8 (without the padding), `scales` [N] float32, `D`."""
-        np.savez(path, D=np.int64(self.D), bits=self.codes[:, :(self.D + 7) // 8].cpu().numpy(),
-                 scales=self.scales.cpu().numpy())
+        np.savez(path, D=np.int64(self.D), **self._save_bin())
 
     @classmethod
     def load(cls, path):
         f = _read_npz(path)
         index = cls(int(f['D']))
-        index.codes = _padded_codes(path, f['bits'], (index.D + 7) // 8, np.uint8, 16)
-        if f['scales'].shape != (len(index),):
-            raise ValueError('%s: scales [N] expected for bits [N, ...]' % path)
-        index.scales = torch.from_numpy(f['scales'].astype(np.float32)).cuda()
+        index._load_bin(path, f)
         return index
 
 
@@ -789,6 +810,74 @@ class IVFFp4Index(_InvertedLists, _CodedIndex):
         f = _read_npz(path)
         index = cls(int(f['D']), int(f['nlist']))
         index._load_fp4(path, f)
+        index._load_lists(path, f)
+        return index
+
+
+class IVFBinaryIndex(_InvertedLists, _CodedIndex):
+    """The inverted file over sign-bit rows (include/dir_engine.h gives the definitions; numpy restatement:
+    tests/ivfbin_ref.py).  All CUDA: IVFInt8Index's coarse quantiser (centroids [nlist, D] fp32, `ccodes`, `cscales`:
+    assignment and probing by the int8 score, so a row lands in the list IVFInt8Index puts it in) and the database LIST-MAJOR
+    as BinaryIndex stores a row - codes [N, ops.bin_width(D)] uint8, scales [N] fp32 - with ids [N] int32 and list_off
+    [nlist+1] int32; inside a list the rows are in ascending id.  Its raw lists are coarse: pair it with rerank."""
+
+    def __init__(self, D, nlist):
+        self._init_bin(D)
+        self._init_lists(nlist)
+
+    def nbytes(self):
+        """the bytes the database rows take on the device: bits, scales and ids (centroids not counted)"""
+        return sum(int(t.numel()) * t.element_size() for t in (self.codes, self.scales, self.ids))
+
+    def train(self, x, iters=10, seed=0, max_rows=None):
+        """IVFInt8Index.train: the same sample, the same iterations, the same centroids bit for bit."""
+        self._check_train(x)
+        max_rows = 256 * self.nlist if max_rows is None else int(max_rows)
+        self._lloyd_centroids(_training_rows(x, seed, max_rows, self.nlist, 'nlist = %d' % self.nlist), iters, seed)
+        return self
+
+    def add(self, descs):
+        """IVFInt8Index.add's contract: a chunk of ADD_CHUNK_BYTES is quantised to int8 for its assignment and to sign bits
+        for the store, and the two stores are regrouped by that class's stable integer sort, so what the index holds does
+        not depend on how the rows were cut into calls."""
+        self._check_rows(descs)
+        self._need_trained('add')
+        if int(descs.shape[0]) == 0:
+            return self
+        lists, codes, scales = [], [self.codes], [self.scales]
+        for x in _row_chunks(descs, self.D):
+            lists.append(self._assign(*ops.quantize_rows(x)))
+            c, s = ops.quantize_rows_bin(x)
+            codes.append(c)
+            scales.append(s)
+        self.codes, self.scales = self._regroup(lists, [torch.cat(codes), torch.cat(scales)])
+        return self
+
+    def _scan_lists(self, q, qc, qs, probe, col_off, rows, width, tables):
+        # the int8 codes that probed the lists score their rows too: only their sums are new
+        return ops.ivf_scan_bin(qc[rows], qs[rows], self.codes, self.scales, self.ids, self.list_off, probe, col_off, self.D,
+                                width=None if tables is None else width, tables=tables, qsums=ops.code_sums(qc[rows], self.D))
+
+    def search(self, qdescs, k, nprobe=1, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20, plan=DEFAULT_PLAN):
+        """IVFInt8Index.search's contract with the sign-bit scores in place of the int8 ones: the lists of a query are
+        probed and their rows scored by the same int8 codes; a query whose lists hold fewer than k rows ends in (-1, NaN).
+        The queries go in chunks whose score and id rows (8 bytes per column) and code sums fit scratch_bytes.  plan as in
+        IVFInt8Index.search: 'host' synchronises once per chunk, inside ops.ivf_scan_bin; 'device' (and 'auto' where
+        admissible) plans the chunk with ops.ivf_plan and does not."""
+        return self._search_lists(qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, 4, plan)
+
+    def save(self, path):
+        """One .npz: BinaryIndex's arrays (`bits` [N, ceil(D / 8)] uint8, `scales` [N] float32, `D`) and the lists'
+        (`centroids` [nlist, D] float32, `ids` [N] int32, `list_off` [nlist+1] int32, `nlist`).  BinaryIndex.load reads the
+        file as it lies: the rows list-major, without their ids."""
+        self._need_trained('save')
+        np.savez(path, D=np.int64(self.D), **self._save_bin(), **self._save_lists())
+
+    @classmethod
+    def load(cls, path):
+        f = _read_npz(path)
+        index = cls(int(f['D']), int(f['nlist']))
+        index._load_bin(path, f)
         index._load_lists(path, f)
         return index
 

@@ -1052,6 +1052,70 @@ def ivf_scan_fp4(qcodes, qexps, qscales, codes, exps, scales, ids, list_off, pro
     return scores[:, :width], out_ids[:, :width]
 
 
+# ---- the inverted file over sign-bit rows (csrc/ivf_bin.hip) ------------------------------------------------------------
+def code_sums(qcodes, D):
+    """qsums [Q] int32 CUDA, qsums[q] = the sum of qcodes[q][:D] (dir_code_sums): what ivf_scan_bin subtracts from twice its
+    sum over the set bits.  qcodes [Q, >= D] int8 CUDA with unit column stride and any row pitch."""
+    _on_device(qcodes)
+    if qcodes.dtype != torch.int8 or qcodes.dim() != 2:
+        raise TypeError('int8 query codes [Q, ldc] expected')
+    D = int(D)
+    if D < 1 or D > index_bin_max_dim() or qcodes.shape[1] < D:
+        raise ValueError('codes of at least D columns expected, 1 <= D <= %d' % index_bin_max_dim())
+    Q = qcodes.shape[0]
+    qcodes, ldq = _rows_pitch(qcodes, D)
+    qsums = torch.empty(Q, dtype=torch.int32, device=qcodes.device)
+    if Q:
+        call('dir_code_sums', ptr(qcodes), ldq, Q, D, ptr(qsums), stream_ptr())
+    return qsums
+
+
+def ivf_scan_bin(qcodes, qscales, bits, bscales, ids, list_off, probe, col_off, D, width=None, out=None, tables=None,
+                 qsums=None):
+    """ivf_scan over sign-bit rows (dir_ivf_scan_bin) -> (scores [Q,width] fp32, out_ids [Q,width] int32), both CUDA.  qcodes
+    [Q,ldc] int8 / qscales [Q] as quantize_rows gives them (ldc >= D rounded up to 64, zero in D .. that; row slices too);
+    bits [N,ldb] uint8, ldb >= bin_width(D), and bscales [N] fp32 as quantize_rows_bin gives them, ids [N] int32, list_off
+    [nlist+1] int32: a list-major database (index.IVFBinaryIndex).  probe, col_off, width, out and tables under ivf_scan's
+    contract: for r < len(list probe[q][p]), column col_off[q][p] + r carries similarity_bin's score ((float)t * qscales[q])
+    * bscales[n] and the id of row n = list_off[probe[q][p]] + r; a column no slot covers carries id -1; columns at or past
+    width keep what they hold.  qsums: code_sums(qcodes, D) when the caller has it already."""
+    _on_device(qcodes, qscales, bits, bscales, ids, list_off, probe, col_off, qsums, *(out or ()))
+    if qcodes.dtype != torch.int8 or qcodes.dim() != 2:
+        raise TypeError('int8 query codes [Q, ldc] expected')
+    if bits.dtype != torch.uint8 or bits.dim() != 2:
+        raise TypeError('uint8 bits [N, ldb] expected')
+    if qscales.dtype != torch.float32 or bscales.dtype != torch.float32:
+        raise TypeError('float32 scales expected')
+    if qsums is not None and qsums.dtype != torch.int32:
+        raise TypeError('int32 qsums expected')
+    Q, N = qcodes.shape[0], bits.shape[0]
+    nlist = _list_tables(Q, N, ids, list_off, probe, col_off)
+    D = int(D)
+    if D < 1 or D > index_bin_max_dim():
+        raise ValueError('1 <= D <= %d expected, got %d' % (index_bin_max_dim(), D))
+    ldc, ldb = (D + 63) // 64 * 64, bin_width(D)
+    if qcodes.shape[1] < ldc or bits.shape[1] < ldb:
+        raise ValueError('query codes of %d and bits of %d columns at least expected for D = %d' % (ldc, ldb, D))
+    if qscales.dim() != 1 or bscales.dim() != 1 or qscales.numel() != Q or bscales.numel() != N:
+        raise ValueError('qscales [Q] and bscales [N] expected for codes of Q and bits of N rows')
+    if qsums is not None and (qsums.dim() != 1 or qsums.numel() != Q):
+        raise ValueError('qsums [Q] expected for codes of Q rows')
+    qcodes, ldq = _i8_codes(qcodes, ldc)
+    bits, ldb = _i8_codes(bits, ldb)
+    qsums = code_sums(qcodes, D) if qsums is None else qsums.contiguous()
+    qscales, bscales, ids, list_off = qscales.contiguous(), bscales.contiguous(), ids.contiguous(), list_off.contiguous()
+    pair_off, pair_q, pair_col, item_off, items, reach = tables if tables is not None else ivf_probe_tables(list_off, probe, col_off)
+    if width is None and reach is None:
+        raise ValueError('tables of ivf_plan need an explicit width: their reach stays on the device')
+    width = reach if width is None else int(width)
+    scores, out_ids, lds = _scan_out(out, Q, width, bits.device)
+    if Q and width:
+        call('dir_ivf_scan_bin', ptr(qcodes), ldq, ptr(qscales), ptr(qsums), Q, ptr(bits), ldb, ptr(bscales), ptr(ids), N, D,
+             ptr(list_off), nlist, ptr(pair_off), ptr(pair_q), ptr(pair_col), ptr(item_off), items, ptr(scores), ptr(out_ids),
+             lds, width, stream_ptr())
+    return scores[:, :width], out_ids[:, :width]
+
+
 # ---- the product-quantised index (csrc/pq.hip) -------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)     # a constant of the library: asked once, not in every call of a search
 def pq_max_m():

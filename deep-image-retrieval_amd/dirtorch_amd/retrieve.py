@@ -22,6 +22,9 @@ every query scans its P best lists only, --rerank as above.  With P = L the list
 --index ivffp4 --nlist L --nprobe P: an index.IVFFp4Index - IVFInt8Index's lists (the same training, a row in the same
 list) holding Fp4Index's rows (descriptors of at most 7281 values); every query scans its P best lists only.  Its raw
 scores are fp4's, so pair it with --rerank like --index fp4.  With P = L the lists are those of --index fp4.
+--index ivfbin --nlist L --nprobe P: an index.IVFBinaryIndex - the same lists holding BinaryIndex's rows (a sign bit per
+value, a scale and an id per image); every query scans its P best lists only.  Its raw lists are the binary index's, so pair
+it with a long --rerank like --index bin.  With P = L the lists are those of --index bin.
 --index pq --pq-m M: an index.PQIndex trained on the database descriptors themselves (M bytes per image, M dividing the
 descriptor width; at least 256 database images); the lists are ranked by the table scores, --rerank as above.
 --index ivfpq --nlist L --nprobe P --pq-m M: an index.IVFPQIndex trained on the database descriptors themselves (L k-means
@@ -52,7 +55,8 @@ from .utils.convenient import mkdir
 # --index kind -> (its class in dirtorch_amd.index, the flags its constructor takes after the width, whether it is trained)
 INDEX_KINDS = {'int8': ('Int8Index', (), False), 'fp4': ('Fp4Index', (), False), 'bin': ('BinaryIndex', (), False),
                'ivf': ('IVFInt8Index', ('nlist',), True),
-               'ivffp4': ('IVFFp4Index', ('nlist',), True), 'pq': ('PQIndex', ('pq_m',), True), 'ivfpq': ('IVFPQIndex', ('nlist', 'pq_m'), True)}
+               'ivffp4': ('IVFFp4Index', ('nlist',), True), 'ivfbin': ('IVFBinaryIndex', ('nlist',), True),
+               'pq': ('PQIndex', ('pq_m',), True), 'ivfpq': ('IVFPQIndex', ('nlist', 'pq_m'), True)}
 
 
 def query_keys(db):
@@ -92,8 +96,8 @@ def main(argv=None):
         (('--topk',), dict(type=int, default=20, help='neighbours per query')),
         (('--output',), dict(type=str, required=True, help='path of the list: .npz, or text')),
         (('--index',), dict(type=str, default='', choices=[''] + list(INDEX_KINDS), help='scan a quantised copy of the database')),
-        (('--nlist',), dict(type=int, default=0, help='with --index ivf / ivffp4 / ivfpq: the number of k-means lists')),
-        (('--nprobe',), dict(type=int, default=1, help='with --index ivf / ivffp4 / ivfpq: lists scanned per query')),
+        (('--nlist',), dict(type=int, default=0, help='with --index ivf / ivffp4 / ivfbin / ivfpq: the number of k-means lists')),
+        (('--nprobe',), dict(type=int, default=1, help='with --index ivf / ivffp4 / ivfbin / ivfpq: lists scanned per query')),
         (('--pq-m',), dict(type=int, default=0, help='with --index pq / ivfpq: bytes (sub-spaces) per database image')),
         (('--rerank',), dict(type=int, default=0, help='with --index: shortlist size re-scored in fp32 (0 = none)')),
         eval_dir.EXPAND_FLAG,

@@ -138,6 +138,8 @@ const char* dir_version(void);
  *   dir_ivf_scan_i8          Q * width <= L, items * 768 <= L (refused, not cut: Q * width of 2^32 means 32 GiB of score and id
  *                            rows for one chunk; index.py's chunks are scratch_bytes / 8 slots, 2^25 by default)
  *   dir_ivf_scan_fp4         Q * width <= L, items * 768 <= L (refused, not cut, as dir_ivf_scan_i8)
+ *   dir_code_sums            Q * 64 <= L (Q rounded up to 4)
+ *   dir_ivf_scan_bin         Q * width <= L, items * 768 <= L (refused, not cut, as dir_ivf_scan_i8)
  *   dir_pq_encode            N * M <= L (N rounded up to 256)
  *   dir_pq_lut               Q * M * 8 <= L (Q rounded up to 32)
  *   dir_ivfpq_base           Q * nprobe * 128 <= L
@@ -756,6 +758,38 @@ int dir_ivf_scan_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int l
                      const uint8_t* bcodes, int ldb, const uint8_t* bexps, int ldbe, const float* bscales, const int* ids, int N,
                      int D, const int* list_off, int nlist, const int* pair_off, const int* pair_q, const int* pair_col,
                      const int* item_off, int items, float* scores, int* out_ids, int lds, int width, void* stream);
+/* The inverted file over sign-bit rows (ivf_bin.hip; dirtorch_amd/index.py IVFBinaryIndex; numpy restatement:
+ * tests/ivfbin_ref.py): the inverted file's lists with the binary index's rows in them, 1 <= D <= dir_index_bin_max_dim() =
+ * 131072.
+ * Coarse side: the inverted-file int8 index's, unchanged, as for the fp4 inverted file: a row lands in the same list in all
+ *   inverted files, and training is the int8 inverted file's.
+ * Lists: a row is stored as dir_quantize_rows_bin gives it - bits [N][ldb] uint8, scales [N] fp32 - LIST-MAJOR with ids [N]
+ *   int32 and list_off [nlist + 1] int32 as above, ids ascending inside a list.  The query side is dir_quantize_rows_i8's.
+ * Score: that of query q against row n of a probed list is dir_similarity_bin's number, ((float)t * qscales[q]) * bscales[n],
+ *   t = 2 * sum_k qcodes[q][k] * b_k - qsums[q] an exact int32: it does not depend on the tiling, the grouping of the
+ *   queries or the chunking.  CONSEQUENCE: with nprobe = nlist a search returns the binary index's lists bit for bit; with
+ *   fewer lists those of the numpy restatement.
+ * dir_code_sums: qsums[q] = sum_{k < D} qcodes[q][k] for q < Q, int32 (index_bin.hip's code_sums_kernel, one wave per row);
+ *   qcodes [Q][ldq] int8, ldq >= D, read up to D only.  The caller of the scan makes them once per query chunk.
+ * dir_ivf_scan_bin: dir_ivf_scan_i8's contract with bits on the database side - the same inverted probe table (pair_off,
+ *   pair_q, pair_col, item_off, items: 256 rows a tile, 32 pairs a group; `items` any upper bound), the same outputs: for
+ *   every pair and r < len_l, scores[q][col + r] = the score above against row list_off[l] + r and out_ids[q][col + r] =
+ *   ids[list_off[l] + r]; out_ids[q][0 .. width) pre-filled with -1 BY THIS CALL; columns at or past `width` untouched; a
+ *   pair that would pass `width` or whose query is outside [0, Q) stores nothing.  qcodes [Q][ldq]: 16-byte aligned, ldq %
+ *   16 == 0 and >= D rounded up to 64, Q * ldq < 2^31, ZERO in bytes D .. D rounded up to 64 (dir_quantize_rows_i8 writes
+ *   them so) and read no further than that, whatever ldq is.  bits [N][ldb]: 16-byte aligned, ldb % 16 == 0 and >= D rounded
+ *   up to 128, divided by 8, ldb * 256 < 2^31; what the bits past D hold does not matter: they meet zero query codes.
+ *   qsums [Q] from dir_code_sums; the scan allocates nothing.  The slots of one query must not overlap.  LDS-DMA loaders
+ *   (the query rows of a group gathered by a per-lane offset, cut by 16-byte chunk at D rounded up to 64),
+ *   v_mfma_i32_32x32x32_i8 on bits widened to 0 / 1 code bytes in registers, K slabs of 1024 holding both operands, two
+ *   stages of 64 KB, no K rotation.
+ * Both: a negative count, D < 1 or above the max dim, a pitch below its minimum or a null pointer fail with DIR_ERR_INVALID
+ *   before anything is launched; Q == 0 (or width == 0) is DIR_OK and launches nothing. */
+int dir_code_sums(const int8_t* qcodes, int ldq, int Q, int D, int* qsums, void* stream);
+int dir_ivf_scan_bin(const int8_t* qcodes, int ldq, const float* qscales, const int* qsums, int Q, const uint8_t* bits, int ldb,
+                     const float* bscales, const int* ids, int N, int D, const int* list_off, int nlist, const int* pair_off,
+                     const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
+                     int lds, int width, void* stream);
 /* The product-quantised index (pq.hip; dirtorch_amd/index.py PQIndex; numpy restatement: tests/pq_ref.py).
  * A row of D fp32 values is cut into M sub-vectors of dsub = D / M values (M divides D, 1 <= M <= dir_pq_max_m(), D <=
  * dir_index_i8_max_dim()); sub-vector m is replaced by the number of one of the 256 centroids of sub-space m, so a row is

@@ -207,6 +207,8 @@ def bench_kernel_name(k):
             'fill_ids_fp4_kernel': 'fill_noise_kernel', 'ivf_scan_fp4_kernel': 'sim_split_lc_kernel',
             # the probe tables of both scans by list, one workgroup (csrc/ivf_plan.hip; no timed bench.py step launches it): an integer sort
             'ivf_plan_kernel': 'rank_sort_kernel',
+            # the inverted file over sign-bit rows: its id pre-fill and list-major scan (csrc/ivf_bin.hip; no timed bench.py step launches them)
+            'fill_ids_bin_kernel': 'fill_noise_kernel', 'ivf_scan_bin_kernel': 'sim_split_lc_kernel',
             # the product-quantised index: encoder, query tables and the table scan (csrc/pq.hip; no timed bench.py step launches them)
             'pq_encode_kernel': 'expand_rows_kernel', 'pq_lut_kernel': 'expand_rows_kernel', 'pq_scan_kernel': 'rank_hist_kernel',
             # IVF-PQ: the coarse terms and the query-major scan of the probed lists (csrc/ivfpq.hip; no timed bench.py step launches them)
