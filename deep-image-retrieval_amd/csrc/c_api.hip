@@ -1027,25 +1027,39 @@ int dir_segment_sums(const float* X, int ldx, int N, int D, const int* order, co
     DIR_CATCH
 }
 
+// What the entries of the three list-major scans check alike, in one order: the sizes, D (check_dim), the pitches
+// (pitch_error: the entry's finding, or null), lds, the outputs, and - where there is work - a list, the inputs (null_input:
+// one of the entry's pointers is missing) and the admission rule (admission_error: the entry's finding, or null).  An empty
+// call passes: the launcher returns on it.
+static int ivf_scan_check(const char* who, int (*check_dim)(const char*, int), int D, int Q, int N, int nlist, int items,
+                          int width, int lds, const char* pitch_error, const void* scores, const void* out_ids, bool null_input,
+                          const char* admission_error) {
+    auto bad = [who](const char* what) { return fail(DIR_ERR_INVALID, std::string(who) + ": " + what); };
+    if (Q < 0 || N < 0 || nlist < 0 || items < 0 || width < 0) return bad("negative size");
+    DIR_CHECK(check_dim(who, D));
+    if (pitch_error) return bad(pitch_error);
+    if (lds < width) return bad("lds < width");
+    if (Q == 0 || width == 0) return DIR_OK;
+    if (!scores || !out_ids) return bad("null pointer");
+    if (items > 0 && N > 0) {
+        if (nlist < 1) return bad("items without a list");
+        if (null_input) return bad("null pointer");
+        if (admission_error) return bad(admission_error);
+    }
+    return DIR_OK;
+}
+
 int dir_ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, const int8_t* bcodes, int ldb,
                     const float* bscales, const int* ids, int N, int D, const int* list_off, int nlist, const int* pair_off,
                     const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
                     int lds, int width, void* stream) {
     DIR_TRY
-    if (Q < 0 || N < 0 || nlist < 0 || items < 0 || width < 0) return fail(DIR_ERR_INVALID, "ivf_scan_i8: negative size");
-    DIR_CHECK(index_check_dim("ivf_scan_i8", D));
-    if (ldq < pad64(D) || ldb < pad64(D))
-        return fail(DIR_ERR_INVALID, "ivf_scan_i8: ldq, ldb < D rounded up to a multiple of 64");
-    if (lds < width) return fail(DIR_ERR_INVALID, "ivf_scan_i8: lds < width");
-    if (Q == 0 || width == 0) return DIR_OK;
-    if (!scores || !out_ids) return fail(DIR_ERR_INVALID, "ivf_scan_i8: null pointer");
-    if (items > 0 && N > 0) {
-        if (nlist < 1) return fail(DIR_ERR_INVALID, "ivf_scan_i8: items without a list");
-        if (!qcodes || !qscales || !bcodes || !bscales || !ids || !list_off || !pair_off || !pair_q || !pair_col || !item_off)
-            return fail(DIR_ERR_INVALID, "ivf_scan_i8: null pointer");
-        if (!ivf_scan_i8_admissible(qcodes, ldq, Q, bcodes, ldb))
-            return fail(DIR_ERR_INVALID, "ivf_scan_i8: ldq, ldb % 16 == 0, ldb < 2^23, Q * ldq < 2^31 and 16-byte aligned codes");
-    }
+    DIR_CHECK(ivf_scan_check(
+        "ivf_scan_i8", index_check_dim, D, Q, N, nlist, items, width, lds,
+        ldq < pad64(D) || ldb < pad64(D) ? "ldq, ldb < D rounded up to a multiple of 64" : nullptr, scores, out_ids,
+        !qcodes || !qscales || !bcodes || !bscales || !ids || !list_off || !pair_off || !pair_q || !pair_col || !item_off,
+        ivf_scan_admissible(qcodes, ldq, Q, bcodes, ldb) ? nullptr
+                                                         : "ldq, ldb % 16 == 0, ldb < 2^23, Q * ldq < 2^31 and 16-byte aligned codes"));
     return ivf_scan_i8(qcodes, ldq, qscales, Q, bcodes, ldb, bscales, ids, N, D, list_off, nlist, pair_off, pair_q, pair_col,
                        item_off, items, scores, out_ids, lds, width, (hipStream_t)stream);
     DIR_CATCH
@@ -1056,24 +1070,18 @@ int dir_ivf_scan_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int l
                      int D, const int* list_off, int nlist, const int* pair_off, const int* pair_q, const int* pair_col,
                      const int* item_off, int items, float* scores, int* out_ids, int lds, int width, void* stream) {
     DIR_TRY
-    if (Q < 0 || N < 0 || nlist < 0 || items < 0 || width < 0) return fail(DIR_ERR_INVALID, "ivf_scan_fp4: negative size");
-    DIR_CHECK(fp4_check_dim("ivf_scan_fp4", D));
-    if (ldq < pad64(D) / 2 || ldb < pad64(D) / 2)
-        return fail(DIR_ERR_INVALID, "ivf_scan_fp4: ldq, ldb < half of D rounded up to a multiple of 64");
-    if (ldqe < fp4_exps_width(D) || ldbe < fp4_exps_width(D))
-        return fail(DIR_ERR_INVALID, "ivf_scan_fp4: ldqe, ldbe < 8 * ceil(D / 256)");
-    if (lds < width) return fail(DIR_ERR_INVALID, "ivf_scan_fp4: lds < width");
-    if (Q == 0 || width == 0) return DIR_OK;
-    if (!scores || !out_ids) return fail(DIR_ERR_INVALID, "ivf_scan_fp4: null pointer");
-    if (items > 0 && N > 0) {
-        if (nlist < 1) return fail(DIR_ERR_INVALID, "ivf_scan_fp4: items without a list");
-        if (!qcodes || !qexps || !qscales || !bcodes || !bexps || !bscales || !ids || !list_off || !pair_off || !pair_q ||
-            !pair_col || !item_off)
-            return fail(DIR_ERR_INVALID, "ivf_scan_fp4: null pointer");
-        if (!ivf_scan_fp4_admissible(qcodes, ldq, qexps, ldqe, Q, bcodes, ldb, bexps, ldbe, D))
-            return fail(DIR_ERR_INVALID, "ivf_scan_fp4: ldq, ldb % 16 == 0, ldb < 2^23, Q * ldq < 2^31 and 16-byte aligned codes, "
-                                         "ldqe, ldbe % 8 == 0 and 8-byte aligned block bytes");
-    }
+    DIR_CHECK(ivf_scan_check(
+        "ivf_scan_fp4", fp4_check_dim, D, Q, N, nlist, items, width, lds,
+        ldq < pad64(D) / 2 || ldb < pad64(D) / 2           ? "ldq, ldb < half of D rounded up to a multiple of 64"
+        : ldqe < fp4_exps_width(D) || ldbe < fp4_exps_width(D) ? "ldqe, ldbe < 8 * ceil(D / 256)"
+                                                               : nullptr,
+        scores, out_ids,
+        !qcodes || !qexps || !qscales || !bcodes || !bexps || !bscales || !ids || !list_off || !pair_off || !pair_q || !pair_col ||
+            !item_off,
+        ivf_scan_fp4_admissible(qcodes, ldq, qexps, ldqe, Q, bcodes, ldb, bexps, ldbe, D)
+            ? nullptr
+            : "ldq, ldb % 16 == 0, ldb < 2^23, Q * ldq < 2^31 and 16-byte aligned codes, "
+              "ldqe, ldbe % 8 == 0 and 8-byte aligned block bytes"));
     return ivf_scan_fp4(qcodes, ldq, qexps, ldqe, qscales, Q, bcodes, ldb, bexps, ldbe, bscales, ids, N, D, list_off, nlist,
                         pair_off, pair_q, pair_col, item_off, items, scores, out_ids, lds, width, (hipStream_t)stream);
     DIR_CATCH
@@ -1095,20 +1103,16 @@ int dir_ivf_scan_bin(const int8_t* qcodes, int ldq, const float* qscales, const 
                      const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
                      int lds, int width, void* stream) {
     DIR_TRY
-    if (Q < 0 || N < 0 || nlist < 0 || items < 0 || width < 0) return fail(DIR_ERR_INVALID, "ivf_scan_bin: negative size");
-    DIR_CHECK(bin_check_dim("ivf_scan_bin", D));
-    if (ldq < pad64(D)) return fail(DIR_ERR_INVALID, "ivf_scan_bin: ldq < D rounded up to a multiple of 64");
-    if (ldb < bin_width(D)) return fail(DIR_ERR_INVALID, "ivf_scan_bin: ldb < D rounded up to a multiple of 128, divided by 8");
-    if (lds < width) return fail(DIR_ERR_INVALID, "ivf_scan_bin: lds < width");
-    if (Q == 0 || width == 0) return DIR_OK;
-    if (!scores || !out_ids) return fail(DIR_ERR_INVALID, "ivf_scan_bin: null pointer");
-    if (items > 0 && N > 0) {
-        if (nlist < 1) return fail(DIR_ERR_INVALID, "ivf_scan_bin: items without a list");
-        if (!qcodes || !qscales || !qsums || !bits || !bscales || !ids || !list_off || !pair_off || !pair_q || !pair_col || !item_off)
-            return fail(DIR_ERR_INVALID, "ivf_scan_bin: null pointer");
-        if (!ivf_scan_bin_admissible(qcodes, ldq, Q, bits, ldb))
-            return fail(DIR_ERR_INVALID, "ivf_scan_bin: ldq, ldb % 16 == 0, ldb < 2^23, Q * ldq < 2^31 and 16-byte aligned codes and bits");
-    }
+    DIR_CHECK(ivf_scan_check(
+        "ivf_scan_bin", bin_check_dim, D, Q, N, nlist, items, width, lds,
+        ldq < pad64(D)        ? "ldq < D rounded up to a multiple of 64"
+        : ldb < bin_width(D) ? "ldb < D rounded up to a multiple of 128, divided by 8"
+                             : nullptr,
+        scores, out_ids,
+        !qcodes || !qscales || !qsums || !bits || !bscales || !ids || !list_off || !pair_off || !pair_q || !pair_col || !item_off,
+        ivf_scan_admissible(qcodes, ldq, Q, bits, ldb)
+            ? nullptr
+            : "ldq, ldb % 16 == 0, ldb < 2^23, Q * ldq < 2^31 and 16-byte aligned codes and bits"));
     return ivf_scan_bin(qcodes, ldq, qscales, qsums, Q, bits, ldb, bscales, ids, N, D, list_off, nlist, pair_off, pair_q, pair_col,
                         item_off, items, scores, out_ids, lds, width, (hipStream_t)stream);
     DIR_CATCH

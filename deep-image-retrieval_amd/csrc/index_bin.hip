@@ -142,7 +142,7 @@ int code_sums(const int8_t* qcodes, int ldq, int Q, int D, int* qsums, hipStream
 // STREAM: rows wider than two slabs - the database ring turns, one piece per loader and hand-off.
 template <bool STREAM>
 __device__ __forceinline__ void bin_load(char* smem, int lw, int lane, __amdgpu_buffer_rsrc_t rsrc_p,
-                                         __amdgpu_buffer_rsrc_t rsrc_q, const Fp4Loader& db, int S, int T) {
+                                         __amdgpu_buffer_rsrc_t rsrc_q, const ChunkCutLoader& db, int S, int T) {
     constexpr int OPS = STREAM ? 4 : 3;                // LDS-DMA instructions of this wave after every hand-off
     auto lim = [&](int u) __attribute__((always_inline)) {
         return u < db.last ? 8u : u == db.last ? (uint32_t)db.keep : 0u;
@@ -201,7 +201,7 @@ __global__ void __launch_bounds__(768) sim_bin_kernel(const uint8_t* __restrict_
         // one descriptor per workgroup, based at its rows: Kb bytes of every row are readable
         const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (uint32_t)(((size_t)rows - 1) * ldp + Kb));
         const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc(img + (size_t)qb * S * kBinSub, (uint32_t)(S * kBinSub));
-        const Fp4Loader db(lw, lane, (uint32_t)ldp, Kb, T);
+        const ChunkCutLoader db(lw, lane, (uint32_t)ldp, Kb, T);
         if (T > 2)
             bin_load<true>(smem, lw, lane, rsrc_p, rsrc_q, db, S, T);
         else

@@ -17,7 +17,7 @@
 //   Block bytes, database side: the consumer reads its row's 8 bytes of a slab from global memory with one 8-byte load, one
 //     slab ahead.  Through the stage they would be 2 KB per slab in 8-byte pieces of rows [N][lde]: 256 lanes of DMA
 //     issue for 1/16 of the bytes, against one load per lane that has a whole slab of MFMAs to hide behind.
-// Rows are padded to 64 k (32 bytes) and not to a slab, so the last slab may hold 2, 4 or 6 of its 8 chunks: Fp4Loader
+// Rows are padded to 64 k (32 bytes) and not to a slab, so the last slab may hold 2, 4 or 6 of its 8 chunks: ChunkCutLoader
 // cuts by chunk where StripLoader cuts by half (the codes pitch need not cover a whole slab); the block bytes' pitch does
 // cover whole slabs (8 * ceil(D / 256)), the bytes of the blocks past D rounded up to 64 are replaced by 127 in the kernel.
 #include "dir_common.h"
@@ -174,7 +174,7 @@ __global__ void __launch_bounds__(768) sim_fp4_kernel(const uint8_t* __restrict_
         // one descriptor per workgroup, based at its rows: Kb bytes of every row are readable
         const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (uint32_t)(((size_t)rows - 1) * ldp + Kb));
         const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc(img + (size_t)qb * T * kFp4SlabQ, (uint32_t)(T * kFp4SlabQ));
-        const Fp4Loader db(lw, lane, (uint32_t)ldp, Kb, T);
+        const ChunkCutLoader db(lw, lane, (uint32_t)ldp, Kb, T);
         // the image of a slab: 13 pieces; loader 0 takes the block bytes' piece with its three
         const bool four = lw == 0;
         strip_load<kFp4Stage, kFp4Stages, 11, 12>(smem, T, rot, [&](char* stage, int u) __attribute__((always_inline)) {

@@ -21,7 +21,7 @@
 //   from the pair table, out-of-range for the empty rows of a group - the way the database pieces are addressed; no stage
 //   image is written per list.
 #include "dir_common.h"
-#include "strip_stream.h"
+#include "ivf_scan.h"
 #include "pointwise.h"
 
 #pragma clang fp contract(off)   // the score is defined in single IEEE operations: nothing here may fuse
@@ -81,8 +81,7 @@ int segment_sums(const float* X, int ldx, int N, int D, const int* order, const 
 }
 
 // ---- the scan of the probed lists --------------------------------------------------------------------------------------
-static constexpr int kIvfQG = 32;                   // query rows per group = one 32 x 32 accumulator block
-static constexpr int kIvfStage = kStripSlab + kIvfQG * kStripRow;   // 36864
+static constexpr int kIvfStage = kStripSlab + kIvfSub;   // 36864
 static constexpr int kIvfStages = 4;                // three slabs in flight, one being multiplied
 static constexpr int kIvfLds = kIvfStages * kIvfStage;   // 147456 of 163840
 
@@ -91,9 +90,7 @@ __global__ void __launch_bounds__(256) fill_ids_kernel(int* __restrict__ out_ids
     if (i < total) out_ids[(i / width) * lds + (i % width)] = -1;
 }
 
-// Workgroup b serves list l with item_off[l] <= b < item_off[l + 1]; its place there is tile * groups + group, groups =
-// the 32-pair groups of the list.  pair_off [nlist + 1] is the CSR of the (query, slot) pairs by list, pair_q / pair_col
-// the query and the first output column of every pair.
+// The work item, the query gather and the epilogue: ivf_scan.h.
 __global__ void __launch_bounds__(768) ivf_scan_i8_kernel(const int8_t* __restrict__ qcodes, int ldq, const float* __restrict__ qscales,
                                                          int Q, const int8_t* __restrict__ P, int ldp,
                                                          const float* __restrict__ bscales, const int* __restrict__ ids, int NP,
@@ -105,41 +102,19 @@ __global__ void __launch_bounds__(768) ivf_scan_i8_kernel(const int8_t* __restri
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int bid = blockIdx.x;
-    // the list of this workgroup: the last l with item_off[l] <= bid (uniform: every wave takes the same way out)
-    int lo = 0, hi = nlist;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (item_off[mid] <= bid) lo = mid; else hi = mid;
-    }
-    const int l = lo;
-    const int p0 = pair_off[l], p1 = pair_off[l + 1];
-    const int groups = (p1 - p0 + kIvfQG - 1) / kIvfQG;
-    const int local = bid - item_off[l];
-    if (groups <= 0 || local < 0) return;
-    const int tile = local / groups, grp = local - tile * groups;
-    const int i0 = list_off[l] + tile * kStripRows;
-    const int iend = min(list_off[l + 1], NP);
-    const int rows = min(kStripRows, iend - i0);
-    const int pbase = p0 + grp * kIvfQG;
-    if (i0 < 0 || rows <= 0) return;
+    const IvfItem it(bid, item_off, nlist, pair_off, list_off, NP);
+    if (!it.valid) return;
     const int rot = strip_rot(bid, T);
 
     if (wave >= 8) {
         const int lw = wave - 8;
-        const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (uint32_t)(((size_t)rows - 1) * ldp + Kp));
+        const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)it.i0 * ldp, (uint32_t)(((size_t)it.rows - 1) * ldp + Kp));
         const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc(qcodes, (uint32_t)(((size_t)Q - 1) * ldq + Kp));
         const StripLoader<true> db(lw, lane, (uint32_t)ldp, Kp, T);
-        // query piece lw = rows 8 lw .. 8 lw + 7 of the group: row r is the query of pair pbase + r, gathered where it lies
-        const int qrow = strip_piece_row(lw, lane), qchunk = strip_piece_chunk(lw, lane);
-        uint32_t qvoff = kOOB;                                                 // an empty row of the group reads zeros
-        if (pbase + qrow < p1) {
-            const int q = pair_q[pbase + qrow];
-            if ((unsigned)q < (unsigned)Q) qvoff = (uint32_t)q * (uint32_t)ldq + (uint32_t)qchunk * 16u;
-        }
-        const bool qupper = qchunk >= 4;
+        const IvfQueryLane qs(it, pair_q, Q, ldq, Kp, lw, lane);
         strip_load<kIvfStage, kIvfStages, 9>(smem, T, rot, [&](char* stage, int u) __attribute__((always_inline)) {
             db.issue(rsrc_p, stage, u);
-            dma16(rsrc_q, stage + kStripSlab + lw * kStripPiece, (db.cut(u) && qupper) ? kOOB : qvoff, u * kStripRow);
+            qs.issue(rsrc_q, stage + kStripSlab, u * kStripRow);
         });
         return;
     }
@@ -149,42 +124,27 @@ __global__ void __launch_bounds__(768) ivf_scan_i8_kernel(const int8_t* __restri
     strip_consume<kIvfStage, kIvfStages>(smem, T, rot, [&](const char* stage, int) __attribute__((always_inline)) {
         code_slab_mma<1>(L, stage, acc);
     });
-
-    // scattered epilogue: the lane's 16 pairs are the group rows L.qrow(0, g) + e
-    const int r = tile * kStripRows + wave * 32 + L.lrow;    // the row's place in its list
-    const int n = list_off[l] + r;
-    if (n < iend) {
-        const float sb = bscales[n];
-        const int id = ids[n];
-        // the 16 pairs of this lane in three rounds of independent loads (query, column; scale; then the stores)
-        int qv[16];
-        long cv[16];
-        float sq[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int pi = pbase + L.qrow(0, j >> 2) + (j & 3);
-            const bool ok = pi < p1;
-            qv[j] = ok ? pair_q[pi] : -1;
-            cv[j] = ok ? (long)pair_col[pi] + r : -1;
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            if ((unsigned)qv[j] >= (unsigned)Q || cv[j] >= width) cv[j] = -1;        // a table that does not fit: no store
-            sq[j] = cv[j] >= 0 ? qscales[qv[j]] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            if (cv[j] >= 0) {
-                out[(size_t)qv[j] * ldo + cv[j]] = __fmul_rn(__fmul_rn((float)acc[0][j], sq[j]), sb);
-                out_ids[(size_t)qv[j] * ldo + cv[j]] = id;
-            }
-    }
+    ivf_scatter<false>(it, L, it.r(wave, L), pair_q, pair_col, qscales, nullptr, Q, bscales, ids, out, out_ids, ldo, width,
+                       [&](int j, int) __attribute__((always_inline)) { return (float)acc[0][j]; });
 }
 
-// the scan's admission rules beyond the sizes (c_api.hip reports them): 16-byte pieces, one 2 GB descriptor per operand
-bool ivf_scan_i8_admissible(const int8_t* qcodes, int ldq, int Q, const int8_t* bcodes, int ldb) {
+// the scans' admission rule beyond the sizes (c_api.hip reports it): 16-byte pieces, one 2 GB descriptor per operand
+bool ivf_scan_admissible(const void* qcodes, int ldq, int Q, const void* bcodes, int ldb) {
     return ((ldq | ldb) & 15) == 0 && ((((uintptr_t)qcodes) | ((uintptr_t)bcodes)) & 15) == 0 &&
            (size_t)ldb * kStripRows < (1ull << 31) && (size_t)ldq * (size_t)(Q > 0 ? Q : 1) < (1ull << 31);
+}
+
+// What a list-major scan does before its kernel: the two launch extents (refused, not cut: a caller reaches Q * width >=
+// 2^32 only with score and id rows of 32 GiB for one chunk), then id -1 in every slot.  `who`: the entry, for the message.
+int ivf_scan_begin(const char* who, long Q, int width, int items, int* out_ids, int lds, hipStream_t stream) {
+    const long total = Q * width;
+    if (!launch_fits((total + 255) / 256, 256))
+        return fail(DIR_ERR_INVALID, std::string(who) + ": Q * width must stay below 2^32 (one thread per id slot): cut the queries");
+    if (!launch_fits(items, 768))
+        return fail(DIR_ERR_INVALID, std::string(who) + ": items * 768 must stay below 2^32 (768 threads per item): cut the queries");
+    hipLaunchKernelGGL(fill_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, out_ids, lds, width, total);
+    DIR_HIP_CHECK(hipGetLastError());
+    return DIR_OK;
 }
 
 int ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, const int8_t* bcodes, int ldb,
@@ -192,14 +152,7 @@ int ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, cons
                 const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
                 int lds, int width, hipStream_t stream) {
     if (Q <= 0 || width <= 0) return DIR_OK;
-    const long total = (long)Q * width;
-    // (refused, not cut: a caller reaches Q * width >= 2^32 only with score and id rows of 32 GiB for one chunk)
-    if (!launch_fits((total + 255) / 256, 256))
-        return fail(DIR_ERR_INVALID, "ivf_scan_i8: Q * width must stay below 2^32 (one thread per id slot): cut the queries");
-    if (!launch_fits(items, 768))
-        return fail(DIR_ERR_INVALID, "ivf_scan_i8: items * 768 must stay below 2^32 (768 threads per item): cut the queries");
-    hipLaunchKernelGGL(fill_ids_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, out_ids, lds, width, total);
-    DIR_HIP_CHECK(hipGetLastError());
+    DIR_CHECK(ivf_scan_begin("ivf_scan_i8", Q, width, items, out_ids, lds, stream));
     if (items <= 0 || N <= 0) return DIR_OK;
     const int Kp = pad64(D), T = ceil_div(Kp, kStripRow);
     static std::atomic<uint64_t> attr_done{0};

@@ -6,7 +6,7 @@
 // stages - with sim_fp4_kernel's arithmetic: a stage row of 128 bytes is 256 k of e2m1 codes, a slab is four
 // v_mfma_scale_f32_32x32x64_f8f6f4 steps into one f32x16 accumulator block, and acc is exact (include/dir_engine.h), so a
 // score is dir_similarity_fp4's number whatever the cut.
-//   Database side: Fp4Loader as the flat scan runs it (the last slab cut by 16-byte chunk), the descriptor based at the
+//   Database side: ChunkCutLoader as the flat scan runs it (the last slab cut by 16-byte chunk), the descriptor based at the
 //     tile's first row; the row's 8 block bytes of a slab come from one 8-byte global load per consumer lane, one slab ahead.
 //   Query side: the 32 rows of a group are gathered where they lie by a per-lane row offset from the pair table (kOOB
 //     for an empty row of the group), cut by chunk in the last slab as well: the query pitch is pad64(D) / 2 and need not
@@ -20,24 +20,18 @@
 // LDS: 4 stages x (32 768 database + 4096 query codes) = 147 456 of 163 840 bytes.  92 VGPRs (three waves a SIMD allow 168), no
 // atomics, no scratch.
 #include "dir_common.h"
-#include "strip_stream.h"
+#include "ivf_scan.h"
 #include "pointwise.h"
 
 #pragma clang fp contract(off)   // the score is defined in single IEEE operations: nothing here may fuse
 
 namespace dir {
 
-static constexpr int kIvfFp4QG = 32;                   // query rows per group = one 32 x 32 accumulator block
-static constexpr int kIvfFp4Stage = kStripSlab + kIvfFp4QG * kStripRow;   // 36864
+static constexpr int kIvfFp4Stage = kStripSlab + kIvfSub;   // 36864
 static constexpr int kIvfFp4Stages = 4;                // three slabs in flight, one being multiplied
 static constexpr int kIvfFp4Lds = kIvfFp4Stages * kIvfFp4Stage;           // 147456 of 163840
 
-__global__ void __launch_bounds__(256) fill_ids_fp4_kernel(int* __restrict__ out_ids, int lds, int width, long total) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < total) out_ids[(i / width) * lds + (i % width)] = -1;
-}
-
-// Workgroup b serves list l with item_off[l] <= b < item_off[l + 1]; its place there is tile * groups + group (ivf.hip).
+// The work item, the query gather and the epilogue: ivf_scan.h.
 __global__ void __launch_bounds__(768) ivf_scan_fp4_kernel(const uint8_t* __restrict__ qcodes, int ldq, const uint8_t* __restrict__ QE,
                                                           int ldqe, const float* __restrict__ qscales, int Q,
                                                           const uint8_t* __restrict__ P, int ldp, const uint8_t* __restrict__ PE,
@@ -50,56 +44,29 @@ __global__ void __launch_bounds__(768) ivf_scan_fp4_kernel(const uint8_t* __rest
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int bid = blockIdx.x;
-    // the list of this workgroup: the last l with item_off[l] <= bid (uniform: every wave takes the same way out)
-    int lo = 0, hi = nlist;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (item_off[mid] <= bid) lo = mid; else hi = mid;
-    }
-    const int l = lo;
-    const int p0 = pair_off[l], p1 = pair_off[l + 1];
-    const int groups = (p1 - p0 + kIvfFp4QG - 1) / kIvfFp4QG;
-    const int local = bid - item_off[l];
-    if (groups <= 0 || local < 0) return;
-    const int tile = local / groups, grp = local - tile * groups;
-    const int i0 = list_off[l] + tile * kStripRows;
-    const int iend = min(list_off[l + 1], NP);
-    const int rows = min(kStripRows, iend - i0);
-    const int pbase = p0 + grp * kIvfFp4QG;
-    if (i0 < 0 || rows <= 0) return;
+    const IvfItem it(bid, item_off, nlist, pair_off, list_off, NP);
+    if (!it.valid) return;
     const int rot = strip_rot(bid, T);
 
     if (wave >= 8) {
         const int lw = wave - 8;
-        const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (uint32_t)(((size_t)rows - 1) * ldp + Kb));
+        const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)it.i0 * ldp, (uint32_t)(((size_t)it.rows - 1) * ldp + Kb));
         const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc(qcodes, (uint32_t)(((size_t)Q - 1) * ldq + Kb));
-        const Fp4Loader db(lw, lane, (uint32_t)ldp, Kb, T);
-        // query piece lw = rows 8 lw .. 8 lw + 7 of the group: row r is the query of pair pbase + r, gathered where it lies
-        const int qrow = strip_piece_row(lw, lane), qchunk = strip_piece_chunk(lw, lane);
-        uint32_t qvoff = kOOB;                                                 // an empty row of the group reads zeros
-        if (pbase + qrow < p1) {
-            const int q = pair_q[pbase + qrow];
-            if ((unsigned)q < (unsigned)Q) qvoff = (uint32_t)q * (uint32_t)ldq + (uint32_t)qchunk * 16u;
-        }
+        const ChunkCutLoader db(lw, lane, (uint32_t)ldp, Kb, T);
+        const IvfQueryLane qs(it, pair_q, Q, ldq, Kb, lw, lane);
         strip_load<kIvfFp4Stage, kIvfFp4Stages, 9>(smem, T, rot, [&](char* stage, int u) __attribute__((always_inline)) {
             db.issue(rsrc_p, stage, u);
-            // cut by chunk like the database side: a chunk past Kb would be the next query's codes
-            dma16(rsrc_q, stage + kStripSlab + lw * kStripPiece, (u == db.last && qchunk >= db.keep) ? kOOB : qvoff, u * kStripRow);
+            qs.issue(rsrc_q, stage + kStripSlab, u * kStripRow);
         });
         return;
     }
 
     const StripLane L(wave, lane);
-    const int r = tile * kStripRows + wave * 32 + L.lrow;    // the row's place in its list
-    const int n = list_off[l] + r;
+    const int r = it.r(wave, L), n = it.n(r);
     // the block bytes: 8 per slab and row, one slab ahead, on both sides (a row past the list reads the list's last row's:
     // its scores are not stored; an empty row of the group multiplies zeros under 127)
-    const uint8_t* erow = PE + (size_t)min(n, iend - 1) * ldpe;
-    int qmine = -1;
-    if (pbase + L.lrow < p1) {
-        const int q = pair_q[pbase + L.lrow];
-        if ((unsigned)q < (unsigned)Q) qmine = q;
-    }
+    const uint8_t* erow = PE + (size_t)min(n, it.iend - 1) * ldpe;
+    const int qmine = it.query(pair_q, L.lrow, Q);
     const uint8_t* qerow = QE + (size_t)max(qmine, 0) * ldqe;
     const uint32_t qnone = qmine < 0 ? 0xffffffffu : 0u;
     // byte s of a step's scale dword is block 2 s + lhi of the slab; in the last slab the blocks past Kb hold 127
@@ -128,44 +95,16 @@ __global__ void __launch_bounds__(768) ivf_scan_fp4_kernel(const uint8_t* __rest
         const uint32_t aexp[1] = {eq};
         fp4_slab_mma<1>(L, stage, aexp, eb, acc);
     });
-
-    // scattered epilogue: the lane's 16 pairs are the group rows L.qrow(0, g) + e
-    if (n < iend) {
-        const float sb = bscales[n];
-        const int id = ids[n];
-        // the 16 pairs of this lane in three rounds of independent loads (query, column; scale; then the stores)
-        int qv[16];
-        long cv[16];
-        float sq[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int pi = pbase + L.qrow(0, j >> 2) + (j & 3);
-            const bool ok = pi < p1;
-            qv[j] = ok ? pair_q[pi] : -1;
-            cv[j] = ok ? (long)pair_col[pi] + r : -1;
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            if ((unsigned)qv[j] >= (unsigned)Q || cv[j] >= width) cv[j] = -1;        // a table that does not fit: no store
-            sq[j] = cv[j] >= 0 ? qscales[qv[j]] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            if (cv[j] >= 0) {
-                out[(size_t)qv[j] * ldo + cv[j]] = __fmul_rn(__fmul_rn(acc[0][j], sq[j]), sb);
-                out_ids[(size_t)qv[j] * ldo + cv[j]] = id;
-            }
-    }
+    ivf_scatter<false>(it, L, r, pair_q, pair_col, qscales, nullptr, Q, bscales, ids, out, out_ids, ldo, width,
+                       [&](int j, int) __attribute__((always_inline)) { return acc[0][j]; });
 }
 
-// the scan's admission rules beyond the sizes (c_api.hip reports them): 16-byte pieces of codes and one 2 GB descriptor per
-// operand; one aligned 8-byte load of block bytes per slab and row on both sides, so their pitches cover whole slabs
+// the scan's admission rules beyond the sizes (c_api.hip reports them): ivf_scan_admissible for the codes; one aligned
+// 8-byte load of block bytes per slab and row on both sides, so their pitches cover whole slabs
 bool ivf_scan_fp4_admissible(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe, int Q, const uint8_t* bcodes,
                              int ldb, const uint8_t* bexps, int ldbe, int D) {
-    return ((ldq | ldb) & 15) == 0 && ((((uintptr_t)qcodes) | ((uintptr_t)bcodes)) & 15) == 0 &&
-           (size_t)ldb * kStripRows < (1ull << 31) && (size_t)ldq * (size_t)(Q > 0 ? Q : 1) < (1ull << 31) &&
-           ((ldqe | ldbe) & 7) == 0 && ((((uintptr_t)qexps) | ((uintptr_t)bexps)) & 7) == 0 && ldqe >= 8 * fp4_slabs(D) &&
-           ldbe >= 8 * fp4_slabs(D);
+    return ivf_scan_admissible(qcodes, ldq, Q, bcodes, ldb) && ((ldqe | ldbe) & 7) == 0 &&
+           ((((uintptr_t)qexps) | ((uintptr_t)bexps)) & 7) == 0 && ldqe >= 8 * fp4_slabs(D) && ldbe >= 8 * fp4_slabs(D);
 }
 
 int ivf_scan_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe, const float* qscales, int Q,
@@ -173,14 +112,7 @@ int ivf_scan_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe,
                  int D, const int* list_off, int nlist, const int* pair_off, const int* pair_q, const int* pair_col,
                  const int* item_off, int items, float* scores, int* out_ids, int lds, int width, hipStream_t stream) {
     if (Q <= 0 || width <= 0) return DIR_OK;
-    const long total = (long)Q * width;
-    // (refused, not cut: as in ivf_scan_i8, Q * width >= 2^32 means score and id rows of 32 GiB for one chunk)
-    if (!launch_fits((total + 255) / 256, 256))
-        return fail(DIR_ERR_INVALID, "ivf_scan_fp4: Q * width must stay below 2^32 (one thread per id slot): cut the queries");
-    if (!launch_fits(items, 768))
-        return fail(DIR_ERR_INVALID, "ivf_scan_fp4: items * 768 must stay below 2^32 (768 threads per item): cut the queries");
-    hipLaunchKernelGGL(fill_ids_fp4_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, out_ids, lds, width, total);
-    DIR_HIP_CHECK(hipGetLastError());
+    DIR_CHECK(ivf_scan_begin("ivf_scan_fp4", Q, width, items, out_ids, lds, stream));
     if (items <= 0 || N <= 0) return DIR_OK;
     const int Kb = pad64(D) / 2, T = fp4_slabs(D);
     static std::atomic<uint64_t> attr_done{0};

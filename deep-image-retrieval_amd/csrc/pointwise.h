@@ -82,7 +82,11 @@ int similarity_bin(const int8_t* qcodes, int ldq, const float* qscales, int Q, c
 // the inverted-file int8 index (ivf.hip): the sums of a k-means step, the scan of the probed lists
 int segment_sums(const float* X, int ldx, int N, int D, const int* order, const int* seg_off, int S, float* sums, int lds,
                  hipStream_t stream);
-bool ivf_scan_i8_admissible(const int8_t* qcodes, int ldq, int Q, const int8_t* bcodes, int ldb);
+// ... and what the three list-major scans share on the host: the admission rule of their code operands (16-byte pieces,
+// one 2 GB descriptor each) and the step before their kernel (the two launch-extent refusals under the entry's name `who`,
+// then id -1 in every slot)
+bool ivf_scan_admissible(const void* qcodes, int ldq, int Q, const void* bcodes, int ldb);
+int ivf_scan_begin(const char* who, long Q, int width, int items, int* out_ids, int lds, hipStream_t stream);
 int ivf_scan_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, const int8_t* bcodes, int ldb,
                 const float* bscales, const int* ids, int N, int D, const int* list_off, int nlist, const int* pair_off,
                 const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,
@@ -101,7 +105,6 @@ int ivf_plan(const int* probe, int Q, int nprobe, const int* list_off, int nlist
 // the inverted file over sign-bit rows (ivf_bin.hip): the list-major scan of the probed lists on the int8 matrix cores;
 // code_sums (index_bin.hip): the query sums it takes, the launch of code_sums_kernel
 int code_sums(const int8_t* qcodes, int ldq, int Q, int D, int* qsums, hipStream_t stream);
-bool ivf_scan_bin_admissible(const int8_t* qcodes, int ldq, int Q, const uint8_t* bits, int ldb);
 int ivf_scan_bin(const int8_t* qcodes, int ldq, const float* qscales, const int* qsums, int Q, const uint8_t* bits, int ldb,
                  const float* bscales, const int* ids, int N, int D, const int* list_off, int nlist, const int* pair_off,
                  const int* pair_q, const int* pair_col, const int* item_off, int items, float* scores, int* out_ids,

@@ -1,5 +1,5 @@
 // strip_stream.h — the row-strip LDS-DMA pipeline of the scan kernels (sim_split.hip, index_i8.hip, index_fp4.hip,
-// index_bin.hip, ivf.hip, ivf_fp4.hip, ivf_bin.hip), once.
+// index_bin.hip, and through ivf_scan.h the list-major scans ivf.hip, ivf_fp4.hip, ivf_bin.hip), once.
 //
 // One workgroup per 256 database rows.  Eight consumer waves own a 32-row strip each and multiply it against the query
 // rows of the stage; four loader waves (8 .. 11) only issue LDS-DMA and wait for it.  A stage is 32 KB of database (256
@@ -255,12 +255,12 @@ __host__ __device__ inline int fp4_slabs(int D) { return (pad64(D) + kFp4SlabK -
 // The database side of a loader wave: StripLoader's pieces with a cut by chunk.  Kb (bytes of codes in a row, a multiple
 // of 32; of 16 for rows of bits) leaves 2, 4, 6 or 8 (bits: 1 .. 8) chunks in the last slab; as the scalar offset takes no
 // part in the range check, a lane whose chunk lies past Kb asks for an address that is out of range by itself.
-struct Fp4Loader {
+struct ChunkCutLoader {
     uint32_t pvoff[8];
     uint32_t chunks = 0;     // 3 bits per piece: this lane's chunk of piece i
     int lw, last, keep;      // the last slab and how many chunks of it exist
 
-    __device__ __forceinline__ Fp4Loader(int lw_, int lane, uint32_t pitch, int Kb, int T)
+    __device__ __forceinline__ ChunkCutLoader(int lw_, int lane, uint32_t pitch, int Kb, int T)
         : lw(lw_), last(T - 1), keep((Kb - (T - 1) * kStripRow) >> 4) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -328,7 +328,7 @@ __device__ __forceinline__ void fp4_slab_mma(const StripLane& L, const char* sta
 
 // ---- sign bits ---------------------------------------------------------------------------------------------------------
 // A 128-byte stage row of bits is 1024 k, eight times what a stage row of int8 query codes holds, so the two operands ride
-// in two rings: the database ring keeps the 32 KB slabs above (Fp4Loader's pieces and cut by chunk: a row of bits is a
+// in two rings: the database ring keeps the 32 KB slabs above (ChunkCutLoader's pieces and cut by chunk: a row of bits is a
 // multiple of 16 bytes, 1 .. 8 chunks in the last slab), the query ring holds index_i8.hip's 12 KB images of 128 k, eight
 // of them to a database slab.  Sub-slab s of the walk is chunk s & 7 of slab s >> 3 on the database side.
 static constexpr int kBinSub = kQB * kStripRow;        // 12288: the query image of 128 k

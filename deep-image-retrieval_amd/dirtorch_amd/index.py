@@ -526,6 +526,35 @@ class _InvertedLists:
             centroids = torch.where(empty, centroids, sums)
         self._set_centroids(centroids)
 
+    def train(self, x, iters=10, seed=0, max_rows=None):
+        """The train of the inverted files (IVFPQIndex.train goes on from it).  Spherical Lloyd iterations on the rows of x
+        [n, D] (any kind add takes), or on a sorted np.random.RandomState(seed).choice sample of max_rows of them (default
+        256 * nlist) when x has more.  The initial
+        centroids are the rows np.sort(RandomState(seed).choice(n, nlist, replace=False)) of the sample; an iteration
+        assigns every row to its list, sums each list's members in fp32 (ops.segment_sums) and L2-normalises the sums;
+        an empty list keeps its centroid.  Bitwise reproducible.  Rows already added are not re-assigned: train first."""
+        self._check_train(x)
+        max_rows = 256 * self.nlist if max_rows is None else int(max_rows)
+        self._lloyd_centroids(_training_rows(x, seed, max_rows, self.nlist, 'nlist = %d' % self.nlist), iters, seed)
+        return self
+
+    def _add_lists(self, descs, names, encode):
+        """The add of an inverted file: every chunk x of ADD_CHUNK_BYTES is quantised to int8 and assigned to its lists,
+        encode(x, lists, codes, scales) -> its rows for the stores self.<names>, and the stores are regrouped (_regroup)."""
+        self._check_rows(descs)
+        self._need_trained('add')
+        if int(descs.shape[0]) == 0:
+            return self
+        lists, stores = [], [[getattr(self, name)] for name in names]
+        for x in _row_chunks(descs, self.D):
+            c, s = ops.quantize_rows(x)
+            lists.append(self._assign(c, s))
+            for store, part in zip(stores, encode(x, lists[-1], c, s)):
+                store.append(part)
+        for name, store in zip(names, self._regroup(lists, [torch.cat(store) for store in stores])):
+            setattr(self, name, store)
+        return self
+
     def _regroup(self, new_lists, stores):
         """After n rows were appended: new_lists, their lists (int32 tensors, in add order); stores, the per-row tensors
         with the new rows appended [N + n, ...].  A stable integer sort of the list indices, old rows first, so ids ascend
@@ -686,35 +715,13 @@ class IVFInt8Index(_InvertedLists, _CodedIndex):
         _CodedIndex.__init__(self, D)
         self._init_lists(nlist)
 
-    def train(self, x, iters=10, seed=0, max_rows=None):
-        """Spherical Lloyd iterations on the rows of x [n, D] (any kind add takes), or on a sorted
-        np.random.RandomState(seed).choice sample of max_rows of them (default 256 * nlist) when x has more.  The initial
-        centroids are the rows np.sort(RandomState(seed).choice(n, nlist, replace=False)) of the sample; an iteration
-        assigns every row to its list, sums each list's members in fp32 (ops.segment_sums) and L2-normalises the sums;
-        an empty list keeps its centroid.  Bitwise reproducible.  Rows already added are not re-assigned: train first."""
-        self._check_train(x)
-        max_rows = 256 * self.nlist if max_rows is None else int(max_rows)
-        self._lloyd_centroids(_training_rows(x, seed, max_rows, self.nlist, 'nlist = %d' % self.nlist), iters, seed)
-        return self
-
     def add(self, descs):
         """Append the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap), quantised in chunks of
         ADD_CHUNK_BYTES as Int8Index.add does; their ids continue the count.  The store is regrouped by a stable integer
         sort of the list indices (old rows first, so ids ascend inside a list): what the index holds does not depend on
         how the rows were cut into calls.  The regrouping copies the codes once (twice the index's bytes for a moment)
         and reads the list lengths back to the host."""
-        self._check_rows(descs)
-        self._need_trained('add')
-        if int(descs.shape[0]) == 0:
-            return self
-        lists, codes, scales = [], [self.codes], [self.scales]
-        for x in _row_chunks(descs, self.D):
-            c, s = ops.quantize_rows(x)
-            lists.append(self._assign(c, s))
-            codes.append(c)
-            scales.append(s)
-        self.codes, self.scales = self._regroup(lists, [torch.cat(codes), torch.cat(scales)])
-        return self
+        return self._add_lists(descs, ('codes', 'scales'), lambda x, lists, c, s: (c, s))
 
     def _scan_lists(self, q, qc, qs, probe, col_off, rows, width, tables):
         return ops.ivf_scan(qc[rows], qs[rows], self.codes, self.scales, self.ids, self.list_off, probe, col_off, self.D,
@@ -760,30 +767,11 @@ class IVFFp4Index(_InvertedLists, _CodedIndex):
         """the bytes the database rows take on the device: codes, block bytes, scales and ids (centroids not counted)"""
         return sum(int(t.numel()) * t.element_size() for t in (self.codes, self.exps, self.scales, self.ids))
 
-    def train(self, x, iters=10, seed=0, max_rows=None):
-        """IVFInt8Index.train: the same sample, the same iterations, the same centroids bit for bit."""
-        self._check_train(x)
-        max_rows = 256 * self.nlist if max_rows is None else int(max_rows)
-        self._lloyd_centroids(_training_rows(x, seed, max_rows, self.nlist, 'nlist = %d' % self.nlist), iters, seed)
-        return self
-
     def add(self, descs):
         """IVFInt8Index.add's contract: a chunk of ADD_CHUNK_BYTES is quantised to int8 for its assignment and to fp4 for
         the store, and the three stores are regrouped by that class's stable integer sort, so what the index holds does
         not depend on how the rows were cut into calls."""
-        self._check_rows(descs)
-        self._need_trained('add')
-        if int(descs.shape[0]) == 0:
-            return self
-        lists, codes, exps, scales = [], [self.codes], [self.exps], [self.scales]
-        for x in _row_chunks(descs, self.D):
-            lists.append(self._assign(*ops.quantize_rows(x)))
-            c, e, s = ops.quantize_rows_fp4(x)
-            codes.append(c)
-            exps.append(e)
-            scales.append(s)
-        self.codes, self.exps, self.scales = self._regroup(lists, [torch.cat(codes), torch.cat(exps), torch.cat(scales)])
-        return self
+        return self._add_lists(descs, ('codes', 'exps', 'scales'), lambda x, lists, c, s: ops.quantize_rows_fp4(x))
 
     def _scan_lists(self, q, qc, qs, probe, col_off, rows, width, tables):
         fc, fe, fs = ops.quantize_rows_fp4(q[rows])
@@ -829,29 +817,11 @@ class IVFBinaryIndex(_InvertedLists, _CodedIndex):
         """the bytes the database rows take on the device: bits, scales and ids (centroids not counted)"""
         return sum(int(t.numel()) * t.element_size() for t in (self.codes, self.scales, self.ids))
 
-    def train(self, x, iters=10, seed=0, max_rows=None):
-        """IVFInt8Index.train: the same sample, the same iterations, the same centroids bit for bit."""
-        self._check_train(x)
-        max_rows = 256 * self.nlist if max_rows is None else int(max_rows)
-        self._lloyd_centroids(_training_rows(x, seed, max_rows, self.nlist, 'nlist = %d' % self.nlist), iters, seed)
-        return self
-
     def add(self, descs):
         """IVFInt8Index.add's contract: a chunk of ADD_CHUNK_BYTES is quantised to int8 for its assignment and to sign bits
         for the store, and the two stores are regrouped by that class's stable integer sort, so what the index holds does
         not depend on how the rows were cut into calls."""
-        self._check_rows(descs)
-        self._need_trained('add')
-        if int(descs.shape[0]) == 0:
-            return self
-        lists, codes, scales = [], [self.codes], [self.scales]
-        for x in _row_chunks(descs, self.D):
-            lists.append(self._assign(*ops.quantize_rows(x)))
-            c, s = ops.quantize_rows_bin(x)
-            codes.append(c)
-            scales.append(s)
-        self.codes, self.scales = self._regroup(lists, [torch.cat(codes), torch.cat(scales)])
-        return self
+        return self._add_lists(descs, ('codes', 'scales'), lambda x, lists, c, s: ops.quantize_rows_bin(x))
 
     def _scan_lists(self, q, qc, qs, probe, col_off, rows, width, tables):
         # the int8 codes that probed the lists score their rows too: only their sums are new
@@ -979,16 +949,8 @@ class IVFPQIndex(_InvertedLists, _ProductQuantizer, _CodedIndex):
         a chunk is quantised and assigned as IVFInt8Index.add does, its residuals are encoded (ops.pq_encode), and the
         store is regrouped by that class's stable integer sort, so what the index holds does not depend on how the rows
         were cut into calls."""
-        self._check_rows(descs)
-        self._need_trained('add')
-        if int(descs.shape[0]) == 0:
-            return self
-        lists, codes = [], [self.codes]
-        for x in _row_chunks(descs, self.D):
-            lists.append(self._assign(*ops.quantize_rows(x)))
-            codes.append(ops.pq_encode(self._residuals(x, lists[-1]), self.codebooks))
-        self.codes, = self._regroup(lists, [torch.cat(codes)])
-        return self
+        return self._add_lists(descs, ('codes',),
+                               lambda x, lists, c, s: [ops.pq_encode(self._residuals(x, lists), self.codebooks)])
 
     _inverted_table = False      # the scan is cut query-major: it reads probe and col_off as they are
 

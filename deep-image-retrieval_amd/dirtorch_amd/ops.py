@@ -930,8 +930,8 @@ def ivf_plan(list_off, probe, items_bound):
     include/dir_engine.h gives the definition) -> (col_off [Q,nprobe] int32, tables, counts [2] int32), all CUDA.
     list_off [nlist+1] int32 CUDA, nlist <= 65535; probe [Q,nprobe] int32 CUDA, a list outside [0, nlist) = an empty slot,
     Q * nprobe <= ivf_plan_max_pairs().  col_off: the lists of a query side by side in probe order.  tables = (pair_off,
-    pair_q, pair_col, item_off, items_bound, None): what ivf_scan and ivf_scan_fp4 take as tables= TOGETHER WITH an
-    explicit width= (the reach is not known on the host) - the four tensors equal ivf_probe_tables' bit for bit.
+    pair_q, pair_col, item_off, items_bound, None): what ivf_scan, ivf_scan_fp4 and ivf_scan_bin take as tables= TOGETHER
+    WITH an explicit width= (the reach is not known on the host) - the four tensors equal ivf_probe_tables' bit for bit.
     items_bound: the grid of the scan, any host integer that is at least item_off[nlist] (the scans' surplus workgroups
     return at once) and at most ivf_scan_max_items() - the caller's duty, as the tables of ivf_scan are.  counts =
     (item_off[nlist], reach) stays on the device: for tests and measurements."""
@@ -961,6 +961,23 @@ def ivf_plan(list_off, probe, items_bound):
     else:
         pair_off.zero_(), item_off.zero_(), counts.zero_()
     return col_off.view(Q, nprobe), (pair_off, pair_q, pair_col, item_off, items_bound, None), counts
+
+
+def _ivf_scan(entry, front, Q, N, D, nlist, ids, list_off, probe, col_off, width, out, tables):
+    """What the three scans by list do after their own dtype and shape checks.  front: the entry's arguments up to the
+    database scales, as the library takes them (pointers of tensors the caller holds); the rest is the same for every entry:
+    ids, N, D, list_off, nlist, the inverted probe table (tables, or ivf_probe_tables' for this list_off, probe and col_off),
+    the outputs and the width."""
+    ids, list_off = ids.contiguous(), list_off.contiguous()
+    pair_off, pair_q, pair_col, item_off, items, reach = tables if tables is not None else ivf_probe_tables(list_off, probe, col_off)
+    if width is None and reach is None:
+        raise ValueError('tables of ivf_plan need an explicit width: their reach stays on the device')
+    width = reach if width is None else int(width)
+    scores, out_ids, lds = _scan_out(out, Q, width, ids.device)
+    if Q and width:
+        call(entry, *front, ptr(ids), N, D, ptr(list_off), nlist, ptr(pair_off), ptr(pair_q), ptr(pair_col), ptr(item_off), items,
+             ptr(scores), ptr(out_ids), lds, width, stream_ptr())
+    return scores[:, :width], out_ids[:, :width]
 
 
 def ivf_scan(qcodes, qscales, codes, scales, ids, list_off, probe, col_off, D, width=None, out=None, tables=None):
@@ -993,17 +1010,9 @@ def ivf_scan(qcodes, qscales, codes, scales, ids, list_off, probe, col_off, D, w
         raise ValueError('qscales [Q] and scales [N] expected for codes of Q and N rows')
     qcodes, ldq = _i8_codes(qcodes, ldc)
     codes, ldb = _i8_codes(codes, ldc)
-    qscales, scales, ids, list_off = qscales.contiguous(), scales.contiguous(), ids.contiguous(), list_off.contiguous()
-    pair_off, pair_q, pair_col, item_off, items, reach = tables if tables is not None else ivf_probe_tables(list_off, probe, col_off)
-    if width is None and reach is None:
-        raise ValueError('tables of ivf_plan need an explicit width: their reach stays on the device')
-    width = reach if width is None else int(width)
-    scores, out_ids, lds = _scan_out(out, Q, width, codes.device)
-    if Q and width:
-        call('dir_ivf_scan_i8', ptr(qcodes), ldq, ptr(qscales), Q, ptr(codes), ldb, ptr(scales), ptr(ids), N, D, ptr(list_off),
-             nlist, ptr(pair_off), ptr(pair_q), ptr(pair_col), ptr(item_off), items, ptr(scores),
-             ptr(out_ids), lds, width, stream_ptr())
-    return scores[:, :width], out_ids[:, :width]
+    qscales, scales = qscales.contiguous(), scales.contiguous()
+    return _ivf_scan('dir_ivf_scan_i8', (ptr(qcodes), ldq, ptr(qscales), Q, ptr(codes), ldb, ptr(scales)), Q, N, D, nlist, ids,
+                     list_off, probe, col_off, width, out, tables)
 
 
 # ---- the inverted file over fp4 codes (csrc/ivf_fp4.hip) ----------------------------------------------------------------
@@ -1016,7 +1025,7 @@ def ivf_scan_fp4(qcodes, qexps, qscales, codes, exps, scales, ids, list_off, pro
     r < len(list probe[q][p]), column col_off[q][p] + r carries similarity_fp4's score (acc * qscales[q]) * scales[n] and
     the id of row n = list_off[probe[q][p]] + r; a column no slot covers carries id -1; columns at or past width keep
     what they hold.  tables: ivf_probe_tables' result for these list_off, probe and col_off (the call then does not
-    synchronise with the host)."""
+    synchronise with the host), or ivf_plan's tables for this list_off and probe with its col_off and an explicit width."""
     _on_device(qcodes, qexps, qscales, codes, exps, scales, ids, list_off, probe, col_off, *(out or ()))
     for t in (qcodes, qexps, codes, exps):
         if t.dtype != torch.uint8 or t.dim() != 2:
@@ -1039,17 +1048,9 @@ def ivf_scan_fp4(qcodes, qexps, qscales, codes, exps, scales, ids, list_off, pro
     qexps, ldqe = _i8_codes(qexps, lde, align=8)
     codes, ldb = _i8_codes(codes, ldc)
     exps, ldbe = _i8_codes(exps, lde, align=8)
-    qscales, scales, ids, list_off = qscales.contiguous(), scales.contiguous(), ids.contiguous(), list_off.contiguous()
-    pair_off, pair_q, pair_col, item_off, items, reach = tables if tables is not None else ivf_probe_tables(list_off, probe, col_off)
-    if width is None and reach is None:
-        raise ValueError('tables of ivf_plan need an explicit width: their reach stays on the device')
-    width = reach if width is None else int(width)
-    scores, out_ids, lds = _scan_out(out, Q, width, codes.device)
-    if Q and width:
-        call('dir_ivf_scan_fp4', ptr(qcodes), ldq, ptr(qexps), ldqe, ptr(qscales), Q, ptr(codes), ldb, ptr(exps), ldbe,
-             ptr(scales), ptr(ids), N, D, ptr(list_off), nlist, ptr(pair_off), ptr(pair_q), ptr(pair_col), ptr(item_off),
-             items, ptr(scores), ptr(out_ids), lds, width, stream_ptr())
-    return scores[:, :width], out_ids[:, :width]
+    qscales, scales = qscales.contiguous(), scales.contiguous()
+    return _ivf_scan('dir_ivf_scan_fp4', (ptr(qcodes), ldq, ptr(qexps), ldqe, ptr(qscales), Q, ptr(codes), ldb, ptr(exps), ldbe,
+                                          ptr(scales)), Q, N, D, nlist, ids, list_off, probe, col_off, width, out, tables)
 
 
 # ---- the inverted file over sign-bit rows (csrc/ivf_bin.hip) ------------------------------------------------------------
@@ -1103,17 +1104,9 @@ def ivf_scan_bin(qcodes, qscales, bits, bscales, ids, list_off, probe, col_off, 
     qcodes, ldq = _i8_codes(qcodes, ldc)
     bits, ldb = _i8_codes(bits, ldb)
     qsums = code_sums(qcodes, D) if qsums is None else qsums.contiguous()
-    qscales, bscales, ids, list_off = qscales.contiguous(), bscales.contiguous(), ids.contiguous(), list_off.contiguous()
-    pair_off, pair_q, pair_col, item_off, items, reach = tables if tables is not None else ivf_probe_tables(list_off, probe, col_off)
-    if width is None and reach is None:
-        raise ValueError('tables of ivf_plan need an explicit width: their reach stays on the device')
-    width = reach if width is None else int(width)
-    scores, out_ids, lds = _scan_out(out, Q, width, bits.device)
-    if Q and width:
-        call('dir_ivf_scan_bin', ptr(qcodes), ldq, ptr(qscales), ptr(qsums), Q, ptr(bits), ldb, ptr(bscales), ptr(ids), N, D,
-             ptr(list_off), nlist, ptr(pair_off), ptr(pair_q), ptr(pair_col), ptr(item_off), items, ptr(scores), ptr(out_ids),
-             lds, width, stream_ptr())
-    return scores[:, :width], out_ids[:, :width]
+    qscales, bscales = qscales.contiguous(), bscales.contiguous()
+    return _ivf_scan('dir_ivf_scan_bin', (ptr(qcodes), ldq, ptr(qscales), ptr(qsums), Q, ptr(bits), ldb, ptr(bscales)), Q, N, D,
+                     nlist, ids, list_off, probe, col_off, width, out, tables)
 
 
 # ---- the product-quantised index (csrc/pq.hip) -------------------------------------------------------------------------

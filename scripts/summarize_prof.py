@@ -200,15 +200,15 @@ def bench_kernel_name(k):
             # the binary index: quantiser, query sums and scan (csrc/index_bin.hip; no timed bench.py step launches them)
             'quantize_rows_bin_kernel': 'l2norm_rows_kernel', 'code_sums_kernel': 'split_queries_kernel',
             'sim_bin_kernel': 'sim_split_lc_kernel',
-            # the inverted file: the sums of a k-means step, the id pre-fill and the scan of the probed lists (csrc/ivf.hip; no timed bench.py step launches them)
+            # the inverted file: the sums of a k-means step, the id pre-fill of the three list-major scans and the scan of the probed lists (csrc/ivf.hip; no timed bench.py step launches them)
             'segment_sums_kernel': 'expand_rows_kernel', 'fill_ids_kernel': 'fill_noise_kernel',
             'ivf_scan_i8_kernel': 'sim_split_lc_kernel',
-            # the inverted file over fp4 codes: its id pre-fill and list-major scan (csrc/ivf_fp4.hip; no timed bench.py step launches them)
-            'fill_ids_fp4_kernel': 'fill_noise_kernel', 'ivf_scan_fp4_kernel': 'sim_split_lc_kernel',
+            # the inverted file over fp4 codes: its list-major scan (csrc/ivf_fp4.hip; no timed bench.py step launches it)
+            'ivf_scan_fp4_kernel': 'sim_split_lc_kernel',
             # the probe tables of both scans by list, one workgroup (csrc/ivf_plan.hip; no timed bench.py step launches it): an integer sort
             'ivf_plan_kernel': 'rank_sort_kernel',
-            # the inverted file over sign-bit rows: its id pre-fill and list-major scan (csrc/ivf_bin.hip; no timed bench.py step launches them)
-            'fill_ids_bin_kernel': 'fill_noise_kernel', 'ivf_scan_bin_kernel': 'sim_split_lc_kernel',
+            # the inverted file over sign-bit rows: its list-major scan (csrc/ivf_bin.hip; no timed bench.py step launches it)
+            'ivf_scan_bin_kernel': 'sim_split_lc_kernel',
             # the product-quantised index: encoder, query tables and the table scan (csrc/pq.hip; no timed bench.py step launches them)
             'pq_encode_kernel': 'expand_rows_kernel', 'pq_lut_kernel': 'expand_rows_kernel', 'pq_scan_kernel': 'rank_hist_kernel',
             # IVF-PQ: the coarse terms and the query-major scan of the probed lists (csrc/ivfpq.hip; no timed bench.py step launches them)
