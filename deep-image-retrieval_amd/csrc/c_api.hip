@@ -5,6 +5,7 @@
 
 #include "engine.h"
 #include "pointwise.h"
+#include "strip_stream.h"
 
 namespace dir {
 const char* last_error();
@@ -877,23 +878,64 @@ int dir_label_rank(const float* scores, int lds, int Q, int N, const int* labels
 }
 
 int dir_index_i8_max_dim(void) { return index_i8_max_dim(); }
+int dir_index_fp4_max_dim(void) { return index_fp4_max_dim(); }
+int dir_index_bin_max_dim(void) { return index_bin_max_dim(); }
 
-static int index_check_dim(const char* who, int D) {
+// 1 <= D <= the widest row of a code format; max_name: the host query that gives it
+static int check_dim(const char* who, int D, int max, const char* max_name) {
     if (D < 1) return fail(DIR_ERR_INVALID, std::string(who) + ": D < 1");
-    if (D > index_i8_max_dim()) return fail(DIR_ERR_INVALID, std::string(who) + ": D exceeds dir_index_i8_max_dim()");
+    if (D > max) return fail(DIR_ERR_INVALID, std::string(who) + ": D exceeds " + max_name);
+    return DIR_OK;
+}
+static int index_check_dim(const char* who, int D) { return check_dim(who, D, index_i8_max_dim(), "dir_index_i8_max_dim()"); }
+static int fp4_check_dim(const char* who, int D) { return check_dim(who, D, index_fp4_max_dim(), "dir_index_fp4_max_dim()"); }
+static int bin_check_dim(const char* who, int D) { return check_dim(who, D, index_bin_max_dim(), "dir_index_bin_max_dim()"); }
+
+extern "C++" {   // (templates: the findings are callables)
+// What the entries of the three row quantisers check alike, in one order: the size, D (check_dim), ldx, the pitches of the
+// outputs (pitch_error() -> the entry's finding, or null) and - where there are rows - the pointers (null_pointer: one of the
+// entry's is missing) and the alignment of the store (align_error() -> the entry's finding, or null).  The two findings are
+// callables: they are worked out only behind the D check, so no width is computed from a D out of range.  An empty call
+// passes: the launcher returns on it.
+template <class Pitch, class Align>
+static int quantize_rows_check(const char* who, int (*check_dim)(const char*, int), int N, int D, int ldx, Pitch&& pitch_error,
+                               bool null_pointer, Align&& align_error) {
+    auto bad = [who](const char* what) { return fail(DIR_ERR_INVALID, std::string(who) + ": " + what); };
+    if (N < 0) return bad("negative size");
+    DIR_CHECK(check_dim(who, D));
+    if (ldx < D) return bad("ldx < D");
+    if (const char* what = pitch_error()) return bad(what);
+    if (N == 0) return DIR_OK;
+    if (null_pointer) return bad("null pointer");
+    if (const char* what = align_error()) return bad(what);
     return DIR_OK;
 }
 
+// ... and the entries of the three flat scans: the sizes, D, the pitches of the operands, lds and - where there is work - the
+// pointers and the admission rule of the scan (admission_error() -> the entry's finding, or null).
+template <class Pitch, class Admission>
+static int flat_scan_check(const char* who, int (*check_dim)(const char*, int), int Q, int N, int D, int lds, Pitch&& pitch_error,
+                           bool null_pointer, Admission&& admission_error) {
+    auto bad = [who](const char* what) { return fail(DIR_ERR_INVALID, std::string(who) + ": " + what); };
+    if (Q < 0 || N < 0) return bad("negative size");
+    DIR_CHECK(check_dim(who, D));
+    if (const char* what = pitch_error()) return bad(what);
+    if (lds < N) return bad("lds < N");
+    if (Q == 0 || N == 0) return DIR_OK;
+    if (null_pointer) return bad("null pointer");
+    if (const char* what = admission_error()) return bad(what);
+    return DIR_OK;
+}
+
+}  // extern "C++"
+
 int dir_quantize_rows_i8(const float* X, int ldx, int N, int D, int8_t* codes, int ldc, float* scales, void* stream) {
     DIR_TRY
-    if (N < 0) return fail(DIR_ERR_INVALID, "quantize_rows_i8: negative size");
-    DIR_CHECK(index_check_dim("quantize_rows_i8", D));
-    if (ldx < D) return fail(DIR_ERR_INVALID, "quantize_rows_i8: ldx < D");
-    if (ldc < pad64(D)) return fail(DIR_ERR_INVALID, "quantize_rows_i8: ldc < D rounded up to a multiple of 64");
-    if (N == 0) return DIR_OK;
-    if (!X || !codes || !scales) return fail(DIR_ERR_INVALID, "quantize_rows_i8: null pointer");
-    if ((ldc & 3) != 0 || ((uintptr_t)codes & 3) != 0)
-        return fail(DIR_ERR_INVALID, "quantize_rows_i8: ldc % 4 == 0 and 4-byte aligned codes");
+    DIR_CHECK(quantize_rows_check(
+        "quantize_rows_i8", index_check_dim, N, D, ldx,
+        [&]() -> const char* { return ldc < pad64(D) ? "ldc < D rounded up to a multiple of 64" : nullptr; },
+        !X || !codes || !scales,
+        [&]() -> const char* { return (ldc & 3) != 0 || ((uintptr_t)codes & 3) != 0 ? "ldc % 4 == 0 and 4-byte aligned codes" : nullptr; }));
     return quantize_rows_i8(X, ldx, N, D, codes, ldc, scales, (hipStream_t)stream);
     DIR_CATCH
 }
@@ -901,41 +943,31 @@ int dir_quantize_rows_i8(const float* X, int ldx, int N, int D, int8_t* codes, i
 int dir_similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, const int8_t* bcodes, int ldb,
                       const float* bscales, int N, int D, float* scores, int lds, void* stream) {
     DIR_TRY
-    if (Q < 0 || N < 0) return fail(DIR_ERR_INVALID, "similarity_i8: negative size");
-    DIR_CHECK(index_check_dim("similarity_i8", D));
-    if (ldq < D) return fail(DIR_ERR_INVALID, "similarity_i8: ldq < D");
-    if (ldb < pad64(D)) return fail(DIR_ERR_INVALID, "similarity_i8: ldb < D rounded up to a multiple of 64");
-    if (lds < N) return fail(DIR_ERR_INVALID, "similarity_i8: lds < N");
-    if (Q == 0 || N == 0) return DIR_OK;
-    if (!qcodes || !qscales || !bcodes || !bscales || !scores) return fail(DIR_ERR_INVALID, "similarity_i8: null pointer");
-    if (!similarity_i8_admissible(bcodes, ldb, D))
-        return fail(DIR_ERR_INVALID, "similarity_i8: ldb % 16 == 0, ldb < 2^23 and 16-byte aligned bcodes");
+    DIR_CHECK(flat_scan_check(
+        "similarity_i8", index_check_dim, Q, N, D, lds,
+        [&]() -> const char* {
+            return ldq < D ? "ldq < D" : ldb < pad64(D) ? "ldb < D rounded up to a multiple of 64" : nullptr;
+        },
+        !qcodes || !qscales || !bcodes || !bscales || !scores,
+        [&]() -> const char* {
+            return similarity_i8_admissible(bcodes, ldb, D) ? nullptr : "ldb % 16 == 0, ldb < 2^23 and 16-byte aligned bcodes";
+        }));
     return similarity_i8(qcodes, ldq, qscales, Q, bcodes, ldb, bscales, N, D, scores, lds, (hipStream_t)stream);
     DIR_CATCH
 }
 
-int dir_index_fp4_max_dim(void) { return index_fp4_max_dim(); }
-
-static int fp4_check_dim(const char* who, int D) {
-    if (D < 1) return fail(DIR_ERR_INVALID, std::string(who) + ": D < 1");
-    if (D > index_fp4_max_dim()) return fail(DIR_ERR_INVALID, std::string(who) + ": D exceeds dir_index_fp4_max_dim()");
-    return DIR_OK;
-}
-
-static int fp4_exps_width(int D) { return 8 * ceil_div(pad64(D), 256); }   // block bytes of whole slabs of 256 k
-
 int dir_quantize_rows_fp4(const float* X, int ldx, int N, int D, uint8_t* codes, int ldc, uint8_t* exps, int lde,
                           float* scales, void* stream) {
     DIR_TRY
-    if (N < 0) return fail(DIR_ERR_INVALID, "quantize_rows_fp4: negative size");
-    DIR_CHECK(fp4_check_dim("quantize_rows_fp4", D));
-    if (ldx < D) return fail(DIR_ERR_INVALID, "quantize_rows_fp4: ldx < D");
-    if (ldc < pad64(D) / 2) return fail(DIR_ERR_INVALID, "quantize_rows_fp4: ldc < half of D rounded up to a multiple of 64");
-    if (lde < fp4_exps_width(D)) return fail(DIR_ERR_INVALID, "quantize_rows_fp4: lde < 8 * ceil(D / 256)");
-    if (N == 0) return DIR_OK;
-    if (!X || !codes || !exps || !scales) return fail(DIR_ERR_INVALID, "quantize_rows_fp4: null pointer");
-    if ((ldc & 1) != 0 || ((uintptr_t)codes & 1) != 0)
-        return fail(DIR_ERR_INVALID, "quantize_rows_fp4: ldc % 2 == 0 and 2-byte aligned codes");
+    DIR_CHECK(quantize_rows_check(
+        "quantize_rows_fp4", fp4_check_dim, N, D, ldx,
+        [&]() -> const char* {
+            return ldc < pad64(D) / 2        ? "ldc < half of D rounded up to a multiple of 64"
+                   : lde < fp4_exp_bytes(D) ? "lde < 8 * ceil(D / 256)"
+                                            : nullptr;
+        },
+        !X || !codes || !exps || !scales,
+        [&]() -> const char* { return (ldc & 1) != 0 || ((uintptr_t)codes & 1) != 0 ? "ldc % 2 == 0 and 2-byte aligned codes" : nullptr; }));
     return quantize_rows_fp4(X, ldx, N, D, codes, ldc, exps, lde, scales, (hipStream_t)stream);
     DIR_CATCH
 }
@@ -944,44 +976,33 @@ int dir_similarity_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int
                        const uint8_t* bcodes, int ldb, const uint8_t* bexps, int ldbe, const float* bscales, int N, int D,
                        float* scores, int lds, void* stream) {
     DIR_TRY
-    if (Q < 0 || N < 0) return fail(DIR_ERR_INVALID, "similarity_fp4: negative size");
-    DIR_CHECK(fp4_check_dim("similarity_fp4", D));
-    if (ldq < (D + 1) / 2) return fail(DIR_ERR_INVALID, "similarity_fp4: ldq < ceil(D / 2)");
-    if (ldqe < ceil_div(D, 32)) return fail(DIR_ERR_INVALID, "similarity_fp4: ldqe < ceil(D / 32)");
-    if (ldb < pad64(D) / 2) return fail(DIR_ERR_INVALID, "similarity_fp4: ldb < half of D rounded up to a multiple of 64");
-    if (ldbe < fp4_exps_width(D)) return fail(DIR_ERR_INVALID, "similarity_fp4: ldbe < 8 * ceil(D / 256)");
-    if (lds < N) return fail(DIR_ERR_INVALID, "similarity_fp4: lds < N");
-    if (Q == 0 || N == 0) return DIR_OK;
-    if (!qcodes || !qexps || !qscales || !bcodes || !bexps || !bscales || !scores)
-        return fail(DIR_ERR_INVALID, "similarity_fp4: null pointer");
-    if (!similarity_fp4_admissible(bcodes, ldb, bexps, ldbe, D))
-        return fail(DIR_ERR_INVALID, "similarity_fp4: ldb % 16 == 0, ldb < 2^23 and 16-byte aligned bcodes, ldbe % 8 == 0 and "
-                                     "8-byte aligned bexps");
+    DIR_CHECK(flat_scan_check(
+        "similarity_fp4", fp4_check_dim, Q, N, D, lds,
+        [&]() -> const char* {
+            return ldq < (D + 1) / 2          ? "ldq < ceil(D / 2)"
+                   : ldqe < ceil_div(D, 32)   ? "ldqe < ceil(D / 32)"
+                   : ldb < pad64(D) / 2       ? "ldb < half of D rounded up to a multiple of 64"
+                   : ldbe < fp4_exp_bytes(D) ? "ldbe < 8 * ceil(D / 256)"
+                                              : nullptr;
+        },
+        !qcodes || !qexps || !qscales || !bcodes || !bexps || !bscales || !scores,
+        [&]() -> const char* {
+            return similarity_fp4_admissible(bcodes, ldb, bexps, ldbe, D)
+                       ? nullptr
+                       : "ldb % 16 == 0, ldb < 2^23 and 16-byte aligned bcodes, ldbe % 8 == 0 and 8-byte aligned bexps";
+        }));
     return similarity_fp4(qcodes, ldq, qexps, ldqe, qscales, Q, bcodes, ldb, bexps, ldbe, bscales, N, D, scores, lds,
                           (hipStream_t)stream);
     DIR_CATCH
 }
 
-int dir_index_bin_max_dim(void) { return index_bin_max_dim(); }
-
-static int bin_check_dim(const char* who, int D) {
-    if (D < 1) return fail(DIR_ERR_INVALID, std::string(who) + ": D < 1");
-    if (D > index_bin_max_dim()) return fail(DIR_ERR_INVALID, std::string(who) + ": D exceeds dir_index_bin_max_dim()");
-    return DIR_OK;
-}
-
-static int bin_width(int D) { return ceil_div(D, 128) * 16; }   // bytes of a row of bits: D rounded up to 128, divided by 8
-
 int dir_quantize_rows_bin(const float* X, int ldx, int N, int D, uint8_t* bits, int ldb, float* scales, void* stream) {
     DIR_TRY
-    if (N < 0) return fail(DIR_ERR_INVALID, "quantize_rows_bin: negative size");
-    DIR_CHECK(bin_check_dim("quantize_rows_bin", D));
-    if (ldx < D) return fail(DIR_ERR_INVALID, "quantize_rows_bin: ldx < D");
-    if (ldb < bin_width(D)) return fail(DIR_ERR_INVALID, "quantize_rows_bin: ldb < D rounded up to a multiple of 128, divided by 8");
-    if (N == 0) return DIR_OK;
-    if (!X || !bits || !scales) return fail(DIR_ERR_INVALID, "quantize_rows_bin: null pointer");
-    if ((ldb & 3) != 0 || ((uintptr_t)bits & 3) != 0)
-        return fail(DIR_ERR_INVALID, "quantize_rows_bin: ldb % 4 == 0 and 4-byte aligned bits");
+    DIR_CHECK(quantize_rows_check(
+        "quantize_rows_bin", bin_check_dim, N, D, ldx,
+        [&]() -> const char* { return ldb < bin_row_bytes(D) ? "ldb < D rounded up to a multiple of 128, divided by 8" : nullptr; },
+        !X || !bits || !scales,
+        [&]() -> const char* { return (ldb & 3) != 0 || ((uintptr_t)bits & 3) != 0 ? "ldb % 4 == 0 and 4-byte aligned bits" : nullptr; }));
     return quantize_rows_bin(X, ldx, N, D, bits, ldb, scales, (hipStream_t)stream);
     DIR_CATCH
 }
@@ -989,15 +1010,13 @@ int dir_quantize_rows_bin(const float* X, int ldx, int N, int D, uint8_t* bits, 
 int dir_similarity_bin(const int8_t* qcodes, int ldq, const float* qscales, int Q, const uint8_t* bits, int ldb,
                        const float* bscales, int N, int D, float* scores, int lds, void* stream) {
     DIR_TRY
-    if (Q < 0 || N < 0) return fail(DIR_ERR_INVALID, "similarity_bin: negative size");
-    DIR_CHECK(bin_check_dim("similarity_bin", D));
-    if (ldq < D) return fail(DIR_ERR_INVALID, "similarity_bin: ldq < D");
-    if (ldb < bin_width(D)) return fail(DIR_ERR_INVALID, "similarity_bin: ldb < D rounded up to a multiple of 128, divided by 8");
-    if (lds < N) return fail(DIR_ERR_INVALID, "similarity_bin: lds < N");
-    if (Q == 0 || N == 0) return DIR_OK;
-    if (!qcodes || !qscales || !bits || !bscales || !scores) return fail(DIR_ERR_INVALID, "similarity_bin: null pointer");
-    if (!similarity_bin_admissible(bits, ldb))
-        return fail(DIR_ERR_INVALID, "similarity_bin: ldb % 16 == 0, ldb < 2^23 and 16-byte aligned bits");
+    DIR_CHECK(flat_scan_check(
+        "similarity_bin", bin_check_dim, Q, N, D, lds,
+        [&]() -> const char* {
+            return ldq < D ? "ldq < D" : ldb < bin_row_bytes(D) ? "ldb < D rounded up to a multiple of 128, divided by 8" : nullptr;
+        },
+        !qcodes || !qscales || !bits || !bscales || !scores,
+        [&]() -> const char* { return flat_scan_admissible(bits, ldb) ? nullptr : "ldb % 16 == 0, ldb < 2^23 and 16-byte aligned bits"; }));
     return similarity_bin(qcodes, ldq, qscales, Q, bits, ldb, bscales, N, D, scores, lds, (hipStream_t)stream);
     DIR_CATCH
 }
@@ -1073,7 +1092,7 @@ int dir_ivf_scan_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int l
     DIR_CHECK(ivf_scan_check(
         "ivf_scan_fp4", fp4_check_dim, D, Q, N, nlist, items, width, lds,
         ldq < pad64(D) / 2 || ldb < pad64(D) / 2           ? "ldq, ldb < half of D rounded up to a multiple of 64"
-        : ldqe < fp4_exps_width(D) || ldbe < fp4_exps_width(D) ? "ldqe, ldbe < 8 * ceil(D / 256)"
+        : ldqe < fp4_exp_bytes(D) || ldbe < fp4_exp_bytes(D) ? "ldqe, ldbe < 8 * ceil(D / 256)"
                                                                : nullptr,
         scores, out_ids,
         !qcodes || !qexps || !qscales || !bcodes || !bexps || !bscales || !ids || !list_off || !pair_off || !pair_q || !pair_col ||
@@ -1106,7 +1125,7 @@ int dir_ivf_scan_bin(const int8_t* qcodes, int ldq, const float* qscales, const 
     DIR_CHECK(ivf_scan_check(
         "ivf_scan_bin", bin_check_dim, D, Q, N, nlist, items, width, lds,
         ldq < pad64(D)        ? "ldq < D rounded up to a multiple of 64"
-        : ldb < bin_width(D) ? "ldb < D rounded up to a multiple of 128, divided by 8"
+        : ldb < bin_row_bytes(D) ? "ldb < D rounded up to a multiple of 128, divided by 8"
                              : nullptr,
         scores, out_ids,
         !qcodes || !qscales || !qsums || !bits || !bscales || !ids || !list_off || !pair_off || !pair_q || !pair_col || !item_off,

@@ -24,7 +24,7 @@
 // D = 2048 (two slabs) the whole strip is resident after the prologue.  No K rotation: a row pitch of 256 bytes makes a
 // workgroup's strip one contiguous 64 KB, which spreads over the channels by itself.
 #include "dir_common.h"
-#include "strip_stream.h"
+#include "flat_scan.h"
 #include "pointwise.h"
 
 #pragma clang fp contract(off)   // the definition is in single IEEE operations: nothing here may fuse
@@ -32,11 +32,8 @@
 namespace dir {
 
 static constexpr int kBinMaxDim = 131072;          // 127 * 131072 = 16 646 144 < 2^24: (float)t is exact
-static constexpr int kBinQB = 96;                  // query rows per block
 
 int index_bin_max_dim() { return kBinMaxDim; }
-
-__host__ __device__ inline int bin_row_bytes(int D) { return ((D + 127) >> 7) * 16; }   // D rounded up to 128, in bits
 
 // ---- quantisation ------------------------------------------------------------------------------------------------------
 // One wave per row, quantize_rows_i8_kernel's walk: lane l owns the quads k = 256 j + 4 l + 0..3, j ascending, and its two
@@ -103,13 +100,9 @@ __global__ void __launch_bounds__(256) quantize_rows_bin_kernel(const float* __r
 }
 
 int quantize_rows_bin(const float* X, int ldx, int N, int D, uint8_t* bits, int ldb, float* scales, hipStream_t stream) {
-    if (N <= 0) return DIR_OK;
-    const long blocks = ((long)N + 3) / 4;
-    if (!launch_fits(blocks, 256))
-        return fail(DIR_ERR_INVALID, "quantize_rows_bin: N * 64 must stay below 2^32 (one wave per row): cut the rows");
-    hipLaunchKernelGGL(quantize_rows_bin_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, X, ldx, N, D, bits, ldb, scales);
-    DIR_HIP_CHECK(hipGetLastError());
-    return DIR_OK;
+    return rows_launch("quantize_rows_bin", "N", N, [&](unsigned blocks) {
+        hipLaunchKernelGGL(quantize_rows_bin_kernel, dim3(blocks), dim3(256), 0, stream, X, ldx, N, D, bits, ldb, scales);
+    });
 }
 
 // ---- the scan ----------------------------------------------------------------------------------------------------------
@@ -129,13 +122,9 @@ __global__ void __launch_bounds__(256) code_sums_kernel(const int8_t* __restrict
 
 // the sums of Q rows for a caller that keeps them (the list scan of ivf_bin.hip takes them as an argument)
 int code_sums(const int8_t* qcodes, int ldq, int Q, int D, int* qsums, hipStream_t stream) {
-    if (Q <= 0) return DIR_OK;
-    const long blocks = ((long)Q + 3) / 4;
-    if (!launch_fits(blocks, 256))
-        return fail(DIR_ERR_INVALID, "code_sums: Q * 64 must stay below 2^32 (one wave per row): cut the rows");
-    hipLaunchKernelGGL(code_sums_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qcodes, ldq, Q, D, Q, qsums);
-    DIR_HIP_CHECK(hipGetLastError());
-    return DIR_OK;
+    return rows_launch("code_sums", "Q", Q, [&](unsigned blocks) {
+        hipLaunchKernelGGL(code_sums_kernel, dim3(blocks), dim3(256), 0, stream, qcodes, ldq, Q, D, Q, qsums);
+    });
 }
 
 // S sub-slabs of 128 k = the 16-byte chunks of a row of bits; T = ceil(S / 8) database slabs.
@@ -192,15 +181,12 @@ __global__ void __launch_bounds__(768) sim_bin_kernel(const uint8_t* __restrict_
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile = blockIdx.x, qb = blockIdx.y;
-    const int i0 = tile * kStripRows;
-    const int rows = min(kStripRows, NP - i0);
+    const FlatFrame f(NP);
 
     if (wave >= 8) {
         const int lw = wave - 8;
-        // one descriptor per workgroup, based at its rows: Kb bytes of every row are readable
-        const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (uint32_t)(((size_t)rows - 1) * ldp + Kb));
-        const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc(img + (size_t)qb * S * kBinSub, (uint32_t)(S * kBinSub));
+        // Kb bytes of every row are readable
+        const __amdgpu_buffer_rsrc_t rsrc_p = f.database(P, ldp, Kb), rsrc_q = f.image(img, S, kBinSub);
         const ChunkCutLoader db(lw, lane, (uint32_t)ldp, Kb, T);
         if (T > 2)
             bin_load<true>(smem, lw, lane, rsrc_p, rsrc_q, db, S, T);
@@ -216,61 +202,31 @@ __global__ void __launch_bounds__(768) sim_bin_kernel(const uint8_t* __restrict_
         bin_sub_mma<3>(L, smem + ((s >> 3) % kBinDbStages) * kStripSlab, s & 7, smem + kBinQOff + (s % kBinQStages) * kBinSub, acc);
     }
 
-    const int n = i0 + wave * 32 + L.lrow;
-    if (n < NP) {
-        const float sb = bscales[n];
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int q = qb * kBinQB + L.qrow(j, g) + e;
-                    if (q < NQ) {
-                        const int t = 2 * acc[j][4 * g + e] - qsum[q];
-                        out[(size_t)q * ldo + n] = __fmul_rn(__fmul_rn((float)t, qscales[q]), sb);
-                    }
-                }
-    }
+    flat_store(f, L, f.n(wave, L), qscales, bscales, out, ldo, NQ, [&](int j, int i, int q) __attribute__((always_inline)) {
+        return (float)(2 * acc[j][i] - qsum[q]);
+    });
 }
 
 int similarity_bin(const int8_t* qcodes, int ldq, const float* qscales, int Q, const uint8_t* bits, int ldb,
                    const float* bscales, int N, int D, float* scores, int lds, hipStream_t stream) {
-    if (Q <= 0 || N <= 0) return DIR_OK;
-    const int Kb = bin_row_bytes(D), S = Kb / 16, T = ceil_div(S, 8), qblocks = ceil_div(Q, kBinQB);
-    if (qblocks > kMaxGridYZ) return fail(DIR_ERR_INVALID, "similarity_bin: more than 65535 * 96 queries in one call");
-    if (!launch_fits(ceil_div(N, kStripRows), 768))
-        return fail(DIR_ERR_INVALID, "similarity_bin: N * 3 must stay below 2^32 (768 threads per 256 rows): cut the database");
-    static std::atomic<uint64_t> attr_done{0};
-    DIR_HIP_CHECK(ensure_dynamic_lds((const void*)sim_bin_kernel, kBinLds, attr_done));
+    const int Kb = bin_row_bytes(D), S = Kb / 16, T = ceil_div(S, 8), qblocks = ceil_div(Q, kQB);
     // stream-ordered scratch: the query image, then the query sums of whole blocks
-    int8_t* img = nullptr;
     const size_t img_bytes = (size_t)qblocks * S * kBinSub;
-    if (hipMallocAsync((void**)&img, img_bytes + (size_t)qblocks * kBinQB * sizeof(int), stream) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(DIR_ERR_NOMEM, "similarity_bin: no stream-ordered scratch for the query image");
-    }
-    int* qsum = (int*)(img + img_bytes);
-    hipError_t e = code_image(qcodes, ldq, Q, D, img, S, qblocks, stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(code_sums_kernel, dim3(qblocks * kBinQB / 4), dim3(256), 0, stream, qcodes, ldq, Q, D,
-                           qblocks * kBinQB, qsum);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(sim_bin_kernel, dim3(ceil_div(N, kStripRows), qblocks), dim3(768), kBinLds, stream, bits, ldb, N, Kb,
-                           (const int8_t*)img, (const int*)qsum, qscales, bscales, scores, lds, Q, S, T);
-        e = hipGetLastError();
-    }
-    const hipError_t fe = hipFreeAsync(img, stream);
-    if (e == hipSuccess) e = fe;
-    DIR_HIP_CHECK(e);
-    return DIR_OK;
-}
-
-// the scan's admission rules beyond the sizes (c_api.hip reports them): 16-byte pieces, one 2 GB descriptor per tile
-bool similarity_bin_admissible(const uint8_t* bits, int ldb) {
-    return (ldb & 15) == 0 && (((uintptr_t)bits) & 15) == 0 && (size_t)ldb * kStripRows < (1ull << 31);
+    static std::atomic<uint64_t> attr_done{0};
+    return flat_scan_launch(
+        "similarity_bin", Q, N, img_bytes + (size_t)qblocks * kQB * sizeof(int), (const void*)sim_bin_kernel, kBinLds, attr_done,
+        stream,
+        [&](char* img) {
+            const hipError_t e = code_image(qcodes, ldq, Q, D, (int8_t*)img, S, qblocks, stream);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(code_sums_kernel, dim3(qblocks * kQB / 4), dim3(256), 0, stream, qcodes, ldq, Q, D, qblocks * kQB,
+                               (int*)(img + img_bytes));
+            return hipGetLastError();
+        },
+        [&](char* img, dim3 grid) {
+            hipLaunchKernelGGL(sim_bin_kernel, grid, dim3(768), kBinLds, stream, bits, ldb, N, Kb, (const int8_t*)img,
+                               (const int*)(img + img_bytes), qscales, bscales, scores, lds, Q, S, T);
+        });
 }
 
 }  // namespace dir

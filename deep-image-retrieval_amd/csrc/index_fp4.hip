@@ -21,7 +21,7 @@
 // cuts by chunk where StripLoader cuts by half (the codes pitch need not cover a whole slab); the block bytes' pitch does
 // cover whole slabs (8 * ceil(D / 256)), the bytes of the blocks past D rounded up to 64 are replaced by 127 in the kernel.
 #include "dir_common.h"
-#include "strip_stream.h"
+#include "flat_scan.h"
 #include "pointwise.h"
 
 #pragma clang fp contract(off)   // the definition is in single IEEE operations: nothing here may fuse
@@ -29,8 +29,7 @@
 namespace dir {
 
 static constexpr int kFp4MaxDim = 7281;            // 36 * 64 * 7281 = 16 775 424 < 2^24: every partial sum is exact in fp32
-static constexpr int kFp4QB = 96;                  // query rows per block
-static constexpr int kFp4SlabCodes = kFp4QB * kStripRow;          // 12288
+static constexpr int kFp4SlabCodes = kQB * kStripRow;             // 12288
 static constexpr int kFp4SlabQ = kFp4SlabCodes + kStripPiece;     // + the block bytes (768 of a 1 KiB piece)
 static constexpr int kFp4Stage = kStripSlab + kFp4SlabQ;
 static constexpr int kFp4Stages = 3;
@@ -109,14 +108,9 @@ __global__ void __launch_bounds__(256) quantize_rows_fp4_kernel(const float* __r
 
 int quantize_rows_fp4(const float* X, int ldx, int N, int D, uint8_t* codes, int ldc, uint8_t* exps, int lde, float* scales,
                       hipStream_t stream) {
-    if (N <= 0) return DIR_OK;
-    const long blocks = ((long)N + 3) / 4;
-    if (!launch_fits(blocks, 256))
-        return fail(DIR_ERR_INVALID, "quantize_rows_fp4: N * 64 must stay below 2^32 (one wave per row): cut the rows");
-    hipLaunchKernelGGL(quantize_rows_fp4_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, X, ldx, N, D, codes, ldc, exps, lde,
-                       scales);
-    DIR_HIP_CHECK(hipGetLastError());
-    return DIR_OK;
+    return rows_launch("quantize_rows_fp4", "N", N, [&](unsigned blocks) {
+        hipLaunchKernelGGL(quantize_rows_fp4_kernel, dim3(blocks), dim3(256), 0, stream, X, ldx, N, D, codes, ldc, exps, lde, scales);
+    });
 }
 
 // ---- the scan ----------------------------------------------------------------------------------------------------------
@@ -128,10 +122,10 @@ __global__ void __launch_bounds__(256) fp4_image_kernel(const uint8_t* __restric
                                                       uint8_t* __restrict__ img) {
     const int t = blockIdx.x, qb = blockIdx.y, T = gridDim.x;
     uint8_t* dst = img + ((size_t)qb * T + t) * kFp4SlabQ;
-    for (int item = threadIdx.x; item < kFp4QB * 8; item += 256) {
+    for (int item = threadIdx.x; item < kQB * 8; item += 256) {
         const int row = item >> 3, pos = item & 7;
         const int chunk = strip_chunk(pos, row);
-        const int q = qb * kFp4QB + row;
+        const int q = qb * kQB + row;
         const int k0 = t * kFp4SlabK + chunk * 32;
         u32x4_t w = {0u, 0u, 0u, 0u};
         if (q < Q) {
@@ -145,8 +139,8 @@ __global__ void __launch_bounds__(256) fp4_image_kernel(const uint8_t* __restric
     {
         const int item = threadIdx.x;                   // 256 dwords: 192 of block bytes, 64 of zeros
         uint32_t w = 0;
-        if (item < 2 * kFp4QB) {
-            const int lhi = item / kFp4QB, q = qb * kFp4QB + item % kFp4QB;
+        if (item < 2 * kQB) {
+            const int lhi = item / kQB, q = qb * kQB + item % kQB;
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const int b = t * 8 + s * 2 + lhi;
@@ -164,16 +158,13 @@ __global__ void __launch_bounds__(768) sim_fp4_kernel(const uint8_t* __restrict_
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile = blockIdx.x, qb = blockIdx.y;
-    const int i0 = tile * kStripRows;
-    const int rows = min(kStripRows, NP - i0);
-    const int rot = strip_rot(tile, T);
+    const FlatFrame f(NP);
+    const int rot = strip_rot(f.tile, T);
 
     if (wave >= 8) {
         const int lw = wave - 8;
-        // one descriptor per workgroup, based at its rows: Kb bytes of every row are readable
-        const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (uint32_t)(((size_t)rows - 1) * ldp + Kb));
-        const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc(img + (size_t)qb * T * kFp4SlabQ, (uint32_t)(T * kFp4SlabQ));
+        // Kb bytes of every row are readable
+        const __amdgpu_buffer_rsrc_t rsrc_p = f.database(P, ldp, Kb), rsrc_q = f.image(img, T, kFp4SlabQ);
         const ChunkCutLoader db(lw, lane, (uint32_t)ldp, Kb, T);
         // the image of a slab: 13 pieces; loader 0 takes the block bytes' piece with its three
         const bool four = lw == 0;
@@ -187,10 +178,9 @@ __global__ void __launch_bounds__(768) sim_fp4_kernel(const uint8_t* __restrict_
     }
 
     const StripLane L(wave, lane);
-    const int n = i0 + wave * 32 + L.lrow;
+    const int n = f.n(wave, L);
     // the row's block bytes: 8 per slab, one slab ahead (a row past NP reads the last row's; its scores are not stored)
     const uint8_t* erow = PE + (size_t)min(n, NP - 1) * ldpe;
-    const int sh = 8 * L.lhi;
     // byte s of a step's scale dword is block 2 s + lhi of the slab; in the last slab the blocks past Kb hold 127
     const int lastb = (Kb >> 4) - (T - 1) * 8;
     uint32_t pad = 0;
@@ -202,60 +192,35 @@ __global__ void __launch_bounds__(768) sim_fp4_kernel(const uint8_t* __restrict_
     strip_consume<kFp4Stage, kFp4Stages>(smem, T, rot, [&](const char* stage, int u) __attribute__((always_inline)) {
         const u32x2_t cur = nxt;
         if (++t < T) nxt = *(const u32x2_t*)(erow + 8 * strip_slab(t, rot, T));
-        uint32_t e = ((cur[0] >> sh) & 0xffu) | (((cur[0] >> (16 + sh)) & 0xffu) << 8) | (((cur[1] >> sh) & 0xffu) << 16) |
-                     (((cur[1] >> (16 + sh)) & 0xffu) << 24);
+        uint32_t e = fp4_pick_bytes(cur, L.lhi);
         if (u == T - 1) e = (e & ~pad) | (0x7f7f7f7fu & pad);
         fp4_slab_mma<3>(L, stage, e, acc);
     });
 
-    if (n < NP) {
-        const float sb = bscales[n];
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int q = qb * kFp4QB + L.qrow(j, g) + e;
-                    if (q < NQ) out[(size_t)q * ldo + n] = __fmul_rn(__fmul_rn(acc[j][4 * g + e], qscales[q]), sb);
-                }
-    }
+    flat_store(f, L, n, qscales, bscales, out, ldo, NQ, [&](int j, int i, int) __attribute__((always_inline)) { return acc[j][i]; });
 }
 
 int similarity_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe, const float* qscales, int Q,
                    const uint8_t* bcodes, int ldb, const uint8_t* bexps, int ldbe, const float* bscales, int N, int D,
                    float* scores, int lds, hipStream_t stream) {
-    if (Q <= 0 || N <= 0) return DIR_OK;
-    const int Kb = pad64(D) / 2, T = fp4_slabs(D), qblocks = ceil_div(Q, kFp4QB);
-    if (qblocks > kMaxGridYZ) return fail(DIR_ERR_INVALID, "similarity_fp4: more than 65535 * 96 queries in one call");
-    if (!launch_fits(ceil_div(N, kStripRows), 768))
-        return fail(DIR_ERR_INVALID, "similarity_fp4: N * 3 must stay below 2^32 (768 threads per 256 rows): cut the database");
+    const int Kb = pad64(D) / 2, T = fp4_slabs(D), qblocks = ceil_div(Q, kQB);
     static std::atomic<uint64_t> attr_done{0};
-    DIR_HIP_CHECK(ensure_dynamic_lds((const void*)sim_fp4_kernel, kFp4Lds, attr_done));
-    uint8_t* img = nullptr;
-    const size_t img_bytes = (size_t)qblocks * T * kFp4SlabQ;
-    if (hipMallocAsync((void**)&img, img_bytes, stream) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(DIR_ERR_NOMEM, "similarity_fp4: no stream-ordered scratch for the query image");
-    }
-    hipLaunchKernelGGL(fp4_image_kernel, dim3(T, qblocks), dim3(256), 0, stream, qcodes, ldq, qexps, ldqe, Q, D, img);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(sim_fp4_kernel, dim3(ceil_div(N, kStripRows), qblocks), dim3(768), kFp4Lds, stream, bcodes, ldb, bexps,
-                           ldbe, N, Kb, (const uint8_t*)img, qscales, bscales, scores, lds, Q, T);
-        e = hipGetLastError();
-    }
-    const hipError_t fe = hipFreeAsync(img, stream);
-    if (e == hipSuccess) e = fe;
-    DIR_HIP_CHECK(e);
-    return DIR_OK;
+    return flat_scan_launch(
+        "similarity_fp4", Q, N, (size_t)qblocks * T * kFp4SlabQ, (const void*)sim_fp4_kernel, kFp4Lds, attr_done, stream,
+        [&](char* img) {
+            hipLaunchKernelGGL(fp4_image_kernel, dim3(T, qblocks), dim3(256), 0, stream, qcodes, ldq, qexps, ldqe, Q, D, (uint8_t*)img);
+            return hipGetLastError();
+        },
+        [&](char* img, dim3 grid) {
+            hipLaunchKernelGGL(sim_fp4_kernel, grid, dim3(768), kFp4Lds, stream, bcodes, ldb, bexps, ldbe, N, Kb, (const uint8_t*)img,
+                               qscales, bscales, scores, lds, Q, T);
+        });
 }
 
-// the scan's admission rules beyond the sizes (c_api.hip reports them): 16-byte pieces, one 2 GB descriptor per tile, one
-// aligned 8-byte load of block bytes per slab
+// the scan's admission rules beyond the sizes (c_api.hip reports them): flat_scan_admissible's, and one aligned 8-byte load
+// of block bytes per slab
 bool similarity_fp4_admissible(const uint8_t* bcodes, int ldb, const uint8_t* bexps, int ldbe, int D) {
-    return (ldb & 15) == 0 && (((uintptr_t)bcodes) & 15) == 0 && (size_t)ldb * kStripRows < (1ull << 31) &&
-           (ldbe & 7) == 0 && (((uintptr_t)bexps) & 7) == 0 && ldbe >= 8 * fp4_slabs(D);
+    return flat_scan_admissible(bcodes, ldb) && (ldbe & 7) == 0 && (((uintptr_t)bexps) & 7) == 0 && ldbe >= fp4_exp_bytes(D);
 }
 
 }  // namespace dir

@@ -15,7 +15,7 @@
 // L2.  Three stages, two in flight; further query blocks on grid.y.  Rows are padded to 64 and not to a slab, hence the
 // loader's half-slab cut.  Bytes per launch: N * ldb (codes, once per query block) + Q * N * 4 (scores).
 #include "dir_common.h"
-#include "strip_stream.h"
+#include "flat_scan.h"
 #include "pointwise.h"
 
 #pragma clang fp contract(off)   // the definition is in single IEEE operations: nothing here may fuse
@@ -23,8 +23,7 @@
 namespace dir {
 
 static constexpr int kI8MaxDim = 131072;          // 127 * 127 * 131072 = 2 114 060 288 < 2^31
-static constexpr int kI8QB = 96;                  // query rows per block
-static constexpr int kI8SlabQ = kI8QB * kStripRow;    // 12288
+static constexpr int kI8SlabQ = kQB * kStripRow;      // 12288
 static constexpr int kI8Stage = kStripSlab + kI8SlabQ;
 static constexpr int kI8Stages = 3;
 static constexpr int kI8Lds = kI8Stages * kI8Stage;   // 135168 of 163840
@@ -89,13 +88,9 @@ __global__ void __launch_bounds__(256) quantize_rows_i8_kernel(const float* __re
 }
 
 int quantize_rows_i8(const float* X, int ldx, int N, int D, int8_t* codes, int ldc, float* scales, hipStream_t stream) {
-    if (N <= 0) return DIR_OK;
-    const long blocks = ((long)N + 3) / 4;
-    if (!launch_fits(blocks, 256))
-        return fail(DIR_ERR_INVALID, "quantize_rows_i8: N * 64 must stay below 2^32 (one wave per row): cut the rows");
-    hipLaunchKernelGGL(quantize_rows_i8_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, X, ldx, N, D, codes, ldc, scales);
-    DIR_HIP_CHECK(hipGetLastError());
-    return DIR_OK;
+    return rows_launch("quantize_rows_i8", "N", N, [&](unsigned blocks) {
+        hipLaunchKernelGGL(quantize_rows_i8_kernel, dim3(blocks), dim3(256), 0, stream, X, ldx, N, D, codes, ldc, scales);
+    });
 }
 
 // ---- the scan ----------------------------------------------------------------------------------------------------------
@@ -106,10 +101,10 @@ __global__ void __launch_bounds__(256) code_image_kernel(const int8_t* __restric
                                                        int8_t* __restrict__ img) {
     const int t = blockIdx.x, qb = blockIdx.y, T = gridDim.x;
     int8_t* dst = img + ((size_t)qb * T + t) * kI8SlabQ;
-    for (int item = threadIdx.x; item < kI8QB * 8; item += 256) {
+    for (int item = threadIdx.x; item < kQB * 8; item += 256) {
         const int row = item >> 3, pos = item & 7;
         const int chunk = strip_chunk(pos, row);
-        const int q = qb * kI8QB + row;
+        const int q = qb * kQB + row;
         const int k0 = t * kStripRow + chunk * 16;
         u32x4_t w = {0u, 0u, 0u, 0u};
         if (q < Q) {
@@ -135,16 +130,13 @@ __global__ void __launch_bounds__(768) sim_i8_kernel(const int8_t* __restrict__ 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile = blockIdx.x, qb = blockIdx.y;
-    const int i0 = tile * kStripRows;
-    const int rows = min(kStripRows, NP - i0);
-    const int rot = strip_rot(tile, T);
+    const FlatFrame f(NP);
+    const int rot = strip_rot(f.tile, T);
 
     if (wave >= 8) {
         const int lw = wave - 8;
-        // one descriptor per workgroup, based at its rows: Kp = D rounded up to 64 bytes of every row are readable
-        const __amdgpu_buffer_rsrc_t rsrc_p = buffer_rsrc(P + (size_t)i0 * ldp, (uint32_t)(((size_t)rows - 1) * ldp + Kp));
-        const __amdgpu_buffer_rsrc_t rsrc_q = buffer_rsrc(img + (size_t)qb * T * kI8SlabQ, (uint32_t)(T * kI8SlabQ));
+        // Kp = D rounded up to 64 bytes of every row are readable
+        const __amdgpu_buffer_rsrc_t rsrc_p = f.database(P, ldp, Kp), rsrc_q = f.image(img, T, kI8SlabQ);
         const StripLoader<true> db(lw, lane, (uint32_t)ldp, Kp, T);
         strip_load<kI8Stage, kI8Stages, 11>(smem, T, rot, [&](char* stage, int u) __attribute__((always_inline)) {
             db.issue(rsrc_p, stage, u);
@@ -160,52 +152,31 @@ __global__ void __launch_bounds__(768) sim_i8_kernel(const int8_t* __restrict__ 
         code_slab_mma<3>(L, stage, acc);
     });
 
-    const int n = i0 + wave * 32 + L.lrow;
-    if (n < NP) {
-        const float sb = bscales[n];
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int q = qb * kI8QB + L.qrow(j, g) + e;
-                    if (q < NQ) out[(size_t)q * ldo + n] = __fmul_rn(__fmul_rn((float)acc[j][4 * g + e], qscales[q]), sb);
-                }
-    }
+    flat_store(f, L, f.n(wave, L), qscales, bscales, out, ldo, NQ,
+               [&](int j, int i, int) __attribute__((always_inline)) { return (float)acc[j][i]; });
 }
 
 int similarity_i8(const int8_t* qcodes, int ldq, const float* qscales, int Q, const int8_t* bcodes, int ldb,
                   const float* bscales, int N, int D, float* scores, int lds, hipStream_t stream) {
-    if (Q <= 0 || N <= 0) return DIR_OK;
-    const int Kp = pad64(D), T = ceil_div(Kp, kStripRow), qblocks = ceil_div(Q, kI8QB);
-    if (qblocks > kMaxGridYZ) return fail(DIR_ERR_INVALID, "similarity_i8: more than 65535 * 96 queries in one call");
-    if (!launch_fits(ceil_div(N, kStripRows), 768))
-        return fail(DIR_ERR_INVALID, "similarity_i8: N * 3 must stay below 2^32 (768 threads per 256 rows): cut the database");
+    const int Kp = pad64(D), T = ceil_div(Kp, kStripRow), qblocks = ceil_div(Q, kQB);
     static std::atomic<uint64_t> attr_done{0};
-    DIR_HIP_CHECK(ensure_dynamic_lds((const void*)sim_i8_kernel, kI8Lds, attr_done));
-    int8_t* img = nullptr;
-    const size_t img_bytes = (size_t)qblocks * T * kI8SlabQ;
-    if (hipMallocAsync((void**)&img, img_bytes, stream) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(DIR_ERR_NOMEM, "similarity_i8: no stream-ordered scratch for the query image");
-    }
-    hipError_t e = code_image(qcodes, ldq, Q, D, img, T, qblocks, stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(sim_i8_kernel, dim3(ceil_div(N, kStripRows), qblocks), dim3(768), kI8Lds, stream, bcodes, ldb, N, Kp,
-                           (const int8_t*)img, qscales, bscales, scores, lds, Q, T);
-        e = hipGetLastError();
-    }
-    const hipError_t fe = hipFreeAsync(img, stream);
-    if (e == hipSuccess) e = fe;
-    DIR_HIP_CHECK(e);
-    return DIR_OK;
+    return flat_scan_launch(
+        "similarity_i8", Q, N, (size_t)qblocks * T * kI8SlabQ, (const void*)sim_i8_kernel, kI8Lds, attr_done, stream,
+        [&](char* img) { return code_image(qcodes, ldq, Q, D, (int8_t*)img, T, qblocks, stream); },
+        [&](char* img, dim3 grid) {
+            hipLaunchKernelGGL(sim_i8_kernel, grid, dim3(768), kI8Lds, stream, bcodes, ldb, N, Kp, (const int8_t*)img, qscales,
+                               bscales, scores, lds, Q, T);
+        });
 }
 
-// the scan's admission rules beyond the sizes (c_api.hip reports them): 16-byte pieces, one 2 GB descriptor per tile
+// the flat scans' admission rules beyond the sizes (c_api.hip reports them): 16-byte pieces, one 2 GB descriptor per tile
+bool flat_scan_admissible(const void* rows, int ldb) {
+    return (ldb & 15) == 0 && (((uintptr_t)rows) & 15) == 0 && (size_t)ldb * kStripRows < (1ull << 31);
+}
+
+// ... and one 2 GB descriptor for the image of a query block
 bool similarity_i8_admissible(const int8_t* bcodes, int ldb, int D) {
-    return (ldb & 15) == 0 && (((uintptr_t)bcodes) & 15) == 0 && (size_t)ldb * kStripRows < (1ull << 31) &&
-           (size_t)ceil_div(pad64(D), kStripRow) * kI8SlabQ < (1ull << 31);
+    return flat_scan_admissible(bcodes, ldb) && (size_t)ceil_div(pad64(D), kStripRow) * kI8SlabQ < (1ull << 31);
 }
 
 // ---- re-scoring a shortlist --------------------------------------------------------------------------------------------

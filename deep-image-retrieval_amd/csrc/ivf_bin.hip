@@ -33,8 +33,6 @@ static constexpr int kIvfBinStage = kStripSlab + 8 * kIvfSub;   // 65536: 1024 k
 static constexpr int kIvfBinStages = 2;
 static constexpr int kIvfBinLds = kIvfBinStages * kIvfBinStage;    // 131072 of 163840
 
-__host__ __device__ inline int ivf_bin_row_bytes(int D) { return ((D + 127) >> 7) * 16; }   // D rounded up to 128, in bits
-
 // The work item, the query gather and the epilogue: ivf_scan.h.
 // Kp: bytes of query codes in a row (pad64(D)); Kb: bytes of bits in a row; S = Kb / 16 sub-slabs, T = ceil(S / 8) slabs.
 __global__ void __launch_bounds__(768) ivf_scan_bin_kernel(const int8_t* __restrict__ qcodes, int ldq, const float* __restrict__ qscales,
@@ -87,7 +85,7 @@ int ivf_scan_bin(const int8_t* qcodes, int ldq, const float* qscales, const int*
     if (Q <= 0 || width <= 0) return DIR_OK;
     DIR_CHECK(ivf_scan_begin("ivf_scan_bin", Q, width, items, out_ids, lds, stream));
     if (items <= 0 || N <= 0) return DIR_OK;
-    const int Kp = pad64(D), Kb = ivf_bin_row_bytes(D), S = Kb / 16, T = ceil_div(S, 8);
+    const int Kp = pad64(D), Kb = bin_row_bytes(D), S = Kb / 16, T = ceil_div(S, 8);
     static std::atomic<uint64_t> attr_done{0};
     DIR_HIP_CHECK(ensure_dynamic_lds((const void*)ivf_scan_bin_kernel, kIvfBinLds, attr_done));
     hipLaunchKernelGGL(ivf_scan_bin_kernel, dim3((unsigned)items), dim3(768), kIvfBinLds, stream, qcodes, ldq, qscales, qsums, Q,

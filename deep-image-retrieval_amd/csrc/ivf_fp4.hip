@@ -104,7 +104,7 @@ __global__ void __launch_bounds__(768) ivf_scan_fp4_kernel(const uint8_t* __rest
 bool ivf_scan_fp4_admissible(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe, int Q, const uint8_t* bcodes,
                              int ldb, const uint8_t* bexps, int ldbe, int D) {
     return ivf_scan_admissible(qcodes, ldq, Q, bcodes, ldb) && ((ldqe | ldbe) & 7) == 0 &&
-           ((((uintptr_t)qexps) | ((uintptr_t)bexps)) & 7) == 0 && ldqe >= 8 * fp4_slabs(D) && ldbe >= 8 * fp4_slabs(D);
+           ((((uintptr_t)qexps) | ((uintptr_t)bexps)) & 7) == 0 && ldqe >= fp4_exp_bytes(D) && ldbe >= fp4_exp_bytes(D);
 }
 
 int ivf_scan_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldqe, const float* qscales, int Q,

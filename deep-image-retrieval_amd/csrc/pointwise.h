@@ -74,9 +74,11 @@ int similarity_fp4(const uint8_t* qcodes, int ldq, const uint8_t* qexps, int ldq
 // the binary descriptor index (index_bin.hip): sign bits + row scales, the scan on the int8 matrix cores against int8 queries
 // (code_image: index_i8.hip's query image [qblocks][T][96][128], the launch of its code_image_kernel)
 hipError_t code_image(const int8_t* qcodes, int ldq, int Q, int D, int8_t* img, int T, int qblocks, hipStream_t stream);
+// ... and the admission rule of the database operand of the three flat scans (index_i8.hip): 16-byte pieces, one 2 GB
+// descriptor per tile - the one condition of the binary index (their launchers are templates: flat_scan.h)
+bool flat_scan_admissible(const void* rows, int ldb);
 int index_bin_max_dim();
 int quantize_rows_bin(const float* X, int ldx, int N, int D, uint8_t* bits, int ldb, float* scales, hipStream_t stream);
-bool similarity_bin_admissible(const uint8_t* bits, int ldb);
 int similarity_bin(const int8_t* qcodes, int ldq, const float* qscales, int Q, const uint8_t* bits, int ldb,
                    const float* bscales, int N, int D, float* scores, int lds, hipStream_t stream);
 // the inverted-file int8 index (ivf.hip): the sums of a k-means step, the scan of the probed lists

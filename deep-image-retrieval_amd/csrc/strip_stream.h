@@ -251,6 +251,8 @@ typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 
 static constexpr int kFp4SlabK = 2 * kStripRow;    // 256 k in a stage row
 __host__ __device__ inline int fp4_slabs(int D) { return (pad64(D) + kFp4SlabK - 1) / kFp4SlabK; }
+// bytes of block bytes in a row: 8 per slab, whole slabs (the codes of a row are pad64(D) / 2 bytes)
+__host__ __device__ inline int fp4_exp_bytes(int D) { return 8 * fp4_slabs(D); }
 
 // The database side of a loader wave: StripLoader's pieces with a cut by chunk.  Kb (bytes of codes in a row, a multiple
 // of 32; of 16 for rows of bits) leaves 2, 4, 6 or 8 (bits: 1 .. 8) chunks in the last slab; as the scalar offset takes no
@@ -331,6 +333,7 @@ __device__ __forceinline__ void fp4_slab_mma(const StripLane& L, const char* sta
 // in two rings: the database ring keeps the 32 KB slabs above (ChunkCutLoader's pieces and cut by chunk: a row of bits is a
 // multiple of 16 bytes, 1 .. 8 chunks in the last slab), the query ring holds index_i8.hip's 12 KB images of 128 k, eight
 // of them to a database slab.  Sub-slab s of the walk is chunk s & 7 of slab s >> 3 on the database side.
+__host__ __device__ inline int bin_row_bytes(int D) { return ((D + 127) >> 7) * 16; }   // bytes of a row of bits: D rounded up to 128
 static constexpr int kBinSub = kQB * kStripRow;        // 12288: the query image of 128 k
 static constexpr int kBinDbStages = 3, kBinQStages = 4;
 static constexpr int kBinQOff = kBinDbStages * kStripSlab;

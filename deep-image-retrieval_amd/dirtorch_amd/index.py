@@ -171,21 +171,117 @@ def _padded_codes(path, codes, width, dtype, pitch):
     return store
 
 
+def _scales_of(path, f, N, rows):
+    """the saved `scales` of N rows -> fp32 CUDA; rows: how the message names what they belong to"""
+    if f['scales'].shape != (N,):
+        raise ValueError('%s: scales [N] expected for %s' % (path, rows))
+    return torch.from_numpy(f['scales'].astype(np.float32)).cuda()
+
+
+class _Int8Store:
+    """The code store of a format, once per format: `names`, the per-row CUDA tensors an index keeps (in the order its
+    quantiser returns and its scorer takes them), max_dim() the widest row, empty(D) -> those tensors with no rows,
+    quantize(x) -> those of the rows of a chunk, save(index) -> the store's arrays of a .npz, load(path, f, D) -> the tensors
+    from such arrays.  Here the int8 one: codes [N, D rounded up to 64] int8 (padding zero), scales [N] fp32."""
+    names = ('codes', 'scales')
+    max_dim = staticmethod(ops.index_i8_max_dim)
+    quantize = staticmethod(ops.quantize_rows)
+
+    @staticmethod
+    def empty(D):
+        return (torch.empty(0, _round_up(D, 64), dtype=torch.int8, device='cuda'),
+                torch.empty(0, dtype=torch.float32, device='cuda'))
+
+    @staticmethod
+    def save(index):
+        """`codes` [N, D] int8 (without the padding), `scales` [N] float32"""
+        return dict(codes=index.codes[:, :index.D].cpu().numpy(), scales=index.scales.cpu().numpy())
+
+    @staticmethod
+    def load(path, f, D):
+        codes = _padded_codes(path, f['codes'], D, np.int8, 64)
+        return codes, _scales_of(path, f, len(codes), 'codes [N, D]')
+
+
+class _Fp4Store:
+    """The fp4 store: codes [N, ldc] uint8, exps [N, lde] uint8, scales [N] fp32; (ldc, lde) = ops.fp4_widths(D)."""
+    names = ('codes', 'exps', 'scales')
+    max_dim = staticmethod(ops.index_fp4_max_dim)
+    quantize = staticmethod(ops.quantize_rows_fp4)
+
+    @staticmethod
+    def empty(D):
+        ldc, lde = ops.fp4_widths(D)
+        return (torch.empty(0, ldc, dtype=torch.uint8, device='cuda'), torch.empty(0, lde, dtype=torch.uint8, device='cuda'),
+                torch.empty(0, dtype=torch.float32, device='cuda'))
+
+    @staticmethod
+    def save(index):
+        """`codes` [N, ceil(D / 2)] uint8, `exps` [N, ceil(D / 32)] uint8 (both without the padding), `scales` [N] float32"""
+        nc, ne = (index.D + 1) // 2, (index.D + 31) // 32
+        return dict(codes=index.codes[:, :nc].cpu().numpy(), exps=index.exps[:, :ne].cpu().numpy(),
+                    scales=index.scales.cpu().numpy())
+
+    @staticmethod
+    def load(path, f, D):
+        ldc, lde = ops.fp4_widths(D)
+        codes = _padded_codes(path, f['codes'], (D + 1) // 2, np.uint8, ldc)
+        N, ne = len(codes), (D + 31) // 32
+        if f['exps'].dtype != np.uint8 or f['exps'].shape != (N, ne):
+            raise ValueError('%s: exps [N, %d] uint8 expected for codes of N rows' % (path, ne))
+        exps = torch.full((N, lde), 127, dtype=torch.uint8, device='cuda')
+        exps[:, :ne] = torch.from_numpy(f['exps']).cuda()
+        return codes, exps, _scales_of(path, f, N, 'codes [N, ...]')
+
+
+class _BinStore:
+    """The sign-bit store: the bits as codes [N, ops.bin_width(D)] uint8 (padding zero), scales [N] fp32."""
+    names = ('codes', 'scales')
+    max_dim = staticmethod(ops.index_bin_max_dim)
+    quantize = staticmethod(ops.quantize_rows_bin)
+
+    @staticmethod
+    def empty(D):
+        return (torch.empty(0, ops.bin_width(D), dtype=torch.uint8, device='cuda'),
+                torch.empty(0, dtype=torch.float32, device='cuda'))
+
+    @staticmethod
+    def save(index):
+        """`bits` [N, ceil(D / 8)] uint8 (without the padding), `scales` [N] float32"""
+        return dict(bits=index.codes[:, :(index.D + 7) // 8].cpu().numpy(), scales=index.scales.cpu().numpy())
+
+    @staticmethod
+    def load(path, f, D):
+        codes = _padded_codes(path, f['bits'], (D + 7) // 8, np.uint8, 16)
+        return codes, _scales_of(path, f, len(codes), 'bits [N, ...]')
+
+
 class _CodedIndex:
-    """What every index shares: `codes` [N, ldc], one row per database row, CUDA - int8 with ldc = D rounded up to 64 (padding
-    zero) and `scales` [N] fp32 for the int8 indexes, which is what the constructor makes, with their half of save and load;
-    the fp4 store (_init_fp4: codes, `exps` and scales) with its half of save and load for the two fp4 indexes;
-    the sign-bit store (_init_bin: bits as `codes`, and scales) with its half of save and load for the two binary indexes;
-    uint8 with ldc = M rounded up to 4 and scales None for the product-quantised ones, which replace both - what a search
+    """What every index shares: a code store (`_store`: one of the classes above, the int8 one unless a class says otherwise)
+    whose tensors - `codes` [N, ldc], one row per database row, and what the format keeps beside it - are attributes of the
+    index, made empty by the constructor, with the store's half of save and load (_save_store, _load_store); the
+    product-quantised indexes replace codes by uint8 ones with ldc = M rounded up to 4 and scales by None - what a search
     does around its scan (the argument checks, the fp32 re-rank of a shortlist) and the blocked scan loop."""
+
+    _store = _Int8Store
 
     def __init__(self, D):
         D = int(D)
-        if D < 1 or D > ops.index_i8_max_dim():
-            raise ValueError('1 <= D <= %d expected, got %d' % (ops.index_i8_max_dim(), D))
+        if D < 1 or D > self._store.max_dim():
+            raise ValueError('1 <= D <= %d expected, got %d' % (self._store.max_dim(), D))
         self.D = D
-        self.codes = torch.empty(0, _round_up(D, 64), dtype=torch.int8, device='cuda')
-        self.scales = torch.empty(0, dtype=torch.float32, device='cuda')
+        self._set_store(self._store.empty(D))
+
+    def _stored(self):
+        """the store's tensors, in the order of its names"""
+        return [getattr(self, name) for name in self._store.names]
+
+    def _set_store(self, tensors):
+        for name, t in zip(self._store.names, tensors):
+            setattr(self, name, t)
+
+    def _load_store(self, path, f):
+        self._set_store(self._store.load(path, f, self.D))
 
     def __len__(self):
         return int(self.codes.shape[0])
@@ -286,75 +382,22 @@ class _CodedIndex:
             out[r0:r1] = ops.gather_scores(q[r0:r1], picked, torch.from_numpy(local).cuda())
         return out
 
-    def _save_i8(self):
-        """the int8 store's arrays of a .npz: `codes` [N, D] int8 (without the padding), `scales` [N] float32"""
-        return dict(codes=self.codes[:, :self.D].cpu().numpy(), scales=self.scales.cpu().numpy())
 
-    def _load_i8(self, path, f):
-        self.codes = _padded_codes(path, f['codes'], self.D, np.int8, 64)
-        if f['scales'].shape != (len(self),):
-            raise ValueError('%s: scales [N] expected for codes [N, D]' % path)
-        self.scales = torch.from_numpy(f['scales'].astype(np.float32)).cuda()
+class _FlatIndex(_CodedIndex):
+    """add, search, save, load and nbytes of the flat coded indexes.  A class states its `_store`, `_code_queries` (fp32
+    queries -> the coded tensors of its scorer) and `_score(coded, r0, r1, b0, b1)`: the scores of the coded queries r0 .. r1
+    against the stored rows b0 .. b1, one ops.similarity_* call written out flat (it runs once per block of every search)."""
 
-    def _init_fp4(self, D):
-        """the empty fp4 store in place of the int8 one: codes [0, ldc] uint8, exps [0, lde] uint8, scales [0] fp32"""
-        D = int(D)
-        if D < 1 or D > ops.index_fp4_max_dim():
-            raise ValueError('1 <= D <= %d expected, got %d' % (ops.index_fp4_max_dim(), D))
-        self.D = D
-        ldc, lde = ops.fp4_widths(D)
-        self.codes = torch.empty(0, ldc, dtype=torch.uint8, device='cuda')
-        self.exps = torch.empty(0, lde, dtype=torch.uint8, device='cuda')
-        self.scales = torch.empty(0, dtype=torch.float32, device='cuda')
-
-    def _save_fp4(self):
-        """the fp4 store's arrays of a .npz: `codes` [N, ceil(D / 2)] uint8, `exps` [N, ceil(D / 32)] uint8 (both without the
-        padding), `scales` [N] float32"""
-        nc, ne = (self.D + 1) // 2, (self.D + 31) // 32
-        return dict(codes=self.codes[:, :nc].cpu().numpy(), exps=self.exps[:, :ne].cpu().numpy(),
-                    scales=self.scales.cpu().numpy())
-
-    def _load_fp4(self, path, f):
-        D = self.D
-        ldc, lde = ops.fp4_widths(D)
-        self.codes = _padded_codes(path, f['codes'], (D + 1) // 2, np.uint8, ldc)
-        if f['exps'].dtype != np.uint8 or f['exps'].shape != (len(self), (D + 31) // 32):
-            raise ValueError('%s: exps [N, %d] uint8 expected for codes of N rows' % (path, (D + 31) // 32))
-        self.exps = torch.full((len(self), lde), 127, dtype=torch.uint8, device='cuda')
-        self.exps[:, :(D + 31) // 32] = torch.from_numpy(f['exps']).cuda()
-        if f['scales'].shape != (len(self),):
-            raise ValueError('%s: scales [N] expected for codes [N, ...]' % path)
-        self.scales = torch.from_numpy(f['scales'].astype(np.float32)).cuda()
-
-    def _init_bin(self, D):
-        """the empty sign-bit store in place of the int8 one: codes [0, ops.bin_width(D)] uint8, scales [0] fp32"""
-        D = int(D)
-        if D < 1 or D > ops.index_bin_max_dim():
-            raise ValueError('1 <= D <= %d expected, got %d' % (ops.index_bin_max_dim(), D))
-        self.D = D
-        self.codes = torch.empty(0, ops.bin_width(D), dtype=torch.uint8, device='cuda')
-        self.scales = torch.empty(0, dtype=torch.float32, device='cuda')
-
-    def _save_bin(self):
-        """the sign-bit store's arrays of a .npz: `bits` [N, ceil(D / 8)] uint8 (without the padding), `scales` [N] float32"""
-        return dict(bits=self.codes[:, :(self.D + 7) // 8].cpu().numpy(), scales=self.scales.cpu().numpy())
-
-    def _load_bin(self, path, f):
-        self.codes = _padded_codes(path, f['bits'], (self.D + 7) // 8, np.uint8, 16)
-        if f['scales'].shape != (len(self),):
-            raise ValueError('%s: scales [N] expected for bits [N, ...]' % path)
-        self.scales = torch.from_numpy(f['scales'].astype(np.float32)).cuda()
-
-
-class Int8Index(_CodedIndex):
-    """codes [N, ldc] int8 (ldc = D rounded up to 64, padding zero) and scales [N] fp32, both CUDA."""
+    def nbytes(self):
+        """the bytes the database rows take on the device: the store's tensors"""
+        return sum(int(t.numel()) * t.element_size() for t in self._stored())
 
     def add(self, descs):
         """Append the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap).  They are quantised in
         chunks of ADD_CHUNK_BYTES, so a database that lives in a host file is never resident on the device as fp32."""
         self._check_rows(descs)
         if int(descs.shape[0]):
-            self.codes, self.scales = _appended([self.codes, self.scales], descs, self.D, ops.quantize_rows)
+            self._set_store(_appended(self._stored(), descs, self.D, self._store.quantize))
         return self
 
     def search(self, qdescs, k, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20, db_rows=None):
@@ -365,116 +408,62 @@ class Int8Index(_CodedIndex):
         or memmap has the candidates' rows gathered on the host in chunks of scratch_bytes - and vals carries the fp32
         scores of the k best of them."""
         def scan(q, keep):
-            qc, qs = ops.quantize_rows(q)
+            coded = self._code_queries(q)
 
             def scorer(r0, r1):
-                return lambda b0, b1: ops.similarity_i8(qc[r0:r1], qs[r0:r1], self.codes[b0:b1], self.scales[b0:b1], self.D)
+                return lambda b0, b1: self._score(coded, r0, r1, b0, b1)
             return self._scan_blocks(q.shape[0], keep, same_set, scratch_bytes, db_rows, scorer)
         return self._search(qdescs, k, rerank, source, same_set, scratch_bytes, scan)
 
     def save(self, path):
-        """One .npz: `codes` [N, D] int8 (without the padding), `scales` [N] float32, `D`."""
-        np.savez(path, D=np.int64(self.D), **self._save_i8())
+        """One .npz: the store's arrays (its save gives them) and `D`."""
+        np.savez(path, D=np.int64(self.D), **self._store.save(self))
 
     @classmethod
     def load(cls, path):
         f = _read_npz(path)
         index = cls(int(f['D']))
-        index._load_i8(path, f)
+        index._load_store(path, f)
         return index
 
 
-class Fp4Index(_CodedIndex):
+class Int8Index(_FlatIndex):
+    """codes [N, ldc] int8 (ldc = D rounded up to 64, padding zero) and scales [N] fp32, both CUDA.  save: one .npz of
+    `codes` [N, D] int8 (without the padding), `scales` [N] float32, `D`."""
+    _code_queries = staticmethod(ops.quantize_rows)
+
+    def _score(self, coded, r0, r1, b0, b1):
+        qc, qs = coded
+        return ops.similarity_i8(qc[r0:r1], qs[r0:r1], self.codes[b0:b1], self.scales[b0:b1], self.D)
+
+
+class Fp4Index(_FlatIndex):
     """The fp4 index (include/dir_engine.h gives the definition; numpy restatement: tests/fp4_ref.py): half of Int8Index's
     bytes.  codes [N, ldc] uint8 (two e2m1 values per byte), exps [N, lde] uint8 (one e8m0 byte per block of 32 values) and
     scales [N] fp32, all CUDA; (ldc, lde) = ops.fp4_widths(D).  A score is the exact inner product of the two dequantised
-    rows, so the lists do not depend on how the scan or the adds were cut."""
+    rows, so the lists do not depend on how the scan or the adds were cut.  save: one .npz of `codes` [N, ceil(D / 2)]
+    uint8, `exps` [N, ceil(D / 32)] uint8 (both without the padding), `scales` [N] float32, `D`."""
+    _store = _Fp4Store
+    _code_queries = staticmethod(ops.quantize_rows_fp4)
 
-    def __init__(self, D):
-        self._init_fp4(D)
-
-    def nbytes(self):
-        """the bytes the database rows take on the device: codes, block bytes and scales"""
-        return sum(int(t.numel()) * t.element_size() for t in (self.codes, self.exps, self.scales))
-
-    def add(self, descs):
-        """Int8Index.add's contract: the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap), quantised
-        in chunks of ADD_CHUNK_BYTES."""
-        self._check_rows(descs)
-        if int(descs.shape[0]):
-            self.codes, self.exps, self.scales = _appended([self.codes, self.exps, self.scales], descs, self.D,
-                                                           ops.quantize_rows_fp4)
-        return self
-
-    def search(self, qdescs, k, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20, db_rows=None):
-        """Int8Index.search's contract with the fp4 scores in place of the int8 ones: (idx [Q,k] int32, vals [Q,k] float32);
-        rerank = 0: ranked by the quantised scores; rerank = R: the R best are re-scored against `source` in fp32."""
-        def scan(q, keep):
-            qc, qe, qs = ops.quantize_rows_fp4(q)
-
-            def scorer(r0, r1):
-                return lambda b0, b1: ops.similarity_fp4(qc[r0:r1], qe[r0:r1], qs[r0:r1], self.codes[b0:b1], self.exps[b0:b1],
-                                                         self.scales[b0:b1], self.D)
-            return self._scan_blocks(q.shape[0], keep, same_set, scratch_bytes, db_rows, scorer)
-        return self._search(qdescs, k, rerank, source, same_set, scratch_bytes, scan)
-
-    def save(self, path):
-        """One .npz: `codes` [N, ceil(D / 2)] uint8, `exps` [N, ceil(D / 32)] uint8 (both without the padding), `scales` [N]
-        float32, `D`."""
-        np.savez(path, D=np.int64(self.D), **self._save_fp4())
-
-    @classmethod
-    def load(cls, path):
-        f = _read_npz(path)
-        index = cls(int(f['D']))
-        index._load_fp4(path, f)
-        return index
+    def _score(self, coded, r0, r1, b0, b1):
+        qc, qe, qs = coded
+        return ops.similarity_fp4(qc[r0:r1], qe[r0:r1], qs[r0:r1], self.codes[b0:b1], self.exps[b0:b1], self.scales[b0:b1], self.D)
 
 
-class BinaryIndex(_CodedIndex):
+class BinaryIndex(_FlatIndex):
     """The binary index (include/dir_engine.h gives the definition; numpy restatement: tests/bin_ref.py): one sign bit
     per value and one fp32 scale per row, a quarter of Fp4Index's bytes.  codes [N, ldb] uint8 (ldb = ops.bin_width(D),
     bit k & 7 of byte k >> 3, padding zero) and scales [N] fp32, both CUDA.  The queries are coded as Int8Index codes
     them, and a score is ((float)t * qscale) * scale with t an exact int32, so the lists do not depend on how the scan
-    or the adds were cut.  Its raw lists are coarse: pair it with rerank."""
+    or the adds were cut.  Its raw lists are coarse: pair it with rerank.  save: one .npz of `bits` [N, ceil(D / 8)] uint8
+    (without the padding), `scales` [N] float32, `D`."""
+    _store = _BinStore
+    _code_queries = staticmethod(ops.quantize_rows)
 
-    def __init__(self, D):
-        self._init_bin(D)
-
-    def nbytes(self):
-        """the bytes the database rows take on the device: bits (rows padded to 128 bits) and scales"""
-        return sum(int(t.numel()) * t.element_size() for t in (self.codes, self.scales))
-
-    def add(self, descs):
-        """Int8Index.add's contract: the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap), coded
-        in chunks of ADD_CHUNK_BYTES."""
-        self._check_rows(descs)
-        if int(descs.shape[0]):
-            self.codes, self.scales = _appended([self.codes, self.scales], descs, self.D, ops.quantize_rows_bin)
-        return self
-
-    def search(self, qdescs, k, rerank=0, source=None, same_set=False, scratch_bytes=256 << 20, db_rows=None):
-        """Int8Index.search's contract with the sign-bit scores in place of the int8 ones: (idx [Q,k] int32, vals [Q,k]
-        float32); rerank = 0: ranked by the quantised scores; rerank = R: the R best are re-scored against `source` in
-        fp32."""
-        def scan(q, keep):
-            qc, qs = ops.quantize_rows(q)
-
-            def scorer(r0, r1):
-                return lambda b0, b1: ops.similarity_bin(qc[r0:r1], qs[r0:r1], self.codes[b0:b1], self.scales[b0:b1], self.D)
-            return self._scan_blocks(q.shape[0], keep, same_set, scratch_bytes, db_rows, scorer)
-        return self._search(qdescs, k, rerank, source, same_set, scratch_bytes, scan)
-
-    def save(self, path):
-        """One .npz: `bits` [N, ceil(D / 8)] uint8 (without the padding), `scales` [N] float32, `D`."""
-        np.savez(path, D=np.int64(self.D), **self._save_bin())
-
-    @classmethod
-    def load(cls, path):
-        f = _read_npz(path)
-        index = cls(int(f['D']))
-        index._load_bin(path, f)
-        return index
+    def _score(self, coded, r0, r1, b0, b1):
+        qc, qs = coded
+        return ops.similarity_bin(qc[r0:r1], qs[r0:r1], self.codes[b0:b1], self.scales[b0:b1], self.D)
 
 
 class _InvertedLists:
@@ -705,15 +694,40 @@ class _ProductQuantizer:
         self.codebooks = torch.from_numpy(np.ascontiguousarray(codebooks, dtype=np.float32)).cuda()
 
 
-class IVFInt8Index(_InvertedLists, _CodedIndex):
-    """The inverted-file int8 index (include/dir_engine.h gives the definitions).  All CUDA: centroids [nlist, D] fp32 with
-    their codes `ccodes` and scales `cscales`; the database LIST-MAJOR - codes [N, ldc] int8, scales [N] fp32, ids [N] int32
-    (a row's number in add order: what Int8Index reports) - and list_off [nlist+1] int32, a CSR from 0 to N; inside a list
-    the rows are in ascending id."""
+class _InvertedFile(_InvertedLists, _CodedIndex):
+    """The constructor, nbytes, save and load of the three inverted files over a code store (`_store`); a class adds its add,
+    its _scan_lists and its search."""
 
     def __init__(self, D, nlist):
         _CodedIndex.__init__(self, D)
         self._init_lists(nlist)
+
+    def nbytes(self):
+        """the bytes the database rows take on the device: the store's tensors and ids (centroids not counted)"""
+        return sum(int(t.numel()) * t.element_size() for t in self._stored() + [self.ids])
+
+    def save(self, path):
+        """One .npz: the arrays of the flat index over the same store (`D` with them) and the lists' (`centroids` [nlist, D]
+        float32, `ids` [N] int32, `list_off` [nlist+1] int32, `nlist`).  The flat class's load reads the file as it lies: the
+        rows list-major, without their ids."""
+        self._need_trained('save')
+        np.savez(path, D=np.int64(self.D), **self._store.save(self), **self._save_lists())
+
+    @classmethod
+    def load(cls, path):
+        f = _read_npz(path)
+        index = cls(int(f['D']), int(f['nlist']))
+        index._load_store(path, f)
+        index._load_lists(path, f)
+        return index
+
+
+class IVFInt8Index(_InvertedFile):
+    """The inverted-file int8 index (include/dir_engine.h gives the definitions).  All CUDA: centroids [nlist, D] fp32 with
+    their codes `ccodes` and scales `cscales`; the database LIST-MAJOR - codes [N, ldc] int8, scales [N] fp32, ids [N] int32
+    (a row's number in add order: what Int8Index reports) - and list_off [nlist+1] int32, a CSR from 0 to N; inside a list
+    the rows are in ascending id.  save: one .npz of `centroids` [nlist, D] float32, `codes` [N, D] int8 (without the
+    padding), `scales` [N] float32, `ids` [N] int32, `list_off` [nlist+1] int32, `D`, `nlist`."""
 
     def add(self, descs):
         """Append the rows of descs [n, D] (fp32 CUDA tensor, CPU tensor, ndarray or memmap), quantised in chunks of
@@ -737,35 +751,15 @@ class IVFInt8Index(_InvertedLists, _CodedIndex):
         never waits for the host.  The lists are the same bits."""
         return self._search_lists(qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, 0, plan)
 
-    def save(self, path):
-        """One .npz: `centroids` [nlist, D] float32, `codes` [N, D] int8 (without the padding), `scales` [N] float32, `ids`
-        [N] int32, `list_off` [nlist+1] int32, `D`, `nlist`."""
-        self._need_trained('save')
-        np.savez(path, D=np.int64(self.D), **self._save_i8(), **self._save_lists())
 
-    @classmethod
-    def load(cls, path):
-        f = _read_npz(path)
-        index = cls(int(f['D']), int(f['nlist']))
-        index._load_i8(path, f)
-        index._load_lists(path, f)
-        return index
-
-
-class IVFFp4Index(_InvertedLists, _CodedIndex):
+class IVFFp4Index(_InvertedFile):
     """The inverted file over fp4 codes (include/dir_engine.h gives the definitions; numpy restatement: tests/ivffp4_ref.py).
     All CUDA: IVFInt8Index's coarse quantiser (centroids [nlist, D] fp32, `ccodes`, `cscales`: assignment and probing by the
     int8 score, so a row lands in the list IVFInt8Index puts it in) and the database LIST-MAJOR as Fp4Index stores a row -
     codes [N, ldc] uint8, exps [N, lde] uint8, scales [N] fp32, (ldc, lde) = ops.fp4_widths(D) - with ids [N] int32 and
-    list_off [nlist+1] int32; inside a list the rows are in ascending id."""
-
-    def __init__(self, D, nlist):
-        self._init_fp4(D)
-        self._init_lists(nlist)
-
-    def nbytes(self):
-        """the bytes the database rows take on the device: codes, block bytes, scales and ids (centroids not counted)"""
-        return sum(int(t.numel()) * t.element_size() for t in (self.codes, self.exps, self.scales, self.ids))
+    list_off [nlist+1] int32; inside a list the rows are in ascending id.  save: one .npz of Fp4Index's arrays and the
+    lists'."""
+    _store = _Fp4Store
 
     def add(self, descs):
         """IVFInt8Index.add's contract: a chunk of ADD_CHUNK_BYTES is quantised to int8 for its assignment and to fp4 for
@@ -787,35 +781,16 @@ class IVFFp4Index(_InvertedLists, _CodedIndex):
         ldc, lde = ops.fp4_widths(self.D)
         return self._search_lists(qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, ldc + lde + 4, plan)
 
-    def save(self, path):
-        """One .npz: Fp4Index's arrays (`codes` [N, ceil(D / 2)] uint8, `exps` [N, ceil(D / 32)] uint8, `scales` [N] float32,
-        `D`) and the lists' (`centroids` [nlist, D] float32, `ids` [N] int32, `list_off` [nlist+1] int32, `nlist`)."""
-        self._need_trained('save')
-        np.savez(path, D=np.int64(self.D), **self._save_fp4(), **self._save_lists())
 
-    @classmethod
-    def load(cls, path):
-        f = _read_npz(path)
-        index = cls(int(f['D']), int(f['nlist']))
-        index._load_fp4(path, f)
-        index._load_lists(path, f)
-        return index
-
-
-class IVFBinaryIndex(_InvertedLists, _CodedIndex):
+class IVFBinaryIndex(_InvertedFile):
     """The inverted file over sign-bit rows (include/dir_engine.h gives the definitions; numpy restatement:
     tests/ivfbin_ref.py).  All CUDA: IVFInt8Index's coarse quantiser (centroids [nlist, D] fp32, `ccodes`, `cscales`:
     assignment and probing by the int8 score, so a row lands in the list IVFInt8Index puts it in) and the database LIST-MAJOR
     as BinaryIndex stores a row - codes [N, ops.bin_width(D)] uint8, scales [N] fp32 - with ids [N] int32 and list_off
-    [nlist+1] int32; inside a list the rows are in ascending id.  Its raw lists are coarse: pair it with rerank."""
-
-    def __init__(self, D, nlist):
-        self._init_bin(D)
-        self._init_lists(nlist)
-
-    def nbytes(self):
-        """the bytes the database rows take on the device: bits, scales and ids (centroids not counted)"""
-        return sum(int(t.numel()) * t.element_size() for t in (self.codes, self.scales, self.ids))
+    [nlist+1] int32; inside a list the rows are in ascending id.  Its raw lists are coarse: pair it with rerank.  save: one
+    .npz of BinaryIndex's arrays and the lists'; BinaryIndex.load reads the file as it lies, the rows list-major, without
+    their ids."""
+    _store = _BinStore
 
     def add(self, descs):
         """IVFInt8Index.add's contract: a chunk of ADD_CHUNK_BYTES is quantised to int8 for its assignment and to sign bits
@@ -835,21 +810,6 @@ class IVFBinaryIndex(_InvertedLists, _CodedIndex):
         IVFInt8Index.search: 'host' synchronises once per chunk, inside ops.ivf_scan_bin; 'device' (and 'auto' where
         admissible) plans the chunk with ops.ivf_plan and does not."""
         return self._search_lists(qdescs, k, nprobe, rerank, source, same_set, scratch_bytes, 4, plan)
-
-    def save(self, path):
-        """One .npz: BinaryIndex's arrays (`bits` [N, ceil(D / 8)] uint8, `scales` [N] float32, `D`) and the lists'
-        (`centroids` [nlist, D] float32, `ids` [N] int32, `list_off` [nlist+1] int32, `nlist`).  BinaryIndex.load reads the
-        file as it lies: the rows list-major, without their ids."""
-        self._need_trained('save')
-        np.savez(path, D=np.int64(self.D), **self._save_bin(), **self._save_lists())
-
-    @classmethod
-    def load(cls, path):
-        f = _read_npz(path)
-        index = cls(int(f['D']), int(f['nlist']))
-        index._load_bin(path, f)
-        index._load_lists(path, f)
-        return index
 
 
 class PQIndex(_ProductQuantizer, _CodedIndex):

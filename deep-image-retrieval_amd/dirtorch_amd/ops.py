@@ -664,17 +664,33 @@ def _slot_ends(lens, probe, col_off):
     return col_off.long() + torch.where(probe >= 0, lens[probe.long().clamp(min=0)], lens.new_zeros(()))
 
 
-def quantize_rows(X):
-    """fp32 rows -> (codes int8 [N, ldc], scales fp32 [N]), both CUDA (dir_quantize_rows_i8; include/dir_engine.h gives
-    the definition): ldc = D rounded up to a multiple of 64, the padding bytes zero.  X [N,D] fp32 CUDA with unit column
-    stride and any row pitch."""
+def _rows_in(X, max_dim):
+    """the head of the row quantisers: fp32 CUDA rows [N, D] of 1 <= D <= max_dim -> (X as the library can address it, its row
+    pitch, N, D)"""
     _on_device(X)
     if X.dtype != torch.float32 or X.dim() != 2:
         raise TypeError('float32 rows [N,D] expected')
     N, D = X.shape
-    if D < 1 or D > index_i8_max_dim():
-        raise ValueError('1 <= D <= %d expected, got %d' % (index_i8_max_dim(), D))
+    if D < 1 or D > max_dim:
+        raise ValueError('1 <= D <= %d expected, got %d' % (max_dim, D))
     X, ldx = _rows_pitch(X, D)
+    return X, ldx, N, D
+
+
+def _scales_out(rows, qscales, Q, bscales, N, out, device):
+    """The tail of the flat similarity wrappers ahead of their library call: the shape check of the scales (rows: how its
+    message names the two sides), their contiguous form and out= -> (qscales, bscales, out, its row pitch)"""
+    if qscales.dim() != 1 or bscales.dim() != 1 or qscales.numel() != Q or bscales.numel() != N:
+        raise ValueError('scales [Q] and [N] expected for ' + rows)
+    out, lds = _score_out(out, Q, N, device)
+    return qscales.contiguous(), bscales.contiguous(), out, lds
+
+
+def quantize_rows(X):
+    """fp32 rows -> (codes int8 [N, ldc], scales fp32 [N]), both CUDA (dir_quantize_rows_i8; include/dir_engine.h gives
+    the definition): ldc = D rounded up to a multiple of 64, the padding bytes zero.  X [N,D] fp32 CUDA with unit column
+    stride and any row pitch."""
+    X, ldx, N, D = _rows_in(X, index_i8_max_dim())
     ldc = (D + 63) // 64 * 64
     codes = torch.empty(N, ldc, dtype=torch.int8, device=X.device)
     scales = torch.empty(N, dtype=torch.float32, device=X.device)
@@ -698,12 +714,9 @@ def similarity_i8(qcodes, qscales, bcodes, bscales, D, out=None):
     ldc = (D + 63) // 64 * 64
     if D < 1 or D > index_i8_max_dim() or qcodes.shape[1] < ldc or bcodes.shape[1] < ldc:
         raise ValueError('codes of a width of at least D rounded up to 64 expected, 1 <= D <= %d' % index_i8_max_dim())
-    if qscales.dim() != 1 or bscales.dim() != 1 or qscales.numel() != Q or bscales.numel() != N:
-        raise ValueError('scales [Q] and [N] expected for codes of Q and N rows')
     qcodes, ldq = _rows_pitch(qcodes, ldc)
     bcodes, ldb = _i8_codes(bcodes, ldc)
-    qscales, bscales = qscales.contiguous(), bscales.contiguous()
-    out, lds = _score_out(out, Q, N, bcodes.device)
+    qscales, bscales, out, lds = _scales_out('codes of Q and N rows', qscales, Q, bscales, N, out, bcodes.device)
     if Q and N:
         call('dir_similarity_i8', ptr(qcodes), ldq, ptr(qscales), Q, ptr(bcodes), ldb, ptr(bscales), N, D, ptr(out), lds,
              stream_ptr())
@@ -726,13 +739,7 @@ def quantize_rows_fp4(X):
     """fp32 rows -> (codes uint8 [N, ldc], exps uint8 [N, lde], scales fp32 [N]), all CUDA (dir_quantize_rows_fp4;
     include/dir_engine.h gives the definition): e2m1 codes two to a byte, one e8m0 byte per block of 32, one power of two
     per row; (ldc, lde) = fp4_widths(D), the padding written.  X [N,D] fp32 CUDA with unit column stride and any row pitch."""
-    _on_device(X)
-    if X.dtype != torch.float32 or X.dim() != 2:
-        raise TypeError('float32 rows [N,D] expected')
-    N, D = X.shape
-    if D < 1 or D > index_fp4_max_dim():
-        raise ValueError('1 <= D <= %d expected, got %d' % (index_fp4_max_dim(), D))
-    X, ldx = _rows_pitch(X, D)
+    X, ldx, N, D = _rows_in(X, index_fp4_max_dim())
     ldc, lde = fp4_widths(D)
     codes = torch.empty(N, ldc, dtype=torch.uint8, device=X.device)
     exps = torch.empty(N, lde, dtype=torch.uint8, device=X.device)
@@ -762,14 +769,11 @@ def similarity_fp4(qcodes, qexps, qscales, bcodes, bexps, bscales, D, out=None):
         raise ValueError('codes of %d and block bytes of %d columns at least expected for D = %d' % (ldc, lde, D))
     if qexps.shape[0] != Q or bexps.shape[0] != N:
         raise ValueError('block bytes of Q and N rows expected for codes of Q and N rows')
-    if qscales.dim() != 1 or bscales.dim() != 1 or qscales.numel() != Q or bscales.numel() != N:
-        raise ValueError('scales [Q] and [N] expected for codes of Q and N rows')
     qcodes, ldq = _rows_pitch(qcodes, ldc)
     qexps, ldqe = _rows_pitch(qexps, lde)
     bcodes, ldb = _i8_codes(bcodes, ldc)
     bexps, ldbe = _i8_codes(bexps, lde, align=8)
-    qscales, bscales = qscales.contiguous(), bscales.contiguous()
-    out, lds = _score_out(out, Q, N, bcodes.device)
+    qscales, bscales, out, lds = _scales_out('codes of Q and N rows', qscales, Q, bscales, N, out, bcodes.device)
     if Q and N:
         call('dir_similarity_fp4', ptr(qcodes), ldq, ptr(qexps), ldqe, ptr(qscales), Q, ptr(bcodes), ldb, ptr(bexps), ldbe,
              ptr(bscales), N, D, ptr(out), lds, stream_ptr())
@@ -792,13 +796,7 @@ def quantize_rows_bin(X):
     """fp32 rows -> (bits uint8 [N, ldb], scales fp32 [N]), both CUDA (dir_quantize_rows_bin; include/dir_engine.h gives
     the definition): bit k & 7 of byte k >> 3 is set where x_k has a clear sign bit, scale = sumsq / sumabs; ldb =
     bin_width(D), the padding bits zero.  X [N,D] fp32 CUDA with unit column stride and any row pitch."""
-    _on_device(X)
-    if X.dtype != torch.float32 or X.dim() != 2:
-        raise TypeError('float32 rows [N,D] expected')
-    N, D = X.shape
-    if D < 1 or D > index_bin_max_dim():
-        raise ValueError('1 <= D <= %d expected, got %d' % (index_bin_max_dim(), D))
-    X, ldx = _rows_pitch(X, D)
+    X, ldx, N, D = _rows_in(X, index_bin_max_dim())
     ldb = bin_width(D)
     bits = torch.empty(N, ldb, dtype=torch.uint8, device=X.device)
     scales = torch.empty(N, dtype=torch.float32, device=X.device)
@@ -827,12 +825,9 @@ def similarity_bin(qcodes, qscales, bits, bscales, D, out=None):
     ldb = bin_width(D)
     if qcodes.shape[1] < D or bits.shape[1] < ldb:
         raise ValueError('query codes of %d and bits of %d columns at least expected for D = %d' % (D, ldb, D))
-    if qscales.dim() != 1 or bscales.dim() != 1 or qscales.numel() != Q or bscales.numel() != N:
-        raise ValueError('scales [Q] and [N] expected for codes of Q and bits of N rows')
     qcodes, ldq = _rows_pitch(qcodes, D)
     bits, ldb = _i8_codes(bits, ldb)
-    qscales, bscales = qscales.contiguous(), bscales.contiguous()
-    out, lds = _score_out(out, Q, N, bits.device)
+    qscales, bscales, out, lds = _scales_out('codes of Q and bits of N rows', qscales, Q, bscales, N, out, bits.device)
     if Q and N:
         call('dir_similarity_bin', ptr(qcodes), ldq, ptr(qscales), Q, ptr(bits), ldb, ptr(bscales), N, D, ptr(out), lds,
              stream_ptr())

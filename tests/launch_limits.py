@@ -20,7 +20,7 @@ Out of scope: the conv kernels (conv_*.hip, stem_*.hip) and engine.hip.  Their l
 rule that an activation tensor of one engine call stays below 2^31 bytes, which tests/test_model_gpu.py tests."""
 from collections import namedtuple
 
-FILES = ('index_i8', 'ivf', 'ivfpq', 'pq', 'topk', 'ranking', 'label_rank', 'expand_lists',
+FILES = ('index_i8', 'index_fp4', 'index_bin', 'ivf', 'ivfpq', 'pq', 'topk', 'ranking', 'label_rank', 'expand_lists',
          'diffusion', 'pointwise', 'resize', 'gemm_f32', 'cov_f32', 'sim_split')
 
 Y_LIMIT = 65535
@@ -57,6 +57,27 @@ ROWS = [
            lambda Q, **_: _up(Q, 96), lambda L: dict(N=1, Q=96 * L + 1), 'Q', b'65535', axis='y'),
     split('index_i8', 'gather_scores_kernel', 1, 'dir_gather_scores',
           lambda Q, R, **_: _up(Q * R, 4) * 256, lambda L: dict(Q=4 * (L // 256) // 64 + 1, R=64), 'Q'),
+    # ---- index_fp4.hip, index_bin.hip (their refusals are index_i8.hip's rows_launch and flat_scan_launch) --------------------
+    refuse('index_fp4', 'quantize_rows_fp4_kernel', 1, 'dir_quantize_rows_fp4',
+           lambda N, **_: _up(N, 4) * 256, lambda L: dict(N=4 * (L // 256) + 1), 'N', b'N * 64'),
+    bounded('index_fp4', 'fp4_image_kernel', 1, 'dir_similarity_fp4',
+            'x = ceil(pad64(D) / 256) * 256 <= 2^13 by D <= dir_index_fp4_max_dim() = 7281; y = ceil(Q / 96), which the '
+            'entry holds to 65535 before this launch (the sim_fp4_kernel row)'),
+    refuse('index_fp4', 'sim_fp4_kernel', 1, 'dir_similarity_fp4',
+           lambda N, **_: _up(N, 256) * 768, lambda L: dict(N=256 * (L // 768) + 1, Q=1), 'N', b'N * 3'),
+    refuse('index_fp4', 'sim_fp4_kernel', 1, 'dir_similarity_fp4',
+           lambda Q, **_: _up(Q, 96), lambda L: dict(N=1, Q=96 * L + 1), 'Q', b'65535', axis='y'),
+    refuse('index_bin', 'quantize_rows_bin_kernel', 1, 'dir_quantize_rows_bin',
+           lambda N, **_: _up(N, 4) * 256, lambda L: dict(N=4 * (L // 256) + 1), 'N', b'N * 64'),
+    refuse('index_bin', 'code_sums_kernel', 2, 'dir_code_sums',
+           lambda Q, **_: _up(Q, 4) * 256, lambda L: dict(Q=4 * (L // 256) + 1), 'Q', b'Q * 64'),
+    bounded('index_bin', 'code_sums_kernel', 2, 'dir_similarity_bin',
+            'the scan-side site: x = ceil(Q / 96) * 24 * 256 <= 65535 * 6144 < 2^29, ceil(Q / 96) held to 65535 by the entry '
+            'before this launch (the sim_bin_kernel row)'),
+    refuse('index_bin', 'sim_bin_kernel', 1, 'dir_similarity_bin',
+           lambda N, **_: _up(N, 256) * 768, lambda L: dict(N=256 * (L // 768) + 1, Q=1), 'N', b'N * 3'),
+    refuse('index_bin', 'sim_bin_kernel', 1, 'dir_similarity_bin',
+           lambda Q, **_: _up(Q, 96), lambda L: dict(N=1, Q=96 * L + 1), 'Q', b'65535', axis='y'),
     # ---- ivf.hip --------------------------------------------------------------------------------------------------------
     bounded('ivf', 'segment_sums_kernel', 1, 'dir_segment_sums', 'x = ceil(D / 256) * 256 <= 2^31 + 255 for an int D'),
     refuse('ivf', 'segment_sums_kernel', 1, 'dir_segment_sums',

@@ -65,7 +65,7 @@ def test_host_query(lib):
 
 
 def test_inventory_lists_every_launch_site():
-    assert len(set(FILES)) == len(FILES) == 14
+    assert len(set(FILES)) == len(FILES) == 16
     found = {}
     for name in FILES:
         for kernel in _launch_sites(name):
@@ -114,6 +114,11 @@ def _calls(lib, p):
     return {
         'dir_quantize_rows_i8': lambda N: lib.dir_quantize_rows_i8(p, 4, N, 4, p, 64, p, None),
         'dir_similarity_i8': lambda N, Q: lib.dir_similarity_i8(p, 64, p, Q, p, 64, p, N, 64, p, N, None),
+        'dir_quantize_rows_fp4': lambda N: lib.dir_quantize_rows_fp4(p, 4, N, 4, p, 32, p, 8, p, None),
+        'dir_similarity_fp4': lambda N, Q: lib.dir_similarity_fp4(p, 32, p, 8, p, Q, p, 32, p, 8, p, N, 64, p, N, None),
+        'dir_quantize_rows_bin': lambda N: lib.dir_quantize_rows_bin(p, 4, N, 4, p, 16, p, None),
+        'dir_code_sums': lambda Q: lib.dir_code_sums(p, 4, Q, 4, p, None),
+        'dir_similarity_bin': lambda N, Q: lib.dir_similarity_bin(p, 64, p, Q, p, 16, p, N, 64, p, N, None),
         'dir_segment_sums': lambda S: lib.dir_segment_sums(p, 1, 1, 1, p, p, S, p, 1, None),
         'dir_ivf_scan_i8': lambda Q, width, items: lib.dir_ivf_scan_i8(p, 64, p, Q, p, 64, p, p, 1, 64, p, 1, p, p, p, p, items, p, p,
                                                                        width, width, None),
